@@ -46,6 +46,7 @@ import torch  # noqa: E402
 # measurement plumbing kept out of this file (tools/): the timed region and the line are here
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_calibrate import choose_arm  # noqa: E402
+from bench_dump import dump_outputs  # noqa: E402
 from bench_cpu import (colour_projection_torch_cpu, cpu_baseline, cpu_colour_loop, cpu_torch_loop, distinct_image_lines,  # noqa: E402,F401
                        host_cores)
 from bench_launch import launch_check, launch_ranks  # noqa: E402
@@ -170,7 +171,14 @@ def parse():
                     help="no GPU work: every rank joins a gloo process group, takes its share of the views, plans its calls, and "
                          "rank 0 prints one line with n_gpus = the group's size (value null).  What tests/ run on CPU to see that "
                          "`bench.py --gpus N` starts N ranks by itself")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, rank 0 writes what the timed path computed in its last step -- the arrays its "
+                         "caller receives -- as DIR/<name>.npy (float32 / float64, at most 64 MB in all: larger arrays as a "
+                         "seeded sample of rows beside <name>_rows.npy; tools/bench_dump.py).  Inputs are seeded, so two builds "
+                         "run with the same arguments can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.workload is None:
         a.workload = "R1" if a.entry else "R2"
     return a
@@ -293,6 +301,9 @@ def bench_colors(a, dev, rank, world, dist):
         step(timed=(k == a.steps - 1))
     _barrier(dist, dev)
     dt = _max_over_ranks(dist, time.perf_counter() - t0, dev)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, {"color_sums": csum, "hits": hits, "first_view": first})
     seen = torch.tensor([int(hits.sum().item()) if (dist is None or rank == 0 or a.collective == "allreduce") else 0], device=dev)
     call_ms = sum(e0.elapsed_time(e1) for e0, e1 in ev) / len(ev)
     if rank == 0:
@@ -329,6 +340,8 @@ def bench_colors(a, dev, rank, world, dist):
                           "parallelism": f"views r::{world} per GPU + one RCCL {a.collective} of colour sums/counts per pass" if world > 1 else "single GPU"},
                "voxel_view_hits_per_step": n_seen,
                "roofline": r4_roofline(ach, algo, call_ms, r4pmc, None if a.no_line_count else int(lines))}
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if not a.no_cpu_baseline and world == 1:
             from oracle import oracle
             nv = min(400, V)                                           # ~10 s on one core
@@ -412,6 +425,9 @@ def bench_entry(a, dev, rank, world, dist):
         step()
     _barrier(dist, dev)
     dt = _max_over_ranks(dist, time.perf_counter() - t0, dev)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, agg.result())
     # per-kernel HIP events in a pass of their own, after the timed region: with one view per call the event records (two
     # per kernel group) are a measurable share of a call, so they stay out of the number that is reported
     voxproj_host.profile_enable(True)
@@ -457,6 +473,8 @@ def bench_entry(a, dev, rank, world, dist):
                             "avg_launch_ms": round(gather_ms, 4)}}
         ach = algo / len(calls) / (gather_ms * 1e-3) / 1e9 if gather_ms > 0 else 0.0
         res["roofline"].update(achieved=round(ach, 1), frac=round(ach / HBM_PEAK_GBS, 4), bytes_per_launch=int(algo / len(calls)))
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if not a.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(s, C, min(a.cpu_views, n_views), host_cores())
         print(json.dumps(res), flush=True)
@@ -763,6 +781,11 @@ def main():
     step_ev[a.steps].record()
     barrier()
     dt = time.perf_counter() - t0
+    # the last timed step's result, before anything below runs more passes into the same rows (multi-rank: the aggregator's rows,
+    # which count / out alias)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, {"count": count, "out": out, **({"views": agg.views} if agg is not None else {})})
     step_list = sorted(step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(a.steps))
     voxproj_host.workspace_status(ws, dev)
     prof = voxproj_host.profile_read()
@@ -917,6 +940,8 @@ def main():
                                            "run's views per launch; null when the kernel sources changed since) -- not measured in this run",
                          "bytes_per_launch": gather_bytes // len(calls), "avg_launch_ms": round(gather_ms, 4)},
         }
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if not a.no_cpu_baseline and world == 1:      # reported on rank 0 at N=1 only (bench contract)
             ncores = host_cores()
             res["cpu_baseline"] = cpu_baseline(scene, C, min(a.cpu_views, n_views), ncores)

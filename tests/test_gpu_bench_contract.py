@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,6 +37,50 @@ def test_bench_line_single_gpu():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == d["unit"] and cb["sample"]
     assert d["box_miss_voxels"] == 0
+
+
+def _load_dump(path):
+    got = {f[:-4]: np.load(os.path.join(path, f)) for f in os.listdir(path)}
+    assert all(f.endswith(".npy") for f in os.listdir(path)) and all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(os.path.getsize(os.path.join(path, f)) for f in os.listdir(path)) <= 64 * 10 ** 6
+    return got
+
+
+def test_bench_dumps_the_last_timed_step_the_same_way_twice(tmp_path):
+    """--dump-outputs: the hit counts and feature sums of the last timed step, whole at S0, equal to what the line reports; the inputs
+    are seeded, so a second process with the same arguments writes the same counts and the same sums."""
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "S0", "--steps", "3", "--warmup", "1",
+                            "--no-cpu-baseline", "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert d["dumped_outputs"]["arrays"] == {"count": [10001], "out": [10001, 32]}
+        got = _load_dump(tmp_path / name)
+        assert set(got) == {"count", "out"} and got["count"].dtype == np.float64 and got["out"].dtype == np.float32
+        assert int(got["count"].sum()) == d["hit_pixels_per_step"]
+        assert abs(got["out"].astype(np.float64).sum() - d["checksum"]) <= 1e-6 * d["checksum_abs"]
+        runs.append(got)
+    assert np.array_equal(runs[0]["count"], runs[1]["count"])
+    a, b = runs[0]["out"], runs[1]["out"]
+    assert (np.abs(a - b) / (np.abs(a).max(axis=1, keepdims=True) + 1e-30)).max() <= 1e-6
+
+
+def test_bench_dump_samples_the_rows_of_outputs_beyond_64_mb(tmp_path):
+    # R1's feature sums are 80001 x 512 fp32 = 164 MB: a seeded sample of rows beside their indices, the hit counts whole
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "R1", "--views", "4", "--steps", "1", "--warmup", "0",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    got = _load_dump(tmp_path)
+    assert set(got) == {"count", "out", "out_rows"} and got["count"].shape == (80001,)
+    k = got["out_rows"].shape[0]
+    assert got["out"].shape == (k, 512) and 20000 < k < 80001 and d["dumped_outputs"]["arrays"]["out"] == [k, 512]
+    assert np.all(np.diff(got["out_rows"]) > 0) and got["out_rows"][-1] <= 80000
+    assert int(got["count"].sum()) == d["hit_pixels_per_step"]
+    hit = got["count"][got["out_rows"].astype(np.int64)] > 0                  # rows no pixel reached stay zero
+    assert np.all(got["out"][~hit] == 0) and np.all(np.abs(got["out"][hit]).max(axis=1) > 0)
 
 
 def _no_launcher_env():

@@ -2,7 +2,7 @@
 same shape (every ray leaps to its end in a few evaluations: ray set-up, image store, launch) and on a grid whose only voxel sits
 in a far corner.  python3 tools/march_fixed_cost.py"""
 import os, sys
-ROOT = "/root/repo" if os.path.isdir("/root/repo/tests") else os.environ["GRAFT_REPO_ROOT"]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "3d-semantic-segmentation_amd")]
 import numpy as np, torch, voxproj_host
 from synthetic_scene import make_scene
