@@ -50,7 +50,13 @@ VOXEL_PLY = "minkowski_grid.ply"
 MAX_IMAGES = 216                 # AGG:106
 DOWNSAMPLE_FACTOR = 0.5          # AGG:209
 CHECKPOINT_EVERY = 20            # AGG:318
+DEPTH_MIN, DEPTH_MAX = 0.01, 10.0   # DPF:167-168
 _NEVER = 2 ** 30
+
+
+def ray_opts(W, H, voxel_size):
+    """The projector's opts of a view: [W, H, depth_min, depth_max, ray_increment = voxel_size / 2] (DPF:167-169)."""
+    return [float(W), float(H), DEPTH_MIN, DEPTH_MAX, float(np.float32(voxel_size * 0.5))]
 
 
 class VoxelFeatureAggregator:
@@ -111,7 +117,7 @@ class VoxelFeatureAggregator:
         self._reported = 0
 
     def _opts(self, W, H):
-        return [float(W), float(H), 0.01, 10.0, float(np.float32(self.voxel_size * 0.5))]   # DPF:167-169
+        return ray_opts(W, H, self.voxel_size)
 
     def _to_device_ready(self, t):
         """A small host tensor (poses, intrinsics) as a float32 device tensor that is READY -- for the caller's stream

@@ -28,6 +28,7 @@
 //   vp_aux.h     RGB projection, nearest-voxel map, streaming-read probe
 //   vp_prep.h    feature-map up-sampler (PTD:119-127), occupancy builder (BSO:30-53)
 //   vp_aggregate.h  the aggregator's per-view fp16 accumulate over the hit rows (AGG:307-313)
+//   vp_render.h  the transpose: every pixel copies the row of its first-hit voxel (k_render_walk, k_render_small)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 #include <hip/hip_runtime.h>
@@ -53,6 +54,7 @@
 #include "vp_aux.h"
 #include "vp_prep.h"
 #include "vp_aggregate.h"
+#include "vp_render.h"
 
 // ------------------------------------------------------------------------------------------------
 // host helpers
@@ -110,15 +112,19 @@ size_t vp_workspace_bytes(int B, int V, int H, int W, int C, int dimz, int dimy,
 
 static int workspace_status_impl(void *workspace, void *stream_, bool drain_all);
 
+// ids_out != NULL: march only (vp_first_hit_ids) -- tables, k_zero_call and k_first_hit writing the first-hit image straight into
+// ids_out; no work list, no gather, feats / count / out unused.  Such a call leaves nothing for VP_FLAG_GATHER_ONLY or
+// vp_copy_hit_image to take up.
 static int project_impl(const float *feats, bool feats_f16, const int64_t *occ, const float *vmi, const float *intr,
                         const float *opts_host, int32_t *count, float *out, int32_t *views_hit,
                         const float *grid_origin_host, float voxel_size,
                         int B, int V, int H, int W, int C, int dimz, int dimy, int dimx, int64_t n_rows,
-                        void *workspace, size_t workspace_bytes, void *stream_, int flags)
+                        void *workspace, size_t workspace_bytes, void *stream_, int flags, int32_t *ids_out = nullptr)
 {
+    const bool march_only = ids_out != nullptr;
     if (feats_f16 && (C % 8 != 0 || ((uintptr_t)feats & 15) != 0 || ((uintptr_t)out & 15) != 0))
         return fail(VP_EINVAL, "fp16 feature maps need C %% 8 == 0 and 16-byte aligned feats/out");
-    if (!feats || !occ || !vmi || !intr || !opts_host || !count || !out || !grid_origin_host || !workspace)
+    if ((!march_only && (!feats || !count || !out)) || !occ || !vmi || !intr || !opts_host || !grid_origin_host || !workspace)
         return fail(VP_EINVAL, "null pointer argument");
     // What VP_FLAG_GATHER_ONLY and vp_copy_hit_image rely on (first-hit images of the last call, its arguments) is valid only
     // once a call has queued all of its launches: withdrawn when a call fails -- refused arguments, refused flag, HIP error --
@@ -352,15 +358,17 @@ static int project_impl(const float *feats, bool feats_f16, const int64_t *occ, 
         ProfSpan sp; sp.begin(0, s1);
         // one launch clears the per-call status words and the per-call histogram, and checks the workspace header
         hipLaunchKernelGGL(k_zero_call, dim3((unsigned)((n_rows + 1023) / 1024)), dim3(256), 0, s1, status, cnt_call, (long long)n_rows,
-                           status0, rec.sticky_dev, WS_MAGIC, rec.gen, expect_tables, hit_waves, plan.dyn_px_min > 0 ? l.n_hitcnt : 0ll);
+                           status0, rec.sticky_dev, WS_MAGIC, rec.gen, expect_tables, hit_waves,
+                           (plan.dyn_px_min > 0 && !march_only) ? l.n_hitcnt : 0ll);
         sp.end();
     }
     if (!gather_only) {
         FirstHitArgs fa;
         fa.occ = (const long long *)occ; fa.vmi = vmi; fa.intr = intr; fa.near2 = near2; fa.dist = dist;
-        fa.nby = l.nby; fa.nbx = l.nbx; fa.nblk = l.nblk; fa.hit = hit; fa.cnt_call = cnt_call;
+        fa.nby = l.nby; fa.nbx = l.nbx; fa.nblk = l.nblk; fa.hit = march_only ? (int *)ids_out : hit; fa.cnt_call = cnt_call;
         fa.heavy_list = heavy_list; fa.heavy_t = ((one_view && !one_split) || heavy_t < 0) ? heavy_t : 2147483647;      // (the march enlists heavy voxels for one-view calls without parts only)
         fa.hit_waves = (plan.dyn_px_min > 0 && l.n_hitcnt > 0) ? hit_waves : nullptr;
+        if (march_only) { fa.heavy_t = 2147483647; fa.hit_waves = nullptr; }      // the IDs do not depend on either
         fa.status = status; fa.sticky = rec.sticky_dev;
         const dim3 grid((W + 15) / 16, (H + 15) / 16, B * V);
         ProfSpan sp; sp.begin(1, s1);
@@ -390,8 +398,15 @@ static int project_impl(const float *feats, bool feats_f16, const int64_t *occ, 
         // the gather's work list: touched voxels by size class, largest first (needs the finished histogram); its trailing
         // workgroups compute the view table, which is phase 2's too -- behind the march, not in front of it (in pipelined
         // mode a kernel with that many registers waits for a wavefront of the previous call's gather to retire)
-        VP_LAUNCH_WORKLIST(s1);
+        if (!march_only) VP_LAUNCH_WORKLIST(s1);
         sp.end();
+    }
+    if (march_only) {
+        // (hit_guard withdraws what the previous call left for VP_FLAG_GATHER_ONLY / vp_copy_hit_image: this call replaced it)
+        VP_HIP(hipGetLastError());
+        ps->last_q = 0;
+        if (flags & VP_FLAG_SYNC) return workspace_status_impl(workspace, stream_, true);
+        return VP_OK;
     }
     if (pipe && !gather_only) VP_HIP(hipEventRecord(ps->fh_done[q], s1));
 
@@ -514,6 +529,53 @@ int vp_project_features_f16(const void *feats_f16, const int64_t *occ, const flo
     return project_impl((const float *)feats_f16, true, occ, vmi, intr, opts_host, count, out, views_hit,
                         grid_origin_host, voxel_size, B, V, H, W, C, dimz, dimy, dimx, n_rows, workspace,
                         workspace_bytes, stream_, flags);
+}
+
+int vp_first_hit_ids(const int64_t *occ, const float *vmi, const float *intr, const float *opts_host,
+                     const float *grid_origin_host, float voxel_size, int B, int V, int H, int W,
+                     int dimz, int dimy, int dimx, int64_t n_rows, int32_t *ids,
+                     void *workspace, size_t workspace_bytes, void *stream_, int flags)
+{
+    const int allowed = VP_FLAG_SYNC | VP_FLAG_REUSE_ACCEL | VP_FLAG_VERIFY_ACCEL | VP_FLAG_EXACT_MARCH;
+    if (flags & ~allowed) return fail(VP_EINVAL, "vp_first_hit_ids accepts VP_FLAG_SYNC, _REUSE_ACCEL, _VERIFY_ACCEL and _EXACT_MARCH only (flags 0x%x)", flags);
+    if (!ids) return fail(VP_EINVAL, "null pointer argument");
+    return project_impl(nullptr, false, occ, vmi, intr, opts_host, nullptr, nullptr, nullptr, grid_origin_host, voxel_size,
+                        B, V, H, W, 1, dimz, dimy, dimx, n_rows, workspace, workspace_bytes, stream_, flags, ids);
+}
+
+// blocks of the render kernels (grid-stride beyond: 4 tiles of 64 pixels per block and pass)
+#ifndef RENDER_MAX_BLOCKS
+#define RENDER_MAX_BLOCKS (1 << 20)
+#endif
+
+int vp_render_features(const int32_t *ids, int64_t n_pixels, const float *rows, int64_t n_rows, int C, void *dst,
+                       int dst_is_f16, int32_t *bad_ids, void *stream_)
+{
+    if (!ids || !rows || !dst) return fail(VP_EINVAL, "null pointer argument");
+    if (n_pixels <= 0 || n_rows <= 0 || C <= 0) return fail(VP_EINVAL, "non-positive dimension (n_pixels, n_rows or C)");
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long tiles = (n_pixels + 63) / 64;
+    const dim3 grid((unsigned)std::min<long long>((tiles + 3) / 4, RENDER_MAX_BLOCKS));
+    const bool al16 = (((uintptr_t)rows | (uintptr_t)dst) & 15) == 0;
+    int *bad = (int *)bad_ids;
+#define VP_RENDER(KERNEL) hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, stream, (const int *)ids, (long long)n_pixels, rows, \
+                                             (long long)n_rows, C, dst_t, bad)
+    // rows narrower than a wavefront's lanes (C < 64, aligned or not) go to k_render_small, which deals a tile's elements to
+    // all 64 lanes; the walk would leave most lanes idle on every pixel
+    if (dst_is_f16) {
+        _Float16 *dst_t = (_Float16 *)dst;
+        if (C < 64) VP_RENDER((k_render_small<_Float16>));
+        else if (C % 8 == 0 && al16) VP_RENDER((k_render_walk<8, 1, _Float16>));
+        else VP_RENDER((k_render_walk<1, 4, _Float16>));
+    } else {
+        float *dst_t = (float *)dst;
+        if (C < 64) VP_RENDER((k_render_small<float>));
+        else if (C % 4 == 0 && al16) VP_RENDER((k_render_walk<4, 2, float>));
+        else VP_RENDER((k_render_walk<1, 4, float>));
+    }
+#undef VP_RENDER
+    VP_HIP(hipGetLastError());
+    return VP_OK;
 }
 
 static int read_status(void *workspace, hipStream_t stream, int *st /* [2][ST_WORDS] */)

@@ -51,6 +51,7 @@ EXPORTS = [
     "vp_stream_read", "vp_workspace_table_builds", "vp_colors_workspace_bytes",
     "vp_upsample_workspace_bytes", "vp_upsample_features", "vp_voxel_coords", "vp_scatter_occupancy",
     "vp_aggregate_view_f16", "vp_workspace_create", "vp_workspace_set_option",
+    "vp_first_hit_ids", "vp_render_features",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -162,6 +163,11 @@ def lib():
                                                ctypes.c_int, vp, vp, vp]
             L.vp_aggregate_view_f16.restype = ctypes.c_int
             L.vp_aggregate_view_f16.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, vp]
+            L.vp_first_hit_ids.restype = ctypes.c_int
+            L.vp_first_hit_ids.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float] + \
+                [ctypes.c_int] * 7 + [ctypes.c_int64, vp, vp, ctypes.c_size_t, vp, ctypes.c_int]
+            L.vp_render_features.restype = ctypes.c_int
+            L.vp_render_features.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int, vp, vp]
             if L.vp_abi_version() != VP_ABI_VERSION:
                 raise VoxprojError(f"{LIB_PATH} has ABI version {L.vp_abi_version()}, this package needs {VP_ABI_VERSION}: rebuild it")
             _lib = L
@@ -378,6 +384,100 @@ def hit_image(ws, device):
     check(lib().vp_copy_hit_image(ptr, dst.data_ptr(), B, V, H, W, C, dimz, dimy, dimx, n_rows, stream))
     torch.cuda.current_stream(device).synchronize()
     return dst
+
+
+def _require(cond, msg):
+    if not cond:
+        raise ValueError(msg)
+
+
+def _require_tensors(*specs):
+    """(tensor, name, dtypes) triples: every dtype is checked first, then that each tensor is on a GPU."""
+    import torch
+    for t, name, dtypes in specs:
+        _require(isinstance(t, torch.Tensor), f"{name} must be a torch tensor")
+        _require(t.dtype in dtypes, f"{name} must be {' or '.join(str(d) for d in dtypes)}, not {t.dtype}")
+    for t, name, _ in specs:
+        _require(t.is_cuda, f"{name} must be a CUDA tensor: there is no CPU path")
+
+
+def first_hit_ids(occ, vmi, intr, opts5, grid_origin3, voxel_size, H, W, n_rows, workspace=None, exact_march=None):
+    """vp_first_hit_ids: the first-hit voxel ID of every pixel (0 = the ray hits nothing) for any cameras, without feature
+    maps -- int32 [B,V,H,W], bit-identical to the hit image a forward call with the same arguments leaves.  occ int64
+    [B,Z,Y,X], vmi float32 [B*V*16] camera->world, intr float32 [B,4], all on one CUDA device; opts5 / grid_origin3 python
+    floats as for project_features_raw.  Blocking.  The tables built on ``workspace`` (default: this module's per-device one)
+    are reused like project_features_raw reuses them."""
+    import torch
+    _require(len(opts5) == 5, "opts5 must hold 5 values: W, H, depth_min, depth_max, ray_increment")
+    _require(len(grid_origin3) == 3, "grid_origin3 must hold 3 values")
+    _require_tensors((occ, "occ", (torch.int64,)), (vmi, "vmi", (torch.float32,)), (intr, "intr", (torch.float32,)))
+    _require(occ.dim() == 4 and occ.is_contiguous(), "occ must be a contiguous [B,Z,Y,X] tensor")
+    _require(vmi.device == occ.device and intr.device == occ.device, "occ, vmi and intr must be on one device")
+    B, dimz, dimy, dimx = (int(v) for v in occ.shape)
+    vmi = vmi.contiguous().reshape(-1)
+    intr = intr.contiguous()
+    _require(vmi.numel() % (16 * B) == 0 and vmi.numel() > 0, "vmi must hold B*V*16 floats")
+    _require(intr.numel() == 4 * B, "intr must be [B,4]")
+    V = vmi.numel() // (16 * B)
+    H, W, n_rows = int(H), int(W), int(n_rows)
+    dev = occ.device
+    ws = workspace if workspace is not None else get_workspace(dev)
+    ptr = ws.ensure(workspace_bytes(B, V, H, W, 1, dimz, dimy, dimx, n_rows), dev)
+    key = (occ._version, occ.data_ptr(), tuple(occ.shape), n_rows)
+    prev = ws.accel_key
+    reuse = prev is not None and prev[0]() is occ and prev[1] == key and ACCEL_CACHE
+    if exact_march is None:
+        exact_march = EXACT_MARCH
+    flags = VP_FLAG_SYNC | (VP_FLAG_REUSE_ACCEL if reuse else 0) | (VP_FLAG_EXACT_MARCH if exact_march else 0)
+    ids = torch.empty((B, V, H, W), dtype=torch.int32, device=dev)
+    o = (ctypes.c_float * 5)(*[float(v) for v in opts5])
+    g = (ctypes.c_float * 3)(*[float(v) for v in grid_origin3])
+    with torch.cuda.device(dev):
+        rc = lib().vp_first_hit_ids(occ.data_ptr(), vmi.data_ptr(), intr.data_ptr(), o, g, ctypes.c_float(float(voxel_size)),
+                                    B, V, H, W, dimz, dimy, dimx, n_rows, ids.data_ptr(), ptr, ws.capacity(),
+                                    torch.cuda.current_stream(dev).cuda_stream, flags)
+    if rc != VP_OK:
+        ws.accel_key = None
+        check(rc)
+    ws.accel_key = (weakref.ref(occ), key)
+    return ids
+
+
+def render_features(ids, rows, dtype=None, out=None, check=True):
+    """vp_render_features: out[..., :] = rows[ids[...], :] -- every pixel takes the row of its first-hit voxel; zeros where
+    the ID is 0 (a miss) or outside [0, n_rows).  ids int32 CUDA (e.g. [B,V,H,W] from first_hit_ids), rows float32 [n_rows, C]
+    on the same device; returns ids.shape + (C,) in ``dtype`` (float32 or float16, rounded to nearest-even), or fills ``out``.
+    Asynchronous on the current stream, except with ``check``: then the out-of-range IDs are counted, the call synchronises and
+    raises VoxprojError if there were any.  The adjoint of the forward projection (project_features_autograd uses it)."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    _require(dtype in (torch.float32, torch.float16), f"dtype must be torch.float32 or torch.float16, not {dtype}")
+    _require_tensors((ids, "ids", (torch.int32,)), (rows, "rows", (torch.float32,)))
+    _require(rows.dim() == 2 and rows.shape[0] > 0 and rows.shape[1] > 0, "rows must be [n_rows, C] with n_rows, C >= 1")
+    _require(rows.device == ids.device, "ids and rows must be on one device")
+    _require(ids.numel() > 0, "ids is empty")
+    ids = ids.contiguous()
+    rows = rows.contiguous()
+    n_rows, C = (int(v) for v in rows.shape)
+    shape = tuple(ids.shape) + (C,)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=ids.device)
+    _require(isinstance(out, torch.Tensor) and out.is_cuda and out.device == ids.device and out.dtype == dtype
+             and tuple(out.shape) == shape and out.is_contiguous(), f"out must be a contiguous {dtype} CUDA tensor of shape {shape}")
+    bad = torch.zeros(1, dtype=torch.int32, device=ids.device) if check else None
+    with torch.cuda.device(ids.device):
+        stream = torch.cuda.current_stream(ids.device)
+        _check_rc(lib().vp_render_features(ids.data_ptr(), ids.numel(), rows.data_ptr(), n_rows, C, out.data_ptr(),
+                                           int(dtype == torch.float16), bad.data_ptr() if bad is not None else None,
+                                           stream.cuda_stream))
+    if check:
+        n_bad = int(bad.item())
+        if n_bad:
+            raise VoxprojError(f"render_features: {n_bad} pixel(s) carry an ID outside [0, {n_rows}) (rendered as zeros)")
+    return out
+
+
+_check_rc = check
 
 
 def counters(ws, device):

@@ -332,11 +332,47 @@ long long vp_workspace_table_builds(const void *workspace);
 
 /*
  * Copies the first-hit ID image i32 [B,V,H,W] of the LAST vp_project_features call on this
- * workspace into dst (device pointer).  Test/diagnostic hook: the reference has no such output,
- * the parity tests use it to compare the pixel -> voxel assignment of K.cu:47-82 directly.
+ * workspace into dst (device pointer), asynchronously on `stream`.  The parity tests use it to compare the pixel -> voxel
+ * assignment of K.cu:47-82 directly (the reference has no such output); it is also how a caller keeps a forward call's
+ * assignment for its adjoint: copy it on the same stream right behind the call, before another call on the workspace,
+ * and hand it to vp_render_features later (project_features_autograd.py does).  VP_EINVAL when the last call on the
+ * workspace failed or was a vp_first_hit_ids call.
  */
 int vp_copy_hit_image(const void *workspace, int32_t *dst, int B, int V, int H, int W,
                       int C, int dimz, int dimy, int dimx, int64_t n_rows, void *stream);
+
+/*
+ * The projector's transpose.  vp_project_features computes out[id, :] += sum of feats[p, :] over the pixels p whose ray hits
+ * voxel id first; its adjoint copies, for every pixel, the row of that voxel:  dst[p, :] = rows[hit[p], :].  The same copy
+ * shows a per-voxel table (an aggregation result) from any camera.  No reference counterpart (its autograd Function,
+ * tests/backward_test.py:74-79 of the CUDA extension, is the closest).  Added after VP_ABI_VERSION 4 without changing it
+ * or any existing entry point: callers detect the two functions by symbol (dlsym), not by the version number.
+ *
+ * vp_first_hit_ids: the march alone -- the first-hit voxel ID image i32 [B,V,H,W] (0 = the ray hits nothing) that
+ *   vp_project_features would leave for the same occ / vmi / intr / opts / grid arguments, bit for bit, written into `ids`
+ *   (device).  No feature maps, no work list, no gather.  Arguments as for vp_project_features; the workspace needs
+ *   vp_workspace_bytes(B, V, H, W, 1, dimz, dimy, dimx, n_rows) bytes and follows the same rules (tables built on it are
+ *   shared with vp_project_features calls of the same grid, VP_FLAG_REUSE_ACCEL / VP_FLAG_VERIFY_ACCEL as there).  flags:
+ *   VP_FLAG_SYNC | VP_FLAG_REUSE_ACCEL | VP_FLAG_VERIFY_ACCEL | VP_FLAG_EXACT_MARCH only, any other bit is VP_EINVAL.  Host
+ *   checks as vp_project_features (opts width/height = W/H, B*V <= 65535, rayIncrement > 0, workspace size and alignment,
+ *   ...); device errors (a ray hitting an ID outside [1, n_rows): the pixel reads 0; stuck rays; stale tables) go to the
+ *   workspace's sticky words like those of every other call.  It counts as a call on the workspace: a following
+ *   VP_FLAG_GATHER_ONLY call or vp_copy_hit_image returns VP_EINVAL (there is no forward call to take up).
+ *
+ * vp_render_features: dst[p, :] = rows[ids[p], :] for p < n_pixels (ids flattened, e.g. B*V*H*W of vp_first_hit_ids or
+ *   vp_copy_hit_image), rows f32 [n_rows, C] device, dst [n_pixels, C] device, f32 or (dst_is_f16) IEEE binary16 rounded to
+ *   nearest-even (torch's .half()).  ID 0 (a miss) gives zeros, NOT rows[0] -- row 0 receives no pixel in the forward, so
+ *   this is the exact adjoint.  IDs < 0 or >= n_rows give zeros and are never read; each such pixel adds 1 to *bad_ids
+ *   (device i32, may be NULL).  fp32 rows are copied bit for bit.  Any C >= 1 (16-byte loads/stores when C % 4 == 0, or
+ *   C % 8 == 0 for an f16 dst, with 16-byte aligned rows and dst); 64-bit offsets.  Asynchronous on `stream`; refused on the
+ *   host: null ids / rows / dst, n_pixels <= 0, n_rows <= 0, C <= 0.
+ */
+int vp_first_hit_ids(const int64_t *occ, const float *vmi, const float *intr, const float *opts_host,
+                     const float *grid_origin_host, float voxel_size,
+                     int B, int V, int H, int W, int dimz, int dimy, int dimx, int64_t n_rows,
+                     int32_t *ids, void *workspace, size_t workspace_bytes, void *stream, int flags);
+int vp_render_features(const int32_t *ids, int64_t n_pixels, const float *rows, int64_t n_rows, int C,
+                       void *dst, int dst_is_f16, int32_t *bad_ids, void *stream);
 
 #ifdef __cplusplus
 }
