@@ -19,10 +19,12 @@ VoxelFeatureAggregator (fast mode), then one RCCL all-reduce of the per-voxel {f
 view-count i32 [N+1]} -- the rank's last call cut by voxel ID so that half of the sums travel under the other half's gather
 (view_sharding.project_final_call_and_reduce); total work fixed, "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with "roofline" for the dominant kernel
-(k_gather, HBM-bound; HIP events on its launch stream, recorded live during the timed steps) and
-"cpu_baseline" (the CPU oracle -- a port of the reference kernel -- timed on this box's host cores on a
-bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs: set
+up, warm up, time the steps, write --dump-outputs, print.  --full adds everything else, in runs of its own around the timed
+region: the untimed pre-pass that counts the dominant kernel's algorithmic bytes and checks the timed result against it,
+"roofline" for that kernel (k_gather, HBM-bound; HIP events on its launch stream, recorded live during the timed steps),
+the on-box streaming-read ceiling, the other collective arm, and "cpu_baseline" (the CPU oracle -- a port of the reference
+kernel -- timed on this box's host cores on a bounded sample of the same workload).
 """
 import argparse
 import json
@@ -87,7 +89,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-line-count", action="store_true", help="R4: skip the exact count of distinct image lines (an upper bound takes its place in bytes_per_launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the pre-pass and checks against it, roofline and per-call figures, the other "
+                         "collective arm, the entry point's drop-in comparison and the CPU baselines (off: the line carries the "
+                         "headline and what the timed steps recorded)")
+    ap.add_argument("--no-line-count", action="store_true", help="R4 with --full: skip the exact count of distinct image lines (an upper bound takes its place in bytes_per_launch)")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS) + ["R4"],
                     help="R2 (default) = BASELINE metric config; R1 = config 2; S0 = config 1; R4 = config 5, the RGB path "
                          "(500k voxels x 1000 views, uint8 images; its own kernel, no HBM-roofline claim); A1 = the problem size the "
@@ -119,9 +125,9 @@ def parse():
                          "fill the chip worse; profiles/r03_rank_workloads.log)")
     ap.add_argument("--pool", type=int, default=32, help="distinct resident feature maps")
     ap.add_argument("--views", type=int, default=0, help="override the number of views (0 = workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-pipeline", action="store_true", help="plain calls: phase 1 and 2 serial on one stream")
-    ap.add_argument("--cpu-views", type=int, default=96, help="views in the cpu_baseline sample (about 10 s on 16 cores at R2; the single-thread sample is an eighth of it)")
+    ap.add_argument("--cpu-views", type=int, default=96, help="--full: views in the cpu_baseline sample (about 10 s on 16 cores at R2; the single-thread sample is an eighth of it)")
     ap.add_argument("--dtype", default="f32", choices=("f32", "f16"), help="feature-map storage type; f32 is the "
                     "BASELINE metric config, f16 the lossless half-bandwidth mode of SURVEY 8f/n4 (extra, not the headline)")
     ap.add_argument("--rehearse-dist", action="store_true", help="with one process: create the process group anyway (RCCL "
@@ -156,17 +162,17 @@ def parse():
                          "the one-view kernel with n workgroups per CU); -1 = the library's default")
     ap.add_argument("--no-split-collective", action="store_true",
                     help="multi-rank step: the TIMED arm does not cut the pass's last call into two row ranges (VP_OPT_ROW_BEGIN/_END "
-                         "+ VP_FLAG_GATHER_ONLY) whose first half is all-reduced under the second half's gather.  Either way the "
-                         "other arm is run after the timed region and both are reported (collective.arms)")
+                         "+ VP_FLAG_GATHER_ONLY) whose first half is all-reduced under the second half's gather.  Either way, with "
+                         "--full the other arm is run after the timed region and both are reported (collective.arms)")
     ap.add_argument("--collective-arm", default="auto", choices=("auto", "split", "whole"),
                     help="multi-rank step: which collective arm the timed region runs.  auto (default) = a short untimed calibration "
-                         "of both arms (2 steps each, MAX over ranks) picks the faster one; the other arm runs after the timed "
-                         "region either way and both are reported (collective.arms, collective.calibration)")
+                         "of both arms (2 steps each, MAX over ranks) picks the faster one; with --full the other arm runs "
+                         "after the timed region either way and both are reported (collective.arms, collective.calibration)")
     ap.add_argument("--scene-seed", type=int, default=0,
                     help="seed of the synthetic scene (default 0 = the scene every committed number is quoted on; other seeds: another "
                          "clutter layout and hand tremor on the trajectory legs -- a check that nothing is tuned to one scene)")
     ap.add_argument("--no-other-arm", action="store_true",
-                    help="multi-rank step: skip the steps of the other collective arm after the timed region")
+                    help="multi-rank step with --full: skip the steps of the other collective arm after the timed region")
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU work: every rank joins a gloo process group, takes its share of the views, plans its calls, and "
                          "rank 0 prints one line with n_gpus = the group's size (value null).  What tests/ run on CPU to see that "
@@ -308,6 +314,17 @@ def bench_colors(a, dev, rank, world, dist):
     call_ms = sum(e0.elapsed_time(e1) for e0, e1 in ev) / len(ev)
     if rank == 0:
         n_seen = int(seen.item())
+        res = {"metric": "Mvoxel-views/sec", "value": round(N * V / (dt / a.steps) / 1e6, 1), "unit": "Mvoxel-views/s",
+               "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
+               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64 projection, f32 colour sums",
+               "data": "synthetic",
+               "config": {"workload": f"R4: {N} voxels x {V} views x {W}x{H}x3 uint8 images, DPC semantics (nearest pixel, no "
+                                      f"occlusion), room-shell scene seed 0", "views_per_call": chunk, "resident_images": pool,
+                          "parallelism": f"views r::{world} per GPU + one RCCL {a.collective} of colour sums/counts per pass" if world > 1 else "single GPU"},
+               "voxel_view_hits_per_step": n_seen}
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+    if rank == 0 and a.full:
         per_call_hits = n_seen / max(1, len(calls) * world)
         # Algorithmic bytes of one call: every DISTINCT 64-byte line of an image that holds a sampled pixel has to come in once
         # (images are not shared between views), counted exactly by a float64 torch restatement of the projection on the
@@ -331,17 +348,7 @@ def bench_colors(a, dev, rank, world, dist):
                 r4pmc = None
         except OSError:
             pass
-        res = {"metric": "Mvoxel-views/sec", "value": round(N * V / (dt / a.steps) / 1e6, 1), "unit": "Mvoxel-views/s",
-               "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
-               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64 projection, f32 colour sums",
-               "data": "synthetic",
-               "config": {"workload": f"R4: {N} voxels x {V} views x {W}x{H}x3 uint8 images, DPC semantics (nearest pixel, no "
-                                      f"occlusion), room-shell scene seed 0", "views_per_call": chunk, "resident_images": pool,
-                          "parallelism": f"views r::{world} per GPU + one RCCL {a.collective} of colour sums/counts per pass" if world > 1 else "single GPU"},
-               "voxel_view_hits_per_step": n_seen,
-               "roofline": r4_roofline(ach, algo, call_ms, r4pmc, None if a.no_line_count else int(lines))}
-        if dumped is not None:
-            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+        res["roofline"] = r4_roofline(ach, algo, call_ms, r4pmc, None if a.no_line_count else int(lines))
         if not a.no_cpu_baseline and world == 1:
             from oracle import oracle
             nv = min(400, V)                                           # ~10 s on one core
@@ -354,6 +361,7 @@ def bench_colors(a, dev, rank, world, dist):
                                        sample=f"{nv} of the workload's views, all {N} voxels, {dtc:.1f} s wall "
                                               "(oracle_rgb_project: scalar C restatement of debug_project_colors.py:54-81)")
             res["cpu_torch_loop"] = cpu_colour_loop(s, img_np, min(400, V), host_cores())
+    if rank == 0:
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()
@@ -399,23 +407,24 @@ def bench_entry(a, dev, rank, world, dist):
         else:
             agg.flush()
 
-    # untimed pre-pass through the raw C-ABI: algorithmic bytes of the dominant kernel for exactly these calls
-    occ64 = torch.from_numpy(s.occ[None].astype(np.int64)).to(dev)
-    cnt = torch.zeros(n_vox + 1, dtype=torch.int32, device=dev)
-    out = torch.zeros(n_vox + 1, C, device=dev)
-    intr_d = torch.from_numpy(s.intr[None]).to(dev)
-    ws0 = voxproj_host.Workspace()
-    algo = 0
-    for ci, vs in enumerate(calls):
-        slot = vs[0] % pool if (vs[0] % pool) + len(vs) <= pool else 0
-        cnt.zero_()
-        voxproj_host.project_features_raw(feats[slot:slot + len(vs)][None], occ64, c2w[vs].reshape(-1).contiguous(), intr_d,
-                                          [float(v) for v in s.opts()], cnt, out, [float(v) for v in s.grid_origin],
-                                          s.voxel_size, workspace=ws0, sync=True, reuse_accel=(ci > 0 or None))
-        ph, nt = int(cnt.sum().item()), int((cnt > 0).sum().item())
-        algo += ph * C * 4 + nt * C * 4 * 2 + len(vs) * H * W * 4 + (n_vox + 1) * 4 * 2
-    ws0.release()
-    del ws0, out
+    if a.full:
+        # untimed pre-pass through the raw C-ABI: algorithmic bytes of the dominant kernel for exactly these calls
+        occ64 = torch.from_numpy(s.occ[None].astype(np.int64)).to(dev)
+        cnt = torch.zeros(n_vox + 1, dtype=torch.int32, device=dev)
+        out = torch.zeros(n_vox + 1, C, device=dev)
+        intr_d = torch.from_numpy(s.intr[None]).to(dev)
+        ws0 = voxproj_host.Workspace()
+        algo = 0
+        for ci, vs in enumerate(calls):
+            slot = vs[0] % pool if (vs[0] % pool) + len(vs) <= pool else 0
+            cnt.zero_()
+            voxproj_host.project_features_raw(feats[slot:slot + len(vs)][None], occ64, c2w[vs].reshape(-1).contiguous(), intr_d,
+                                              [float(v) for v in s.opts()], cnt, out, [float(v) for v in s.grid_origin],
+                                              s.voxel_size, workspace=ws0, sync=True, reuse_accel=(ci > 0 or None))
+            ph, nt = int(cnt.sum().item()), int((cnt > 0).sum().item())
+            algo += ph * C * 4 + nt * C * 4 * 2 + len(vs) * H * W * 4 + (n_vox + 1) * 4 * 2
+        ws0.release()
+        del ws0, out
     step()                                                     # builds the aggregator's tables, sizes its workspace
     for _ in range(a.warmup):
         step()
@@ -428,17 +437,30 @@ def bench_entry(a, dev, rank, world, dist):
     dumped = None
     if a.dump_outputs and rank == 0:
         dumped = dump_outputs(a.dump_outputs, agg.result())
-    # per-kernel HIP events in a pass of their own, after the timed region: with one view per call the event records (two
-    # per kernel group) are a measurable share of a call, so they stay out of the number that is reported
-    voxproj_host.profile_enable(True)
-    for _ in range(a.steps):
-        step()
-    _barrier(dist, dev)
-    prof = voxproj_host.profile_read()
-    voxproj_host.profile_enable(False)
+    if a.full:
+        # per-kernel HIP events in a pass of their own, after the timed region: with one view per call the event records (two
+        # per kernel group) are a measurable share of a call, so they stay out of the number that is reported
+        voxproj_host.profile_enable(True)
+        for _ in range(a.steps):
+            step()
+        _barrier(dist, dev)
+        prof = voxproj_host.profile_read()
+        voxproj_host.profile_enable(False)
     if rank == 0:
         r = agg.result()
         n_out = int(r["xyz"].shape[0])
+        ms_view = dt / a.steps / len(my_views) * 1e3
+        res = {"metric": "Mvoxel-views/sec", "value": round(n_vox * n_views / (dt / a.steps) / 1e6, 3), "unit": "Mvoxel-views/s",
+               "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
+               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+               "config": {"workload": f"{a.workload} through the entry point's aggregator, --mode {a.entry}: {n_vox} voxels x {n_views} "
+                                      f"views x {W}x{H}x{C} fp32 feature maps resident, {SCENE_NAME.get(a.workload, 'room-shell scene seed 0')}",
+                          "views_per_call": per_call, "resident_feature_maps": pool,
+                          "parallelism": f"views r::{world} per GPU + RCCL {a.collective}" if world > 1 else "single GPU"},
+               "entry": {"mode": a.entry, "ms_per_view": round(ms_view, 4), "rows_out": n_out}}
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+    if rank == 0 and a.full:
         # the drop-in module, one view per blocking call, same maps (compiled front; DPF:141-208 call pattern)
         import project_features_cuda as dropin
         out = torch.zeros(n_vox + 1, C, device=dev)
@@ -453,30 +475,20 @@ def bench_entry(a, dev, rank, world, dist):
                 dropin.project_features_cuda(feats[k % pool][None, None], occ64, vm[k], intr_d, opts, cnt, out, pm, org, s.voxel_size)
             d1 = (time.perf_counter() - t1) / nv
             best = d1 if best is None else min(best, d1)
-        ms_view = dt / a.steps / len(my_views) * 1e3
         launches = max(prof["gather_launches"], 1)
         gather_ms = prof["gather_ms"] / launches
-        res = {"metric": "Mvoxel-views/sec", "value": round(n_vox * n_views / (dt / a.steps) / 1e6, 3), "unit": "Mvoxel-views/s",
-               "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
-               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-               "config": {"workload": f"{a.workload} through the entry point's aggregator, --mode {a.entry}: {n_vox} voxels x {n_views} "
-                                      f"views x {W}x{H}x{C} fp32 feature maps resident, {SCENE_NAME.get(a.workload, 'room-shell scene seed 0')}",
-                          "views_per_call": per_call, "resident_feature_maps": pool,
-                          "parallelism": f"views r::{world} per GPU + RCCL {a.collective}" if world > 1 else "single GPU"},
-               "entry": {"mode": a.entry, "ms_per_view": round(ms_view, 4), "rows_out": n_out,
-                         "dropin_ms_per_view": round(best * 1e3, 4), "entry_over_dropin": round(ms_view / (best * 1e3), 3),
-                         "dropin_what": "project_features_cuda (compiled module), one view per blocking call"},
-               "phase_ms_per_step": {"prep": round(prof["prep_ms"] / a.steps, 3), "first_hit": round(prof["first_hit_ms"] / a.steps, 3),
-                                     "gather": round(prof["gather_ms"] / a.steps, 3), "combine_parts": round(prof["heavy_ms"] / a.steps, 3),
-                                     "note": "HIP events of an extra pass after the timed region"},
-               "roofline": {"bound": "hbm", "kernel": "k_gather", "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None,
-                            "avg_launch_ms": round(gather_ms, 4)}}
+        res["entry"].update(dropin_ms_per_view=round(best * 1e3, 4), entry_over_dropin=round(ms_view / (best * 1e3), 3),
+                            dropin_what="project_features_cuda (compiled module), one view per blocking call")
+        res["phase_ms_per_step"] = {"prep": round(prof["prep_ms"] / a.steps, 3), "first_hit": round(prof["first_hit_ms"] / a.steps, 3),
+                                    "gather": round(prof["gather_ms"] / a.steps, 3), "combine_parts": round(prof["heavy_ms"] / a.steps, 3),
+                                    "note": "HIP events of an extra pass after the timed region"}
+        res["roofline"] = {"bound": "hbm", "kernel": "k_gather", "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None,
+                           "avg_launch_ms": round(gather_ms, 4)}
         ach = algo / len(calls) / (gather_ms * 1e-3) / 1e9 if gather_ms > 0 else 0.0
         res["roofline"].update(achieved=round(ach, 1), frac=round(ach / HBM_PEAK_GBS, 4), bytes_per_launch=int(algo / len(calls)))
-        if dumped is not None:
-            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if not a.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(s, C, min(a.cpu_views, n_views), host_cores())
+    if rank == 0:
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()
@@ -670,8 +682,8 @@ def main():
     #          while the second gather runs.  Same bytes on the links, about half of them hidden; the cut itself costs a
     #          second, shorter gather launch.
     #   whole  the last call as it is, then one collective per tensor.
-    # The timed region runs the default arm (split; --no-split-collective: whole), the other arm runs after it for the same
-    # number of steps, and the line carries both (collective.arms).  collective_ms_exposed = pass - (zeroing + projection),
+    # The timed region runs the default arm (split; --no-split-collective: whole); with --full the other arm runs after it for
+    # the same number of steps, and the line carries both (collective.arms).  collective_ms_exposed = pass - (zeroing + projection),
     # the latter from HIP events around it.
     state = {"exposed_s": 0.0, "proj_s": 0.0}
     dst = 0 if a.collective == "reduce" else None
@@ -703,39 +715,41 @@ def main():
         for ci in range(len(calls)):
             one_call(ci)
 
-    # untimed pre-pass: algorithmic bytes of the dominant kernel per launch (deterministic across steps)
-    hit_px, touched, gather_bytes, cnt, max_px, heavy_px = 0, 0, 0, {}, 0, 0
-    per_call = []
-    out.zero_()
-    for ci in range(len(calls)):
-        count.zero_()
-        # alone on the device, HIP events around its kernels: what each call's march and gather do by themselves
-        voxproj_host.profile_enable(True)
-        one_call(ci, sync=True)
-        pc = voxproj_host.profile_read()
-        voxproj_host.profile_enable(False)
-        ph, nt = int(count.sum().item()), int((count > 0).sum().item())
-        hit_px += ph
-        touched += nt
-        # voxels above the library's per-call threshold (min(256 + 64*B*V, 2048) pixels) are summed in parts by wavefronts of the same
-        # k_gather launch: every hit pixel's row and every touched output row count for this kernel
-        c1 = voxproj_host.counters(ws, dev)
-        heavy = count > c1["heavy_t"]                  # the threshold in force: --heavy-threshold or min(256 + 64 * views per call, 2048)
-        heavy_px += int(count[heavy].sum().item())
-        bytes_call = ph * C * esize + nt * C * 4 * 2 + len(calls[ci][1]) * H * W * 4 + n_rows * 4 * 2
-        gather_bytes += bytes_call
-        for k in c1:
-            cnt[k] = max(cnt.get(k, 0), c1[k]) if k == "heavy_t" else cnt.get(k, 0) + c1[k]
-        max_px = max(max_px, int(count.max().item()))
-        per_call.append({"views": len(calls[ci][1]), "hit_pixels": ph, "miss": round(1.0 - ph / float(len(calls[ci][1]) * H * W), 3),
-                         "touched": nt, "heavy": c1["n_heavy"], "parts": c1["n_parts"], "max_pixels_per_voxel": int(count.max().item()),
-                         "bytes": bytes_call})
-        if pc["gather_launches"] == 1:
-            per_call[-1].update(gather_ms_alone=round(pc["gather_ms"], 3), march_ms_alone=round(pc["first_hit_ms"], 3),
-                                frac_alone=round(bytes_call / (pc["gather_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
+    if a.full:
+        # untimed pre-pass: algorithmic bytes of the dominant kernel per launch (deterministic across steps), and the plain
+        # result the timed steps are checked against
+        hit_px, touched, gather_bytes, cnt, max_px, heavy_px = 0, 0, 0, {}, 0, 0
+        per_call = []
+        out.zero_()
+        for ci in range(len(calls)):
+            count.zero_()
+            # alone on the device, HIP events around its kernels: what each call's march and gather do by themselves
+            voxproj_host.profile_enable(True)
+            one_call(ci, sync=True)
+            pc = voxproj_host.profile_read()
+            voxproj_host.profile_enable(False)
+            ph, nt = int(count.sum().item()), int((count > 0).sum().item())
+            hit_px += ph
+            touched += nt
+            # voxels above the library's per-call threshold (min(256 + 64*B*V, 2048) pixels) are summed in parts by wavefronts of the same
+            # k_gather launch: every hit pixel's row and every touched output row count for this kernel
+            c1 = voxproj_host.counters(ws, dev)
+            heavy = count > c1["heavy_t"]                  # the threshold in force: --heavy-threshold or min(256 + 64 * views per call, 2048)
+            heavy_px += int(count[heavy].sum().item())
+            bytes_call = ph * C * esize + nt * C * 4 * 2 + len(calls[ci][1]) * H * W * 4 + n_rows * 4 * 2
+            gather_bytes += bytes_call
+            for k in c1:
+                cnt[k] = max(cnt.get(k, 0), c1[k]) if k == "heavy_t" else cnt.get(k, 0) + c1[k]
+            max_px = max(max_px, int(count.max().item()))
+            per_call.append({"views": len(calls[ci][1]), "hit_pixels": ph, "miss": round(1.0 - ph / float(len(calls[ci][1]) * H * W), 3),
+                             "touched": nt, "heavy": c1["n_heavy"], "parts": c1["n_parts"], "max_pixels_per_voxel": int(count.max().item()),
+                             "bytes": bytes_call})
+            if pc["gather_launches"] == 1:
+                per_call[-1].update(gather_ms_alone=round(pc["gather_ms"], 3), march_ms_alone=round(pc["first_hit_ms"], 3),
+                                    frac_alone=round(bytes_call / (pc["gather_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
 
-    ref_checksum = out.double().sum(0)       # plain (unpipelined) result of one full pass on this rank
-    ref_abs = out.double().abs().sum(0)
+        ref_checksum = out.double().sum(0)       # plain (unpipelined) result of one full pass on this rank
+        ref_abs = out.double().abs().sum(0)
 
     def barrier():
         if dist is not None:
@@ -793,7 +807,7 @@ def main():
     exposed_ms = state["exposed_s"] / max(1, a.steps) * 1e3
     proj_ms = state["proj_s"] / max(1, a.steps) * 1e3
     reduced = {}      # checksums of the scene for the line (compared across runs by tests/test_gpu_bench_contract.py)
-    verify = not os.environ.get("VOXPROJ_BENCH_NOVERIFY")
+    verify = a.full and not os.environ.get("VOXPROJ_BENCH_NOVERIFY")
     if dist is None and verify:
         # the timed passes must have produced the same result as the plain pre-pass
         assert int(count.sum().item()) == hit_px, "hit-count total changed between the pre-pass and the timed steps"
@@ -801,7 +815,7 @@ def main():
     if verify:
         last = voxproj_host.counters(ws if agg is None else agg.ws, dev)
         assert last["bad_id"] == 0 and last["box_miss"] == 0, last
-    if dist is None:
+    if dist is None and a.full:
         # one more pass timed exactly like the placement tries (after the timed region; diagnostic only)
         for rep in range(2):
             torch.cuda.synchronize(dev)
@@ -846,7 +860,7 @@ def main():
         dt, exposed_ms = float(t[0].item()), float(t[1].item())
         name = {True: "split", False: "whole"}
         arms = {name[default_split]: {"ms_per_step": round(dt / a.steps * 1e3, 3), "collective_ms_exposed": round(exposed_ms, 3)}}
-        if not a.no_other_arm and h_rows > 0:
+        if a.full and not a.no_other_arm and h_rows > 0:
             # the other arm, same number of steps, bracketed the same way (never the headline)
             state["exposed_s"] = 0.0
             barrier()
@@ -868,22 +882,16 @@ def main():
                         "the two collective arms left different scenes"
     split = default_split
 
-    algo_local = hit_px * C * esize + touched * C * 4 * 2 + len(calls) * n_rows * 4 * 2 + len(my_views) * H * W * 4 * 2
-    if dist is not None:
-        t = torch.tensor([algo_local], dtype=torch.float64, device=dev)
-        dist.all_reduce(t)
-        algo_local = float(t.item())
-    stream_gbs = voxproj_host.stream_read_gbs(feats) if rank == 0 else 0.0   # on-box streaming-read ceiling
+    if a.full:
+        algo_local = hit_px * C * esize + touched * C * 4 * 2 + len(calls) * n_rows * 4 * 2 + len(my_views) * H * W * 4 * 2
+        if dist is not None:
+            t = torch.tensor([algo_local], dtype=torch.float64, device=dev)
+            dist.all_reduce(t)
+            algo_local = float(t.item())
+        stream_gbs = voxproj_host.stream_read_gbs(feats) if rank == 0 else 0.0   # on-box streaming-read ceiling
     if rank == 0:
         ms_step = dt / a.steps * 1e3
         value = n_vox * n_views / (dt / a.steps) / 1e6
-        launches = max(prof["gather_launches"], 1)
-        if split:
-            launches = a.steps * len(calls)      # the split call's two launches count as the one call whose bytes they move
-        gather_ms = prof["gather_ms"] / launches
-        ach = (gather_bytes / len(calls)) / (gather_ms * 1e-3) / 1e9 if gather_ms > 0 else 0.0
-        # whole-path algorithmic bytes per step (SURVEY 8d): feature rows + output RMW + counts + ID image w+r
-        algo_step = algo_local      # summed over ranks
         res = {
             "metric": "Mvoxel-views/sec", "value": round(value, 3), "unit": "Mvoxel-views/s",
             "n_gpus": dist.get_world_size() if dist is not None else 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 3),
@@ -897,14 +905,13 @@ def main():
                                        f"per pass, waited for inside the pass (backend {a.dist_backend})")
                        if world > 1 else "single GPU (one-rank process group: rehearsal of the multi-rank path)" if dist is not None
                        else "single GPU"},
-            "achieved_hbm_gbs_whole_path": round(algo_step / (dt / a.steps) / 1e9, 1),
             "step_ms": {"min": round(step_list[0], 3), "median": round(step_list[len(step_list) // 2], 3), "max": round(step_list[-1], 3)},
             "phase_ms_per_step": {"prep": round(prof["prep_ms"] / a.steps, 3),
                                   "first_hit": round(prof["first_hit_ms"] / a.steps, 3),
                                   "gather": round(prof["gather_ms"] / a.steps, 3),
                                   "combine_parts": round(prof["heavy_ms"] / a.steps, 3),
                                   "overlapped": pipeline},
-            "pool_placement": placement, "device": device_info(dev), **reduced,
+            "pool_placement": placement, "device": device_info(dev),
             **({"collective": {"op": "reduce to rank 0" if a.collective == "reduce" else "all-reduce", "backend": a.dist_backend,
                                "through": "VoxelFeatureAggregator.add_views / add_final_views (aggregate_voxel_features_onthefly.py, fast mode)",
                                "bytes_per_rank": n_rows * C * 4 + 2 * n_rows * 4,
@@ -921,10 +928,23 @@ def main():
                                "note": "max over ranks; the headline value includes the collective (no overlap between passes); "
                                        "collective_ms_exposed = pass - (zeroing + projection), the latter from HIP events.  split: the "
                                        "rank's last call is cut into two row ranges and the first half's sums are reduced under the "
-                                       "second half's gather; whole: the call as it is, then the collectives.  The arm that is not "
-                                       "timed runs after the timed region, same number of steps"}} if dist is not None else {}),
-            "hit_pixels_per_step": hit_px, "miss_fraction": round(1.0 - hit_px / float(len(my_views) * H * W), 4),
+                                       "second half's gather; whole: the call as it is, then the collectives.  With --full the arm "
+                                       "that is not timed runs after the timed region, same number of steps"}} if dist is not None else {}),
             "march_share_of_device_time": round(prof["first_hit_ms"] / max(1e-9, prof["first_hit_ms"] + prof["gather_ms"] + prof["heavy_ms"]), 4),
+        }
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+    if rank == 0 and a.full:
+        launches = max(prof["gather_launches"], 1)
+        if split:
+            launches = a.steps * len(calls)      # the split call's two launches count as the one call whose bytes they move
+        gather_ms = prof["gather_ms"] / launches
+        ach = (gather_bytes / len(calls)) / (gather_ms * 1e-3) / 1e9 if gather_ms > 0 else 0.0
+        # whole-path algorithmic bytes per step (SURVEY 8d): feature rows + output RMW + counts + ID image w+r
+        algo_step = algo_local      # summed over ranks
+        res.update({
+            "achieved_hbm_gbs_whole_path": round(algo_step / (dt / a.steps) / 1e9, 1), **reduced,
+            "hit_pixels_per_step": hit_px, "miss_fraction": round(1.0 - hit_px / float(len(my_views) * H * W), 4),
             "box_miss_voxels": cnt["box_miss"], "heavy_voxels_per_step": cnt["n_heavy"], "heavy_pixels_per_step": heavy_px, "heavy_threshold": cnt["heavy_t"],
             "parts_per_step": cnt["n_parts"], "max_pixels_per_voxel_call": max_px, "per_call": per_call,
             "roofline": {"bound": "hbm", "kernel": "k_gather", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
@@ -939,14 +959,13 @@ def main():
                          "traffic_source": f"profiles/{PMC_PROFILE} (rocprofv3 --pmc passes of this build, rescaled to this "
                                            "run's views per launch; null when the kernel sources changed since) -- not measured in this run",
                          "bytes_per_launch": gather_bytes // len(calls), "avg_launch_ms": round(gather_ms, 4)},
-        }
-        if dumped is not None:
-            res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+        })
         if not a.no_cpu_baseline and world == 1:      # reported on rank 0 at N=1 only (bench contract)
             ncores = host_cores()
             res["cpu_baseline"] = cpu_baseline(scene, C, min(a.cpu_views, n_views), ncores)
             res["cpu_baseline_1t"] = cpu_baseline(scene, C, max(1, min(a.cpu_views // 8, n_views)), 1)      # the oracle single-threaded too
             res["cpu_torch_loop"] = cpu_torch_loop(scene, min(300, n_views), ncores)
+    if rank == 0:
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()

@@ -1,6 +1,6 @@
 """bench.py's output contract on the plumbing workload (S0: 10k voxels x 8 views x 64x64x32): ONE JSON line with the
-metric, the roofline object and the CPU baseline at N=1; the two-rank code path (views r::2 + all-reduce) rehearsed
-with gloo on one GPU."""
+metric, and with --full the roofline object and the CPU baseline at N=1; the two-rank code path (views r::2 + all-reduce)
+rehearsed with gloo on one GPU."""
 import json
 import os
 import subprocess
@@ -21,7 +21,7 @@ def _last_json(out):
 
 def test_bench_line_single_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "S0", "--steps", "2", "--warmup", "1",
-                        "--cpu-views", "2"], capture_output=True, text=True, timeout=600)
+                        "--full", "--cpu-views", "2"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -39,6 +39,23 @@ def test_bench_line_single_gpu():
     assert d["box_miss_voxels"] == 0
 
 
+def test_plain_bench_line_is_the_headline_alone():
+    # without --full: set-up, warm-up, the timed steps and the line -- no pre-pass, roofline, checks or CPU baselines
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "S0", "--steps", "2", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "step_ms", "phase_ms_per_step"):
+        assert k in d, k
+    assert d["metric"] == "Mvoxel-views/sec" and d["unit"] == "Mvoxel-views/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and abs(d["value"] - 10000 * 8 / (d["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "cpu_baseline_1t", "cpu_torch_loop", "checksum", "hit_pixels_per_step", "per_call"):
+        assert k not in d, k
+    assert "ms_per_pass_after_timed_region" not in d["pool_placement"]
+
+
 def _load_dump(path):
     got = {f[:-4]: np.load(os.path.join(path, f)) for f in os.listdir(path)}
     assert all(f.endswith(".npy") for f in os.listdir(path)) and all(v.dtype in (np.float32, np.float64) for v in got.values())
@@ -52,7 +69,7 @@ def test_bench_dumps_the_last_timed_step_the_same_way_twice(tmp_path):
     runs = []
     for name in ("a", "b"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "S0", "--steps", "3", "--warmup", "1",
-                            "--no-cpu-baseline", "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600)
+                            "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         d = _last_json(r.stdout)
         assert d["steps"] == 3 and d["ms_per_step"] > 0
@@ -70,7 +87,7 @@ def test_bench_dumps_the_last_timed_step_the_same_way_twice(tmp_path):
 def test_bench_dump_samples_the_rows_of_outputs_beyond_64_mb(tmp_path):
     # R1's feature sums are 80001 x 512 fp32 = 164 MB: a seeded sample of rows beside their indices, the hit counts whole
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "R1", "--views", "4", "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     got = _load_dump(tmp_path)
@@ -95,7 +112,7 @@ def test_bench_gloo_rehearsal_started_by_bench_itself(ranks):
     of both arms found faster (round 5: no arm is the default by guess), both arms are in the line, the integers travel in one
     tensor, and the line shows the ranks' spread."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--workload", "S0", "--steps", "2", "--warmup", "1",
-                        "--dist-backend", "gloo", "--single-device"], capture_output=True, text=True, timeout=900, env=_no_launcher_env())
+                        "--dist-backend", "gloo", "--single-device", "--full"], capture_output=True, text=True, timeout=900, env=_no_launcher_env())
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     assert d["n_gpus"] == ranks and d["scaling"] == "strong" and "cpu_baseline" not in d
@@ -146,7 +163,7 @@ def test_bench_two_ranks_allreduce_variant():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29535", os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--workload", "S0", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo",
-                        "--single-device", "--collective", "reduce", "--no-other-arm", "--no-split-collective"],
+                        "--single-device", "--collective", "reduce", "--no-other-arm", "--no-split-collective", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]          # bench verifies reduced counts exactly and sums against the ranks' own
     d = _last_json(r.stdout)
@@ -162,7 +179,7 @@ def test_bench_two_ranks_at_the_r2_shape():
     single-rank run of the same 32 views."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     # every run's pool holds all of its views (32 maps for the single rank, 16 per rank), so view v reads the map seeded by v in both
-    common = ["--workload", "R2", "--views", "32", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    common = ["--workload", "R2", "--views", "32", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, capture_output=True, text=True, timeout=900)
     assert r1.returncode == 0, r1.stderr[-3000:]
     one = _last_json(r1.stdout)
@@ -197,7 +214,7 @@ def _check_common(d):
 def test_bench_config2_r1_leg():
     # BASELINE config 2 at its own shape (80k voxels, 484x274x512), a 12-view slice of it to keep the test short
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "R1", "--views", "12", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     _check_common(d)
@@ -206,7 +223,7 @@ def test_bench_config2_r1_leg():
 
 def test_bench_config5_rgb_leg():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "R4", "--views", "16", "--chunk", "8",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     _check_common(d)
@@ -216,7 +233,7 @@ def test_bench_config5_rgb_leg():
 @pytest.mark.parametrize("mode", ["parity", "fast"])
 def test_bench_entry_point_leg(mode):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--entry", mode, "--views", "10", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     _check_common(d)
@@ -266,7 +283,7 @@ def test_bench_multi_rank_path_over_a_one_rank_rccl_communicator():
     box.  RCCL initialised before the first pipelined call used to cost the march/gather overlap (63 vs 54 ms per R2
     pass): asserted here on the R1 workload."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "R1", "--steps", "5", "--warmup", "1",
-                        "--no-cpu-baseline", "--rehearse-dist", "--min-calls", "2"],      # two calls: something to overlap
+                        "--full", "--no-cpu-baseline", "--rehearse-dist", "--min-calls", "2"],      # two calls: something to overlap
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)

@@ -71,7 +71,7 @@ def write_pmc_json(prof_dir, out_path):
             runs[key].update({k: {"launches": len(v["FETCH_SIZE"]), "FETCH_SIZE_KB_per_launch": round(sum(v["FETCH_SIZE"]) / len(v["FETCH_SIZE"]), 1),
                                   "WRITE_SIZE_KB_per_launch": round(sum(v["WRITE_SIZE"]) / max(1, len(v["WRITE_SIZE"])), 1)}
                               for k, v in per.items() if v.get("FETCH_SIZE") and v.get("WRITE_SIZE")})
-    doc = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), python3 bench.py --steps 1 --warmup 0 "
+    doc = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), python3 bench.py --full --steps 1 --warmup 0 "
                      "--no-cpu-baseline --views 120 --chunk 60 | --views 200 --chunk 100 --dtype f16 | --workload R1 | --workload R2T | "
                      "--workload A1, MI355X (tools/profile_round.sh); the trajectory legs' launches differ (close-ups, misses): their "
                      "figures are means over the launches of one pass",
@@ -111,7 +111,7 @@ def write_r4_pmc_json(prof_dir, out_path, views_per_call=1000):
                         "l1_misses_in_flight_per_l1": round(m["TCP_TCC_READ_REQ_LATENCY_sum"] / 256.0 / cycles, 2),
                         "l1_stalled_behind_pending_lines": round(m.get("TCP_PENDING_STALL_CYCLES_sum", 0.0) / 256.0 / cycles, 3),
                         "launch_cycles": int(cycles)})
-    doc = {"source": "rocprofv3 --pmc passes of python3 bench.py --workload R4 --steps 1 --warmup 0 --no-cpu-baseline (tools/r4_round.sh), MI355X",
+    doc = {"source": "rocprofv3 --pmc passes of python3 bench.py --full --workload R4 --steps 1 --warmup 0 --no-cpu-baseline (tools/r4_round.sh), MI355X",
            "source_digest": source_digest(), "views_per_call": views_per_call,
            "FETCH_SIZE_KB_per_launch": round(m["FETCH_SIZE"], 1), "WRITE_SIZE_KB_per_launch": round(m["WRITE_SIZE"], 1), "summary": summary}
     with open(out_path, "w") as f:

@@ -16,11 +16,11 @@ tail -n 3 gpurun_out/${tag}_gputest.log > $P/${tag}_gputest_tail.txt
 grep '^{' gpurun_out/prof_$tag/bench_f32_under_rocprof.log | tail -1 > $P/${tag}_bench_under_rocprof.json
 { echo "# rocprofv3 summaries, round ${tag#r0}, final build (MI355X, ROCm 7.2), produced by tools/profile_round.sh $tag + tools/summarize_prof.py"
   echo "# commands (cd \$GRAFT_REPO_ROOT; TMPDIR=/tmp):"
-  echo "#   rocprofv3 --kernel-trace --stats -d <out>/trace     -- python3 bench.py --no-cpu-baseline              (same run's JSON line: profiles/${tag}_bench_under_rocprof.json)"
-  echo "#   rocprofv3 --kernel-trace --stats -d <out>/trace_f16 -- python3 bench.py --no-cpu-baseline --dtype f16"
-  echo "#   rocprofv3 --pmc FETCH_SIZE -d <out>/fetch_<dt> -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --views 120 --chunk 60   |   --views 200 --chunk 100 --dtype f16"
+  echo "#   rocprofv3 --kernel-trace --stats -d <out>/trace     -- python3 bench.py --full --no-cpu-baseline              (same run's JSON line: profiles/${tag}_bench_under_rocprof.json)"
+  echo "#   rocprofv3 --kernel-trace --stats -d <out>/trace_f16 -- python3 bench.py --full --no-cpu-baseline --dtype f16"
+  echo "#   rocprofv3 --pmc FETCH_SIZE -d <out>/fetch_<dt> -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --views 120 --chunk 60   |   --views 200 --chunk 100 --dtype f16"
   echo "#   rocprofv3 --pmc WRITE_SIZE -d <out>/write_<dt> -- (same)      (separate passes; counter passes serialise kernels: their durations are not the bench's)"
-  echo "#   rocprofv3 --kernel-trace --stats -d <out>/trace_R4  -- python3 bench.py --workload R4 --no-cpu-baseline"
+  echo "#   rocprofv3 --kernel-trace --stats -d <out>/trace_R4  -- python3 bench.py --full --workload R4 --no-cpu-baseline"
   echo "# k_gather averages over ALL launches of a process (placement pass 10, pre-pass 5, warm-up 5, timed 15, after-pass 10 = 45 at 5 calls of 60 views per pass);"
   echo "# FETCH_SIZE is in KB and counts 64 B per 128-B request for 16-B-per-lane streaming reads on gfx950 -> doubled in profiles/${tag}_pmc_traffic.json's reader"
   cat gpurun_out/prof_$tag/summary.txt | cut -c1-420; } > $P/${tag}_rocprofv3_summary.txt

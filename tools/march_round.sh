@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 out=gpurun_out/march_$tag
 rm -rf $out; mkdir -p $out
-cmd="python3 bench.py --no-pipeline --steps 1 --warmup 0 --views 60 --no-cpu-baseline"
+cmd="python3 bench.py --full --no-pipeline --steps 1 --warmup 0 --views 60 --no-cpu-baseline"
 i=0
 for lib in "$@"; do
   i=$((i+1)); export VOXPROJ_LIB=$PWD/$lib

@@ -13,10 +13,10 @@ export TMPDIR=/tmp
 out=gpurun_out/prof_$tag
 mkdir -p $out
 run() { local name=$1; shift; echo "[prof] $name $(date +%T)"; timeout -k 10 400 "$@" > $out/$name.log 2>&1 || { echo "[prof] $name FAILED"; tail -5 $out/$name.log; exit 1; }; }
-trace() { local name=$1; shift; run bench_${name}_under_rocprof rocprofv3 --kernel-trace --stats -d $out/trace_$name -o t --output-format csv -- python3 bench.py --no-cpu-baseline "$@"; }
+trace() { local name=$1; shift; run bench_${name}_under_rocprof rocprofv3 --kernel-trace --stats -d $out/trace_$name -o t --output-format csv -- python3 bench.py --full --no-cpu-baseline "$@"; }
 pmc() { local name=$1; shift
-  run pmc_fetch_$name rocprofv3 --pmc FETCH_SIZE -d $out/fetch_$name -o c --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline "$@"
-  run pmc_write_$name rocprofv3 --pmc WRITE_SIZE -d $out/write_$name -o c --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline "$@"; }
+  run pmc_fetch_$name rocprofv3 --pmc FETCH_SIZE -d $out/fetch_$name -o c --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "$@"
+  run pmc_write_$name rocprofv3 --pmc WRITE_SIZE -d $out/write_$name -o c --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "$@"; }
 case $part in
 a)
   trace f32

@@ -11,7 +11,7 @@ rm -rf $out; mkdir -p $out
 step() { local name=$1; shift; echo "[traj] $name $(date +%T)"; timeout -k 10 300 "$@" > $out/$name.log 2>&1; local rc=$?; echo "[traj] $name rc $rc"
          if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "[traj] $name timed out: stopping"; exit $rc; fi; return 0; }
 for w in R2T R2; do
-  one="python3 bench.py --workload $w --views 60 --min-calls 1 --steps 1 --warmup 0 --no-cpu-baseline $*"
+  one="python3 bench.py --full --workload $w --views 60 --min-calls 1 --steps 1 --warmup 0 --no-cpu-baseline $*"
   step trace_$w rocprofv3 --kernel-trace --stats -d $out/trace_$w -o t --output-format csv -- $one
   step fetch_$w rocprofv3 --pmc FETCH_SIZE -d $out/fetch_$w -o c --output-format csv -- $one
   step write_$w rocprofv3 --pmc WRITE_SIZE -d $out/write_$w -o c --output-format csv -- $one
