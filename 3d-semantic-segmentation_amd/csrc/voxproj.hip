@@ -29,6 +29,7 @@
 //   vp_prep.h    feature-map up-sampler (PTD:119-127), occupancy builder (BSO:30-53)
 //   vp_aggregate.h  the aggregator's per-view fp16 accumulate over the hit rows (AGG:307-313)
 //   vp_render.h  the transpose: every pixel copies the row of its first-hit voxel (k_render_walk, k_render_small)
+//   vp_query.h   text query of a feature table: cosine logits, argmax label, softmax margin on the matrix cores (k_query)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 #include <hip/hip_runtime.h>
@@ -55,6 +56,7 @@
 #include "vp_prep.h"
 #include "vp_aggregate.h"
 #include "vp_render.h"
+#include "vp_query.h"
 
 // ------------------------------------------------------------------------------------------------
 // host helpers
@@ -574,6 +576,53 @@ int vp_render_features(const int32_t *ids, int64_t n_pixels, const float *rows, 
         else VP_RENDER((k_render_walk<1, 4, float>));
     }
 #undef VP_RENDER
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+size_t vp_query_workspace_bytes(int P, int C)
+{
+    if (P < 1 || P > QUERY_MAX_P || C < 1 || C > QUERY_MAX_C) return 0;
+    return align256((size_t)query_ppad(P) * query_cpad(C) * sizeof(float));
+}
+
+int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, int64_t row_stride, const float *text, int P,
+                      float scale, float *logits, int32_t *labels, float *margin, int32_t *n_nonfinite, void *workspace,
+                      size_t workspace_bytes, void *stream_)
+{
+    if (!rows || !labels || !text) return fail(VP_EINVAL, "null pointer argument (rows, labels or text)");
+    if (n_rows < 1 || n_rows > INT32_MAX) return fail(VP_EINVAL, "n_rows = %lld outside [1, 2^31 - 1]", (long long)n_rows);
+    if (C < 1 || C > QUERY_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, QUERY_MAX_C);
+    if (P < 1 || P > QUERY_MAX_P) return fail(VP_EINVAL, "P = %d outside [1, %d]", P, QUERY_MAX_P);
+    if (row_stride < C) return fail(VP_EINVAL, "row_stride %lld < C = %d", (long long)row_stride, C);
+    if (!(scale > 0.0f) || !std::isfinite(scale)) return fail(VP_EINVAL, "scale must be finite and > 0 (got %g)", (double)scale);
+    const size_t need = vp_query_workspace_bytes(P, C);
+    if (!workspace || workspace_bytes < need) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t esz = rows_is_f16 ? 2 : 4;
+    const bool vec = C % (16 / esz) == 0 && ((uintptr_t)rows & 15) == 0 && ((size_t)row_stride * esz) % 16 == 0;
+    const dim3 grid((unsigned)((n_rows + 16 * QUERY_WAVES - 1) / (16 * QUERY_WAVES))), block(64 * QUERY_WAVES);
+#define VP_QUERY(T, VEC) hipLaunchKernelGGL((k_query<T, VEC, false>), grid, block, 0, stream, (const T *)rows, (long long)n_rows, C, \
+                                            (long long)row_stride, (const T *)workspace, P, scale, logits, (int *)labels, margin, \
+                                            (int *)n_nonfinite)
+#define VP_QUERY1(T) hipLaunchKernelGGL((k_query<T, true, true>), grid, block, 0, stream, (const T *)rows, (long long)n_rows, C, \
+                                        (long long)row_stride, (const T *)workspace, P, scale, logits, (int *)labels, margin, \
+                                        (int *)n_nonfinite)
+    // rows of one chunk with 16-byte loads (C <= 512 fp16, <= 256 fp32): the variant without chunk loops
+    if (rows_is_f16) {
+        hipLaunchKernelGGL((k_query_text<_Float16>), dim3(query_ppad(P)), dim3(64), 0, stream, text, P, C, (_Float16 *)workspace);
+        if (vec && C <= QUERY_NS * QueryTraits<_Float16>::W) VP_QUERY1(_Float16);
+        else if (vec) VP_QUERY(_Float16, true);
+        else VP_QUERY(_Float16, false);
+    } else {
+        hipLaunchKernelGGL((k_query_text<float>), dim3(query_ppad(P)), dim3(64), 0, stream, text, P, C, (float *)workspace);
+        if (vec && C <= QUERY_NS * QueryTraits<float>::W) VP_QUERY1(float);
+        else if (vec) VP_QUERY(float, true);
+        else VP_QUERY(float, false);
+    }
+#undef VP_QUERY
+#undef VP_QUERY1
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

@@ -51,7 +51,7 @@ EXPORTS = [
     "vp_stream_read", "vp_workspace_table_builds", "vp_colors_workspace_bytes",
     "vp_upsample_workspace_bytes", "vp_upsample_features", "vp_voxel_coords", "vp_scatter_occupancy",
     "vp_aggregate_view_f16", "vp_workspace_create", "vp_workspace_set_option",
-    "vp_first_hit_ids", "vp_render_features",
+    "vp_first_hit_ids", "vp_render_features", "vp_query_workspace_bytes", "vp_query_features",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -168,6 +168,11 @@ def lib():
                 [ctypes.c_int] * 7 + [ctypes.c_int64, vp, vp, ctypes.c_size_t, vp, ctypes.c_int]
             L.vp_render_features.restype = ctypes.c_int
             L.vp_render_features.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int, vp, vp]
+            L.vp_query_workspace_bytes.restype = ctypes.c_size_t
+            L.vp_query_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+            L.vp_query_features.restype = ctypes.c_int
+            L.vp_query_features.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int,
+                                            ctypes.c_float, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
             if L.vp_abi_version() != VP_ABI_VERSION:
                 raise VoxprojError(f"{LIB_PATH} has ABI version {L.vp_abi_version()}, this package needs {VP_ABI_VERSION}: rebuild it")
             _lib = L
@@ -475,6 +480,53 @@ def render_features(ids, rows, dtype=None, out=None, check=True):
         if n_bad:
             raise VoxprojError(f"render_features: {n_bad} pixel(s) carry an ID outside [0, {n_rows}) (rendered as zeros)")
     return out
+
+
+def query_features(rows, text, scale=1.0, want_logits=True, want_margin=True, check=True):
+    """vp_query_features: score every row of a feature table against P text embeddings.  rows float16 or float32 CUDA [N, C]
+    (any row stride, unit channel stride), text [P, C] (any float dtype; used as float32) on the same device, scale > 0 the
+    logit multiplier (1.0: cosine similarity; LSeg's head multiplies by its logit_scale).  Returns (labels int32 [N],
+    logits float32 [N, P] or None, margin float32 [N] or None) on the rows' device: label = argmax of
+    scale * cos(row, text_j) (lowest index on ties), margin = softmax top-1 minus top-2 (1 when P = 1).  A row with a
+    non-finite element gets label -1 and NaN logits / margin.  Asynchronous on the current stream, except with ``check``: then
+    the call synchronises and raises VoxprojError if any row was non-finite."""
+    import torch
+    _require_tensors((rows, "rows", (torch.float16, torch.float32)),
+                     (text, "text", (torch.float16, torch.bfloat16, torch.float32, torch.float64)))
+    _require(rows.dim() == 2 and rows.shape[1] > 0, "rows must be [N, C] with C >= 1")
+    _require(text.dim() == 2 and text.shape[0] > 0, "text must be [P, C] with P >= 1")
+    _require(rows.device == text.device, "rows and text must be on one device")
+    N, C = (int(v) for v in rows.shape)
+    P = int(text.shape[0])
+    _require(int(text.shape[1]) == C, f"text has {int(text.shape[1])} channels, rows have {C}")
+    _require(1 <= P <= 1024 and C <= 2048, f"P = {P} must be in [1, 1024] and C = {C} in [1, 2048]")
+    scale = float(scale)
+    _require(scale > 0 and scale != float("inf"), f"scale must be finite and > 0, not {scale}")
+    dev = rows.device
+    if rows.stride(1) != 1 or rows.stride(0) < C:
+        rows = rows.contiguous()
+    text = text.to(torch.float32).contiguous()
+    labels = torch.empty(N, dtype=torch.int32, device=dev)
+    logits = torch.empty((N, P), dtype=torch.float32, device=dev) if want_logits else None
+    margin = torch.empty(N, dtype=torch.float32, device=dev) if want_margin else None
+    if N == 0:
+        return labels, logits, margin
+    bad = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+    L = lib()
+    nbytes = int(L.vp_query_workspace_bytes(P, C))
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    ws_ptr = (ws.data_ptr() + 255) & ~255
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_query_features(rows.data_ptr(), int(rows.dtype == torch.float16), N, C, int(rows.stride(0)),
+                                      text.data_ptr(), P, scale, logits.data_ptr() if logits is not None else None,
+                                      labels.data_ptr(), margin.data_ptr() if margin is not None else None,
+                                      bad.data_ptr() if bad is not None else None, ws_ptr, nbytes, stream.cuda_stream))
+    if check:
+        n_bad = int(bad.item())
+        if n_bad:
+            raise VoxprojError(f"query_features: {n_bad} row(s) hold a non-finite element (label -1, NaN logits)")
+    return labels, logits, margin
 
 
 _check_rc = check

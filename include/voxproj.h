@@ -374,6 +374,39 @@ int vp_first_hit_ids(const int64_t *occ, const float *vmi, const float *intr, co
 int vp_render_features(const int32_t *ids, int64_t n_pixels, const float *rows, int64_t n_rows, int C,
                        void *dst, int dst_is_f16, int32_t *bad_ids, void *stream);
 
+/*
+ * Text query of a per-voxel feature table (the reference's stage 5.1, the `query` sub-commands of
+ * voxel_to_gaussian/voxeltovoxel_logits.py and voxeltoGaussian_logits.py; the margin is logit_confidence_map.py's per-pixel
+ * confidence).  Added after VP_ABI_VERSION 4 without changing it or any existing entry point: callers detect the two
+ * functions by symbol (dlsym), not by the version number.
+ *
+ *   x^ = x / max(|x|, 1e-12)   t^_j = t_j / max(|t_j|, 1e-12)   (torch.nn.functional.normalize)
+ *   logit_j = scale * (x^ . t^_j),  label = argmax_j logit_j (lowest j on exact ties),
+ *   margin  = softmax(logit)[label] - second-largest softmax entry (1 when P = 1).
+ *
+ * vp_query_workspace_bytes: bytes of the caller's scratch for a query of P prompts of C channels (the normalised text,
+ *   zero-padded to 16-prompt / 32-channel tiles); 0 when P is outside [1, 1024] or C outside [1, 2048].  Grows with P and C.
+ *
+ * vp_query_features: rows [n_rows, C] device, IEEE binary16 (rows_is_f16) or f32, row r at rows + r * row_stride elements
+ *   (row_stride >= C); text f32 [P, C] device, row-major, any alignment; scale > 0 multiplies every logit (1: cosine; LSeg's
+ *   head uses its logit_scale).  Writes labels i32 [n_rows], and when not NULL logits f32 [n_rows, P] row-major and margin
+ *   f32 [n_rows].  fp16 rows run on v_mfma_f32_16x16x32_f16 with the normalised text rounded to binary16; f32 rows on
+ *   v_mfma_f32_16x16x4_f32 with f32 text, never rounded to binary16.  Every logit is within
+ *   scale * (2^-11 + 2 * C * 2^-24) of the float64 value.  A zero row gives logits 0, label 0, margin 0 (1 when P = 1).  A
+ *   row with a non-finite element gives label -1, NaN logits and margin, and adds 1 to *n_nonfinite (device i32, may be
+ *   NULL; not reset by the call).  Results are bit-identical from run to run and a row's outputs do not depend on the other
+ *   rows of the call (for the same dtype, C and alignment).  16-byte row loads when C % 8 == 0 (fp16) or C % 4 == 0 (f32)
+ *   with 16-byte aligned rows and row stride, element loads otherwise; 64-bit offsets.  workspace: device,
+ *   vp_query_workspace_bytes(P, C) bytes, 256-byte aligned, not shared with a call still running on another stream.  No
+ *   allocation, no host synchronisation: asynchronous on `stream`.  Refused on the host (VP_EINVAL): null rows / labels /
+ *   text, n_rows outside [1, 2^31 - 1], C outside [1, 2048], P outside [1, 1024], row_stride < C, scale <= 0 or not
+ *   finite; VP_EWORKSPACE: a workspace that is NULL, too small or not 256-byte aligned.
+ */
+size_t vp_query_workspace_bytes(int P, int C);
+int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, int64_t row_stride, const float *text,
+                      int P, float scale, float *logits, int32_t *labels, float *margin, int32_t *n_nonfinite,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
