@@ -30,6 +30,7 @@
 //   vp_aggregate.h  the aggregator's per-view fp16 accumulate over the hit rows (AGG:307-313)
 //   vp_render.h  the transpose: every pixel copies the row of its first-hit voxel (k_render_walk, k_render_small)
 //   vp_query.h   text query of a feature table: cosine logits, argmax label, softmax margin on the matrix cores (k_query)
+//   vp_splat.h   tile-based Gaussian splatting of D-channel features with a fused label / confidence epilogue (stage 5.2)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 #include <hip/hip_runtime.h>
@@ -57,6 +58,7 @@
 #include "vp_aggregate.h"
 #include "vp_render.h"
 #include "vp_query.h"
+#include "vp_splat.h"
 
 // ------------------------------------------------------------------------------------------------
 // host helpers
@@ -623,6 +625,118 @@ int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, 
     }
 #undef VP_QUERY
 #undef VP_QUERY1
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+size_t vp_splat_workspace_bytes(int64_t n_gaussians, int W, int H, int64_t capacity)
+{
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX || W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH || capacity < 0 ||
+        capacity > INT32_MAX)
+        return 0;
+    SplatLayout l;
+    return splat_layout(n_gaussians, W, H, capacity, l) ? l.bytes : 0;
+}
+
+int vp_splat_project(const float *means, const float *quats, const float *scales, const float *opacities, int64_t n_gaussians,
+                     const float *viewmat, float fx, float fy, float cx, float cy, int W, int H, float near_plane,
+                     float far_plane, float eps2d, int64_t *n_isect, int32_t *n_nonfinite, void *workspace,
+                     size_t workspace_bytes, void *stream_)
+{
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
+        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
+    if (n_gaussians > 0 && (!means || !quats || !scales || !opacities))
+        return fail(VP_EINVAL, "null pointer argument (means, quats, scales or opacities)");
+    if (!viewmat) return fail(VP_EINVAL, "null viewmat");
+    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(viewmat[k])) return fail(VP_EINVAL, "viewmat[%d] is not finite", k);
+    if (!(fx > 0.0f) || !(fy > 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail(VP_EINVAL, "fx, fy must be finite and > 0, cx, cy finite (got %g %g %g %g)", (double)fx, (double)fy,
+                    (double)cx, (double)cy);
+    if (!(near_plane > 0.0f) || !(far_plane > near_plane) || !(eps2d >= 0.0f) || !std::isfinite(eps2d))
+        return fail(VP_EINVAL, "need 0 < near < far and a finite eps2d >= 0 (got %g %g %g)", (double)near_plane,
+                    (double)far_plane, (double)eps2d);
+    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    SplatLayout l;   // rocprim's scratch sizes depend on the device: queried after the checks that need no GPU
+    if (!splat_layout(n_gaussians, W, H, 0, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    SplatCam cam;
+    for (int k = 0; k < 12; ++k) cam.r[k] = viewmat[k];
+    cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy;
+    cam.near_z = near_plane; cam.far_z = far_plane; cam.eps2d = eps2d;
+    cam.W = W; cam.H = H; cam.tiles_x = l.tiles_x;
+    long long *total = (long long *)(ws + l.total), *offs = (long long *)(ws + l.offs);
+    if (n_gaussians > 0) {
+        hipLaunchKernelGGL(k_splat_project, dim3((unsigned)((n_gaussians + 255) / 256)), dim3(256), 0, stream, means, quats,
+                           scales, opacities, (long long)n_gaussians, cam, (SplatRec *)(ws + l.rec), (int4 *)(ws + l.box),
+                           (int *)(ws + l.count), (int *)n_nonfinite);
+        VP_HIP(hipGetLastError());
+        size_t tmp = l.scan_bytes;
+        VP_HIP(rocprim::inclusive_scan(ws + l.scan_tmp, tmp, (const int *)(ws + l.count), offs, (size_t)n_gaussians,
+                                       rocprim::plus<long long>(), stream));
+    }
+    hipLaunchKernelGGL(k_splat_total, dim3(1), dim3(1), 0, stream, (const long long *)offs, (long long)n_gaussians, total,
+                       (long long *)n_isect);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H, int64_t capacity,
+                       int32_t *labels, float *confidence, float *alpha, float *logits, int32_t *status, void *workspace,
+                       size_t workspace_bytes, void *stream_)
+{
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
+        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
+    if (!labels || (n_gaussians > 0 && !features)) return fail(VP_EINVAL, "null pointer argument (labels or features)");
+    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
+    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
+    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    const long long n_tiles = (long long)l.tiles_x * l.tiles_y;
+    const long long *total = (const long long *)(ws + l.total);
+    unsigned long long *k0 = (unsigned long long *)(ws + l.keys0), *k1 = (unsigned long long *)(ws + l.keys1);
+    int *v0 = (int *)(ws + l.vals0), *v1 = (int *)(ws + l.vals1);
+    longlong2 *ranges = (longlong2 *)(ws + l.ranges);
+    // emit: one thread per Gaussian (at least one workgroup, which also pads [total, capacity) and raises the status)
+    const long long n_emit = std::max<long long>(n_gaussians, 1);
+    const unsigned g_emit = (unsigned)((n_emit + 255) / 256);
+    hipLaunchKernelGGL(k_splat_emit, dim3(g_emit), dim3(256), 0, stream, (const SplatRec *)(ws + l.rec),
+                       (const int4 *)(ws + l.box), (const long long *)(ws + l.offs), (long long)n_gaussians, l.tiles_x,
+                       n_tiles, total, (long long)capacity, k0, v0, (int *)status);
+    VP_HIP(hipGetLastError());
+    if (capacity > 0) {
+        size_t tmp = l.sort_bytes;
+        VP_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, tmp, k0, k1, v0, v1, (size_t)capacity, 0u, (unsigned)l.end_bit,
+                                         stream));
+    }
+    VP_HIP(hipMemsetAsync(ranges, 0, (size_t)n_tiles * sizeof(longlong2), stream));
+    if (capacity > 0) {
+        hipLaunchKernelGGL(k_splat_ranges, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, stream, k1, total,
+                           (long long)capacity, ranges);
+        VP_HIP(hipGetLastError());
+    }
+    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+#define VP_SPLAT(DT) hipLaunchKernelGGL((k_splat_blend<DT>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), v1, ranges, \
+                                        total, (long long)capacity, features, D, (long long)row_stride, W, H, (int *)labels, \
+                                        confidence, alpha, logits)
+    if (D <= 8) VP_SPLAT(8);
+    else if (D <= 16) VP_SPLAT(16);
+    else if (D <= 32) VP_SPLAT(32);
+    else VP_SPLAT(64);
+#undef VP_SPLAT
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

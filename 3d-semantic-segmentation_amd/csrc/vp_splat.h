@@ -1,0 +1,330 @@
+// vp_splat.h -- tile-based Gaussian splatting of D-channel features (the reference's stage 5.2, gsplat's classic forward pass)
+// with a fused argmax label / softmax-confidence epilogue.  Included by voxproj.hip only.
+#pragma once
+
+#if !__has_include(<rocprim/device/device_radix_sort.hpp>)
+#error "vp_splat.h needs rocPRIM's headers (ROCm's include/rocprim): the Gaussian splatting sort is rocprim::radix_sort_pairs"
+#endif
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// The contract (INTEGRATION.md "Gaussian splatting"; tests/splat_reference.py is its float64 statement):
+//
+// k_splat_project   one thread per Gaussian.  Depth z = ((r20 mx + r21 my) + r22 mz) + t2 in fp32 (no contraction: the
+//   Makefile's -ffp-contract=off), culled when z < near or z > far.  The rest in float64, rounded to fp32 once at the end:
+//   Sigma = M M^T with M = R(q/|q|) diag(s), Sigma_c = R_w Sigma R_w^T, the clamped EWA Jacobian, Sigma2 = J Sigma_c J^T +
+//   eps2d I, conic = Sigma2^-1 (culled when det <= 0), mean2d = (fx px/z + cx, fy py/z + cy).  Float64 here keeps the fp32
+//   records within one rounding of the float64 oracle's values, so the blend's decisions differ from it only within the
+//   oracle's fragile band.  Opacity below 1/255, a zero quaternion or a box off the image: no tiles.  A non-finite mean /
+//   quaternion / scale / opacity culls the Gaussian and adds 1 to *n_nonfinite.
+//   Support box: sigma <= ln(255 o) holds inside |dx| <= sqrt(2 ln(255 o) Sigma2_00) (likewise y); the pixel range adds one
+//   pixel on each side, clipped to the image, and its 16x16 tiles are the Gaussian's tiles.
+// k_splat_emit      one thread per Gaussian, after an inclusive scan of the tile counts (rocprim, int64): key
+//   tile << 32 | bits(z) (z > 0, so the bits order like the floats) and value = Gaussian index, in index order; slots
+//   [total, capacity) get the key n_tiles << 32 (after every real tile).  rocprim::radix_sort_pairs is stable and sorts bits
+//   [0, 32 + bits(n_tiles)): each tile's run is in (z, index) order.
+// k_splat_ranges    one thread per sorted key: [start, end) of every tile's run.
+// k_splat_blend<DT> one 256-thread workgroup per 16x16 tile, one pixel per thread, DT >= D accumulators in registers.  The
+//   tile's run is staged through LDS in batches of SPLAT_BATCH(DT) Gaussians (records, then the feature rows zero-padded to
+//   DT).  Per visited pair: sigma, one exp, the 1/255 and 1e-4 tests and DT FMAs.  A pixel stops at the first Gaussian that
+//   would take T to <= 1e-4 (that one is not added); the workgroup leaves when every pixel has stopped
+//   (__syncthreads_count).  No atomics: each pixel's sum is in the sorted order, so images are bit-identical run to run.
+//   Epilogue: label = argmax over the D channels (lowest index on ties), confidence = softmax top-1 minus top-2
+//   = (1 - exp(m2 - m1)) / sum_c exp(f_c - m1) (1 when D = 1), alpha = 1 - T; logits planar [D, H, W].  Only the outputs
+//   whose pointer is non-NULL are written.
+// Every kernel after the scan reads the device total first: a total above the workspace's capacity writes nothing (the
+// emit kernel raises *status instead), so a too-small workspace never leaves a partial image.
+// ------------------------------------------------------------------------------------------------
+constexpr int SPLAT_TILE = 16;
+constexpr int SPLAT_THREADS = SPLAT_TILE * SPLAT_TILE;
+constexpr int SPLAT_MAX_D = 64;
+constexpr int SPLAT_MAX_WH = 32768;
+
+__host__ __device__ constexpr int splat_batch(int DT) { return DT <= 32 ? 256 : 128; }   // LDS: 41 KiB at DT 32, 37 KiB at 64
+
+struct SplatCam {
+    float r[12];                 // world -> camera [R | t], row-major 3 x 4
+    float fx, fy, cx, cy, near_z, far_z, eps2d;
+    int W, H, tiles_x;
+};
+
+struct SplatRec {                // 32 bytes per Gaussian
+    float mx, my, A, B;          // mean2d and the conic's first two terms
+    float C, o, z;               // conic's third term, opacity, fp32 depth (the sort key)
+    int pad;
+};
+
+__global__ __launch_bounds__(256) void k_splat_project(const float *__restrict__ means, const float *__restrict__ quats,
+                                                       const float *__restrict__ scales, const float *__restrict__ opac,
+                                                       long long n, SplatCam cam, SplatRec *__restrict__ rec,
+                                                       int4 *__restrict__ box, int *__restrict__ count, int *n_nonfinite)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int cnt = 0;
+    SplatRec g = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0};
+    int4 b = make_int4(0, 0, -1, -1);
+    const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2];
+    const float qw = quats[4 * i], qx = quats[4 * i + 1], qy = quats[4 * i + 2], qz = quats[4 * i + 3];
+    const float sx = scales[3 * i], sy = scales[3 * i + 1], sz = scales[3 * i + 2], o = opac[i];
+    const bool finite = isfinite(mx) && isfinite(my) && isfinite(mz) && isfinite(qw) && isfinite(qx) && isfinite(qy) &&
+                        isfinite(qz) && isfinite(sx) && isfinite(sy) && isfinite(sz) && isfinite(o);
+    if (!finite && n_nonfinite) atomicAdd(n_nonfinite, 1);
+    const float *r = cam.r;
+    const float z = ((r[8] * mx + r[9] * my) + r[10] * mz) + r[11];
+    const double qn2 = (double)qw * qw + (double)qx * qx + (double)qy * qy + (double)qz * qz;
+    if (finite && z >= cam.near_z && z <= cam.far_z && qn2 > 0.0 && (double)o >= 1.0 / 255.0) {
+        const double qi = 1.0 / sqrt(qn2), w = qw * qi, x = qx * qi, y = qy * qi, zq = qz * qi;
+        const double Rq[3][3] = {{1.0 - 2.0 * (y * y + zq * zq), 2.0 * (x * y - w * zq), 2.0 * (x * zq + w * y)},
+                                 {2.0 * (x * y + w * zq), 1.0 - 2.0 * (x * x + zq * zq), 2.0 * (y * zq - w * x)},
+                                 {2.0 * (x * zq - w * y), 2.0 * (y * zq + w * x), 1.0 - 2.0 * (x * x + y * y)}};
+        const double s[3] = {sx, sy, sz};
+        double M[3][3], Rw[3][3], p[3];
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) {
+                M[a][c] = Rq[a][c] * s[c];
+                Rw[a][c] = r[4 * a + c];
+            }
+        for (int a = 0; a < 3; ++a) p[a] = Rw[a][0] * mx + Rw[a][1] * my + Rw[a][2] * mz + (double)r[4 * a + 3];
+        // V = R_w M, Sigma_c = V V^T
+        double V[3][3], S[3][3];
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) V[a][c] = Rw[a][0] * M[0][c] + Rw[a][1] * M[1][c] + Rw[a][2] * M[2][c];
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) S[a][c] = V[a][0] * V[c][0] + V[a][1] * V[c][1] + V[a][2] * V[c][2];
+        const double zd = p[2], fx = cam.fx, fy = cam.fy, cx = cam.cx, cy = cam.cy;
+        const double limxp = (cam.W - cx) / fx + 0.3 * (0.5 * cam.W) / fx, limxn = cx / fx + 0.3 * (0.5 * cam.W) / fx;
+        const double limyp = (cam.H - cy) / fy + 0.3 * (0.5 * cam.H) / fy, limyn = cy / fy + 0.3 * (0.5 * cam.H) / fy;
+        const double ux = p[0] / zd, uy = p[1] / zd;
+        const double tx = zd * fmin(fmax(ux, -limxn), limxp), ty = zd * fmin(fmax(uy, -limyn), limyp);
+        const double J[2][3] = {{fx / zd, 0.0, -fx * tx / (zd * zd)}, {0.0, fy / zd, -fy * ty / (zd * zd)}};
+        double JS[2][3];
+        for (int a = 0; a < 2; ++a)
+            for (int c = 0; c < 3; ++c) JS[a][c] = J[a][0] * S[0][c] + J[a][1] * S[1][c] + J[a][2] * S[2][c];
+        const double s00 = JS[0][0] * J[0][0] + JS[0][1] * J[0][1] + JS[0][2] * J[0][2] + cam.eps2d;
+        const double s01 = JS[0][0] * J[1][0] + JS[0][1] * J[1][1] + JS[0][2] * J[1][2];
+        const double s11 = JS[1][0] * J[1][0] + JS[1][1] * J[1][1] + JS[1][2] * J[1][2] + cam.eps2d;
+        const double det = s00 * s11 - s01 * s01;
+        const double mxd = fx * ux + cx, myd = fy * uy + cy;
+        if (det > 0.0 && isfinite(det) && isfinite(mxd) && isfinite(myd)) {
+            const double ext = 2.0 * fmax(log(255.0 * (double)o), 0.0);
+            const double rx = sqrt(ext * s00), ry = sqrt(ext * s11);
+            // pixel j's sample is j + 0.5: |j + 0.5 - mx| <= rx, widened by one pixel each side
+            const double jlo = floor(mxd - rx - 1.5), jhi = ceil(mxd + rx + 0.5);
+            const double ilo = floor(myd - ry - 1.5), ihi = ceil(myd + ry + 0.5);
+            if (jhi >= 0.0 && ilo <= cam.H - 1.0 && ihi >= 0.0 && jlo <= cam.W - 1.0) {
+                b.x = (int)fmax(jlo, 0.0) / SPLAT_TILE;
+                b.y = (int)fmax(ilo, 0.0) / SPLAT_TILE;
+                b.z = (int)fmin(jhi, cam.W - 1.0) / SPLAT_TILE;
+                b.w = (int)fmin(ihi, cam.H - 1.0) / SPLAT_TILE;
+                cnt = (b.z - b.x + 1) * (b.w - b.y + 1);
+                g.mx = (float)mxd;
+                g.my = (float)myd;
+                g.A = (float)(s11 / det);
+                g.B = (float)(-s01 / det);
+                g.C = (float)(s00 / det);
+                g.o = o;
+                g.z = z;
+            }
+        }
+    }
+    if (!cnt) b = make_int4(0, 0, -1, -1);
+    rec[i] = g;
+    box[i] = b;
+    count[i] = cnt;
+}
+
+// total = the scan's last element (0 without Gaussians), into the workspace and, when given, the caller's int64
+__global__ void k_splat_total(const long long *__restrict__ offs, long long n, long long *total, long long *n_isect)
+{
+    const long long t = n > 0 ? offs[n - 1] : 0;
+    *total = t;
+    if (n_isect) *n_isect = t;
+}
+
+__global__ __launch_bounds__(256) void k_splat_emit(const SplatRec *__restrict__ rec, const int4 *__restrict__ box,
+                                                    const long long *__restrict__ offs, long long n, int tiles_x,
+                                                    long long n_tiles, const long long *total_p, long long capacity,
+                                                    unsigned long long *__restrict__ keys, int *__restrict__ vals, int *status)
+{
+    const long long total = *total_p;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (total > capacity) {
+        if (gid == 0 && status) *status = 1;
+        return;
+    }
+    if (gid < n) {
+        const int4 b = box[gid];
+        long long k = offs[gid] - (long long)(b.z - b.x + 1) * (b.w - b.y + 1);
+        if (b.z >= b.x) {
+            const unsigned long long zb = __float_as_uint(rec[gid].z);
+            for (int ty = b.y; ty <= b.w; ++ty)
+                for (int tx = b.x; tx <= b.z; ++tx, ++k) {
+                    keys[k] = ((unsigned long long)(ty * tiles_x + tx) << 32) | zb;
+                    vals[k] = (int)gid;
+                }
+        }
+    }
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long k = total + gid; k < capacity; k += stride) {
+        keys[k] = (unsigned long long)n_tiles << 32;
+        vals[k] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_splat_ranges(const unsigned long long *__restrict__ keys, const long long *total_p,
+                                                      long long capacity, longlong2 *__restrict__ ranges)
+{
+    const long long total = *total_p;
+    if (total > capacity) return;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long tile = (long long)(keys[i] >> 32);
+    const long long prev = i > 0 ? (long long)(keys[i - 1] >> 32) : -1;
+    if (tile != prev) {
+        ranges[tile].x = i;
+        if (prev >= 0) ranges[prev].y = i;
+    }
+    if (i == total - 1) ranges[tile].y = total;
+}
+
+template <int DT>
+__global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
+    const SplatRec *__restrict__ rec, const int *__restrict__ vals, const longlong2 *__restrict__ ranges,
+    const long long *total_p, long long capacity, const float *__restrict__ feats, int D, long long stride, int W, int H,
+    int *__restrict__ labels, float *__restrict__ confidence, float *__restrict__ alpha_out, float *__restrict__ logits)
+{
+    constexpr int NB = splat_batch(DT);
+    __shared__ float4 s_ga[NB];              // mx, my, A, B
+    __shared__ float2 s_gb[NB];              // C, o
+    __shared__ int s_id[NB];
+    __shared__ float s_f[NB * DT];            // feature rows, zero past D
+    if (*total_p > capacity) return;
+    const int tid = threadIdx.x;
+    const int px = blockIdx.x * SPLAT_TILE + (tid & (SPLAT_TILE - 1)), py = blockIdx.y * SPLAT_TILE + tid / SPLAT_TILE;
+    const bool inside = px < W && py < H;
+    const float sx = px + 0.5f, sy = py + 0.5f;
+    const longlong2 rg = ranges[(long long)blockIdx.y * gridDim.x + blockIdx.x];
+    float acc[DT];
+#pragma unroll
+    for (int c = 0; c < DT; ++c) acc[c] = 0.0f;
+    float T = 1.0f;
+    bool done = !inside;
+    for (long long b0 = rg.x; b0 < rg.y; b0 += NB) {
+        if (__syncthreads_count(done) == SPLAT_THREADS) break;      // also keeps the LDS of the last batch until all read it
+        const int nb = (int)(rg.y - b0 < NB ? rg.y - b0 : NB);
+        for (int k = tid; k < nb; k += SPLAT_THREADS) {
+            const int g = vals[b0 + k];
+            const SplatRec r = rec[g];
+            s_id[k] = g;
+            s_ga[k] = make_float4(r.mx, r.my, r.A, r.B);
+            s_gb[k] = make_float2(r.C, r.o);
+        }
+        __syncthreads();
+        for (int e = tid; e < nb * DT; e += SPLAT_THREADS) {
+            const int k = e / DT, c = e % DT;
+            s_f[e] = c < D ? feats[(long long)s_id[k] * stride + c] : 0.0f;
+        }
+        __syncthreads();
+        if (!done) {
+            for (int k = 0; k < nb; ++k) {
+                const float4 ga = s_ga[k];
+                const float2 gb = s_gb[k];
+                const float dx = ga.x - sx, dy = ga.y - sy;
+                const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
+                if (sigma < 0.0f) continue;
+                const float a = fminf(0.999f, gb.y * __expf(-sigma));
+                if (a < 1.0f / 255.0f) continue;
+                const float Tn = T * (1.0f - a);
+                if (Tn <= 1e-4f) {
+                    done = true;
+                    break;
+                }
+                const float wgt = a * T;
+                const float *f = s_f + k * DT;
+#pragma unroll
+                for (int c = 0; c < DT; ++c) acc[c] = fmaf(f[c], wgt, acc[c]);
+                T = Tn;
+            }
+        }
+    }
+    if (!inside) return;
+    const long long pix = (long long)py * W + px, hw = (long long)H * W;
+    float m1 = acc[0];
+    int lab = 0;
+#pragma unroll
+    for (int c = 1; c < DT; ++c)
+        if (c < D && acc[c] > m1) {
+            m1 = acc[c];
+            lab = c;
+        }
+    labels[pix] = lab;
+    if (confidence) {
+        float m2 = -INFINITY, s = 0.0f;
+#pragma unroll
+        for (int c = 0; c < DT; ++c)
+            if (c < D) {
+                if (c != lab && acc[c] > m2) m2 = acc[c];
+                s += expf(acc[c] - m1);
+            }
+        confidence[pix] = D == 1 ? 1.0f : (1.0f - expf(m2 - m1)) / s;
+    }
+    if (alpha_out) alpha_out[pix] = 1.0f - T;
+    if (logits) {
+#pragma unroll
+        for (int c = 0; c < DT; ++c)
+            if (c < D) logits[c * hw + pix] = acc[c];
+    }
+}
+
+// workspace layout of one (N, W, H, capacity); the part before `keys0` does not depend on the capacity
+struct SplatLayout {
+    size_t total, rec, box, count, offs, scan_tmp, keys0, keys1, vals0, vals1, sort_tmp, ranges, bytes;
+    size_t scan_bytes, sort_bytes;
+    int tiles_x, tiles_y, end_bit;
+};
+
+inline int splat_bits(long long v)
+{
+    int b = 0;
+    while (b < 63 && (1LL << b) <= v) ++b;
+    return b;
+}
+
+// host only: the rocprim calls with a NULL scratch pointer only report their scratch sizes
+inline bool splat_layout(long long n, int W, int H, long long capacity, SplatLayout &l)
+{
+    l.tiles_x = (W + SPLAT_TILE - 1) / SPLAT_TILE;
+    l.tiles_y = (H + SPLAT_TILE - 1) / SPLAT_TILE;
+    const long long n_tiles = (long long)l.tiles_x * l.tiles_y;
+    l.end_bit = 32 + splat_bits(n_tiles);                 // the padding key n_tiles << 32 needs the bit of n_tiles too
+    l.scan_bytes = 0;
+    l.sort_bytes = 0;
+    if (n > 0 && rocprim::inclusive_scan(nullptr, l.scan_bytes, (const int *)nullptr, (long long *)nullptr, (size_t)n,
+                                         rocprim::plus<long long>()) != hipSuccess)
+        return false;
+    if (capacity > 0 &&
+        rocprim::radix_sort_pairs(nullptr, l.sort_bytes, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                  (const int *)nullptr, (int *)nullptr, (size_t)capacity, 0u, (unsigned)l.end_bit) != hipSuccess)
+        return false;
+    size_t off = 0;
+    l.total = off;    off += align256(sizeof(long long));
+    l.rec = off;      off += align256((size_t)n * sizeof(SplatRec));
+    l.box = off;      off += align256((size_t)n * sizeof(int4));
+    l.count = off;    off += align256((size_t)n * sizeof(int));
+    l.offs = off;     off += align256((size_t)n * sizeof(long long));
+    l.scan_tmp = off; off += align256(l.scan_bytes);
+    l.keys0 = off;    off += align256((size_t)capacity * sizeof(unsigned long long));
+    l.keys1 = off;    off += align256((size_t)capacity * sizeof(unsigned long long));
+    l.vals0 = off;    off += align256((size_t)capacity * sizeof(int));
+    l.vals1 = off;    off += align256((size_t)capacity * sizeof(int));
+    l.sort_tmp = off; off += align256(l.sort_bytes);
+    l.ranges = off;   off += align256((size_t)n_tiles * sizeof(longlong2));
+    l.bytes = off;
+    return true;
+}
+
+}  // namespace

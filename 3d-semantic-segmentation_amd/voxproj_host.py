@@ -3,6 +3,7 @@
 PyTorch is used only for device memory and streams.  There is NO CPU fallback: if the HIP library is
 missing or no GPU is visible, the product entry points raise.
 """
+import collections
 import ctypes
 import os
 import subprocess
@@ -52,6 +53,7 @@ EXPORTS = [
     "vp_upsample_workspace_bytes", "vp_upsample_features", "vp_voxel_coords", "vp_scatter_occupancy",
     "vp_aggregate_view_f16", "vp_workspace_create", "vp_workspace_set_option",
     "vp_first_hit_ids", "vp_render_features", "vp_query_workspace_bytes", "vp_query_features",
+    "vp_splat_workspace_bytes", "vp_splat_project", "vp_splat_rasterize",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -173,6 +175,14 @@ def lib():
             L.vp_query_features.restype = ctypes.c_int
             L.vp_query_features.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int,
                                             ctypes.c_float, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+            L.vp_splat_workspace_bytes.restype = ctypes.c_size_t
+            L.vp_splat_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64]
+            L.vp_splat_project.restype = ctypes.c_int
+            L.vp_splat_project.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
+                [ctypes.c_int] * 2 + [ctypes.c_float] * 3 + [vp, vp, vp, ctypes.c_size_t, vp]
+            L.vp_splat_rasterize.restype = ctypes.c_int
+            L.vp_splat_rasterize.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
             if L.vp_abi_version() != VP_ABI_VERSION:
                 raise VoxprojError(f"{LIB_PATH} has ABI version {L.vp_abi_version()}, this package needs {VP_ABI_VERSION}: rebuild it")
             _lib = L
@@ -527,6 +537,144 @@ def query_features(rows, text, scale=1.0, want_logits=True, want_margin=True, ch
         if n_bad:
             raise VoxprojError(f"query_features: {n_bad} row(s) hold a non-finite element (label -1, NaN logits)")
     return labels, logits, margin
+
+
+SplatResult = collections.namedtuple("SplatResult", "labels confidence alpha logits n_isect n_nonfinite")
+
+
+class SplatWorkspace:
+    """Grow-only device scratch of the Gaussian splatting calls (vp_splat_*), allocated through torch's allocator.  Unlike
+    Workspace it is not announced to the library: the splatting calls keep no state with the buffer."""
+
+    def __init__(self):
+        self.buf = None
+
+    def ensure(self, nbytes, device, keep=0):
+        """A 256-byte aligned pointer to at least ``nbytes``; when the buffer grows, its first ``keep`` bytes are copied."""
+        import torch
+        if self.buf is None or self.buf.device != device or self.capacity() < nbytes:
+            old = self.buf
+            self.buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
+            if keep and old is not None and old.device == device:
+                o = (old.data_ptr() + 255) & ~255
+                self.buf[self.ptr() - self.buf.data_ptr():][:keep].copy_(old[o - old.data_ptr():][:keep])
+        return self.ptr()
+
+    def ptr(self):
+        return (self.buf.data_ptr() + 255) & ~255
+
+    def capacity(self):
+        return 0 if self.buf is None else self.buf.numel() - (self.ptr() - self.buf.data_ptr())
+
+
+def _splat_camera(viewmat, K, W, H):
+    import torch
+    vm = torch.as_tensor(viewmat, dtype=torch.float64).detach().cpu().reshape(-1)
+    k = torch.as_tensor(K, dtype=torch.float64).detach().cpu()
+    _require(vm.numel() == 16, "viewmat must be a [4, 4] world-to-camera matrix")
+    _require(tuple(k.shape) == (3, 3), "K must be [3, 3]")
+    _require(1 <= int(W) <= 32768 and 1 <= int(H) <= 32768, f"image size {W} x {H} outside [1, 32768]")
+    return (ctypes.c_float * 16)(*vm.tolist()), [float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])]
+
+
+def splat_project(means, quats, scales, opacities, viewmat, K, W, H, *, near=0.01, far=1e10, eps2d=0.3, workspace=None,
+                  n_nonfinite=None):
+    """vp_splat_project: screen-space records of every Gaussian into ``workspace`` (a SplatWorkspace; grown to the
+    projection's size).  Returns the device int64 [1] intersection count (not read here).  ``n_nonfinite``: optional device
+    int32 [1] that counts the Gaussians culled for a non-finite parameter."""
+    import torch
+    _require_tensors(*((t, name, (torch.float32,)) for t, name in
+                       ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
+    N = int(means.shape[0]) if means.dim() == 2 else -1
+    _require(tuple(means.shape) == (N, 3) and N >= 0, "means must be [N, 3]")
+    _require(tuple(quats.shape) == (N, 4), f"quats must be [{N}, 4]")
+    _require(tuple(scales.shape) == (N, 3), f"scales must be [{N}, 3]")
+    _require(tuple(opacities.shape) == (N,), f"opacities must be [{N}]")
+    dev = means.device
+    _require(all(t.device == dev for t in (quats, scales, opacities)), "the Gaussian tensors must be on one device")
+    vm, (fx, fy, cx, cy) = _splat_camera(viewmat, K, W, H)
+    means, quats, scales, opacities = (t.contiguous() for t in (means, quats, scales, opacities))
+    ws = workspace if workspace is not None else SplatWorkspace()
+    L = lib()
+    nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), 0))
+    _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}")
+    ptr = ws.ensure(nbytes, dev)
+    n_isect = torch.zeros(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_splat_project(means.data_ptr(), quats.data_ptr(), scales.data_ptr(), opacities.data_ptr(), N, vm,
+                                     fx, fy, cx, cy, int(W), int(H), float(near), float(far), float(eps2d), n_isect.data_ptr(),
+                                     n_nonfinite.data_ptr() if n_nonfinite is not None else None, ptr, ws.capacity(),
+                                     stream.cuda_stream))
+    return n_isect
+
+
+def splat_rasterize(features, n_gaussians, W, H, capacity, workspace, *, want_logits=False, want_alpha=False,
+                    want_confidence=True, status=None):
+    """vp_splat_rasterize after splat_project on ``workspace``: sort ``capacity`` intersection keys, blend, epilogue.  The
+    workspace grows to ``capacity`` (the projection's bytes kept).  Returns (labels int32 [H,W], confidence f32 [H,W] or None,
+    alpha f32 [H,W] or None, logits f32 [D,H,W] or None).  ``status``: optional device int32 [1], set to 1 when the device
+    count exceeds ``capacity`` (then no output is written)."""
+    import torch
+    _require_tensors((features, "features", (torch.float32,)))
+    _require(features.dim() == 2 and int(features.shape[0]) == int(n_gaussians), f"features must be [{n_gaussians}, D]")
+    D = int(features.shape[1])
+    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
+    if features.stride(1) != 1 or features.stride(0) < D:
+        features = features.contiguous()
+    dev = features.device
+    L = lib()
+    keep = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), 0))
+    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
+    ptr = workspace.ensure(nbytes, dev, keep=keep)
+    labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+    conf = torch.empty((H, W), dtype=torch.float32, device=dev) if want_confidence else None
+    alpha = torch.empty((H, W), dtype=torch.float32, device=dev) if want_alpha else None
+    logits = torch.empty((D, H, W), dtype=torch.float32, device=dev) if want_logits else None
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_splat_rasterize(features.data_ptr(), D, max(int(features.stride(0)), D), int(n_gaussians), int(W), int(H),
+                                       int(capacity), labels.data_ptr(), p(conf), p(alpha), p(logits), p(status), ptr,
+                                       workspace.capacity(), stream.cuda_stream))
+    return labels, conf, alpha, logits
+
+
+def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, *, want_logits=False, want_alpha=False,
+                   want_confidence=True, near=0.01, far=1e10, eps2d=0.3, workspace=None, check=True):
+    """Splat D-channel per-Gaussian features into one W x H view (vp_splat_project + vp_splat_rasterize; the contract is in
+    include/voxproj.h).  means f32 [N,3], quats f32 [N,4] (w, x, y, z; normalised here), scales f32 [N,3] and opacities f32
+    [N] (both activated), features f32 [N,D] (D <= 64, any row stride), all on one GPU; viewmat [4,4] world-to-camera and K
+    [3,3] (any device; read on the host).  Reads the 8-byte intersection count once to size the workspace (a SplatWorkspace,
+    kept and regrown across calls when given).  Returns SplatResult(labels int32 [H,W], confidence f32 [H,W] or None, alpha
+    f32 [H,W] or None, logits f32 [D,H,W] or None, n_isect int, n_nonfinite device int32 [1]).  With ``check`` the call
+    synchronises once more and raises VoxprojError when a Gaussian had a non-finite parameter (it is culled)."""
+    import torch
+    for t, name in ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"), (features, "features")):
+        _require(isinstance(t, torch.Tensor) and t.dtype == torch.float32, f"{name} must be a torch.float32 tensor")
+    _require(features.dim() == 2 and features.shape[0] == means.shape[0],
+             "features must be [N, D] with one row per Gaussian")
+    _require(1 <= int(features.shape[1]) <= 64, f"D = {int(features.shape[1])} outside [1, 64]")
+    _require_tensors(*((t, name, (torch.float32,)) for t, name in
+                       ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"), (features, "features"))))
+    _require(features.device == means.device, "features and the Gaussians must be on one device")
+    ws = workspace if workspace is not None else SplatWorkspace()
+    bad = torch.zeros(1, dtype=torch.int32, device=means.device)
+    status = torch.zeros(1, dtype=torch.int32, device=means.device)
+    n_isect = splat_project(means, quats, scales, opacities, viewmat, K, W, H, near=near, far=far, eps2d=eps2d,
+                            workspace=ws, n_nonfinite=bad)
+    cap = int(n_isect.item())
+    _require(cap <= 2 ** 31 - 1, f"{cap} tile intersections: more than 2^31 - 1")
+    labels, conf, alpha, logits = splat_rasterize(features, int(means.shape[0]), W, H, cap, ws, want_logits=want_logits,
+                                                  want_alpha=want_alpha, want_confidence=want_confidence, status=status)
+    if check:
+        st, n_bad = (int(v) for v in torch.cat([status, bad]).tolist())
+        if st:
+            raise VoxprojError("splat_features: the intersection count outgrew the workspace (no image written)")
+        if n_bad:
+            raise VoxprojError(f"splat_features: {n_bad} Gaussian(s) have a non-finite parameter (culled)")
+    return SplatResult(labels, conf, alpha, logits, cap, bad)
 
 
 _check_rc = check

@@ -407,6 +407,58 @@ int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, 
                       int P, float scale, float *logits, int32_t *labels, float *margin, int32_t *n_nonfinite,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Gaussian splatting of per-Gaussian features (the reference's stage 5.2, voxel_to_gaussian/render_semantics_logits.py,
+ * which calls gsplat's rasterization() in classic mode without a background).  Forward only.  Added after VP_ABI_VERSION 4
+ * without changing it or any existing entry point: callers detect the three functions by symbol (dlsym).
+ *
+ * Per Gaussian: mean mu (world), quaternion q = (w, x, y, z) (normalised here; |q| = 0 culls), scale s (activated), opacity
+ * o (activated), feature row f of D channels.  Camera: world-to-camera [R | t] (COLMAP: x right, y down, z forward), fx, fy,
+ * cx, cy, W x H.  z = ((r20 mx + r21 my) + r22 mz) + t2 in fp32 (no FMA); culled when z < near or z > far.
+ * Sigma2 = J R Sigma R^T J^T + eps2d I with Sigma = M M^T, M = R(q) diag(s) and gsplat's Jacobian clamp
+ * (tx = z clamp(px/z, -(cx/fx + 0.15 W/fx), (W - cx)/fx + 0.15 W/fx), likewise y); culled when det(Sigma2) <= 0.
+ * mean2d = (fx px/z + cx, fy py/z + cy).  Pixel (j, i) samples (j + 0.5, i + 0.5); Gaussians in ascending (fp32 z, index):
+ * sigma = (A dx^2 + C dy^2)/2 + B dx dy with (A, B, C) = Sigma2^-1 and d = mean2d - sample, skipped when sigma < 0;
+ * a = min(0.999, o exp(-sigma)), skipped when a < 1/255; Tn = T (1 - a); when Tn <= 1e-4 the pixel stops (that Gaussian
+ * is not added); else out += f a T, T = Tn.  alpha = 1 - T; no background.  Every (Gaussian, pixel) pair with a >= 1/255 is
+ * visited: a Gaussian's tiles cover the box |dx| <= sqrt(2 ln(255 o) Sigma2_00), |dy| <= sqrt(2 ln(255 o) Sigma2_11) widened
+ * by one pixel.  Epilogue: label = argmax over the D channels (lowest index on ties; 0 where nothing reaches), confidence =
+ * softmax top-1 minus top-2 (1 when D = 1).  The projection runs in float64 past the fp32 depth; the blend in fp32 with no
+ * atomics: results are bit-identical from run to run.
+ *
+ * vp_splat_workspace_bytes: bytes of the caller's scratch for n_gaussians Gaussians, a W x H image and room for `capacity`
+ *   (tile, Gaussian) intersections; 0 when n_gaussians or capacity is outside [0, 2^31 - 1] or W, H outside [1, 32768],
+ *   and 0 without a usable GPU (rocPRIM sizes its scratch for the current device's architecture).
+ *   vp_splat_project needs the size at capacity 0, which is a prefix of every larger capacity's layout: a workspace can be
+ *   regrown between the two calls by copying those bytes.
+ *
+ * vp_splat_project: means f32 [n,3], quats f32 [n,4], scales f32 [n,3], opacities f32 [n], device, contiguous; viewmat f32
+ *   [4,4] row-major, HOST memory (rows 0-2 read during the call).  Writes the screen-space records and the number of
+ *   intersections into the workspace and, when not NULL, into *n_isect (device i64).  A non-finite mean, quaternion, scale
+ *   or opacity culls that Gaussian and adds 1 to *n_nonfinite (device i32, may be NULL; not reset by the call).
+ *
+ * vp_splat_rasterize: after vp_splat_project on the same workspace, stream, n_gaussians, W and H.  features f32, row g at
+ *   features + g * row_stride (row_stride >= D, unit channel stride), D in [1, 64].  Sorts `capacity` keys
+ *   (rocprim::radix_sort_pairs; pass the project call's count for no wasted work), then blends one 16x16 tile per
+ *   workgroup.  Writes labels i32 [H,W] and, each only when not NULL, confidence f32 [H,W], alpha f32 [H,W] and logits f32
+ *   planar [D,H,W].  When the device count exceeds `capacity` nothing is written to any output and *status (device i32, may
+ *   be NULL; not reset by the call) is set to 1.
+ *
+ * Both: 64-bit offsets; no allocation, no host synchronisation: asynchronous on `stream`; workspace 256-byte aligned, not
+ * shared with a call still running on another stream.  Refused on the host (VP_EINVAL): n_gaussians outside [0, 2^31 - 1],
+ * null pointers (the Gaussian arrays / features when n_gaussians > 0, viewmat, labels), W or H outside [1, 32768], a
+ * non-finite viewmat, fx, fy <= 0, near <= 0 or far <= near, eps2d < 0, D outside [1, 64], row_stride < D, capacity outside
+ * [0, 2^31 - 1]; VP_EWORKSPACE: a workspace that is NULL, smaller than vp_splat_workspace_bytes or not 256-byte aligned.
+ */
+size_t vp_splat_workspace_bytes(int64_t n_gaussians, int W, int H, int64_t capacity);
+int vp_splat_project(const float *means, const float *quats, const float *scales, const float *opacities,
+                     int64_t n_gaussians, const float *viewmat, float fx, float fy, float cx, float cy, int W, int H,
+                     float near_plane, float far_plane, float eps2d, int64_t *n_isect, int32_t *n_nonfinite,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H,
+                       int64_t capacity, int32_t *labels, float *confidence, float *alpha, float *logits,
+                       int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

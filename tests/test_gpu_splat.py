@@ -1,0 +1,293 @@
+"""Gaussian splatting (vp_splat_project / vp_splat_rasterize, voxproj_host.splat_features, render_semantics_logits.py) on the
+GPU against the float64 contract of tests/splat_reference.py.
+
+Bounds, on the pixels the oracle does not mark fragile (no decision within a relative 1e-5 of its threshold, no top-1 /
+top-2 gap within 2B):
+  logits     |out - out64| <= B = 1e-4 * max_g |f_g| + 1e-6.  A logit is sum_g f_g w_g with sum_g w_g <= 1; the kernel's
+             weights differ from float64 by the fp32 rounding of mean2d / conic (shared with the oracle, which rounds them
+             the same way), of sigma, exp and the running product T: a few 1e-6 relative at most, more than 10x inside B.
+  alpha      |alpha - alpha64| <= 1e-5 (the same weights, f = 1).
+  labels     exact.
+  confidence |conf - conf64| <= 2B + 1e-6 (softmax top-1 minus top-2 moves by at most twice the largest logit change).
+Every comparison also asserts a minimum count of non-fragile pixels that some Gaussian reaches, so it cannot pass vacuously.
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (HERE, ROOT, os.path.join(ROOT, "3d-semantic-segmentation_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import splat_reference as ref  # noqa: E402
+import voxproj_host  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+
+def rot(yaw, pitch):
+    cy, sy, cp, sp = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch)
+    return np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) @ np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
+
+
+def camera(W, H, yaw=0.05, pitch=-0.03, t=(0.02, -0.01, 0.1), f=0.9):
+    vm = np.eye(4)
+    vm[:3, :3] = rot(yaw, pitch)
+    vm[:3, 3] = t
+    K = np.array([[f * W, 0, 0.5 * W + 0.3], [0, f * W, 0.5 * H - 0.2], [0, 0, 1]])
+    return vm.astype(np.float32), K.astype(np.float32)
+
+
+def scene(n, D, seed, z=(1.0, 4.0), spread=1.2, scale=0.05, op_lo=0.3):
+    rng = np.random.default_rng(seed)
+    means = np.stack([rng.uniform(-spread, spread, n), rng.uniform(-0.8 * spread, 0.8 * spread, n), rng.uniform(*z, n)], 1)
+    q = rng.normal(size=(n, 4))
+    scales = scale * np.exp(rng.normal(0, 0.6, size=(n, 3)))
+    op = np.where(rng.uniform(size=n) < 0.2, rng.uniform(0.001, 0.05, n), rng.uniform(op_lo, 0.99, n))
+    feats = rng.normal(0, 1, size=(n, D))
+    return dict(means=means.astype(np.float32), quats=q.astype(np.float32), scales=scales.astype(np.float32),
+                opacities=op.astype(np.float32), features=feats.astype(np.float32))
+
+
+def dev(s):
+    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(DEV) for k, v in s.items()}
+
+
+def run(s, vm, K, W, H, feats=None, **kw):
+    t = dev(s)
+    kw.setdefault("want_logits", True)
+    kw.setdefault("want_alpha", True)
+    kw.setdefault("check", False)
+    return voxproj_host.splat_features(t["means"], t["quats"], t["scales"], t["opacities"],
+                                       feats if feats is not None else t["features"], vm, K, W, H, **kw)
+
+
+def compare(s, vm, K, W, H, r, min_good_frac=0.8, min_reached=1, **kw):
+    B = ref.value_bound(s["features"])
+    o = ref.splat64(s["means"], s["quats"], s["scales"], s["opacities"], s["features"], vm, K, W, H, value_tol=2 * B, **kw)
+    good = ~o["fragile"]
+    reached = good & (o["visits"] > 0)
+    assert good.sum() >= min_good_frac * W * H, f"only {good.sum()} of {W * H} pixels are not fragile"
+    assert reached.sum() >= min_reached, f"only {reached.sum()} non-fragile pixels are reached by a Gaussian"
+    lab = r.labels.cpu().numpy()
+    assert np.array_equal(lab[good], o["label"][good]), f"{(lab[good] != o['label'][good]).sum()} labels differ"
+    if r.logits is not None:
+        err = np.abs(r.logits.cpu().numpy().astype(np.float64) - o["logits"])[:, good]
+        assert err.size == 0 or err.max() <= B, f"logit error {err.max():.3e} > {B:.3e}"
+    if r.alpha is not None:
+        ea = np.abs(r.alpha.cpu().numpy() - o["alpha"])[good]
+        assert ea.max() <= 1e-5, f"alpha error {ea.max():.3e}"
+    if r.confidence is not None:
+        ec = np.abs(r.confidence.cpu().numpy() - o["confidence"])[good]
+        assert ec.max() <= 2 * B + 1e-6, f"confidence error {ec.max():.3e}"
+    return o, good
+
+
+@pytest.mark.parametrize("D", [1, 3, 13, 32, 33, 64])
+@pytest.mark.parametrize("seed", [0, 1])
+def test_random_scenes(D, seed):
+    W, H = 61, 47
+    s = scene(400, D, seed)
+    vm, K = camera(W, H)
+    r = run(s, vm, K, W, H)
+    compare(s, vm, K, W, H, r, min_reached=W * H // 3)
+
+
+def test_larger_image_and_seed():
+    W, H = 203, 133
+    s = scene(3000, 13, 7, scale=0.03)
+    vm, K = camera(W, H, yaw=-0.1, pitch=0.05)
+    r = run(s, vm, K, W, H)
+    compare(s, vm, K, W, H, r, min_reached=W * H // 3)
+
+
+def test_row_stride_above_d():
+    W, H = 61, 47
+    s = scene(300, 13, 3)
+    vm, K = camera(W, H)
+    wide = torch.zeros((300, 20), device=DEV)
+    wide[:, :13] = torch.from_numpy(s["features"]).to(DEV)
+    wide[:, 13:] = float("nan")                      # never read
+    r = run(s, vm, K, W, H, feats=wide[:, :13])
+    assert r.logits.isfinite().all()
+    compare(s, vm, K, W, H, r, min_reached=W * H // 3)
+
+
+def test_tile_with_more_gaussians_than_one_batch():
+    # 3000 faint Gaussians over the same 16x16 tile: T stays above 1e-4 for many more than 256 of them
+    W, H = 32, 32
+    rng = np.random.default_rng(11)
+    n = 3000
+    s = scene(n, 32, 11)
+    s["means"] = np.stack([rng.uniform(-0.2, 0.2, n), rng.uniform(-0.2, 0.2, n), rng.uniform(1.5, 3.0, n)], 1).astype(np.float32)
+    s["scales"] = np.full((n, 3), 0.3, np.float32)
+    s["opacities"] = rng.uniform(0.01, 0.03, n).astype(np.float32)
+    vm, K = np.eye(4, dtype=np.float32), np.array([[30, 0, 16], [0, 30, 16], [0, 0, 1]], np.float32)
+    r = run(s, vm, K, W, H)
+    o, good = compare(s, vm, K, W, H, r, min_good_frac=0.5, min_reached=W * H // 2)
+    assert o["visits"][good].max() > 2 * 256, "the scene should have pixels with more than two batches of Gaussians"
+
+
+def test_one_gaussian_covering_the_image():
+    W, H = 70, 45
+    s = dict(means=np.array([[0.0, 0.0, 2.0]], np.float32), quats=np.array([[1, 0, 0, 0]], np.float32),
+             scales=np.array([[3.0, 2.0, 0.1]], np.float32), opacities=np.array([0.8], np.float32),
+             features=np.array([[0.5, -1.0, 2.0, 0.25]], np.float32))
+    vm, K = np.eye(4, dtype=np.float32), np.array([[40, 0, 35], [0, 40, 22.5], [0, 0, 1]], np.float32)
+    r = run(s, vm, K, W, H)
+    o, good = compare(s, vm, K, W, H, r, min_good_frac=0.95, min_reached=W * H * 9 // 10)
+    assert r.n_isect == ((W + 15) // 16) * ((H + 15) // 16)
+
+
+def test_near_plane_and_off_screen():
+    W, H = 61, 47
+    s = scene(600, 8, 5, z=(-0.5, 3.0), spread=3.0)
+    vm, K = camera(W, H, t=(0, 0, 0))
+    r = run(s, vm, K, W, H)
+    o, _ = compare(s, vm, K, W, H, r, min_reached=W * H // 4)
+    z = ref.depth32(s["means"], vm)
+    assert (z < 0.01).sum() > 50 and ((z > 0.01) & (z < 0.3)).sum() > 5
+
+
+def test_zero_scale_gaussians():
+    W, H = 61, 47
+    s = scene(500, 5, 9)
+    s["scales"][::2] = 0.0
+    s["opacities"][:] = np.maximum(s["opacities"], 0.5)
+    vm, K = camera(W, H)
+    r = run(s, vm, K, W, H)
+    o, _ = compare(s, vm, K, W, H, r, min_reached=W * H // 5)
+    assert r.n_isect > 0
+
+
+def test_zero_and_all_culled():
+    W, H = 40, 33
+    empty = dict(means=np.zeros((0, 3), np.float32), quats=np.zeros((0, 4), np.float32), scales=np.zeros((0, 3), np.float32),
+                 opacities=np.zeros(0, np.float32), features=np.zeros((0, 6), np.float32))
+    vm, K = camera(W, H)
+    for s in (empty, dict(scene(200, 6, 2), means=np.tile(np.float32([[0, 0, -2.0]]), (200, 1)))):
+        r = run(s, vm, K, W, H)
+        assert r.n_isect == 0
+        assert (r.labels == 0).all() and (r.logits == 0).all() and (r.alpha == 0).all() and (r.confidence == 0).all()
+
+
+def test_nonfinite_parameter_culled_and_counted():
+    W, H = 61, 47
+    s = scene(300, 6, 4)
+    s["means"][3, 1] = np.nan
+    s["scales"][10, 0] = np.inf
+    s["opacities"][20] = np.nan
+    vm, K = camera(W, H)
+    r = run(s, vm, K, W, H)
+    assert int(r.n_nonfinite.item()) == 3
+    compare(s, vm, K, W, H, r, min_reached=W * H // 3)
+    with pytest.raises(voxproj_host.VoxprojError, match="non-finite"):
+        run(s, vm, K, W, H, check=True)
+
+
+def test_bit_identical_runs():
+    W, H = 90, 70
+    s = scene(4000, 32, 6, scale=0.04)
+    vm, K = camera(W, H)
+    a = run(s, vm, K, W, H)
+    b = run(s, vm, K, W, H)
+    for x, y in ((a.labels, b.labels), (a.logits, b.logits), (a.alpha, b.alpha), (a.confidence, b.confidence)):
+        assert x.cpu().numpy().tobytes() == y.cpu().numpy().tobytes()
+
+
+def test_labels_only_matches_full_call():
+    W, H = 77, 51
+    s = scene(1500, 13, 8)
+    vm, K = camera(W, H)
+    full = run(s, vm, K, W, H)
+    lean = run(s, vm, K, W, H, want_logits=False, want_alpha=False)
+    assert lean.logits is None and lean.alpha is None
+    assert lean.labels.cpu().numpy().tobytes() == full.labels.cpu().numpy().tobytes()
+    assert lean.confidence.cpu().numpy().tobytes() == full.confidence.cpu().numpy().tobytes()
+    assert torch.equal(full.labels.long(), torch.argmax(full.logits, dim=0))
+
+
+def test_too_small_workspace_writes_nothing():
+    W, H = 61, 47
+    s = scene(400, 8, 1)
+    vm, K = camera(W, H)
+    t = dev(s)
+    ws = voxproj_host.SplatWorkspace()
+    n = voxproj_host.splat_project(t["means"], t["quats"], t["scales"], t["opacities"], vm, K, W, H, workspace=ws)
+    total = int(n.item())
+    assert total > 10
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    voxproj_host.splat_rasterize(t["features"], 400, W, H, total - 1, ws, want_logits=True, want_alpha=True,
+                                 want_confidence=True, status=status)
+    # the wrapper's outputs start as torch.empty: call the C-ABI again into a sentinel-filled label image
+    torch.cuda.synchronize()
+    assert int(status.item()) == 1
+    lab2 = torch.full((H, W), -7, dtype=torch.int32, device=DEV)
+    L = voxproj_host.lib()
+    nbytes = int(L.vp_splat_workspace_bytes(400, W, H, total - 1))
+    status.zero_()
+    voxproj_host.check(L.vp_splat_rasterize(t["features"].data_ptr(), 8, 8, 400, W, H, total - 1, lab2.data_ptr(), None, None,
+                                            None, status.data_ptr(), ws.ptr(), ws.capacity(), torch.cuda.current_stream().cuda_stream))
+    assert nbytes <= ws.capacity()
+    assert int(status.item()) == 1
+    assert (lab2 == -7).all(), "a too-small workspace must not write a partial image"
+    # the same workspace at the right capacity gives the full call's image
+    lab3, _, _, _ = voxproj_host.splat_rasterize(t["features"], 400, W, H, total, ws, status=status)
+    ref_run = run(s, vm, K, W, H)
+    assert torch.equal(lab3, ref_run.labels)
+    with pytest.raises(voxproj_host.VoxprojError):
+        voxproj_host.check(L.vp_splat_rasterize(t["features"].data_ptr(), 8, 8, 400, W, H, total, lab2.data_ptr(), None, None,
+                                                None, None, ws.ptr(), 1024, torch.cuda.current_stream().cuda_stream))
+
+
+def test_cli_end_to_end(tmp_path):
+    import render_semantics_logits as rsl
+    import synthetic_gaussians as sg
+    from gaussian_ply import read_gaussian_ply, write_gaussian_ply
+    from PIL import Image
+    from query_voxel_features import palette
+    g = sg.make_gaussians(4000, n_classes=13, seed=3, scale_median=0.05)
+    logits = sg.make_logits(g["classes"], 13, seed=3)
+    op, ls, q = sg.to_ply_fields(g)
+    ply = str(tmp_path / "point_cloud.ply")
+    write_gaussian_ply(ply, g["means"], op, ls, q)
+    np.savez(tmp_path / "g.npz", logits=logits, labels=logits.argmax(1).astype(np.int16), prompts=np.array([f"c{i}" for i in range(13)]))
+    w2c, K0 = sg.make_views(2, g["room"], 96, seed=3)
+    cam = str(tmp_path / "camera_params.json")
+    names = sg.write_camera_params(cam, w2c, K0, 96, 64)
+    out = tmp_path / "out"
+    rsl.main(["--gaussians_ply", ply, "--logit_path", str(tmp_path / "g.npz"), "--cam_params", cam, "--out_dir", str(out)])
+    gg = read_gaussian_ply(ply)
+    feats = rsl.pad_logits(logits)
+    for idx, name in enumerate(sorted(names)):
+        v = names.index(name)
+        vm, K = rsl.camera({"R": w2c[v][:3, :3], "tvec": w2c[v][:3, 3], "camera_id": 1},
+                           {"1": {"params": [K0[0, 0], K0[1, 1], K0[0, 2], K0[1, 2]]}}, 96, 64, 96, 64)
+        s = dict(gg, features=feats)
+        lab = torch.load(out / "labels" / f"{idx:05d}_labels.pt")["label_indices"]
+        assert lab.dtype == torch.uint8 and tuple(lab.shape) == (64, 96)
+        lg = np.load(out / "renders" / f"{idx:05d}_logits.npy")
+        assert lg.dtype == np.float32 and lg.shape == (32, 64, 96)
+        conf = np.load(out / "renders" / f"{idx:05d}_confidence.npy")
+        r = voxproj_host.SplatResult(lab.to(DEV).int(), torch.from_numpy(conf), None, torch.from_numpy(lg), 0, None)
+        compare(s, vm.astype(np.float32), K.astype(np.float32), 96, 64, r, min_good_frac=0.7, min_reached=96 * 64 // 3)
+        im = Image.open(out / "renders" / f"{idx:05d}_mask_color.png")
+        assert im.mode == "P" and np.array_equal(np.asarray(im), lab.numpy())
+        assert im.getpalette()[:39] == palette(13).reshape(-1).tolist()
+
+
+def test_workspace_bytes():
+    L = voxproj_host.lib()
+    a = L.vp_splat_workspace_bytes(1000, 64, 48, 0)
+    b = L.vp_splat_workspace_bytes(1000, 64, 48, 10000)
+    assert 0 < a < b and a % 256 == 0 and b % 256 == 0
+    assert b >= a + 10000 * 24                      # two key and two value buffers
+    assert L.vp_splat_workspace_bytes(0, 1, 1, 0) > 0
+    for args in ((-1, 64, 48, 0), (1000, 0, 48, 0), (1000, 64, 40000, 0), (1000, 64, 48, -1), (1 << 31, 64, 48, 0)):
+        assert L.vp_splat_workspace_bytes(*args) == 0

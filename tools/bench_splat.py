@@ -1,0 +1,101 @@
+"""Gaussian splatting of logits (vp_splat_project + vp_splat_rasterize) at the shapes of stage 5.2, one JSON line per leg:
+G in {200k (the reference's 195 120-Gaussian scene), 1M} Gaussians of synthetic_gaussians.make_gaussians, D in {13, 32}
+channels, 876x584 and 1600x1067 views from the synthetic trajectory, labels + confidence only or with the [D,H,W] logits.
+
+  ms_per_view     HIP events around --steps views (cycled over --views cameras) after --warmup: splat_features as the CLI
+                  calls it, the 8-byte count read included
+  project_ms      vp_splat_project alone (projection + rocprim scan of the tile counts), same event timing
+  raster_ms       vp_splat_rasterize alone (emit, rocprim radix sort, ranges, blend), same event timing
+  n_isect         mean (tile, Gaussian) intersections per view = keys sorted
+  isect_px_per_s  n_isect * 256 / raster_ms: the (Gaussian, pixel) pairs the blend may visit (an upper bound: pixels stop
+                  at T <= 1e-4), per second of the whole rasterize call
+  logits_GBs      D*H*W*4 bytes / raster_ms, when logits are written
+The per-kernel split (project / scan / emit / sort / ranges / blend) is in the rocprofv3 --kernel-trace --stats run of one
+leg committed under profiles/ (r08_splat_*).
+
+python tools/bench_splat.py [--steps K] [--warmup W] [--g 200000 1000000] [--d 13 32] [--size 876x584 1600x1067]
+[--logits off on] [--views V]"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "3d-semantic-segmentation_amd")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import synthetic_gaussians as sg  # noqa: E402
+import voxproj_host  # noqa: E402
+
+
+def timed(fn, steps, warmup):
+    for i in range(warmup):
+        fn(i)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(steps):
+        fn(i)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--g", type=int, nargs="+", default=[200000, 1000000])
+    ap.add_argument("--d", type=int, nargs="+", default=[13, 32])
+    ap.add_argument("--size", nargs="+", default=["876x584", "1600x1067"])
+    ap.add_argument("--logits", nargs="+", default=["off", "on"])
+    ap.add_argument("--views", type=int, default=8)
+    args = ap.parse_args(argv)
+    dev = torch.device("cuda:0")
+    for G in args.g:
+        g = sg.make_gaussians(G, seed=0)
+        t = {k: torch.from_numpy(g[k]).to(dev) for k in ("means", "quats", "scales", "opacities")}
+        lg32 = torch.from_numpy(sg.make_logits(g["classes"], 32, seed=0)).to(dev)
+        for size in args.size:
+            W, H = (int(v) for v in size.split("x"))
+            # the trajectory's later frames (the first ones are a close-up of one wall)
+            w2c, K = sg.make_views(args.views * 12, g["room"], W, seed=0)
+            w2c = w2c[::12]
+            for D in args.d:
+                feats = lg32[:, :D].contiguous() if D <= 32 else lg32
+                ws = voxproj_host.SplatWorkspace()
+                for lo in args.logits:
+                    want = lo == "on"
+                    counts = []
+
+                    def full(i):
+                        r = voxproj_host.splat_features(t["means"], t["quats"], t["scales"], t["opacities"], feats,
+                                                        w2c[i % len(w2c)], K, W, H, want_logits=want, workspace=ws,
+                                                        check=False)
+                        counts.append(r.n_isect)
+                    ms = timed(full, args.steps, args.warmup)
+                    caps = {}
+
+                    def proj(i):
+                        n = voxproj_host.splat_project(t["means"], t["quats"], t["scales"], t["opacities"],
+                                                       w2c[i % len(w2c)], K, W, H, workspace=ws)
+                        if i % len(w2c) not in caps:
+                            caps[i % len(w2c)] = int(n.item())
+                    proj_ms = timed(proj, len(w2c), 0)          # fills caps (one count read per camera, not timed below)
+                    proj_ms = timed(lambda i: voxproj_host.splat_project(t["means"], t["quats"], t["scales"], t["opacities"],
+                                                                          w2c[0], K, W, H, workspace=ws), args.steps, args.warmup)
+                    voxproj_host.splat_project(t["means"], t["quats"], t["scales"], t["opacities"], w2c[0], K, W, H, workspace=ws)
+                    raster_ms = timed(lambda i: voxproj_host.splat_rasterize(feats, G, W, H, caps[0], ws, want_logits=want),
+                                      args.steps, args.warmup)
+                    n_isect = float(np.mean(counts))
+                    res = dict(metric="splat_ms_per_view", G=G, D=D, W=W, H=H, logits=want, ms_per_view=round(ms, 4),
+                               project_ms=round(proj_ms, 4), raster_ms=round(raster_ms, 4),
+                               raster_view0_isect=caps[0], n_isect=int(n_isect),
+                               isect_px_per_s=round(caps[0] * 256 / (raster_ms * 1e-3), 1),
+                               logits_GBs=round(D * H * W * 4 / (raster_ms * 1e-3) / 1e9, 2) if want else None,
+                               views=len(w2c), steps=args.steps, warmup=args.warmup)
+                    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
