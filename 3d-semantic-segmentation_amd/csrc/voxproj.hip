@@ -741,6 +741,67 @@ int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t
     return VP_OK;
 }
 
+size_t vp_splat_backward_workspace_bytes(int64_t capacity, int D)
+{
+    if (capacity < 0 || capacity > INT32_MAX || D < 1 || D > SPLAT_MAX_D) return 0;
+    return splat_bwd_bytes(capacity, D);
+}
+
+int vp_splat_rasterize_backward(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H,
+                                int64_t capacity, const float *grad_logits, const float *grad_alpha, float *grad_features,
+                                float *grad_opacities, int32_t *status, void *workspace, size_t workspace_bytes,
+                                void *bwd_workspace, size_t bwd_bytes, void *stream_)
+{
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
+        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
+    if (n_gaussians > 0 && !features) return fail(VP_EINVAL, "null pointer argument (features)");
+    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
+    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
+    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    if (!bwd_workspace) return fail(VP_EWORKSPACE, "backward workspace is NULL");
+    if ((uintptr_t)bwd_workspace & 255) return fail(VP_EWORKSPACE, "backward workspace must be 256-byte aligned");
+    const size_t bwd_need = splat_bwd_bytes(capacity, D);
+    if (bwd_bytes < bwd_need)
+        return fail(VP_EWORKSPACE, "backward workspace has %zu bytes, need %zu", bwd_bytes, bwd_need);
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
+    if (n_gaussians == 0) return VP_OK;                  // no rows to write; nothing can exceed a capacity of 0 either
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    const long long *total = (const long long *)(ws + l.total);
+    const int *count = (const int *)(ws + l.count);
+    const long long *offs = (const long long *)(ws + l.offs);
+    float *part = (float *)bwd_workspace;
+    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+#define VP_SPLAT_BWD(DT) hipLaunchKernelGGL((k_splat_blend_backward<DT>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), \
+                                            (const int4 *)(ws + l.box), count, offs, (const int *)(ws + l.vals1),             \
+                                            (const longlong2 *)(ws + l.ranges), total, (long long)capacity, features, D,      \
+                                            (long long)row_stride, W, H, grad_logits, grad_alpha, part)
+    if (D <= 8) VP_SPLAT_BWD(8);
+    else if (D <= 16) VP_SPLAT_BWD(16);
+    else if (D <= 32) VP_SPLAT_BWD(32);
+    else VP_SPLAT_BWD(64);
+#undef VP_SPLAT_BWD
+    VP_HIP(hipGetLastError());
+    // grid-stride over the Gaussians, at most one resident round (2048 workgroups of 4 wavefronts: 32 per CU on 256 CUs)
+    const int gs = splat_reduce_group(D);
+    const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / gs - 1) / (256 / gs), 2048LL);
+#define VP_SPLAT_RED(GS) hipLaunchKernelGGL((k_splat_grad_reduce<GS>), dim3(g_red), dim3(256), 0, stream, count, offs, \
+                                            (long long)n_gaussians, total, (long long)capacity, (const float *)part, D,   \
+                                            grad_features, grad_opacities, (int *)status)
+    if (gs == 16) VP_SPLAT_RED(16);
+    else if (gs == 32) VP_SPLAT_RED(32);
+    else VP_SPLAT_RED(64);
+#undef VP_SPLAT_RED
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
 static int read_status(void *workspace, hipStream_t stream, int *st /* [2][ST_WORDS] */)
 {
     if (WsState *rec = ws_state(workspace, false)) {

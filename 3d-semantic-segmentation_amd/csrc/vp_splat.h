@@ -280,6 +280,255 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The backward (vp_splat_rasterize_backward): gradients of the logits and alpha with respect to the features f and the
+// activated opacities o, through the branch the forward took.  It reads what vp_splat_rasterize left in the workspace (rec,
+// box, count, offs, the sorted values, the tile ranges, the device total) and writes per-(tile, Gaussian) partials of D + 1
+// floats into its own scratch, at the Gaussian's emission slot for the tile:  slot = offs[g] - count[g] +
+// (ty - b.y)(b.z - b.x + 1) + (tx - b.x), the position k_splat_emit gave the pair.  Every slot of [0, total) is written
+// exactly once (a tile's run holds each of its pairs once): no zero fill, no second sort, no atomics.
+//
+// k_splat_blend_backward<DT>  one 256-thread workgroup per 16x16 tile, pixel per thread; the tile's upstream gradient G
+//   [256 x DT] in registers (the thread's own pixel) and in LDS (for the product).
+//   Sweep 1 replays the forward's decisions (the same fp32 operations in the same order) and keeps per pixel T_final and
+//   CG = sum_k w_k (f_k . G_p) in sorted order.
+//   Sweep 2 replays them again in batches of splat_bwd_batch(DT) Gaussians; per added Gaussian: w = a T, the running prefix
+//   P += w (f . G_p) and the behind-sum S . G_p = CG - P (exactly 0 after the last added Gaussian, since both are the same
+//   fp32 sequence; its error is a few ulp of sum_k w_k |f_k . G_p|), then
+//     dL/da = T (f . G_p) - (S . G_p) / (1 - a) + G_alpha T_final / (1 - a),   Q = dL/da * (o e^-sigma < 0.999 ? e^-sigma : 0).
+//   W[k][p] = w and Q[k][p] go to LDS (0 where the pixel did not add Gaussian k, and from its stop on).  Then
+//   partial_f[k][c] = sum_p W[k][p] G[p][c] (thread = (channel, group of Gaussians), p ascending, 4 pixels per step) and
+//   partial_o[k] = sum_p Q[k][p] (fixed segment sums, then a fixed xor tree).  Once every pixel has stopped, the rest of
+//   the run gets zero partials.
+// k_splat_grad_reduce<GS>  GS = 16, 32 or 64 lanes per Gaussian, lane = channel (channel D: the opacity), grid-stride over
+//   the Gaussians: its count[g] contiguous slots summed in ascending order.  Gaussians without tiles (culled) get rows of
+//   exactly 0.
+// The LDS product was kept against a wave-shuffle reduction of the same sweep (profiles/r09_splat_backward_ab.log): the
+// shuffles' butterfly costs more VALU issue at D = 32 than the product's LDS traffic.
+// Both kernels write nothing when the device total exceeds the capacity (the reduce raises *status).
+// ------------------------------------------------------------------------------------------------
+// Gaussians per backward batch.  LDS: G (256 DT) + W and Q (2 NB 260) + features (NB DT) floats = 100 KiB at DT 32 and 64
+__host__ __device__ constexpr int splat_bwd_batch(int DT) { return DT <= 32 ? 32 : 16; }
+constexpr int SPLAT_BWD_ROW = SPLAT_THREADS + 4;   // W / Q row stride: row k starts k 16-byte slots further round the banks
+
+__device__ inline long long splat_slot(const long long *__restrict__ offs, const int *__restrict__ count,
+                                       const int4 *__restrict__ box, int g)
+{
+    const int4 b = box[g];
+    return offs[g] - count[g] + (long long)((int)blockIdx.y - b.y) * (b.z - b.x + 1) + ((int)blockIdx.x - b.x);
+}
+
+template <int DT>
+__global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
+    const SplatRec *__restrict__ rec, const int4 *__restrict__ box, const int *__restrict__ count,
+    const long long *__restrict__ offs, const int *__restrict__ vals, const longlong2 *__restrict__ ranges,
+    const long long *total_p, long long capacity, const float *__restrict__ feats, int D, long long stride, int W, int H,
+    const float *__restrict__ grad_logits, const float *__restrict__ grad_alpha, float *__restrict__ part)
+{
+    constexpr int NB = splat_bwd_batch(DT);
+    constexpr int KPT = NB * DT / SPLAT_THREADS;          // Gaussians per thread in the product
+    constexpr int QSEG = SPLAT_THREADS / NB;              // threads per Gaussian in the opacity sum
+    static_assert(KPT >= 1 && KPT * SPLAT_THREADS == NB * DT && QSEG * NB == SPLAT_THREADS && QSEG <= 64, "batch shape");
+    __shared__ float s_G[SPLAT_THREADS * DT];
+    __shared__ __attribute__((aligned(16))) float s_W[NB * SPLAT_BWD_ROW];
+    __shared__ float s_Q[NB * SPLAT_BWD_ROW];
+    __shared__ float4 s_ga[NB];
+    __shared__ float2 s_gb[NB];
+    __shared__ long long s_slot[NB];
+    __shared__ float s_f[NB * DT];
+    if (*total_p > capacity) return;
+    const int tid = threadIdx.x;
+    const int px = blockIdx.x * SPLAT_TILE + (tid & (SPLAT_TILE - 1)), py = blockIdx.y * SPLAT_TILE + tid / SPLAT_TILE;
+    const bool inside = px < W && py < H;
+    const float sx = px + 0.5f, sy = py + 0.5f;
+    const long long pix = (long long)py * W + px, hw = (long long)H * W;
+    const longlong2 rg = ranges[(long long)blockIdx.y * gridDim.x + blockIdx.x];
+    const int D1 = D + 1;
+    float gr[DT];
+#pragma unroll
+    for (int c = 0; c < DT; ++c) {
+        gr[c] = grad_logits && inside && c < D ? grad_logits[c * hw + pix] : 0.0f;
+        s_G[tid * DT + c] = gr[c];
+    }
+    const float ga_p = grad_alpha && inside ? grad_alpha[pix] : 0.0f;
+
+    // sweep 1: T_final and CG
+    float T = 1.0f, CG = 0.0f;
+    bool done = !inside;
+    for (long long b0 = rg.x; b0 < rg.y; b0 += NB) {
+        if (__syncthreads_count(done) == SPLAT_THREADS) break;      // also keeps the last batch's LDS until all read it
+        const int nb = (int)(rg.y - b0 < NB ? rg.y - b0 : NB);
+        for (int k = tid; k < nb; k += SPLAT_THREADS) {
+            const SplatRec r = rec[vals[b0 + k]];
+            s_ga[k] = make_float4(r.mx, r.my, r.A, r.B);
+            s_gb[k] = make_float2(r.C, r.o);
+        }
+        for (int e = tid; e < nb * DT; e += SPLAT_THREADS) {
+            const int k = e / DT, c = e % DT;
+            s_f[e] = c < D ? feats[(long long)vals[b0 + k] * stride + c] : 0.0f;
+        }
+        __syncthreads();
+        if (!done) {
+            for (int k = 0; k < nb; ++k) {
+                const float4 ga = s_ga[k];
+                const float2 gb = s_gb[k];
+                const float dx = ga.x - sx, dy = ga.y - sy;
+                const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
+                if (sigma < 0.0f) continue;
+                const float a = fminf(0.999f, gb.y * __expf(-sigma));
+                if (a < 1.0f / 255.0f) continue;
+                const float Tn = T * (1.0f - a);
+                if (Tn <= 1e-4f) {
+                    done = true;
+                    break;
+                }
+                const float *f = s_f + k * DT;
+                float fg = 0.0f;
+#pragma unroll
+                for (int c = 0; c < DT; ++c) fg = fmaf(f[c], gr[c], fg);
+                CG = fmaf(a * T, fg, CG);
+                T = Tn;
+            }
+        }
+    }
+    const float T_final = T;
+
+    // sweep 2: per-pixel weights and opacity terms into LDS, then the tile's partials
+    T = 1.0f;
+    float P = 0.0f;
+    done = !inside;
+    const int pc = tid % DT, pk0 = (tid / DT) * KPT;      // product: channel and first Gaussian of this thread
+    const int qk = tid / QSEG, qs = tid % QSEG;           // opacity sum: Gaussian and segment of this thread
+    for (long long b0 = rg.x; b0 < rg.y; b0 += NB) {
+        if (__syncthreads_count(done) == SPLAT_THREADS) {
+            for (long long i = b0 + tid; i < rg.y; i += SPLAT_THREADS) {
+                const long long slot = splat_slot(offs, count, box, vals[i]);
+                for (int c = 0; c < D1; ++c) part[slot * D1 + c] = 0.0f;
+            }
+            break;
+        }
+        const int nb = (int)(rg.y - b0 < NB ? rg.y - b0 : NB);
+        for (int k = tid; k < nb; k += SPLAT_THREADS) {
+            const int g = vals[b0 + k];
+            const SplatRec r = rec[g];
+            s_ga[k] = make_float4(r.mx, r.my, r.A, r.B);
+            s_gb[k] = make_float2(r.C, r.o);
+            s_slot[k] = splat_slot(offs, count, box, g);
+        }
+        for (int e = tid; e < nb * DT; e += SPLAT_THREADS) {
+            const int k = e / DT, c = e % DT;
+            s_f[e] = c < D ? feats[(long long)vals[b0 + k] * stride + c] : 0.0f;
+        }
+        __syncthreads();
+        for (int k = 0; k < NB; ++k) {
+            float wk = 0.0f, qv = 0.0f;
+            if (!done && k < nb) {
+                const float4 ga = s_ga[k];
+                const float2 gb = s_gb[k];
+                const float dx = ga.x - sx, dy = ga.y - sy;
+                const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
+                if (sigma >= 0.0f) {
+                    const float e = __expf(-sigma);
+                    const float raw = gb.y * e;
+                    const float a = fminf(0.999f, raw);
+                    if (a >= 1.0f / 255.0f) {
+                        const float Tn = T * (1.0f - a);
+                        if (Tn <= 1e-4f) {
+                            done = true;
+                        } else {
+                            const float *f = s_f + k * DT;
+                            float fg = 0.0f;
+#pragma unroll
+                            for (int c = 0; c < DT; ++c) fg = fmaf(f[c], gr[c], fg);
+                            wk = a * T;
+                            P = fmaf(wk, fg, P);
+                            const float inv = 1.0f / (1.0f - a);
+                            const float dLda = T * fg - (CG - P) * inv + ga_p * T_final * inv;
+                            qv = raw < 0.999f ? dLda * e : 0.0f;
+                            T = Tn;
+                        }
+                    }
+                }
+            }
+            s_W[k * SPLAT_BWD_ROW + tid] = wk;
+            s_Q[k * SPLAT_BWD_ROW + tid] = qv;
+        }
+        __syncthreads();
+        float acc[KPT];
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) acc[j] = 0.0f;
+        for (int p = 0; p < SPLAT_THREADS; p += 4) {
+            const float g0 = s_G[p * DT + pc], g1 = s_G[(p + 1) * DT + pc], g2 = s_G[(p + 2) * DT + pc],
+                        g3 = s_G[(p + 3) * DT + pc];
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                const float4 w = *(const float4 *)(s_W + (pk0 + j) * SPLAT_BWD_ROW + p);
+                acc[j] = fmaf(w.x, g0, acc[j]);
+                acc[j] = fmaf(w.y, g1, acc[j]);
+                acc[j] = fmaf(w.z, g2, acc[j]);
+                acc[j] = fmaf(w.w, g3, acc[j]);
+            }
+        }
+        if (pc < D) {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if (pk0 + j < nb) part[s_slot[pk0 + j] * D1 + pc] = acc[j];
+        }
+        float q = 0.0f;
+        for (int i = 0; i < NB; ++i) q += s_Q[qk * SPLAT_BWD_ROW + qs * NB + i];
+#pragma unroll
+        for (int m = QSEG / 2; m >= 1; m /= 2) q += __shfl_xor(q, m);
+        if (qs == 0 && qk < nb) part[s_slot[qk] * D1 + D] = q;
+    }
+}
+
+// lanes per Gaussian in the reduce: the smallest of 16, 32, 64 that holds D + 1 channels (D = 64: lane c and c + 64)
+inline int splat_reduce_group(int D) { return D + 1 <= 16 ? 16 : D + 1 <= 32 ? 32 : 64; }
+
+// GS lanes per Gaussian, grid-stride over the Gaussians; each lane sums its channel over the Gaussian's count[g] contiguous
+// slots in ascending order, four loads in flight
+template <int GS>
+__global__ __launch_bounds__(256) void k_splat_grad_reduce(const int *__restrict__ count, const long long *__restrict__ offs,
+                                                           long long n, const long long *total_p, long long capacity,
+                                                           const float *__restrict__ part, int D, float *__restrict__ grad_f,
+                                                           float *__restrict__ grad_o, int *status)
+{
+    if (*total_p > capacity) {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && status) *status = 1;
+        return;
+    }
+    constexpr int GPB = 256 / GS;                       // Gaussians per workgroup and round
+    const int D1 = D + 1, lane = threadIdx.x % GS;
+    const long long step = (long long)gridDim.x * GPB;
+    for (long long g = (long long)blockIdx.x * GPB + threadIdx.x / GS; g < n; g += step) {
+        const long long s1 = offs[g], s0 = s1 - count[g];
+        for (int c = lane; c < D1; c += GS) {
+            const float *p = part + c;
+            float s = 0.0f;
+            long long k = s0;
+            for (; k + 4 <= s1; k += 4) {
+                const float a0 = p[k * D1], a1 = p[(k + 1) * D1], a2 = p[(k + 2) * D1], a3 = p[(k + 3) * D1];
+                s += a0;
+                s += a1;
+                s += a2;
+                s += a3;
+            }
+            for (; k < s1; ++k) s += p[k * D1];
+            if (c < D) {
+                if (grad_f) grad_f[g * D + c] = s;
+            } else if (grad_o) {
+                grad_o[g] = s;
+            }
+        }
+    }
+}
+
+// bytes of the backward's scratch: one partial row of D + 1 floats per intersection
+inline size_t splat_bwd_bytes(long long capacity, int D)
+{
+    return align256((size_t)(capacity > 0 ? capacity : 1) * (size_t)(D + 1) * sizeof(float));
+}
+
 // workspace layout of one (N, W, H, capacity); the part before `keys0` does not depend on the capacity
 struct SplatLayout {
     size_t total, rec, box, count, offs, scan_tmp, keys0, keys1, vals0, vals1, sort_tmp, ranges, bytes;

@@ -54,6 +54,7 @@ EXPORTS = [
     "vp_aggregate_view_f16", "vp_workspace_create", "vp_workspace_set_option",
     "vp_first_hit_ids", "vp_render_features", "vp_query_workspace_bytes", "vp_query_features",
     "vp_splat_workspace_bytes", "vp_splat_project", "vp_splat_rasterize",
+    "vp_splat_backward_workspace_bytes", "vp_splat_rasterize_backward",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -183,6 +184,12 @@ def lib():
             L.vp_splat_rasterize.restype = ctypes.c_int
             L.vp_splat_rasterize.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+            L.vp_splat_backward_workspace_bytes.restype = ctypes.c_size_t
+            L.vp_splat_backward_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
+            L.vp_splat_rasterize_backward.restype = ctypes.c_int
+            L.vp_splat_rasterize_backward.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp,
+                                                      ctypes.c_size_t, vp]
             if L.vp_abi_version() != VP_ABI_VERSION:
                 raise VoxprojError(f"{LIB_PATH} has ABI version {L.vp_abi_version()}, this package needs {VP_ABI_VERSION}: rebuild it")
             _lib = L
@@ -639,6 +646,51 @@ def splat_rasterize(features, n_gaussians, W, H, capacity, workspace, *, want_lo
                                        int(capacity), labels.data_ptr(), p(conf), p(alpha), p(logits), p(status), ptr,
                                        workspace.capacity(), stream.cuda_stream))
     return labels, conf, alpha, logits
+
+
+def splat_rasterize_backward(features, n_gaussians, W, H, capacity, workspace, grad_logits=None, grad_alpha=None, *,
+                             bwd_workspace=None, want_features=True, want_opacities=True, status=None):
+    """vp_splat_rasterize_backward after splat_rasterize on ``workspace`` with the same features, n_gaussians, W, H and
+    capacity: gradients of sum(grad_logits * logits) + sum(grad_alpha * alpha) with respect to the features and the
+    activated opacities.  grad_logits f32 [D,H,W] and grad_alpha f32 [H,W] on the features' GPU, each may be None (zero).
+    ``bwd_workspace``: a SplatWorkspace for the per-intersection partials (a fresh one when None).  Returns (grad_features
+    f32 [N,D] or None, grad_opacities f32 [N] or None).  ``status``: optional device int32 [1], set to 1 when the device count
+    exceeds ``capacity`` (then nothing is written)."""
+    import torch
+    _require_tensors((features, "features", (torch.float32,)))
+    _require(features.dim() == 2 and int(features.shape[0]) == int(n_gaussians), f"features must be [{n_gaussians}, D]")
+    D = int(features.shape[1])
+    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
+    if features.stride(1) != 1 or features.stride(0) < D:
+        features = features.contiguous()
+    dev = features.device
+    for t, name, shape in ((grad_logits, "grad_logits", (D, H, W)), (grad_alpha, "grad_alpha", (H, W))):
+        if t is not None:
+            _require_tensors((t, name, (torch.float32,)))
+            _require(tuple(t.shape) == tuple(int(v) for v in shape) and t.device == dev,
+                     f"{name} must be {list(shape)} on the features' device")
+    grad_logits = grad_logits.contiguous() if grad_logits is not None else None
+    grad_alpha = grad_alpha.contiguous() if grad_alpha is not None else None
+    L = lib()
+    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= nbytes, "splat_rasterize_backward needs the workspace of a splat_rasterize call")
+    need = int(L.vp_splat_backward_workspace_bytes(int(capacity), D))
+    _require(need > 0, f"no backward workspace size for capacity {capacity}, D = {D}")
+    bw = bwd_workspace if bwd_workspace is not None else SplatWorkspace()
+    bptr = bw.ensure(need, dev)
+    N = int(n_gaussians)
+    gf = torch.empty((N, D), dtype=torch.float32, device=dev) if want_features else None
+    go = torch.empty((N,), dtype=torch.float32, device=dev) if want_opacities else None
+    p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_splat_rasterize_backward(p(features), D, max(int(features.stride(0)), D), N, int(W), int(H),
+                                                int(capacity), p(grad_logits), p(grad_alpha), p(gf), p(go), p(status),
+                                                workspace.ptr(), workspace.capacity(), bptr, bw.capacity(),
+                                                stream.cuda_stream))
+    return gf, go
 
 
 def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, *, want_logits=False, want_alpha=False,

@@ -409,7 +409,8 @@ int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, 
 
 /*
  * Gaussian splatting of per-Gaussian features (the reference's stage 5.2, voxel_to_gaussian/render_semantics_logits.py,
- * which calls gsplat's rasterization() in classic mode without a background).  Forward only.  Added after VP_ABI_VERSION 4
+ * which calls gsplat's rasterization() in classic mode without a background).  Differentiable in the features and the
+ * opacities through vp_splat_rasterize_backward (below), not in the geometry.  Added after VP_ABI_VERSION 4
  * without changing it or any existing entry point: callers detect the three functions by symbol (dlsym).
  *
  * Per Gaussian: mean mu (world), quaternion q = (w, x, y, z) (normalised here; |q| = 0 culls), scale s (activated), opacity
@@ -458,6 +459,43 @@ int vp_splat_project(const float *means, const float *quats, const float *scales
 int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H,
                        int64_t capacity, int32_t *labels, float *confidence, float *alpha, float *logits,
                        int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The splatting backward: gradients of a loss L through the two differentiable outputs, logits [D,H,W] and alpha [H,W],
+ * with respect to the features f [N,D] and the activated opacities o [N].  Added after VP_ABI_VERSION 4 without changing
+ * it; detect the two functions by symbol.  Labels and confidence are not differentiable; geometry gradients (means, quats,
+ * scales) are not computed.
+ *
+ * The contract: the backward differentiates the branch the forward took, with the same (z, index) order and the same
+ * decisions at every pixel (skip when sigma < 0 or a < 1/255; stop at the first Gaussian that would take T to <= 1e-4, which
+ * gets no gradient at that pixel, and neither does any Gaussian after it).  With a = min(0.999, o e^-sigma), w_g = a_g T_g
+ * (T_g the transmittance before g), S_g = sum over the Gaussians k added after g of w_k f_k and T_final the pixel's final T,
+ * per pixel:
+ *   dC_c/df_gc  = w_g                                   (the logits are linear in f)
+ *   dC_c/da_g   = T_g f_gc - S_gc / (1 - a_g)
+ *   dalpha/da_g = T_final / (1 - a_g)
+ *   da/do       = e^-sigma when o e^-sigma < 0.999, else 0.
+ * grad_features[g,c] = sum_p G[c,p] w_g(p);  grad_opacities[g] = sum_p (sum_c G[c,p] dC_c/da_g + G_alpha[p] dalpha/da_g) da/do.
+ * A culled Gaussian (non-finite, near / far, zero quaternion, off-image, o < 1/255) gets rows of exactly 0, and so does one
+ * that no pixel added.  fp32, no float atomics: per-(tile, Gaussian) partials are summed in a fixed order, so gradients are
+ * bit-identical from run to run.  The behind-sum S_g . G is the pixel's C . G minus a running prefix; its error is a few
+ * ulp of sum_k w_k |f_k . G|.
+ *
+ * vp_splat_backward_workspace_bytes: bytes of the backward's own scratch, capacity x (D + 1) floats (at least one row),
+ *   256-byte rounded; 0 when capacity is outside [0, 2^31 - 1] or D outside [1, 64].  Needs no GPU.
+ *
+ * vp_splat_rasterize_backward: after vp_splat_rasterize on this workspace with the same n_gaussians, W, H, capacity,
+ *   features and stream; the workspace is only read.  grad_logits f32 planar [D,H,W] and grad_alpha f32 [H,W], contiguous,
+ *   each may be NULL (read as 0).  Writes grad_features f32 [N,D] (contiguous) and grad_opacities f32 [N], each only when not
+ *   NULL.  When the device count exceeds `capacity` nothing is written and *status (device i32, may be NULL; not reset) is
+ *   set to 1.  Asynchronous on `stream`, no allocation.  Refused on the host as vp_splat_rasterize refuses (VP_EINVAL), and
+ *   with VP_EWORKSPACE for either workspace: NULL, not 256-byte aligned, or smaller than its size function.
+ */
+size_t vp_splat_backward_workspace_bytes(int64_t capacity, int D);
+int vp_splat_rasterize_backward(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H,
+                                int64_t capacity, const float *grad_logits, const float *grad_alpha,
+                                float *grad_features, float *grad_opacities, int32_t *status, void *workspace,
+                                size_t workspace_bytes, void *bwd_workspace, size_t bwd_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -13,8 +13,11 @@ channels, 876x584 and 1600x1067 views from the synthetic trajectory, labels + co
 The per-kernel split (project / scan / emit / sort / ranges / blend) is in the rocprofv3 --kernel-trace --stats run of one
 leg committed under profiles/ (r08_splat_*).
 
+With --backward, every logits-on leg adds a splat_backward_ms_per_view line: vp_splat_rasterize (logits and alpha) and
+vp_splat_rasterize_backward (random gradients on both) on view 0, and their ratio (profiles/r09_splat_backward*).
+
 python tools/bench_splat.py [--steps K] [--warmup W] [--g 200000 1000000] [--d 13 32] [--size 876x584 1600x1067]
-[--logits off on] [--views V]"""
+[--logits off on] [--views V] [--backward]"""
 import argparse
 import json
 import os
@@ -50,6 +53,8 @@ def main(argv=None):
     ap.add_argument("--size", nargs="+", default=["876x584", "1600x1067"])
     ap.add_argument("--logits", nargs="+", default=["off", "on"])
     ap.add_argument("--views", type=int, default=8)
+    ap.add_argument("--backward", action="store_true",
+                    help="after each logits-on leg, one splat_backward_ms_per_view line: rasterize forward vs backward")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     for G in args.g:
@@ -95,6 +100,27 @@ def main(argv=None):
                                logits_GBs=round(D * H * W * 4 / (raster_ms * 1e-3) / 1e9, 2) if want else None,
                                views=len(w2c), steps=args.steps, warmup=args.warmup)
                     print(json.dumps(res), flush=True)
+                    if args.backward and want:
+                        backward_leg(t, feats, G, W, H, w2c[0], K, ws, caps[0], args)
+
+
+def backward_leg(t, feats, G, W, H, vm, K, ws, cap, args):
+    """--backward: vp_splat_rasterize on view 0 (logits and alpha written) against vp_splat_rasterize_backward with a
+    random upstream gradient on both outputs, same event timing."""
+    D = int(feats.shape[1])
+    gen = torch.Generator(feats.device).manual_seed(0)
+    g_logits = torch.randn((D, H, W), device=feats.device, generator=gen)
+    g_alpha = torch.randn((H, W), device=feats.device, generator=gen)
+    bws = voxproj_host.SplatWorkspace()
+    voxproj_host.splat_project(t["means"], t["quats"], t["scales"], t["opacities"], vm, K, W, H, workspace=ws)
+    fwd_ms = timed(lambda i: voxproj_host.splat_rasterize(feats, G, W, H, cap, ws, want_logits=True, want_alpha=True),
+                   args.steps, args.warmup)
+    bwd_ms = timed(lambda i: voxproj_host.splat_rasterize_backward(feats, G, W, H, cap, ws, g_logits, g_alpha,
+                                                                   bwd_workspace=bws), args.steps, args.warmup)
+    res = dict(metric="splat_backward_ms_per_view", G=G, D=D, W=W, H=H, raster_fwd_ms=round(fwd_ms, 4),
+               raster_bwd_ms=round(bwd_ms, 4), bwd_over_fwd=round(bwd_ms / fwd_ms, 2), n_isect=cap,
+               bwd_scratch_MB=round(bws.capacity() / 2 ** 20, 1), steps=args.steps, warmup=args.warmup)
+    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
