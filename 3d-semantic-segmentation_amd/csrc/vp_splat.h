@@ -303,12 +303,19 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
 // k_splat_grad_reduce<GS>  GS = 16, 32 or 64 lanes per Gaussian, lane = channel (channel D: the opacity), grid-stride over
 //   the Gaussians: its count[g] contiguous slots summed in ascending order.  Gaussians without tiles (culled) get rows of
 //   exactly 0.
+// k_splat_blend_backward<DT, true> (vp_splat_rasterize_backward_geometry) is the same sweep with rows of D + 1 + 5 floats: the
+//   five screen-space sums of q = dL/da o e^-sigma (0 at the clamp) follow the opacity's,
+//     g_mx = -sum q (A dx + B dy), g_my = -sum q (B dx + C dy), g_A = -sum q dx^2 / 2, g_B = -sum q dx dy, g_C = -sum q dy^2 / 2.
+//   They need no LDS of their own: the thread that sums a segment of Q[k][.] recomputes dx, dy of those pixels from the
+//   record (the sweep's own fp32 expressions) and carries five more running sums through the same segment and xor tree.
+//   The features' and the opacity's partials are computed exactly as without GEOM: bit-identical gradients.
 // The LDS product was kept against a wave-shuffle reduction of the same sweep (profiles/r09_splat_backward_ab.log): the
 // shuffles' butterfly costs more VALU issue at D = 32 than the product's LDS traffic.
 // Both kernels write nothing when the device total exceeds the capacity (the reduce raises *status).
 // ------------------------------------------------------------------------------------------------
 // Gaussians per backward batch.  LDS: G (256 DT) + W and Q (2 NB 260) + features (NB DT) floats = 100 KiB at DT 32 and 64
 __host__ __device__ constexpr int splat_bwd_batch(int DT) { return DT <= 32 ? 32 : 16; }
+constexpr int SPLAT_SCREEN = 5;                    // screen-space sums per Gaussian: mean2d (x, y) and the conic (A, B, C)
 constexpr int SPLAT_BWD_ROW = SPLAT_THREADS + 4;   // W / Q row stride: row k starts k 16-byte slots further round the banks
 
 __device__ inline long long splat_slot(const long long *__restrict__ offs, const int *__restrict__ count,
@@ -318,7 +325,7 @@ __device__ inline long long splat_slot(const long long *__restrict__ offs, const
     return offs[g] - count[g] + (long long)((int)blockIdx.y - b.y) * (b.z - b.x + 1) + ((int)blockIdx.x - b.x);
 }
 
-template <int DT>
+template <int DT, bool GEOM>
 __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
     const SplatRec *__restrict__ rec, const int4 *__restrict__ box, const int *__restrict__ count,
     const long long *__restrict__ offs, const int *__restrict__ vals, const longlong2 *__restrict__ ranges,
@@ -343,7 +350,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
     const float sx = px + 0.5f, sy = py + 0.5f;
     const long long pix = (long long)py * W + px, hw = (long long)H * W;
     const longlong2 rg = ranges[(long long)blockIdx.y * gridDim.x + blockIdx.x];
-    const int D1 = D + 1;
+    const int D1 = D + (GEOM ? 1 + SPLAT_SCREEN : 1);    // floats per partial row
     float gr[DT];
 #pragma unroll
     for (int c = 0; c < DT; ++c) {
@@ -475,10 +482,42 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
                 if (pk0 + j < nb) part[s_slot[pk0 + j] * D1 + pc] = acc[j];
         }
         float q = 0.0f;
-        for (int i = 0; i < NB; ++i) q += s_Q[qk * SPLAT_BWD_ROW + qs * NB + i];
+        if constexpr (GEOM) {
+            // the five screen sums ride on the opacity sum: Q[k][p] times a factor of the record and the pixel's offset
+            // (recomputed as sweep 2 computed it), in the same fixed order: segments by pixel index, then the xor tree
+            const float4 ga = s_ga[qk];
+            const float2 gb = s_gb[qk];
+            float s5[SPLAT_SCREEN] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            for (int i = 0; i < NB; ++i) {
+                const int p = qs * NB + i;
+                const float v = s_Q[qk * SPLAT_BWD_ROW + p];
+                const float dx = ga.x - ((int)blockIdx.x * SPLAT_TILE + (p & (SPLAT_TILE - 1)) + 0.5f);
+                const float dy = ga.y - ((int)blockIdx.y * SPLAT_TILE + p / SPLAT_TILE + 0.5f);
+                q += v;
+                s5[0] += v * (ga.z * dx + ga.w * dy);
+                s5[1] += v * (ga.w * dx + gb.x * dy);
+                s5[2] += v * (0.5f * dx * dx);
+                s5[3] += v * (dx * dy);
+                s5[4] += v * (0.5f * dy * dy);
+            }
 #pragma unroll
-        for (int m = QSEG / 2; m >= 1; m /= 2) q += __shfl_xor(q, m);
-        if (qs == 0 && qk < nb) part[s_slot[qk] * D1 + D] = q;
+            for (int m = QSEG / 2; m >= 1; m /= 2) {
+                q += __shfl_xor(q, m);
+#pragma unroll
+                for (int j = 0; j < SPLAT_SCREEN; ++j) s5[j] += __shfl_xor(s5[j], m);
+            }
+            if (qs == 0 && qk < nb) {
+                float *row = part + s_slot[qk] * D1 + D;
+                row[0] = q;
+#pragma unroll
+                for (int j = 0; j < SPLAT_SCREEN; ++j) row[1 + j] = -gb.y * s5[j];      // q = Q o, and the sums' sign
+            }
+        } else {
+            for (int i = 0; i < NB; ++i) q += s_Q[qk * SPLAT_BWD_ROW + qs * NB + i];
+#pragma unroll
+            for (int m = QSEG / 2; m >= 1; m /= 2) q += __shfl_xor(q, m);
+            if (qs == 0 && qk < nb) part[s_slot[qk] * D1 + D] = q;
+        }
     }
 }
 
@@ -521,6 +560,165 @@ __global__ __launch_bounds__(256) void k_splat_grad_reduce(const int *__restrict
             }
         }
     }
+}
+
+// The geometry backward's reduce: as k_splat_grad_reduce over rows of D + 1 + SPLAT_SCREEN floats.  The five screen sums of
+// a Gaussian with tiles are also written back into its first slot's row, where k_splat_geom_chain reads them (the reduce
+// has no per-Gaussian scratch of its own: the size function knows the capacity, not N).  Each channel of a Gaussian's rows
+// is read and written by one lane only.
+template <int GS>
+__global__ __launch_bounds__(256) void k_splat_grad_reduce_geom(const int *__restrict__ count,
+                                                                const long long *__restrict__ offs, long long n,
+                                                                const long long *total_p, long long capacity, float *part, int D,
+                                                                float *__restrict__ grad_f, float *__restrict__ grad_o,
+                                                                float *__restrict__ grad_s, int *status)
+{
+    if (*total_p > capacity) {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && status) *status = 1;
+        return;
+    }
+    constexpr int GPB = 256 / GS;
+    const int DR = D + 1 + SPLAT_SCREEN, lane = threadIdx.x % GS;
+    const long long step = (long long)gridDim.x * GPB;
+    for (long long g = (long long)blockIdx.x * GPB + threadIdx.x / GS; g < n; g += step) {
+        const long long s1 = offs[g], s0 = s1 - count[g];
+        for (int c = lane; c < DR; c += GS) {
+            float *p = part + c;
+            float s = 0.0f;
+            long long k = s0;
+            for (; k + 4 <= s1; k += 4) {
+                const float a0 = p[k * DR], a1 = p[(k + 1) * DR], a2 = p[(k + 2) * DR], a3 = p[(k + 3) * DR];
+                s += a0;
+                s += a1;
+                s += a2;
+                s += a3;
+            }
+            for (; k < s1; ++k) s += p[k * DR];
+            if (c < D) {
+                if (grad_f) grad_f[g * D + c] = s;
+            } else if (c == D) {
+                if (grad_o) grad_o[g] = s;
+            } else {
+                if (grad_s) grad_s[g * SPLAT_SCREEN + (c - D - 1)] = s;
+                if (s1 > s0) p[s0 * DR] = s;
+            }
+        }
+    }
+}
+
+// The adjoint of k_splat_project's float64 chain, one thread per Gaussian: the five screen sums (fp32, from the first slot's
+// row) to grad_means / grad_quats / grad_scales, rounded to fp32 once.  The forward's intermediates are recomputed from the
+// Gaussian and the camera with the forward's own expressions.  With X = conic, GX = [[g_A, g_B/2], [g_B/2, g_C]]:
+//   G_Sigma2 = -X GX X,  G_S = J^T G_Sigma2 J,  G_J = 2 G_Sigma2 J S,  Hl = U^T G_S U with U = R_w R(n), n = q / |q|
+//   (dL/dSigma in the Gaussian's own frame, where Sigma = diag(s^2)):  grad_s[c] = 2 s_c Hl_cc;  a rotation R -> R exp([d]x)
+//   gives dL/dd = 2 (Hl_12 (s1^2 - s2^2), Hl_02 (s2^2 - s0^2), Hl_01 (s0^2 - s1^2)): exactly 0 between equal scales;
+//   n -> n (1, d/2) turns it into grad_q = 2 E(n) dL/dd / |q|, tangent to the sphere and so orthogonal to q,
+//   J02 = -fx clamp(ux) / z: the clamp passes d/dux only strictly inside its range, d/dz on both branches,
+//   mean2d = f u + c with the unclamped u = p / z, grad_m = R_w^T G_p.
+// The fp32 depth, the culls and the support box carry no gradient; neither does the camera.  A Gaussian without tiles, or
+// whose five sums are all 0, gets rows of exactly 0.
+__global__ __launch_bounds__(256) void k_splat_geom_chain(const float *__restrict__ means, const float *__restrict__ quats,
+                                                          const float *__restrict__ scales, long long n, SplatCam cam,
+                                                          const int *__restrict__ count, const long long *__restrict__ offs,
+                                                          const long long *total_p, long long capacity,
+                                                          const float *__restrict__ part, int D, float *__restrict__ grad_m,
+                                                          float *__restrict__ grad_q, float *__restrict__ grad_sc)
+{
+    if (*total_p > capacity) return;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double gm[3] = {0.0, 0.0, 0.0}, gq[4] = {0.0, 0.0, 0.0, 0.0}, gsc[3] = {0.0, 0.0, 0.0};
+    const int cnt = count[i];
+    const float *row = part + (offs[i] - cnt) * (long long)(D + 1 + SPLAT_SCREEN) + D + 1;
+    double g5[SPLAT_SCREEN] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    bool any = false;
+    if (cnt > 0)
+        for (int j = 0; j < SPLAT_SCREEN; ++j) {
+            g5[j] = row[j];
+            any |= g5[j] != 0.0;
+        }
+    if (any) {
+        const float *r = cam.r;
+        const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2];
+        const float qw = quats[4 * i], qx = quats[4 * i + 1], qy = quats[4 * i + 2], qz = quats[4 * i + 3];
+        const double qn2 = (double)qw * qw + (double)qx * qx + (double)qy * qy + (double)qz * qz;
+        const double qi = 1.0 / sqrt(qn2), w = qw * qi, x = qx * qi, y = qy * qi, zq = qz * qi;
+        const double Rq[3][3] = {{1.0 - 2.0 * (y * y + zq * zq), 2.0 * (x * y - w * zq), 2.0 * (x * zq + w * y)},
+                                 {2.0 * (x * y + w * zq), 1.0 - 2.0 * (x * x + zq * zq), 2.0 * (y * zq - w * x)},
+                                 {2.0 * (x * zq - w * y), 2.0 * (y * zq + w * x), 1.0 - 2.0 * (x * x + y * y)}};
+        const double s[3] = {scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]};
+        double M[3][3], Rw[3][3], p[3], V[3][3], S[3][3];
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) {
+                M[a][c] = Rq[a][c] * s[c];
+                Rw[a][c] = r[4 * a + c];
+            }
+        for (int a = 0; a < 3; ++a) p[a] = Rw[a][0] * mx + Rw[a][1] * my + Rw[a][2] * mz + (double)r[4 * a + 3];
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) V[a][c] = Rw[a][0] * M[0][c] + Rw[a][1] * M[1][c] + Rw[a][2] * M[2][c];
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) S[a][c] = V[a][0] * V[c][0] + V[a][1] * V[c][1] + V[a][2] * V[c][2];
+        const double zd = p[2], fx = cam.fx, fy = cam.fy, cx = cam.cx, cy = cam.cy;
+        const double limxp = (cam.W - cx) / fx + 0.3 * (0.5 * cam.W) / fx, limxn = cx / fx + 0.3 * (0.5 * cam.W) / fx;
+        const double limyp = (cam.H - cy) / fy + 0.3 * (0.5 * cam.H) / fy, limyn = cy / fy + 0.3 * (0.5 * cam.H) / fy;
+        const double ux = p[0] / zd, uy = p[1] / zd;
+        const double cux = fmin(fmax(ux, -limxn), limxp), cuy = fmin(fmax(uy, -limyn), limyp);
+        const double tx = zd * cux, ty = zd * cuy, iz2 = 1.0 / (zd * zd);
+        const double J[2][3] = {{fx / zd, 0.0, -fx * tx * iz2}, {0.0, fy / zd, -fy * ty * iz2}};
+        double JS[2][3];
+        for (int a = 0; a < 2; ++a)
+            for (int c = 0; c < 3; ++c) JS[a][c] = J[a][0] * S[0][c] + J[a][1] * S[1][c] + J[a][2] * S[2][c];
+        const double s00 = JS[0][0] * J[0][0] + JS[0][1] * J[0][1] + JS[0][2] * J[0][2] + cam.eps2d;
+        const double s01 = JS[0][0] * J[1][0] + JS[0][1] * J[1][1] + JS[0][2] * J[1][2];
+        const double s11 = JS[1][0] * J[1][0] + JS[1][1] * J[1][1] + JS[1][2] * J[1][2] + cam.eps2d;
+        const double det = s00 * s11 - s01 * s01;
+        const double A = s11 / det, B = -s01 / det, C = s00 / det;
+        const double gA = g5[2], hB = 0.5 * g5[3], gC = g5[4];
+        const double y00 = gA * A + hB * B, y01 = gA * B + hB * C, y10 = hB * A + gC * B, y11 = hB * B + gC * C;
+        const double z01 = -(A * y01 + B * y11);
+        const double GZ[2][2] = {{-(A * y00 + B * y10), z01}, {z01, -(B * y01 + C * y11)}};
+        double GJ[2][3], ZJ[2][3], GS[3][3], U[3][3], GU[3][3];
+        for (int a = 0; a < 2; ++a)
+            for (int c = 0; c < 3; ++c) {
+                GJ[a][c] = 2.0 * (GZ[a][0] * JS[0][c] + GZ[a][1] * JS[1][c]);
+                ZJ[a][c] = GZ[a][0] * J[0][c] + GZ[a][1] * J[1][c];
+            }
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) {
+                GS[a][c] = J[0][a] * ZJ[0][c] + J[1][a] * ZJ[1][c];
+                U[a][c] = Rw[a][0] * Rq[0][c] + Rw[a][1] * Rq[1][c] + Rw[a][2] * Rq[2][c];
+            }
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) GU[a][c] = GS[a][0] * U[0][c] + GS[a][1] * U[1][c] + GS[a][2] * U[2][c];
+        // Hl = U^T G_S U, dL/dSigma in the Gaussian's own frame (symmetric: the entries used are computed once)
+#define VP_HL(i, j) (U[0][i] * GU[0][j] + U[1][i] * GU[1][j] + U[2][i] * GU[2][j])
+        for (int c = 0; c < 3; ++c) gsc[c] = 2.0 * s[c] * VP_HL(c, c);
+        const double gd[3] = {2.0 * VP_HL(1, 2) * ((s[1] - s[2]) * (s[1] + s[2])), 2.0 * VP_HL(0, 2) * ((s[2] - s[0]) * (s[2] + s[0])),
+                              2.0 * VP_HL(0, 1) * ((s[0] - s[1]) * (s[0] + s[1]))};
+#undef VP_HL
+        gq[0] = 2.0 * qi * (-x * gd[0] - y * gd[1] - zq * gd[2]);
+        gq[1] = 2.0 * qi * (w * gd[0] - zq * gd[1] + y * gd[2]);
+        gq[2] = 2.0 * qi * (zq * gd[0] + w * gd[1] - x * gd[2]);
+        gq[3] = 2.0 * qi * (-y * gd[0] + x * gd[1] + w * gd[2]);
+        const double g_ux = g5[0] * fx + (ux > -limxn && ux < limxp ? -GJ[0][2] * fx / zd : 0.0);
+        const double g_uy = g5[1] * fy + (uy > -limyn && uy < limyp ? -GJ[1][2] * fy / zd : 0.0);
+        const double g_z = (-GJ[0][0] * fx + GJ[0][2] * fx * cux - GJ[1][1] * fy + GJ[1][2] * fy * cuy) * iz2 -
+                           (g_ux * ux + g_uy * uy) / zd;
+        const double gp[3] = {g_ux / zd, g_uy / zd, g_z};
+        for (int c = 0; c < 3; ++c) gm[c] = Rw[0][c] * gp[0] + Rw[1][c] * gp[1] + Rw[2][c] * gp[2];
+    }
+    if (grad_m)
+        for (int c = 0; c < 3; ++c) grad_m[3 * i + c] = (float)gm[c];
+    if (grad_q)
+        for (int c = 0; c < 4; ++c) grad_q[4 * i + c] = (float)gq[c];
+    if (grad_sc)
+        for (int c = 0; c < 3; ++c) grad_sc[3 * i + c] = (float)gsc[c];
+}
+
+// bytes of the geometry backward's scratch: one partial row of D + 1 + SPLAT_SCREEN floats per intersection
+inline size_t splat_geom_bytes(long long capacity, int D)
+{
+    return align256((size_t)(capacity > 0 ? capacity : 1) * (size_t)(D + 1 + SPLAT_SCREEN) * sizeof(float));
 }
 
 // bytes of the backward's scratch: one partial row of D + 1 floats per intersection

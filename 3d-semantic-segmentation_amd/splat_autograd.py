@@ -3,8 +3,10 @@
 
 Gradients flow from the logits [D,H,W] and alpha [H,W] to the per-Gaussian features [N,D] and the activated opacities [N],
 through the branch the forward took (include/voxproj.h states the contract).  Labels and confidence are returned but not
-differentiable.  Geometry gradients (means, quats, scales) are not implemented: a call whose geometry requires grad raises
-instead of dropping them.  No double backward.
+differentiable.  ``splat_features`` keeps the geometry fixed: a call whose geometry requires grad raises instead of dropping
+the gradient.  ``splat_gaussians`` is differentiable in the means, the quaternions and the activated scales as well, through
+vp_splat_rasterize_backward_geometry (one fused tile sweep for every gradient asked for).  No gradient for the camera, no
+double backward.
 
 Each call keeps its own SplatWorkspace until its backward has run (the backward reads the forward's sorted intersections),
 so calls from several threads or views share no state.  The workspace is freed after the backward, or with the graph.
@@ -14,7 +16,7 @@ from torch.autograd.function import once_differentiable
 
 import voxproj_host as _host
 
-__all__ = ["splat_features", "SplatFeatures"]
+__all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians"]
 
 
 class SplatFeatures(torch.autograd.Function):
@@ -57,7 +59,8 @@ def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, 
 
     Returns (logits f32 [D,H,W], alpha f32 [H,W], labels int32 [H,W], confidence f32 [H,W]); only logits and alpha are
     differentiable.  The images are bit-identical to voxproj_host.splat_features(..., want_logits=True, want_alpha=True).
-    ``check``: raise when a Gaussian has a non-finite parameter (it is culled either way)."""
+    ``check``: raise when a Gaussian has a non-finite parameter (it is culled either way).
+    For gradients of the means, quats and scales use ``splat_gaussians``."""
     for t, name in ((means, "means"), (quats, "quats"), (scales, "scales")):
         if isinstance(t, torch.Tensor) and t.requires_grad:
             raise ValueError(f"{name} requires grad, but geometry gradients are not implemented: only the features and "
@@ -67,3 +70,57 @@ def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, 
                               (features, "features"))))
     return SplatFeatures.apply(features, opacities, means, quats, scales, viewmat, K, int(W), int(H), float(near), float(far),
                                float(eps2d), bool(check))
+
+
+class SplatGaussians(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, quats, scales, opacities, features, viewmat, K, W, H, near, far, eps2d, check):
+        ws = _host.SplatWorkspace()
+        m, q, s, f = means.detach(), quats.detach(), scales.detach(), features.detach()
+        r = _host.splat_features(m, q, s, opacities.detach(), f, viewmat, K, W, H, want_logits=True, want_alpha=True,
+                                 want_confidence=True, near=near, far=far, eps2d=eps2d, workspace=ws, check=check)
+        ctx.ws = ws
+        ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect))
+        ctx.save_for_backward(m, q, s, f)
+        ctx.mark_non_differentiable(r.labels, r.confidence)
+        return r.logits, r.alpha, r.labels, r.confidence
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_logits, grad_alpha, _grad_labels, _grad_confidence):
+        m, q, s, f = ctx.saved_tensors
+        ws, ctx.ws = ctx.ws, None
+        viewmat, K, W, H, eps2d, cap = ctx.view
+        want_m, want_q, want_s, want_o, want_f = ctx.needs_input_grad[:5]
+        gl = grad_logits.float() if grad_logits is not None else None
+        ga = grad_alpha.float() if grad_alpha is not None else None
+        g = dict(means=None, quats=None, scales=None, opacities=None, features=None)
+        if want_m or want_q or want_s:
+            g = _host.splat_rasterize_backward_geometry(m, q, s, f, viewmat, K, W, H, cap, ws, gl, ga, eps2d=eps2d,
+                                                        want_means=want_m, want_quats=want_q, want_scales=want_s,
+                                                        want_features=want_f, want_opacities=want_o)
+        elif want_f or want_o:
+            g["features"], g["opacities"] = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws, grad_logits=gl,
+                                                                           grad_alpha=ga, want_features=want_f,
+                                                                           want_opacities=want_o)
+        return g["means"], g["quats"], g["scales"], g["opacities"], g["features"], None, None, None, None, None, None, None, None
+
+
+def splat_gaussians(means, quats, scales, opacities, features, viewmat, K, W, H, *, near=0.01, far=1e10, eps2d=0.3,
+                    check=True):
+    """Splatting of D-channel per-Gaussian features into one W x H view, differentiable in every Gaussian parameter.
+
+      means f32 [N,3], quats f32 [N,4] (w, x, y, z; any norm), scales f32 [N,3] (activated),
+      opacities f32 [N] (activated), features f32 [N,D]     D <= 64, all on one GPU; any of the five may require grad
+      viewmat [4,4] world-to-camera, K [3,3]                 any device, read on the host; no gradient
+
+    Returns (logits f32 [D,H,W], alpha f32 [H,W], labels int32 [H,W], confidence f32 [H,W]), bit-identical to
+    ``splat_features``'s; only logits and alpha are differentiable.  The gradient of the quaternions is with respect to the
+    tensor as passed (orthogonal to it), the scales' and the opacities' with respect to the activated values.  The backward
+    runs the fused vp_splat_rasterize_backward_geometry once and asks only for what requires grad; without a geometry
+    gradient it is ``splat_features``'s backward.  ``check``: raise when a Gaussian has a non-finite parameter."""
+    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
+                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
+                              (features, "features"))))
+    return SplatGaussians.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), float(near), float(far),
+                                float(eps2d), bool(check))

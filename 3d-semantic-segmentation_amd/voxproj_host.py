@@ -55,6 +55,7 @@ EXPORTS = [
     "vp_first_hit_ids", "vp_render_features", "vp_query_workspace_bytes", "vp_query_features",
     "vp_splat_workspace_bytes", "vp_splat_project", "vp_splat_rasterize",
     "vp_splat_backward_workspace_bytes", "vp_splat_rasterize_backward",
+    "vp_splat_geometry_backward_workspace_bytes", "vp_splat_rasterize_backward_geometry",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -190,6 +191,12 @@ def lib():
             L.vp_splat_rasterize_backward.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp,
                                                       ctypes.c_size_t, vp]
+            L.vp_splat_geometry_backward_workspace_bytes.restype = ctypes.c_size_t
+            L.vp_splat_geometry_backward_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
+            L.vp_splat_rasterize_backward_geometry.restype = ctypes.c_int
+            L.vp_splat_rasterize_backward_geometry.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                               ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
+                [ctypes.c_int] * 2 + [ctypes.c_float, ctypes.c_int64] + [vp] * 10 + [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
             if L.vp_abi_version() != VP_ABI_VERSION:
                 raise VoxprojError(f"{LIB_PATH} has ABI version {L.vp_abi_version()}, this package needs {VP_ABI_VERSION}: rebuild it")
             _lib = L
@@ -691,6 +698,64 @@ def splat_rasterize_backward(features, n_gaussians, W, H, capacity, workspace, g
                                                 workspace.ptr(), workspace.capacity(), bptr, bw.capacity(),
                                                 stream.cuda_stream))
     return gf, go
+
+
+def splat_rasterize_backward_geometry(means, quats, scales, features, viewmat, K, W, H, capacity, workspace, grad_logits=None,
+                                      grad_alpha=None, *, eps2d=0.3, bwd_workspace=None, want_means=True, want_quats=True,
+                                      want_scales=True, want_features=True, want_opacities=True, want_screen=False,
+                                      status=None):
+    """vp_splat_rasterize_backward_geometry after splat_rasterize on ``workspace``: one fused call for the gradients of
+    sum(grad_logits * logits) + sum(grad_alpha * alpha) with respect to the means, the quaternions (as passed), the activated
+    scales, the features and the activated opacities, plus the five screen-space sums per Gaussian (dL/d mean2d, dL/d conic)
+    when ``want_screen``.  means, quats, scales, viewmat, K and eps2d are those of the splat_project call; the rest is as
+    splat_rasterize_backward, whose grad_features / grad_opacities this call reproduces bit for bit.  ``bwd_workspace``: a
+    SplatWorkspace of vp_splat_geometry_backward_workspace_bytes (a fresh one when None).  Returns a dict with the keys
+    means [N,3], quats [N,4], scales [N,3], features [N,D], opacities [N], screen [N,5]; None for what was not asked."""
+    import torch
+    _require_tensors(*((t, name, (torch.float32,)) for t, name in
+                       ((means, "means"), (quats, "quats"), (scales, "scales"), (features, "features"))))
+    N = int(means.shape[0]) if means.dim() == 2 else -1
+    _require(tuple(means.shape) == (N, 3) and N >= 0, "means must be [N, 3]")
+    _require(tuple(quats.shape) == (N, 4), f"quats must be [{N}, 4]")
+    _require(tuple(scales.shape) == (N, 3), f"scales must be [{N}, 3]")
+    _require(features.dim() == 2 and int(features.shape[0]) == N, f"features must be [{N}, D]")
+    D = int(features.shape[1])
+    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
+    dev = features.device
+    _require(all(t.device == dev for t in (means, quats, scales)), "the Gaussian tensors must be on one device")
+    if features.stride(1) != 1 or features.stride(0) < D:
+        features = features.contiguous()
+    means, quats, scales = (t.contiguous() for t in (means, quats, scales))
+    for t, name, shape in ((grad_logits, "grad_logits", (D, H, W)), (grad_alpha, "grad_alpha", (H, W))):
+        if t is not None:
+            _require_tensors((t, name, (torch.float32,)))
+            _require(tuple(t.shape) == tuple(int(v) for v in shape) and t.device == dev,
+                     f"{name} must be {list(shape)} on the features' device")
+    grad_logits = grad_logits.contiguous() if grad_logits is not None else None
+    grad_alpha = grad_alpha.contiguous() if grad_alpha is not None else None
+    vm, (fx, fy, cx, cy) = _splat_camera(viewmat, K, W, H)
+    L = lib()
+    nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}, capacity {capacity}")
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= nbytes, "splat_rasterize_backward_geometry needs the workspace of a splat_rasterize call")
+    need = int(L.vp_splat_geometry_backward_workspace_bytes(int(capacity), D))
+    _require(need > 0, f"no backward workspace size for capacity {capacity}, D = {D}")
+    bw = bwd_workspace if bwd_workspace is not None else SplatWorkspace()
+    bptr = bw.ensure(need, dev)
+    out = {name: torch.empty((N,) + tail, dtype=torch.float32, device=dev) if want else None
+           for name, tail, want in (("means", (3,), want_means), ("quats", (4,), want_quats), ("scales", (3,), want_scales),
+                                    ("features", (D,), want_features), ("opacities", (), want_opacities),
+                                    ("screen", (5,), want_screen))}
+    p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_splat_rasterize_backward_geometry(
+            p(means), p(quats), p(scales), p(features), D, max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy, int(W),
+            int(H), float(eps2d), int(capacity), p(grad_logits), p(grad_alpha), p(out["means"]), p(out["quats"]),
+            p(out["scales"]), p(out["features"]), p(out["opacities"]), p(out["screen"]), p(status), workspace.ptr(),
+            workspace.capacity(), bptr, bw.capacity(), stream.cuda_stream))
+    return out
 
 
 def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, *, want_logits=False, want_alpha=False,

@@ -410,7 +410,8 @@ int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, 
 /*
  * Gaussian splatting of per-Gaussian features (the reference's stage 5.2, voxel_to_gaussian/render_semantics_logits.py,
  * which calls gsplat's rasterization() in classic mode without a background).  Differentiable in the features and the
- * opacities through vp_splat_rasterize_backward (below), not in the geometry.  Added after VP_ABI_VERSION 4
+ * opacities through vp_splat_rasterize_backward, and in the means, quaternions and scales as well through
+ * vp_splat_rasterize_backward_geometry (both below); not in the camera.  Added after VP_ABI_VERSION 4
  * without changing it or any existing entry point: callers detect the three functions by symbol (dlsym).
  *
  * Per Gaussian: mean mu (world), quaternion q = (w, x, y, z) (normalised here; |q| = 0 culls), scale s (activated), opacity
@@ -463,8 +464,8 @@ int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t
 /*
  * The splatting backward: gradients of a loss L through the two differentiable outputs, logits [D,H,W] and alpha [H,W],
  * with respect to the features f [N,D] and the activated opacities o [N].  Added after VP_ABI_VERSION 4 without changing
- * it; detect the two functions by symbol.  Labels and confidence are not differentiable; geometry gradients (means, quats,
- * scales) are not computed.
+ * it; detect the two functions by symbol.  Labels and confidence are not differentiable; the geometry's gradients (means,
+ * quats, scales) come from vp_splat_rasterize_backward_geometry below.
  *
  * The contract: the backward differentiates the branch the forward took, with the same (z, index) order and the same
  * decisions at every pixel (skip when sigma < 0 or a < 1/255; stop at the first Gaussian that would take T to <= 1e-4, which
@@ -496,6 +497,56 @@ int vp_splat_rasterize_backward(const float *features, int D, int64_t row_stride
                                 int64_t capacity, const float *grad_logits, const float *grad_alpha,
                                 float *grad_features, float *grad_opacities, int32_t *status, void *workspace,
                                 size_t workspace_bytes, void *bwd_workspace, size_t bwd_bytes, void *stream);
+
+/*
+ * The geometry backward: one fused call for the gradients of L with respect to the means [N,3], the quaternions [N,4], the
+ * activated scales [N,3], the features and the activated opacities.  Added after VP_ABI_VERSION 4 without changing it;
+ * detect the two functions by symbol.  No gradient with respect to the camera (viewmat, fx, fy, cx, cy) is computed.
+ *
+ * The contract: as above, the branch the forward took is differentiated, with the same (fp32 z, index) order and the same
+ * skip / stop decisions at every pixel.  For a pixel that added Gaussian g, with d = mean2d_g - sample,
+ * sigma = (A dx^2 + C dy^2)/2 + B dx dy, raw = o e^-sigma and dL/da as above, let q = dL/da raw where raw < 0.999 and q = 0
+ * at the clamp.  The screen-space gradients, summed over the pixels that added g, are
+ *   g_mx = -sum q (A dx + B dy)    g_my = -sum q (B dx + C dy)
+ *   g_A  = -sum q dx^2 / 2         g_B  = -sum q dx dy           g_C = -sum q dy^2 / 2
+ * (grad_screen [N,5] in this order: dL/d mean2d and dL/d conic, B counted once as in sigma).  The world-space gradients
+ * are these five sums pushed through the adjoint of the forward's own float64 projection, in this order: conic = Sigma2^-1;
+ * Sigma2 = J R_w Sigma R_w^T J^T + eps2d I; Sigma = M M^T with M = R(q/|q|) diag(s); mean2d = f p/z + c; p = R_w m + t.
+ *   Jacobian clamp: where J clamps p/z the clamped branch is differentiated (tx = z lim: no gradient through p_x / z there,
+ *     the one through z stays); mean2d uses the unclamped p/z.
+ *   Depth: z here is the float64 p[2].  The fp32 depth only sorts and culls and carries no gradient; neither do the
+ *     support box, the 1/255 skip or the 1e-4 stop.
+ *   Activations: grad_quats is with respect to the quaternion as passed (not normalised), so it is orthogonal to q;
+ *     grad_scales is with respect to the activated scales.  Callers chain their own exp / sigmoid.
+ *   Zero rows: a culled Gaussian, and one that no pixel added, gets rows of exactly 0 in every output.
+ *   Determinism: fp32 in the tile sweep, no float atomics; per-(tile, Gaussian) partials in the pair's emission slot, summed
+ *     per Gaussian in ascending slot order: bit-identical from run to run.
+ *   Chain precision: the per-Gaussian chain runs in float64 on the device from the fp32 sums, recomputing the forward's
+ *     intermediates from means / quats / scales / camera, and is rounded to fp32 once.
+ *
+ * vp_splat_geometry_backward_workspace_bytes: bytes of this call's scratch, capacity x (D + 1 + 5) floats (at least one
+ *   row), 256-byte rounded; 0 when capacity is outside [0, 2^31 - 1] or D outside [1, 64].  Needs no GPU.
+ *
+ * vp_splat_rasterize_backward_geometry: after vp_splat_rasterize on this workspace with the same n_gaussians, W, H,
+ *   capacity, features and stream, and with the means, quats, scales, viewmat (HOST memory), fx, fy, cx, cy and eps2d of the
+ *   vp_splat_project call before it; the workspace is only read.  grad_logits f32 planar [D,H,W] and grad_alpha f32 [H,W],
+ *   each may be NULL (read as 0).  Writes, each only when its pointer is not NULL: grad_means f32 [N,3], grad_quats f32
+ *   [N,4], grad_scales f32 [N,3], grad_features f32 [N,D], grad_opacities f32 [N], grad_screen f32 [N,5], all contiguous.
+ *   grad_features and grad_opacities are bit-identical to vp_splat_rasterize_backward's on the same inputs.  means, quats,
+ *   scales and the camera are read only when grad_means, grad_quats or grad_scales is asked for (they may be NULL
+ *   otherwise).  When the device count exceeds `capacity` nothing is written and *status (device i32, may be NULL; not
+ *   reset) is set to 1.  Asynchronous on `stream`, no allocation.  Refused on the host as vp_splat_rasterize_backward
+ *   refuses, with its scratch measured by vp_splat_geometry_backward_workspace_bytes, and, when a world-space gradient is
+ *   asked for, as vp_splat_project refuses its Gaussian arrays and camera (VP_EINVAL).
+ */
+size_t vp_splat_geometry_backward_workspace_bytes(int64_t capacity, int D);
+int vp_splat_rasterize_backward_geometry(const float *means, const float *quats, const float *scales, const float *features,
+                                         int D, int64_t row_stride, int64_t n_gaussians, const float *viewmat, float fx,
+                                         float fy, float cx, float cy, int W, int H, float eps2d, int64_t capacity,
+                                         const float *grad_logits, const float *grad_alpha, float *grad_means,
+                                         float *grad_quats, float *grad_scales, float *grad_features, float *grad_opacities,
+                                         float *grad_screen, int32_t *status, void *workspace, size_t workspace_bytes,
+                                         void *bwd_workspace, size_t bwd_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,9 +15,12 @@ leg committed under profiles/ (r08_splat_*).
 
 With --backward, every logits-on leg adds a splat_backward_ms_per_view line: vp_splat_rasterize (logits and alpha) and
 vp_splat_rasterize_backward (random gradients on both) on view 0, and their ratio (profiles/r09_splat_backward*).
+With --geometry as well, one more splat_geometry_backward_ms_per_view line per leg: the fused
+vp_splat_rasterize_backward_geometry asking for every gradient (means, quats, scales, features, opacities) beside the
+existing backward on the same view and gradients, timed in alternation, and their ratio (profiles/r10_splat_geometry*).
 
 python tools/bench_splat.py [--steps K] [--warmup W] [--g 200000 1000000] [--d 13 32] [--size 876x584 1600x1067]
-[--logits off on] [--views V] [--backward]"""
+[--logits off on] [--views V] [--backward [--geometry]]"""
 import argparse
 import json
 import os
@@ -55,7 +58,11 @@ def main(argv=None):
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--backward", action="store_true",
                     help="after each logits-on leg, one splat_backward_ms_per_view line: rasterize forward vs backward")
+    ap.add_argument("--geometry", action="store_true",
+                    help="with --backward: one splat_geometry_backward_ms_per_view line: the fused geometry backward vs the backward")
     args = ap.parse_args(argv)
+    if args.geometry and not args.backward:
+        ap.error("--geometry needs --backward")
     dev = torch.device("cuda:0")
     for G in args.g:
         g = sg.make_gaussians(G, seed=0)
@@ -121,6 +128,20 @@ def backward_leg(t, feats, G, W, H, vm, K, ws, cap, args):
                raster_bwd_ms=round(bwd_ms, 4), bwd_over_fwd=round(bwd_ms / fwd_ms, 2), n_isect=cap,
                bwd_scratch_MB=round(bws.capacity() / 2 ** 20, 1), steps=args.steps, warmup=args.warmup)
     print(json.dumps(res), flush=True)
+    if args.geometry:
+        gws = voxproj_host.SplatWorkspace()
+        old = lambda i: voxproj_host.splat_rasterize_backward(feats, G, W, H, cap, ws, g_logits, g_alpha,  # noqa: E731
+                                                              bwd_workspace=bws)
+        new = lambda i: voxproj_host.splat_rasterize_backward_geometry(  # noqa: E731
+            t["means"], t["quats"], t["scales"], feats, vm, K, W, H, cap, ws, g_logits, g_alpha, bwd_workspace=gws)
+        # alternated twice: the two readings of each show the run-to-run spread next to the ratio
+        ms = [timed(fn, args.steps, args.warmup) for fn in (old, new, old, new)]
+        bwd, geo = min(ms[0], ms[2]), min(ms[1], ms[3])
+        res = dict(metric="splat_geometry_backward_ms_per_view", G=G, D=D, W=W, H=H, raster_bwd_ms=round(bwd, 4),
+                   geometry_bwd_ms=round(geo, 4), geometry_over_bwd=round(geo / bwd, 3),
+                   raster_bwd_ms_runs=[round(ms[0], 4), round(ms[2], 4)], geometry_bwd_ms_runs=[round(ms[1], 4), round(ms[3], 4)],
+                   n_isect=cap, geometry_scratch_MB=round(gws.capacity() / 2 ** 20, 1), steps=args.steps, warmup=args.warmup)
+        print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
