@@ -99,3 +99,62 @@ def grad_bound(M, Gs, rel=1e-4, abs_=1e-6):
     """The bound the GPU tests hold every gradient entry to: rel * M + abs_ * max|G| over the upstream gradients ``Gs``."""
     gmax = max((float(np.abs(np.asarray(x)).max()) for x in Gs if x is not None and np.asarray(x).size), default=0.0)
     return rel * np.asarray(M) + abs_ * gmax
+
+
+def splat_grad64_at(means, quats, scales, opacities, features, viewmat, K, W, H, pixels, G, G_alpha=None, near=0.01, far=1e10,
+                    eps2d=0.3, cond=True, rec=None):
+    """splat_grad64 for a loss whose upstream gradients are nonzero only at the (row, col) ``pixels`` [P,2]: G [P,D] and
+    G_alpha [P] (None: 0) are their values there.  Built on splat_reference.pixel64 (one pixel against every kept Gaussian,
+    no tiles).  dict(grad_f [N,D], grad_o [N], grad_screen [N,5] (the five sums of splat_geom_reference: dL/d mean2d x, y,
+    dL/d conic A, B, C), M_f, M_o, M_screen, X_f, X_o, X_screen, fragile bool [P], visits int [P], added int [N]).
+
+    X_*: the conditioning terms of the bound, to be added to grad_bound(M_*, ...).  grad_f sums G w, and w is off by at most
+    E relative (splat_reference's derivation): X_f = sum_p |G| w E.  Every term of dL/da e^-sigma and of dL/da o e^-sigma (A dx
+    + B dy) is a product of factors a, 1 - a, 1 / (1 - a) and e^-sigma of the Gaussians the pixel added, each at most twice, so
+    it is off by at most e^(2 S) - 1 relative, S = sum_k (d_k + y_k) over them: X_o and X_screen are M_o's and M_screen's
+    sums with every pixel's term times that factor (coarse on purpose; 0 where the pixel's Gaussians are well conditioned)."""
+    f = np.asarray(features, np.float64)
+    N, D = f.shape
+    rec = rec if rec is not None else ref.records(means, quats, scales, opacities, viewmat, K, W, H, near, far, eps2d)
+    pixels = np.asarray(pixels, np.int64).reshape(-1, 2)
+    P = len(pixels)
+    G = np.asarray(G, np.float64).reshape(P, D)
+    Ga = np.zeros(P) if G_alpha is None else np.asarray(G_alpha, np.float64).reshape(P)
+    out = {k: np.zeros((N, D)) for k in ("grad_f", "M_f", "X_f")}
+    out.update({k: np.zeros(N) for k in ("grad_o", "M_o", "X_o")})
+    out.update({k: np.zeros((N, 5)) for k in ("grad_screen", "M_screen", "X_screen")})
+    added = np.zeros(N, np.int64)
+    fragile, visits = np.zeros(P, bool), np.zeros(P, np.int64)
+    for p, (i, j) in enumerate(pixels):
+        r = ref.pixel64(rec, int(i), int(j), cond)
+        fragile[p], visits[p] = r["fragile"], len(r["sel"])
+        g = rec["order"][r["sel"]]
+        added[g] += 1
+        if not len(g) or (not G[p].any() and Ga[p] == 0):
+            continue
+        a, T, w, e, raw, dx, dy = (r[k] for k in ("a", "T", "w", "e", "raw", "dx", "dy"))
+        fG, fGabs = f[g] @ G[p], np.abs(f[g]) @ np.abs(G[p])
+        CG, CGabs = float((w * fG).sum()), float((w * fGabs).sum())
+        Pfx = np.cumsum(w * fG)
+        inv = 1.0 / (1.0 - a)
+        dLda = T * fG - (CG - Pfx) * inv + Ga[p] * r["T_final"] * inv
+        dLda_abs = T * fGabs + CGabs * inv + abs(Ga[p]) * r["T_final"] * inv
+        live = raw < ref.ALPHA_MAX
+        X = np.expm1(min(2.0 * r["S"], 700.0))
+        out["grad_f"][g] += w[:, None] * G[p][None]
+        out["M_f"][g] += w[:, None] * np.abs(G[p])[None]
+        out["X_f"][g] += (w * r["E"])[:, None] * np.abs(G[p])[None]
+        dado = np.where(live, e, 0.0)
+        out["grad_o"][g] += dLda * dado
+        out["M_o"][g] += dLda_abs * dado
+        out["X_o"][g] += dLda_abs * dado * X
+        A, B, C = rec["A"][r["sel"]], rec["B"][r["sel"]], rec["C"][r["sel"]]
+        q, qa = np.where(live, dLda * raw, 0.0), np.where(live, dLda_abs * raw, 0.0)
+        s = np.stack([-q * (A * dx + B * dy), -q * (B * dx + C * dy), -q * 0.5 * dx * dx, -q * dx * dy, -q * 0.5 * dy * dy], 1)
+        ms = np.stack([qa * (np.abs(A * dx) + np.abs(B * dy)), qa * (np.abs(B * dx) + np.abs(C * dy)), qa * 0.5 * dx * dx,
+                       qa * np.abs(dx * dy), qa * 0.5 * dy * dy], 1)
+        out["grad_screen"][g] += s
+        out["M_screen"][g] += ms
+        out["X_screen"][g] += ms * X
+    out.update(fragile=fragile, visits=visits, added=added)
+    return out

@@ -5,7 +5,11 @@ Bounds, on the pixels the oracle does not mark fragile (no decision within a rel
 top-2 gap within 2B):
   logits     |out - out64| <= B = 1e-4 * max_g |f_g| + 1e-6.  A logit is sum_g f_g w_g with sum_g w_g <= 1; the kernel's
              weights differ from float64 by the fp32 rounding of mean2d / conic (shared with the oracle, which rounds them
-             the same way), of sigma, exp and the running product T: a few 1e-6 relative at most, more than 10x inside B.
+             the same way), of sigma, exp and the running product T.  On the scenes of this file (scales log-normal with
+             sigma 0.6, no needles) that is a few 1e-6 relative, more than 10x inside B.  It is not so for every input: fp32
+             sigma is off by up to SIGMA_GAMMA 2^-24 (0.5 (A dx^2 + C dy^2) + |B dx dy|), which reaches 3e-3 for a thin Gaussian
+             across the pixel axes; splat_reference.py derives that bound, and test_gpu_splat_scale.py and
+             test_gpu_splat_cameras.py hold production-size and badly conditioned scenes to it.
   alpha      |alpha - alpha64| <= 1e-5 (the same weights, f = 1).
   labels     exact.
   confidence |conf - conf64| <= 2B + 1e-6 (softmax top-1 minus top-2 moves by at most twice the largest logit change).
