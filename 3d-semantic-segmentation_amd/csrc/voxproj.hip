@@ -686,25 +686,10 @@ int vp_splat_project(const float *means, const float *quats, const float *scales
     return VP_OK;
 }
 
-int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H, int64_t capacity,
-                       int32_t *labels, float *confidence, float *alpha, float *logits, int32_t *status, void *workspace,
-                       size_t workspace_bytes, void *stream_)
+// emit the (tile, depth) keys of the projected Gaussians, sort them and find every tile's run: what the blend reads
+static int splat_sort_tiles(char *ws, const SplatLayout &l, int64_t n_gaussians, int64_t capacity, int32_t *status,
+                            hipStream_t stream)
 {
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
-        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
-    if (!labels || (n_gaussians > 0 && !features)) return fail(VP_EINVAL, "null pointer argument (labels or features)");
-    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
-    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
-    hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
     const long long n_tiles = (long long)l.tiles_x * l.tiles_y;
     const long long *total = (const long long *)(ws + l.total);
     unsigned long long *k0 = (unsigned long long *)(ws + l.keys0), *k1 = (unsigned long long *)(ws + l.keys1);
@@ -728,10 +713,36 @@ int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t
                            (long long)capacity, ranges);
         VP_HIP(hipGetLastError());
     }
+    return VP_OK;
+}
+
+int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H, int64_t capacity,
+                       int32_t *labels, float *confidence, float *alpha, float *logits, int32_t *status, void *workspace,
+                       size_t workspace_bytes, void *stream_)
+{
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
+        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
+    if (!labels || (n_gaussians > 0 && !features)) return fail(VP_EINVAL, "null pointer argument (labels or features)");
+    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
+    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
+    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    const long long *total = (const long long *)(ws + l.total);
+    const int *v1 = (const int *)(ws + l.vals1);
+    const longlong2 *ranges = (const longlong2 *)(ws + l.ranges);
+    if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
     const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
 #define VP_SPLAT(DT) hipLaunchKernelGGL((k_splat_blend<DT>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), v1, ranges, \
                                         total, (long long)capacity, features, D, (long long)row_stride, W, H, (int *)labels, \
-                                        confidence, alpha, logits)
+                                        confidence, alpha, logits, SplatLoss{})
     if (D <= 8) VP_SPLAT(8);
     else if (D <= 16) VP_SPLAT(16);
     else if (D <= 32) VP_SPLAT(32);
@@ -781,7 +792,7 @@ int vp_splat_rasterize_backward(const float *features, int D, int64_t row_stride
 #define VP_SPLAT_BWD(DT) hipLaunchKernelGGL((k_splat_blend_backward<DT, false>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), \
                                             (const int4 *)(ws + l.box), count, offs, (const int *)(ws + l.vals1),             \
                                             (const longlong2 *)(ws + l.ranges), total, (long long)capacity, features, D,      \
-                                            (long long)row_stride, W, H, grad_logits, grad_alpha, part)
+                                            (long long)row_stride, W, H, grad_logits, grad_alpha, part, SplatLoss{})
     if (D <= 8) VP_SPLAT_BWD(8);
     else if (D <= 16) VP_SPLAT_BWD(16);
     else if (D <= 32) VP_SPLAT_BWD(32);
@@ -861,7 +872,7 @@ int vp_splat_rasterize_backward_geometry(const float *means, const float *quats,
 #define VP_SPLAT_BWD(DT) hipLaunchKernelGGL((k_splat_blend_backward<DT, true>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), \
                                             (const int4 *)(ws + l.box), count, offs, (const int *)(ws + l.vals1),                  \
                                             (const longlong2 *)(ws + l.ranges), total, (long long)capacity, features, D,           \
-                                            (long long)row_stride, W, H, grad_logits, grad_alpha, part)
+                                            (long long)row_stride, W, H, grad_logits, grad_alpha, part, SplatLoss{})
     if (D <= 8) VP_SPLAT_BWD(8);
     else if (D <= 16) VP_SPLAT_BWD(16);
     else if (D <= 32) VP_SPLAT_BWD(32);
@@ -873,6 +884,170 @@ int vp_splat_rasterize_backward_geometry(const float *means, const float *quats,
 #define VP_SPLAT_RED(GS) hipLaunchKernelGGL((k_splat_grad_reduce_geom<GS>), dim3(g_red), dim3(256), 0, stream, count, offs, \
                                             (long long)n_gaussians, total, (long long)capacity, part, D, grad_features,       \
                                             grad_opacities, grad_screen, (int *)status)
+    if (gs == 16) VP_SPLAT_RED(16);
+    else if (gs == 32) VP_SPLAT_RED(32);
+    else VP_SPLAT_RED(64);
+#undef VP_SPLAT_RED
+    VP_HIP(hipGetLastError());
+    if (chain) {
+        hipLaunchKernelGGL(k_splat_geom_chain, dim3((unsigned)((n_gaussians + 255) / 256)), dim3(256), 0, stream, means, quats,
+                           scales, (long long)n_gaussians, cam, count, offs, total, (long long)capacity, (const float *)part, D,
+                           grad_means, grad_quats, grad_scales);
+        VP_HIP(hipGetLastError());
+    }
+    return VP_OK;
+}
+
+size_t vp_splat_loss_workspace_bytes(int W, int H)
+{
+    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH) return 0;
+    const size_t n_tiles = (size_t)((W + SPLAT_TILE - 1) / SPLAT_TILE) * (size_t)((H + SPLAT_TILE - 1) / SPLAT_TILE);
+    return align256(n_tiles * sizeof(double2));
+}
+
+int vp_splat_rasterize_loss(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H,
+                            int64_t capacity, const int32_t *target, const float *pixel_weight, double *loss_stats,
+                            float *pixel_loss, int32_t *labels, float *confidence, float *alpha, float *logits,
+                            int32_t *status, void *workspace, size_t workspace_bytes, void *loss_workspace, size_t loss_bytes,
+                            void *stream_)
+{
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
+        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
+    if (n_gaussians > 0 && !features) return fail(VP_EINVAL, "null pointer argument (features)");
+    if (!target || !loss_stats) return fail(VP_EINVAL, "null pointer argument (target or loss_stats)");
+    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
+    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
+    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    if (!loss_workspace) return fail(VP_EWORKSPACE, "loss workspace is NULL");
+    if ((uintptr_t)loss_workspace & 255) return fail(VP_EWORKSPACE, "loss workspace must be 256-byte aligned");
+    const size_t loss_need = vp_splat_loss_workspace_bytes(W, H);
+    if (loss_bytes < loss_need) return fail(VP_EWORKSPACE, "loss workspace has %zu bytes, need %zu", loss_bytes, loss_need);
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    const long long *total = (const long long *)(ws + l.total);
+    const int *v1 = (const int *)(ws + l.vals1);
+    const longlong2 *ranges = (const longlong2 *)(ws + l.ranges);
+    if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
+    SplatLoss ls = {};
+    ls.target = (const int *)target;
+    ls.weight = pixel_weight;
+    ls.pixel_loss = pixel_loss;
+    ls.tile_sums = (double2 *)loss_workspace;
+    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+#define VP_SPLAT(DT) hipLaunchKernelGGL((k_splat_blend<DT, true>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), v1, \
+                                        ranges, total, (long long)capacity, features, D, (long long)row_stride, W, H,        \
+                                        (int *)labels, confidence, alpha, logits, ls)
+    if (D <= 8) VP_SPLAT(8);
+    else if (D <= 16) VP_SPLAT(16);
+    else if (D <= 32) VP_SPLAT(32);
+    else VP_SPLAT(64);
+#undef VP_SPLAT
+    VP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_splat_loss_sum, dim3(1), block, 0, stream, (const double2 *)loss_workspace,
+                       (long long)l.tiles_x * l.tiles_y, total, (long long)capacity, loss_stats);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_splat_loss_backward(const float *means, const float *quats, const float *scales, const float *features, int D,
+                           int64_t row_stride, int64_t n_gaussians, const float *viewmat, float fx, float fy, float cx,
+                           float cy, int W, int H, float eps2d, int64_t capacity, const int32_t *target,
+                           const float *pixel_weight, const float *logits, const double *loss_stats, int reduction,
+                           const float *grad_loss, const float *grad_alpha, float *grad_means, float *grad_quats,
+                           float *grad_scales, float *grad_features, float *grad_opacities, float *grad_screen,
+                           int32_t *status, void *workspace, size_t workspace_bytes, void *bwd_workspace, size_t bwd_bytes,
+                           void *stream_)
+{
+    const bool chain = grad_means || grad_quats || grad_scales;
+    const bool geom = chain || grad_screen;
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
+        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
+    if (n_gaussians > 0 && !features) return fail(VP_EINVAL, "null pointer argument (features)");
+    if (!target || !loss_stats) return fail(VP_EINVAL, "null pointer argument (target or loss_stats)");
+    if (reduction != VP_LOSS_SUM && reduction != VP_LOSS_MEAN)
+        return fail(VP_EINVAL, "reduction = %d is neither VP_LOSS_SUM nor VP_LOSS_MEAN", reduction);
+    if (chain && n_gaussians > 0 && (!means || !quats || !scales))
+        return fail(VP_EINVAL, "null pointer argument (means, quats or scales, needed by grad_means / grad_quats / grad_scales)");
+    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
+    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
+    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    SplatCam cam = {};
+    if (chain) {
+        if (!viewmat) return fail(VP_EINVAL, "null viewmat");
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(viewmat[k])) return fail(VP_EINVAL, "viewmat[%d] is not finite", k);
+        if (!(fx > 0.0f) || !(fy > 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+            return fail(VP_EINVAL, "fx, fy must be finite and > 0, cx, cy finite (got %g %g %g %g)", (double)fx, (double)fy,
+                        (double)cx, (double)cy);
+        if (!(eps2d >= 0.0f) || !std::isfinite(eps2d)) return fail(VP_EINVAL, "need a finite eps2d >= 0 (got %g)", (double)eps2d);
+        for (int k = 0; k < 12; ++k) cam.r[k] = viewmat[k];
+        cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy; cam.eps2d = eps2d;
+        cam.W = W; cam.H = H;
+    }
+    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    if (!bwd_workspace) return fail(VP_EWORKSPACE, "backward workspace is NULL");
+    if ((uintptr_t)bwd_workspace & 255) return fail(VP_EWORKSPACE, "backward workspace must be 256-byte aligned");
+    const size_t bwd_need = geom ? splat_geom_bytes(capacity, D) : splat_bwd_bytes(capacity, D);
+    if (bwd_bytes < bwd_need)
+        return fail(VP_EWORKSPACE, "backward workspace has %zu bytes, need %zu", bwd_bytes, bwd_need);
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
+    if (n_gaussians == 0) return VP_OK;                  // no rows to write; nothing can exceed a capacity of 0 either
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    const long long *total = (const long long *)(ws + l.total);
+    const int *count = (const int *)(ws + l.count);
+    const long long *offs = (const long long *)(ws + l.offs);
+    float *part = (float *)bwd_workspace;
+    SplatLoss ls = {};
+    ls.target = (const int *)target;
+    ls.weight = pixel_weight;
+    ls.stats = loss_stats;
+    ls.grad_loss = grad_loss;
+    ls.mean = reduction == VP_LOSS_MEAN;
+    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+#define VP_SPLAT_BWD(DT, GEOM) hipLaunchKernelGGL((k_splat_blend_backward<DT, GEOM, true>), grid, block, 0, stream,            \
+                                                  (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), count, offs,     \
+                                                  (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges), total,      \
+                                                  (long long)capacity, features, D, (long long)row_stride, W, H, logits,       \
+                                                  grad_alpha, part, ls)
+    if (geom) {
+        if (D <= 8) VP_SPLAT_BWD(8, true);
+        else if (D <= 16) VP_SPLAT_BWD(16, true);
+        else if (D <= 32) VP_SPLAT_BWD(32, true);
+        else VP_SPLAT_BWD(64, true);
+    } else {
+        if (D <= 8) VP_SPLAT_BWD(8, false);
+        else if (D <= 16) VP_SPLAT_BWD(16, false);
+        else if (D <= 32) VP_SPLAT_BWD(32, false);
+        else VP_SPLAT_BWD(64, false);
+    }
+#undef VP_SPLAT_BWD
+    VP_HIP(hipGetLastError());
+    const int gs = splat_reduce_group(geom ? D + SPLAT_SCREEN : D);
+    const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / gs - 1) / (256 / gs), 2048LL);
+#define VP_SPLAT_RED(GS)                                                                                                       \
+    do {                                                                                                                       \
+        if (geom)                                                                                                              \
+            hipLaunchKernelGGL((k_splat_grad_reduce_geom<GS>), dim3(g_red), dim3(256), 0, stream, count, offs,                 \
+                               (long long)n_gaussians, total, (long long)capacity, part, D, grad_features, grad_opacities,     \
+                               grad_screen, (int *)status);                                                                    \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((k_splat_grad_reduce<GS>), dim3(g_red), dim3(256), 0, stream, count, offs,                      \
+                               (long long)n_gaussians, total, (long long)capacity, (const float *)part, D, grad_features,      \
+                               grad_opacities, (int *)status);                                                                 \
+    } while (0)
     if (gs == 16) VP_SPLAT_RED(16);
     else if (gs == 32) VP_SPLAT_RED(32);
     else VP_SPLAT_RED(64);

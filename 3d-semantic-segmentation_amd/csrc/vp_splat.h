@@ -35,6 +35,10 @@ namespace {
 //   Epilogue: label = argmax over the D channels (lowest index on ties), confidence = softmax top-1 minus top-2
 //   = (1 - exp(m2 - m1)) / sum_c exp(f_c - m1) (1 when D = 1), alpha = 1 - T; logits planar [D, H, W].  Only the outputs
 //   whose pointer is non-NULL are written.
+// k_splat_blend<DT, true> (vp_splat_rasterize_loss) is the same blend with a softmax cross-entropy epilogue: per pixel
+//   l = (m + logf(sum_c expf(C_c - m))) - C_t from its accumulators (m and the sum are the confidence's), weight w (0 when
+//   the target is outside [0, D)); pixel_loss = w l; the workgroup reduces {w l, w} in float64 through a fixed halving tree
+//   (in the feature rows' LDS) to one pair per tile.  k_splat_loss_sum (one workgroup) sums the pairs in ascending tile index.
 // Every kernel after the scan reads the device total first: a total above the workspace's capacity writes nothing (the
 // emit kernel raises *status instead), so a too-small workspace never leaves a partial image.
 // ------------------------------------------------------------------------------------------------
@@ -191,17 +195,61 @@ __global__ __launch_bounds__(256) void k_splat_ranges(const unsigned long long *
     if (i == total - 1) ranges[tile].y = total;
 }
 
+// What the loss variants of the blend kernels read and write besides the images (vp_splat_rasterize_loss,
+// vp_splat_loss_backward); all NULL / 0 in the plain variants, which never look at it.
+struct SplatLoss {
+    const int *target;           // [H,W]; valid when 0 <= target < D
+    const float *weight;         // [H,W] or NULL (1)
+    float *pixel_loss;           // forward: [H,W] or NULL
+    double2 *tile_sums;          // forward: {sum w l, sum w} per tile
+    const double *stats;         // backward, MEAN: {sum w l, sum w}
+    const float *grad_loss;      // backward: [1] or NULL (1)
+    int mean;                    // backward: VP_LOSS_MEAN
+};
+
+// The loss's upstream gradient of one pixel, in place: c[] holds the pixel's D blended logits (the forward's bits) and
+// becomes G[c] = sw (expf(C_c - m) / sum - [c == t]), 0 past D; sw = s w_p, 0 on an ignored pixel.  One function for the
+// replay and the saved arm of the backward: the same fp32 operations, so the same bits.
 template <int DT>
+__device__ inline void splat_loss_grad(float (&c)[DT], int D, int t, float sw)
+{
+    float m = c[0];
+#pragma unroll
+    for (int k = 1; k < DT; ++k)
+        if (k < D && c[k] > m) m = c[k];
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < DT; ++k)
+        if (k < D) {
+            c[k] = expf(c[k] - m);
+            s += c[k];
+        }
+#pragma unroll
+    for (int k = 0; k < DT; ++k) c[k] = k < D && sw != 0.0f ? sw * (c[k] / s - (k == t ? 1.0f : 0.0f)) : 0.0f;
+}
+
+// the scale s of the loss's gradient, read on the device: grad_loss (1 when NULL), over sum w for MEAN (0 when sum w = 0)
+__device__ inline float splat_loss_scale(const SplatLoss &ls)
+{
+    const float g = ls.grad_loss ? *ls.grad_loss : 1.0f;
+    if (!ls.mean) return g;
+    const double sw = ls.stats[1];
+    return sw > 0.0 ? (float)((double)g / sw) : 0.0f;
+}
+
+template <int DT, bool LOSS = false>
 __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
     const SplatRec *__restrict__ rec, const int *__restrict__ vals, const longlong2 *__restrict__ ranges,
     const long long *total_p, long long capacity, const float *__restrict__ feats, int D, long long stride, int W, int H,
-    int *__restrict__ labels, float *__restrict__ confidence, float *__restrict__ alpha_out, float *__restrict__ logits)
+    int *__restrict__ labels, float *__restrict__ confidence, float *__restrict__ alpha_out, float *__restrict__ logits,
+    SplatLoss ls)
 {
     constexpr int NB = splat_batch(DT);
     __shared__ float4 s_ga[NB];              // mx, my, A, B
     __shared__ float2 s_gb[NB];              // C, o
     __shared__ int s_id[NB];
-    __shared__ float s_f[NB * DT];            // feature rows, zero past D
+    __shared__ __attribute__((aligned(16))) float s_f[NB * DT];   // feature rows, zero past D; the loss's tile sums at the end
+    static_assert(NB * DT * sizeof(float) >= SPLAT_THREADS * sizeof(double2), "the tile sums reuse the feature rows' LDS");
     if (*total_p > capacity) return;
     const int tid = threadIdx.x;
     const int px = blockIdx.x * SPLAT_TILE + (tid & (SPLAT_TILE - 1)), py = blockIdx.y * SPLAT_TILE + tid / SPLAT_TILE;
@@ -251,32 +299,91 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
             }
         }
     }
-    if (!inside) return;
+    if (!LOSS && !inside) return;
     const long long pix = (long long)py * W + px, hw = (long long)H * W;
-    float m1 = acc[0];
-    int lab = 0;
+    double2 sums = make_double2(0.0, 0.0);    // LOSS: this pixel's {w l, w}
+    if (inside) {
+        float m1 = acc[0];
+        int lab = 0;
 #pragma unroll
-    for (int c = 1; c < DT; ++c)
-        if (c < D && acc[c] > m1) {
-            m1 = acc[c];
-            lab = c;
-        }
-    labels[pix] = lab;
-    if (confidence) {
-        float m2 = -INFINITY, s = 0.0f;
-#pragma unroll
-        for (int c = 0; c < DT; ++c)
-            if (c < D) {
-                if (c != lab && acc[c] > m2) m2 = acc[c];
-                s += expf(acc[c] - m1);
+        for (int c = 1; c < DT; ++c)
+            if (c < D && acc[c] > m1) {
+                m1 = acc[c];
+                lab = c;
             }
-        confidence[pix] = D == 1 ? 1.0f : (1.0f - expf(m2 - m1)) / s;
-    }
-    if (alpha_out) alpha_out[pix] = 1.0f - T;
-    if (logits) {
+        if (!LOSS || labels) labels[pix] = lab;
+        float m2 = -INFINITY, s = 0.0f;
+        if (confidence || LOSS) {
 #pragma unroll
-        for (int c = 0; c < DT; ++c)
-            if (c < D) logits[c * hw + pix] = acc[c];
+            for (int c = 0; c < DT; ++c)
+                if (c < D) {
+                    if (c != lab && acc[c] > m2) m2 = acc[c];
+                    s += expf(acc[c] - m1);
+                }
+        }
+        if (confidence) confidence[pix] = D == 1 ? 1.0f : (1.0f - expf(m2 - m1)) / s;
+        if (alpha_out) alpha_out[pix] = 1.0f - T;
+        if (logits) {
+#pragma unroll
+            for (int c = 0; c < DT; ++c)
+                if (c < D) logits[c * hw + pix] = acc[c];
+        }
+        if constexpr (LOSS) {
+            // l = (m + logf(sum_c expf(C_c - m))) - C_t: m1 is the maximum and s the confidence's sum, channels ascending
+            const int t = ls.target[pix];
+            const bool valid = t >= 0 && t < D;
+            const float w = valid ? (ls.weight ? ls.weight[pix] : 1.0f) : 0.0f;
+            float ct = 0.0f;
+#pragma unroll
+            for (int c = 0; c < DT; ++c)
+                if (c == t) ct = acc[c];
+            const float wl = w != 0.0f ? w * ((m1 + logf(s)) - ct) : 0.0f;     // weight 0 contributes nothing, whatever l is
+            if (ls.pixel_loss) ls.pixel_loss[pix] = wl;
+            sums = make_double2((double)wl, (double)w);
+        }
+    }
+    if constexpr (LOSS) {
+        // the tile's pair in float64: a fixed halving tree over the 256 pixels, in the feature rows' LDS
+        double2 *s_sum = (double2 *)s_f;
+        __syncthreads();
+        s_sum[tid] = sums;
+        __syncthreads();
+        for (int h = SPLAT_THREADS / 2; h >= 1; h /= 2) {
+            if (tid < h) {
+                const double2 a = s_sum[tid], b = s_sum[tid + h];
+                s_sum[tid] = make_double2(a.x + b.x, a.y + b.y);
+            }
+            __syncthreads();
+        }
+        if (tid == 0) ls.tile_sums[(long long)blockIdx.y * gridDim.x + blockIdx.x] = s_sum[0];
+    }
+}
+
+// loss_stats = the tile pairs summed in float64 in ascending tile index.  One workgroup: its threads stage 256 pairs at a
+// time in LDS, thread 0 adds them in order (float64 addition is not associative: the order is the contract).
+__global__ __launch_bounds__(SPLAT_THREADS) void k_splat_loss_sum(const double2 *__restrict__ tile_sums, long long n_tiles,
+                                                                   const long long *total_p, long long capacity,
+                                                                   double *__restrict__ loss_stats)
+{
+    __shared__ double2 s_sum[SPLAT_THREADS];
+    if (*total_p > capacity) return;
+    const int tid = threadIdx.x;
+    double2 a = make_double2(0.0, 0.0);
+    for (long long t0 = 0; t0 < n_tiles; t0 += SPLAT_THREADS) {
+        const int n = (int)(n_tiles - t0 < SPLAT_THREADS ? n_tiles - t0 : SPLAT_THREADS);
+        __syncthreads();
+        if (tid < n) s_sum[tid] = tile_sums[t0 + tid];
+        __syncthreads();
+        if (tid == 0)
+#pragma unroll 8
+            for (int k = 0; k < n; ++k) {      // unrolled: the LDS reads run ahead of the dependent additions
+                a.x += s_sum[k].x;
+                a.y += s_sum[k].y;
+            }
+    }
+    if (tid == 0) {
+        loss_stats[0] = a.x;
+        loss_stats[1] = a.y;
     }
 }
 
@@ -311,6 +418,10 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
 //   The features' and the opacity's partials are computed exactly as without GEOM: bit-identical gradients.
 // The LDS product was kept against a wave-shuffle reduction of the same sweep (profiles/r09_splat_backward_ab.log): the
 // shuffles' butterfly costs more VALU issue at D = 32 than the product's LDS traffic.
+// k_splat_blend_backward<DT, GEOM, true> (vp_splat_loss_backward) computes its upstream gradient instead of loading it:
+//   G = s w (softmax(C) - onehot(target)) per pixel (splat_loss_grad), with C either read from the logits image the forward
+//   wrote (saved) or blended again in a sweep 0 before sweep 1 (replay: the forward's fp32 operations in its order, gr[] as
+//   the accumulators, so the two arms give the same bits).  s is read on the device (splat_loss_scale).  No LDS is added.
 // Both kernels write nothing when the device total exceeds the capacity (the reduce raises *status).
 // ------------------------------------------------------------------------------------------------
 // Gaussians per backward batch.  LDS: G (256 DT) + W and Q (2 NB 260) + features (NB DT) floats = 100 KiB at DT 32 and 64
@@ -325,12 +436,13 @@ __device__ inline long long splat_slot(const long long *__restrict__ offs, const
     return offs[g] - count[g] + (long long)((int)blockIdx.y - b.y) * (b.z - b.x + 1) + ((int)blockIdx.x - b.x);
 }
 
-template <int DT, bool GEOM>
+template <int DT, bool GEOM, bool LOSS = false>
 __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
     const SplatRec *__restrict__ rec, const int4 *__restrict__ box, const int *__restrict__ count,
     const long long *__restrict__ offs, const int *__restrict__ vals, const longlong2 *__restrict__ ranges,
     const long long *total_p, long long capacity, const float *__restrict__ feats, int D, long long stride, int W, int H,
-    const float *__restrict__ grad_logits, const float *__restrict__ grad_alpha, float *__restrict__ part)
+    const float *__restrict__ grad_logits /* LOSS: the forward's logits image, NULL = replay */,
+    const float *__restrict__ grad_alpha, float *__restrict__ part, SplatLoss ls)
 {
     constexpr int NB = splat_bwd_batch(DT);
     constexpr int KPT = NB * DT / SPLAT_THREADS;          // Gaussians per thread in the product
@@ -352,10 +464,65 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
     const longlong2 rg = ranges[(long long)blockIdx.y * gridDim.x + blockIdx.x];
     const int D1 = D + (GEOM ? 1 + SPLAT_SCREEN : 1);    // floats per partial row
     float gr[DT];
+    if constexpr (LOSS) {
+        // G = s w (softmax(C) - onehot(target)) from the pixel's own logits C: read back (saved) or blended again (replay)
+        int t = -1;
+        float sw = 0.0f;
+        if (inside) {
+            t = ls.target[pix];
+            if (t >= 0 && t < D) sw = splat_loss_scale(ls) * (ls.weight ? ls.weight[pix] : 1.0f);
+        }
 #pragma unroll
-    for (int c = 0; c < DT; ++c) {
-        gr[c] = grad_logits && inside && c < D ? grad_logits[c * hw + pix] : 0.0f;
-        s_G[tid * DT + c] = gr[c];
+        for (int c = 0; c < DT; ++c) gr[c] = grad_logits && inside && c < D ? grad_logits[c * hw + pix] : 0.0f;
+        if (!grad_logits) {
+            // sweep 0: the forward's blend (the same fp32 operations in the same order), gr[] as its accumulators
+            float T = 1.0f;
+            bool done = !inside;
+            for (long long b0 = rg.x; b0 < rg.y; b0 += NB) {
+                if (__syncthreads_count(done) == SPLAT_THREADS) break;
+                const int nb = (int)(rg.y - b0 < NB ? rg.y - b0 : NB);
+                for (int k = tid; k < nb; k += SPLAT_THREADS) {
+                    const SplatRec r = rec[vals[b0 + k]];
+                    s_ga[k] = make_float4(r.mx, r.my, r.A, r.B);
+                    s_gb[k] = make_float2(r.C, r.o);
+                }
+                for (int e = tid; e < nb * DT; e += SPLAT_THREADS) {
+                    const int k = e / DT, c = e % DT;
+                    s_f[e] = c < D ? feats[(long long)vals[b0 + k] * stride + c] : 0.0f;
+                }
+                __syncthreads();
+                if (!done) {
+                    for (int k = 0; k < nb; ++k) {
+                        const float4 ga = s_ga[k];
+                        const float2 gb = s_gb[k];
+                        const float dx = ga.x - sx, dy = ga.y - sy;
+                        const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
+                        if (sigma < 0.0f) continue;
+                        const float a = fminf(0.999f, gb.y * __expf(-sigma));
+                        if (a < 1.0f / 255.0f) continue;
+                        const float Tn = T * (1.0f - a);
+                        if (Tn <= 1e-4f) {
+                            done = true;
+                            break;
+                        }
+                        const float wgt = a * T;
+                        const float *f = s_f + k * DT;
+#pragma unroll
+                        for (int c = 0; c < DT; ++c) gr[c] = fmaf(f[c], wgt, gr[c]);
+                        T = Tn;
+                    }
+                }
+            }
+        }
+        splat_loss_grad<DT>(gr, D, t, sw);
+#pragma unroll
+        for (int c = 0; c < DT; ++c) s_G[tid * DT + c] = gr[c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < DT; ++c) {
+            gr[c] = grad_logits && inside && c < D ? grad_logits[c * hw + pix] : 0.0f;
+            s_G[tid * DT + c] = gr[c];
+        }
     }
     const float ga_p = grad_alpha && inside ? grad_alpha[pix] : 0.0f;
 

@@ -1,0 +1,163 @@
+"""Refine per-Gaussian logits against per-view label maps: the step between ``query_voxel_features.py`` (which writes both
+the per-Gaussian logits and the per-view labels) and ``render_semantics_logits.py`` (which renders the logits).
+
+  refine_gaussian_logits.py --gaussians_ply point_cloud.ply --logit_path X.npz --cam_params camera_params.json
+      --targets_dir DIR [--views NAME ...] [--max_images N] [--downsample_factor F] [--principal_point center|camera]
+      [--weight confidence|none] [--steps 200] [--views_per_step 4] [--lr 0.1] [--seed 0] --out REFINED.npz
+
+Inputs: the 3DGS point cloud and the .npz of ``query_voxel_features.py gaussians`` ('logits' [N, P], 'prompts'), as
+render_semantics_logits.py reads them, with its cameras and image sizes; the targets ``DIR/<name>_labels.npy`` (int16 [H,W],
+-1 = no label; any value outside [0, P) is ignored) and, with --weight confidence, the per-pixel weights
+``DIR/<name>_confidence.npy`` (f32 [H,W]), both as ``query_voxel_features.py views`` writes them.  A target whose size
+differs from the view's render size is an error.
+
+Training: the P real channels of 'logits' (no padding) are the parameters of torch Adam; each step draws --views_per_step
+views with a seeded generator and takes the mean of their weighted cross-entropies, each one fused call
+(splat_autograd.splat_cross_entropy: no logits image, no gradient image).  Before and after, the mean loss and the share of
+labelled pixels whose rendered label agrees with the target are printed over all views.  Every kernel on the path is
+deterministic, so two runs with the same arguments write byte-identical logits.
+
+Output: --out, an .npz with the input's schema: 'labels' int16 [N] (argmax of the refined logits), 'logits' f32 [N, P],
+'prompts' (and 'colors' when the input has them), which render_semantics_logits.py --logit_path reads unchanged.
+Runs on the GPU only; there is no CPU path.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+import render_semantics_logits as rsl
+
+
+def load_target(targets_dir, name, W, H, n_classes, weight="confidence"):
+    """(target int32 [H,W] with every ignored pixel at -1, weight f32 [H,W] or None) of one view; raises ValueError when a
+    file's size is not the render size H x W."""
+    path = os.path.join(targets_dir, name + "_labels.npy")
+    lab = np.load(path)
+    if lab.shape != (H, W):
+        raise ValueError(f"{path}: the target is {lab.shape[1] if lab.ndim == 2 else '?'}x{lab.shape[0]} "
+                         f"(shape {lab.shape}) but the view renders at {W}x{H}")
+    lab = lab.astype(np.int64)
+    target = np.where((lab >= 0) & (lab < n_classes), lab, -1).astype(np.int32)
+    w = None
+    if weight == "confidence":
+        wpath = os.path.join(targets_dir, name + "_confidence.npy")
+        w = np.load(wpath)
+        if w.shape != (H, W):
+            raise ValueError(f"{wpath}: the weights have shape {w.shape} but the view renders at {W}x{H}")
+        w = np.ascontiguousarray(w, dtype=np.float32)
+    return target, w
+
+
+def save_refined(path, logits, prompts=None, colors=None):
+    """The schema of ``query_voxel_features.py gaussians``: labels int16 [N] = argmax, logits f32 [N,P], prompts."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    d = dict(labels=logits.argmax(1).astype(np.int16), logits=logits)
+    if prompts is not None:
+        d["prompts"] = np.asarray(prompts)
+    if colors is not None:
+        d["colors"] = np.asarray(colors, dtype=np.uint8)
+    np.savez(path, **d)
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Refine per-Gaussian logits against per-view label maps (fused GPU loss)")
+    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
+    ap.add_argument("--logit_path", required=True, help=".npz with 'logits' [N, P] (query_voxel_features.py gaussians)")
+    ap.add_argument("--cam_params", required=True, help="camera_params.json")
+    ap.add_argument("--targets_dir", required=True, help="<name>_labels.npy / <name>_confidence.npy per view")
+    ap.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
+    ap.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
+    ap.add_argument("--max_images", type=int, default=None)
+    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
+    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
+    ap.add_argument("--weight", choices=("confidence", "none"), default="confidence")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--views_per_step", type=int, default=4)
+    ap.add_argument("--lr", type=float, default=0.1)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", required=True, help="the refined .npz")
+    return ap
+
+
+def main(argv=None):
+    import aggregate_voxel_features_onthefly as agg
+    import gaussian_ply
+    import prepare_tensor_data as ptd
+    import splat_autograd
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.steps < 0 or args.views_per_step < 1:
+        ap.error("--steps must be >= 0 and --views_per_step >= 1")
+    if not torch.cuda.is_available():
+        raise RuntimeError("refine_gaussian_logits runs on the GPU: there is no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    g = {k: torch.from_numpy(v).to(dev) for k, v in gaussian_ply.read_gaussian_ply(args.gaussians_ply).items()}
+    d = np.load(args.logit_path)
+    if "logits" not in d:
+        raise KeyError(f"{args.logit_path}: no 'logits' array")
+    raw = np.asarray(d["logits"], dtype=np.float32)
+    if raw.ndim != 2 or raw.shape[0] != g["means"].shape[0]:
+        raise ValueError(f"{args.logit_path}: logits {raw.shape} for {g['means'].shape[0]} Gaussians")
+    P = int(raw.shape[1])
+    if not 1 <= P <= 64:
+        raise ValueError(f"{args.logit_path}: {P} classes outside [1, 64]")
+    by_name, cams = ptd.load_camera_params(args.cam_params)
+    names = args.views if args.views else sorted(by_name)
+    if args.max_images is not None:
+        names = names[:args.max_images]
+    if not names:
+        raise ValueError("no views to train on")
+    views = []
+    for name in names:
+        entry = by_name.get(name)
+        if entry is None:
+            raise KeyError(f"no camera entry for {name}")
+        H0, W0 = agg._image_size(entry, cams, args.images_dir, name)
+        W, H = rsl.render_size(W0, H0, args.downsample_factor)
+        vm, K = rsl.camera(entry, cams, W0, H0, W, H, args.principal_point)
+        target, w = load_target(args.targets_dir, name, W, H, P, args.weight)
+        views.append((vm, K, W, H, torch.from_numpy(target).to(dev), torch.from_numpy(w).to(dev) if w is not None else None))
+    param = torch.nn.Parameter(torch.from_numpy(raw).to(dev))
+    opt = torch.optim.Adam([param], lr=args.lr)
+
+    def view_loss(v):
+        vm, K, W, H, target, w = v
+        return splat_autograd.splat_cross_entropy(g["means"], g["quats"], g["scales"], g["opacities"], param, vm, K, W, H,
+                                                  target, w, reduction="mean", check=False)
+
+    def evaluate():
+        with torch.no_grad():
+            loss, agree, total = 0.0, 0, 0
+            for v in views:
+                ce, labels, _, _ = view_loss(v)
+                valid = v[4] >= 0
+                loss += float(ce)
+                agree += int((labels[valid] == v[4][valid]).sum())
+                total += int(valid.sum())
+        return loss / len(views), agree / max(total, 1), total
+
+    l0, a0, total = evaluate()
+    print(f"[REFINE] {len(views)} view(s), {total} labelled pixels, {P} classes, {raw.shape[0]} Gaussians")
+    print(f"[REFINE] before: mean loss {l0:.6f}, pixel agreement {a0:.4f}")
+    gen = torch.Generator().manual_seed(args.seed)
+    k = min(args.views_per_step, len(views))
+    for _ in range(args.steps):
+        pick = torch.randperm(len(views), generator=gen)[:k].tolist()
+        opt.zero_grad(set_to_none=True)
+        loss = 0
+        for i in pick:
+            loss = loss + view_loss(views[i])[0] / k
+        loss.backward()
+        opt.step()
+    l1, a1, _ = evaluate()
+    print(f"[REFINE] after {args.steps} step(s): mean loss {l1:.6f}, pixel agreement {a1:.4f}")
+    prompts = d["prompts"] if "prompts" in d else None
+    save_refined(args.out, param.detach().cpu().numpy(), prompts, d["colors"] if "colors" in d else None)
+    print(f"[REFINE] -> {args.out}")
+    return dict(loss_before=l0, loss_after=l1, agreement_before=a0, agreement_after=a1)
+
+
+if __name__ == "__main__":
+    main()

@@ -6,7 +6,8 @@ through the branch the forward took (include/voxproj.h states the contract).  La
 differentiable.  ``splat_features`` keeps the geometry fixed: a call whose geometry requires grad raises instead of dropping
 the gradient.  ``splat_gaussians`` is differentiable in the means, the quaternions and the activated scales as well, through
 vp_splat_rasterize_backward_geometry (one fused tile sweep for every gradient asked for).  No gradient for the camera, no
-double backward.
+double backward.  ``splat_cross_entropy`` is the fused softmax cross-entropy of the splatted logits against a per-pixel target
+map (vp_splat_rasterize_loss / vp_splat_loss_backward): no logits or gradient image crosses torch.
 
 Each call keeps its own SplatWorkspace until its backward has run (the backward reads the forward's sorted intersections),
 so calls from several threads or views share no state.  The workspace is freed after the backward, or with the graph.
@@ -16,7 +17,7 @@ from torch.autograd.function import once_differentiable
 
 import voxproj_host as _host
 
-__all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians"]
+__all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians", "splat_cross_entropy", "SplatCrossEntropy"]
 
 
 class SplatFeatures(torch.autograd.Function):
@@ -124,3 +125,69 @@ def splat_gaussians(means, quats, scales, opacities, features, viewmat, K, W, H,
                               (features, "features"))))
     return SplatGaussians.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), float(near), float(far),
                                 float(eps2d), bool(check))
+
+
+class SplatCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, quats, scales, opacities, features, viewmat, K, W, H, target, pixel_weight, reduction,
+                keep_logits, near, far, eps2d, check):
+        ws = _host.SplatWorkspace()
+        m, q, s, f = means.detach(), quats.detach(), scales.detach(), features.detach()
+        r = _host.splat_loss(m, q, s, opacities.detach(), f, viewmat, K, W, H, target, pixel_weight, want_alpha=True,
+                             want_logits=keep_logits, near=near, far=far, eps2d=eps2d, workspace=ws, check=check)
+        total, weight = r.loss_stats[0], r.loss_stats[1]
+        if reduction == "mean":
+            loss = torch.where(weight > 0, total / weight, torch.zeros_like(total))
+        else:
+            loss = total
+        ctx.ws = ws
+        ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect), reduction)
+        ctx.maps = (target, pixel_weight, r.loss_stats, r.logits)
+        ctx.save_for_backward(m, q, s, f)
+        ctx.mark_non_differentiable(r.labels, r.confidence, r.alpha)
+        return loss.float(), r.labels, r.confidence, r.alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_labels, _grad_confidence, _grad_alpha):
+        m, q, s, f = ctx.saved_tensors
+        ws, ctx.ws = ctx.ws, None
+        (target, weight, stats, logits), ctx.maps = ctx.maps, None
+        viewmat, K, W, H, eps2d, cap, reduction = ctx.view
+        want_m, want_q, want_s, want_o, want_f = ctx.needs_input_grad[:5]
+        g = dict(means=None, quats=None, scales=None, opacities=None, features=None)
+        if want_m or want_q or want_s or want_o or want_f:
+            # the scale stays on the device: the kernel reads it
+            g = _host.splat_loss_backward(m, q, s, f, viewmat, K, W, H, cap, ws, target, weight, stats, logits=logits,
+                                          reduction=reduction, grad_loss=grad_loss.float().reshape(1).contiguous(),
+                                          eps2d=eps2d, want_means=want_m, want_quats=want_q, want_scales=want_s,
+                                          want_features=want_f, want_opacities=want_o)
+        return (g["means"], g["quats"], g["scales"], g["opacities"], g["features"]) + (None,) * 12
+
+
+# True: the saved arm, the faster one at 1 M Gaussians, D = 32, 1600x1067 (7.15 ms a step against the replay arm's 8.64 ms,
+# profiles/r12_splat_loss.jsonl); False trades that for memory: no [D,H,W] image is allocated
+KEEP_LOGITS_DEFAULT = True
+
+
+def splat_cross_entropy(means, quats, scales, opacities, features, viewmat, K, W, H, target, pixel_weight=None, *,
+                        reduction="mean", keep_logits=KEEP_LOGITS_DEFAULT, near=0.01, far=1e10, eps2d=0.3, check=True):
+    """Softmax cross-entropy of the splatted features (the per-Gaussian logits) of one W x H view against a target map,
+    fused into the splatting kernels (include/voxproj.h states the contract).
+
+      means, quats, scales, opacities, features, viewmat, K   as ``splat_gaussians``; any of the five tensors may require grad
+      target int32 [H,W] on the GPU                           the class of every pixel; a value outside [0, D) ignores the pixel
+      pixel_weight f32 [H,W] or None                          per-pixel weights (None: 1)
+      reduction "mean" (sum w l / sum w; 0 when sum w = 0) or "sum"
+      keep_logits   True: the forward writes the [D,H,W] logits and the backward reads them back; False: the backward blends
+                    each pixel again and nothing of that size is allocated.  The gradients are the same bits either way.
+
+    Returns (loss f32 0-dim, labels int32 [H,W], confidence f32 [H,W], alpha f32 [H,W]); only the loss is differentiable,
+    and the backward asks only for what requires grad.  The gradient flowing into the loss is read by the kernel on the
+    device.  No double backward, no gradient for the camera."""
+    _host._require(reduction in ("mean", "sum"), f"reduction must be 'mean' or 'sum', not {reduction!r}")
+    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
+                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
+                              (features, "features"))))
+    return SplatCrossEntropy.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), target, pixel_weight,
+                                   reduction, bool(keep_logits), float(near), float(far), float(eps2d), bool(check))

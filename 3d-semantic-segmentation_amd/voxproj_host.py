@@ -56,6 +56,7 @@ EXPORTS = [
     "vp_splat_workspace_bytes", "vp_splat_project", "vp_splat_rasterize",
     "vp_splat_backward_workspace_bytes", "vp_splat_rasterize_backward",
     "vp_splat_geometry_backward_workspace_bytes", "vp_splat_rasterize_backward_geometry",
+    "vp_splat_loss_workspace_bytes", "vp_splat_rasterize_loss", "vp_splat_loss_backward",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -65,6 +66,8 @@ VP_OPT_ROW_END = 4
 VP_OPT_ONE_VIEW_GATHER = 5
 VP_OPT_PART_PIXELS = 6
 VP_OPT_ONE_VIEW_SPLIT = 7
+VP_LOSS_SUM = 0
+VP_LOSS_MEAN = 1
 
 
 class VoxprojError(RuntimeError):
@@ -197,6 +200,16 @@ def lib():
             L.vp_splat_rasterize_backward_geometry.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                                                ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
                 [ctypes.c_int] * 2 + [ctypes.c_float, ctypes.c_int64] + [vp] * 10 + [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+            L.vp_splat_loss_workspace_bytes.restype = ctypes.c_size_t
+            L.vp_splat_loss_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+            L.vp_splat_rasterize_loss.restype = ctypes.c_int
+            L.vp_splat_rasterize_loss.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int64] + [vp] * 10 + [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+            L.vp_splat_loss_backward.restype = ctypes.c_int
+            L.vp_splat_loss_backward.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                 ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
+                [ctypes.c_int] * 2 + [ctypes.c_float, ctypes.c_int64] + [vp] * 4 + [ctypes.c_int] + [vp] * 10 + \
+                [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
             if L.vp_abi_version() != VP_ABI_VERSION:
                 raise VoxprojError(f"{LIB_PATH} has ABI version {L.vp_abi_version()}, this package needs {VP_ABI_VERSION}: rebuild it")
             _lib = L
@@ -792,6 +805,159 @@ def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, 
         if n_bad:
             raise VoxprojError(f"splat_features: {n_bad} Gaussian(s) have a non-finite parameter (culled)")
     return SplatResult(labels, conf, alpha, logits, cap, bad)
+
+
+SplatLossResult = collections.namedtuple("SplatLossResult",
+                                         "loss_stats pixel_loss labels confidence alpha logits n_isect n_nonfinite")
+_REDUCTIONS = {"sum": VP_LOSS_SUM, "mean": VP_LOSS_MEAN}
+
+
+def _splat_loss_maps(target, pixel_weight, W, H, dev):
+    import torch
+    _require_tensors((target, "target", (torch.int32,)))
+    _require(tuple(target.shape) == (int(H), int(W)) and target.device == dev, f"target must be int32 [{H}, {W}] on the features' device")
+    if pixel_weight is not None:
+        _require_tensors((pixel_weight, "pixel_weight", (torch.float32,)))
+        _require(tuple(pixel_weight.shape) == (int(H), int(W)) and pixel_weight.device == dev,
+                 f"pixel_weight must be float32 [{H}, {W}] on the features' device")
+        pixel_weight = pixel_weight.contiguous()
+    return target.contiguous(), pixel_weight
+
+
+def splat_rasterize_loss(features, n_gaussians, W, H, capacity, workspace, target, pixel_weight=None, *, want_pixel_loss=False,
+                         want_labels=True, want_confidence=True, want_alpha=False, want_logits=False, loss_workspace=None,
+                         status=None):
+    """vp_splat_rasterize_loss after splat_project on ``workspace``: splat_rasterize with the fused softmax cross-entropy
+    epilogue.  target int32 [H,W] (valid when 0 <= target < D, anything else ignored), pixel_weight f32 [H,W] or None (1).
+    Returns (loss_stats f64 [2] = {sum w l, sum w} on the device, pixel_loss f32 [H,W] or None, labels, confidence, alpha,
+    logits as splat_rasterize, each None unless asked for).  ``loss_workspace``: a SplatWorkspace for the per-tile sums (a
+    fresh one when None)."""
+    import torch
+    _require_tensors((features, "features", (torch.float32,)))
+    _require(features.dim() == 2 and int(features.shape[0]) == int(n_gaussians), f"features must be [{n_gaussians}, D]")
+    D = int(features.shape[1])
+    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
+    if features.stride(1) != 1 or features.stride(0) < D:
+        features = features.contiguous()
+    dev = features.device
+    target, pixel_weight = _splat_loss_maps(target, pixel_weight, W, H, dev)
+    L = lib()
+    keep = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), 0))
+    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
+    ptr = workspace.ensure(nbytes, dev, keep=keep)
+    lw = loss_workspace if loss_workspace is not None else SplatWorkspace()
+    lptr = lw.ensure(int(L.vp_splat_loss_workspace_bytes(int(W), int(H))), dev)
+    img = lambda want, dtype, *lead: torch.empty(lead + (H, W), dtype=dtype, device=dev) if want else None  # noqa: E731
+    stats = torch.zeros(2, dtype=torch.float64, device=dev)
+    ploss = img(want_pixel_loss, torch.float32)
+    labels, conf = img(want_labels, torch.int32), img(want_confidence, torch.float32)
+    alpha, logits = img(want_alpha, torch.float32), img(want_logits, torch.float32, D)
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_splat_rasterize_loss(p(features) if features.numel() else None, D, max(int(features.stride(0)), D),
+                                            int(n_gaussians), int(W), int(H), int(capacity), p(target), p(pixel_weight),
+                                            p(stats), p(ploss), p(labels), p(conf), p(alpha), p(logits), p(status), ptr,
+                                            workspace.capacity(), lptr, lw.capacity(), stream.cuda_stream))
+    return stats, ploss, labels, conf, alpha, logits
+
+
+def splat_loss_backward(means, quats, scales, features, viewmat, K, W, H, capacity, workspace, target, pixel_weight=None,
+                        loss_stats=None, *, logits=None, reduction="mean", grad_loss=None, grad_alpha=None, eps2d=0.3,
+                        bwd_workspace=None, want_means=False, want_quats=False, want_scales=False, want_features=True,
+                        want_opacities=True, want_screen=False, status=None):
+    """vp_splat_loss_backward after splat_rasterize_loss on ``workspace``: the gradients of the (sum or mean) cross-entropy,
+    scaled by ``grad_loss`` (device f32 [1], None = 1), plus sum(grad_alpha * alpha).  ``logits``: the image the forward
+    wrote (the saved arm) or None (the replay arm: the sweep blends each pixel again); both give the same bits.
+    ``loss_stats``: the forward's, read on the device for the mean.  Without a geometry or screen gradient the call runs the
+    sweep of splat_rasterize_backward (means, quats, scales, viewmat and K may then be None), otherwise the geometry
+    sweep.  Returns the dict of splat_rasterize_backward_geometry."""
+    import torch
+    _require(reduction in _REDUCTIONS, f"reduction must be 'sum' or 'mean', not {reduction!r}")
+    _require_tensors((features, "features", (torch.float32,)))
+    _require(features.dim() == 2, "features must be [N, D]")
+    N, D = int(features.shape[0]), int(features.shape[1])
+    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
+    dev = features.device
+    if features.stride(1) != 1 or features.stride(0) < D:
+        features = features.contiguous()
+    chain = want_means or want_quats or want_scales
+    geom = chain or want_screen
+    vm, fx, fy, cx, cy = None, 1.0, 1.0, 0.0, 0.0
+    if chain:
+        _require_tensors(*((t, name, (torch.float32,)) for t, name in ((means, "means"), (quats, "quats"), (scales, "scales"))))
+        _require(tuple(means.shape) == (N, 3) and tuple(quats.shape) == (N, 4) and tuple(scales.shape) == (N, 3),
+                 f"means, quats, scales must be [{N}, 3], [{N}, 4], [{N}, 3]")
+        _require(all(t.device == dev for t in (means, quats, scales)), "the Gaussian tensors must be on one device")
+        means, quats, scales = (t.contiguous() for t in (means, quats, scales))
+        vm, (fx, fy, cx, cy) = _splat_camera(viewmat, K, W, H)
+    else:
+        means = quats = scales = None
+    target, pixel_weight = _splat_loss_maps(target, pixel_weight, W, H, dev)
+    for t, name, shape, dt in ((logits, "logits", (D, H, W), torch.float32), (grad_alpha, "grad_alpha", (H, W), torch.float32),
+                               (grad_loss, "grad_loss", None, torch.float32), (loss_stats, "loss_stats", (2,), torch.float64)):
+        if t is not None:
+            _require_tensors((t, name, (dt,)))
+            _require(t.device == dev and (t.numel() == 1 if shape is None else tuple(t.shape) == tuple(int(v) for v in shape)),
+                     f"{name} must be {'one element' if shape is None else list(shape)} on the features' device")
+    _require(loss_stats is not None, "loss_stats (the forward's) is required")
+    logits = logits.contiguous() if logits is not None else None
+    grad_alpha = grad_alpha.contiguous() if grad_alpha is not None else None
+    L = lib()
+    nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}, capacity {capacity}")
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= nbytes, "splat_loss_backward needs the workspace of a splat_rasterize_loss call")
+    need = int((L.vp_splat_geometry_backward_workspace_bytes if geom else L.vp_splat_backward_workspace_bytes)(int(capacity), D))
+    _require(need > 0, f"no backward workspace size for capacity {capacity}, D = {D}")
+    bw = bwd_workspace if bwd_workspace is not None else SplatWorkspace()
+    bptr = bw.ensure(need, dev)
+    out = {name: torch.empty((N,) + tail, dtype=torch.float32, device=dev) if want else None
+           for name, tail, want in (("means", (3,), want_means), ("quats", (4,), want_quats), ("scales", (3,), want_scales),
+                                    ("features", (D,), want_features), ("opacities", (), want_opacities),
+                                    ("screen", (5,), want_screen))}
+    p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_splat_loss_backward(
+            p(means), p(quats), p(scales), p(features), D, max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy, int(W),
+            int(H), float(eps2d), int(capacity), p(target), p(pixel_weight), p(logits), p(loss_stats), _REDUCTIONS[reduction],
+            p(grad_loss), p(grad_alpha), p(out["means"]), p(out["quats"]), p(out["scales"]), p(out["features"]),
+            p(out["opacities"]), p(out["screen"]), p(status), workspace.ptr(), workspace.capacity(), bptr, bw.capacity(),
+            stream.cuda_stream))
+    return out
+
+
+def splat_loss(means, quats, scales, opacities, features, viewmat, K, W, H, target, pixel_weight=None, *,
+               want_pixel_loss=False, want_labels=True, want_confidence=True, want_alpha=False, want_logits=False, near=0.01,
+               far=1e10, eps2d=0.3, workspace=None, loss_workspace=None, check=True):
+    """Splat the features into one view and take the fused cross-entropy against ``target`` (vp_splat_project +
+    vp_splat_rasterize_loss), as splat_features splats: reads the 8-byte intersection count once to size the sort.
+    Returns SplatLossResult(loss_stats f64 [2] on the device = {sum w l, sum w}, pixel_loss, labels, confidence, alpha,
+    logits, n_isect int, n_nonfinite device int32 [1])."""
+    import torch
+    _require_tensors(*((t, name, (torch.float32,)) for t, name in
+                       ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"), (features, "features"))))
+    _require(features.dim() == 2 and features.shape[0] == means.shape[0], "features must be [N, D] with one row per Gaussian")
+    _require(features.device == means.device, "features and the Gaussians must be on one device")
+    ws = workspace if workspace is not None else SplatWorkspace()
+    bad = torch.zeros(1, dtype=torch.int32, device=means.device)
+    status = torch.zeros(1, dtype=torch.int32, device=means.device)
+    n_isect = splat_project(means, quats, scales, opacities, viewmat, K, W, H, near=near, far=far, eps2d=eps2d,
+                            workspace=ws, n_nonfinite=bad)
+    cap = int(n_isect.item())
+    _require(cap <= 2 ** 31 - 1, f"{cap} tile intersections: more than 2^31 - 1")
+    out = splat_rasterize_loss(features, int(means.shape[0]), W, H, cap, ws, target, pixel_weight,
+                               want_pixel_loss=want_pixel_loss, want_labels=want_labels, want_confidence=want_confidence,
+                               want_alpha=want_alpha, want_logits=want_logits, loss_workspace=loss_workspace, status=status)
+    if check:
+        st, n_bad = (int(v) for v in torch.cat([status, bad]).tolist())
+        if st:
+            raise VoxprojError("splat_loss: the intersection count outgrew the workspace (nothing written)")
+        if n_bad:
+            raise VoxprojError(f"splat_loss: {n_bad} Gaussian(s) have a non-finite parameter (culled)")
+    return SplatLossResult(*out, cap, bad)
 
 
 _check_rc = check

@@ -548,6 +548,71 @@ int vp_splat_rasterize_backward_geometry(const float *means, const float *quats,
                                          float *grad_screen, int32_t *status, void *workspace, size_t workspace_bytes,
                                          void *bwd_workspace, size_t bwd_bytes, void *stream);
 
+/*
+ * Fused softmax cross-entropy on the splatted logits: the loss of one view against a per-pixel target map, computed in the
+ * blend's own epilogue, and its backward without a gradient image.  Added after VP_ABI_VERSION 4 without changing it or
+ * any existing entry point; detect the three functions by symbol.  tests/splat_loss_reference.py states it in float64.
+ *
+ * The contract, with C_p the D blended logits of pixel p exactly as vp_splat_rasterize computes them (same branch, same fp32
+ * operations, same bits):
+ *   Targets and weights: target i32 [H,W], pixel_weight f32 [H,W] or NULL (read as 1).  Pixel p is valid when
+ *     0 <= target[p] < D; every other value (-1, 255, ...) means ignored: weight 0, loss 0, no gradient.
+ *   Per-pixel loss, fp32, channels ascending:  m = max_c C_c,  l_p = (m + logf(sum_c expf(C_c - m))) - C_t  (the precise
+ *     expf / logf, the maximum and the sum of the confidence epilogue).  A pixel nothing reaches has C = 0 and l = log D; it
+ *     is valid unless its target says otherwise.
+ *   loss_stats (device f64 [2]) = {sum_p w_p l_p, sum_p w_p} over the valid pixels: the fp32 values w_p l_p and w_p summed
+ *     in float64 in a fixed order (a halving tree over a tile's 256 pixels, then the tiles in ascending tile index).  A
+ *     valid pixel of weight exactly 0 contributes exactly 0, whatever its l.  No atomics: bit-identical from run to run.
+ *   pixel_loss (f32 [H,W], optional) = w_p l_p, 0 where ignored.  labels, confidence, alpha, logits: vp_splat_rasterize's,
+ *     bit for bit; each may be NULL in this call, labels included.
+ *   Gradient: s = grad_loss (device f32 [1], NULL = 1) for VP_LOSS_SUM, and s = (float)(grad_loss / sum w) (the quotient
+ *     in float64) for VP_LOSS_MEAN, where sum w = loss_stats[1]; sum w = 0 gives s = 0: gradients of exactly 0, and the mean
+ *     loss is defined as 0.  The upstream gradient of the logits is, in fp32,
+ *       G[c,p] = (s w_p) (expf(C_c - m) / sum - [c = t_p])   on valid pixels, 0 elsewhere.
+ *     grad_alpha is optional as in the backward above.  From G on, the contract is vp_splat_rasterize_backward's and
+ *     vp_splat_rasterize_backward_geometry's: same formulas, same zero rows, same fixed-order partials, same determinism.
+ *   Two arms supply C_p: with logits = NULL the tile sweep blends the pixel again before its two sweeps (replay: no image
+ *     is kept between forward and backward); otherwise C_p is read from `logits`, the planar image the forward call wrote
+ *     (saved).  Both arms give bit-identical gradients.
+ *
+ * vp_splat_loss_workspace_bytes: bytes of the forward's per-tile pairs, 256-byte rounded; 0 when W or H is outside
+ *   [1, 32768].  Needs no GPU.
+ *
+ * vp_splat_rasterize_loss: vp_splat_rasterize (after vp_splat_project on the same workspace; sorts `capacity` keys once)
+ *   with the loss epilogue.  Asynchronous on `stream`, no allocation, no host synchronisation.  When the device count
+ *   exceeds `capacity` nothing is written (loss_stats included) and *status is set to 1.  Refused on the host as
+ *   vp_splat_rasterize refuses (labels may be NULL here), plus VP_EINVAL for a NULL target or loss_stats and VP_EWORKSPACE
+ *   for a loss workspace that is NULL, not 256-byte aligned or smaller than vp_splat_loss_workspace_bytes.
+ *
+ * vp_splat_loss_backward: after vp_splat_rasterize_loss (or vp_splat_rasterize) on this workspace with the same
+ *   n_gaussians, W, H, capacity, features and stream; target and pixel_weight as in the forward.  reduction is VP_LOSS_SUM
+ *   or VP_LOSS_MEAN; loss_stats (the forward's) is read only for VP_LOSS_MEAN, on the device.  Without grad_means,
+ *   grad_quats, grad_scales and grad_screen it runs the sweep of vp_splat_rasterize_backward, with `bwd_workspace`
+ *   measured by vp_splat_backward_workspace_bytes; otherwise that of vp_splat_rasterize_backward_geometry, measured by
+ *   vp_splat_geometry_backward_workspace_bytes.  grad_features and grad_opacities are bit-identical between the two.
+ *   means, quats, scales and the camera (viewmat in HOST memory) are read only when grad_means, grad_quats or grad_scales
+ *   is asked for.  Every output is written only when its pointer is not NULL.  When the device count exceeds `capacity`
+ *   nothing is written and *status is set to 1.  Asynchronous on `stream`, no allocation, no host synchronisation.
+ *   Refused on the host as vp_splat_rasterize_backward_geometry refuses, plus VP_EINVAL for a NULL target, a NULL
+ *   loss_stats or an unknown reduction.
+ */
+#define VP_LOSS_SUM 0
+#define VP_LOSS_MEAN 1
+size_t vp_splat_loss_workspace_bytes(int W, int H);
+int vp_splat_rasterize_loss(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H,
+                            int64_t capacity, const int32_t *target, const float *pixel_weight, double *loss_stats,
+                            float *pixel_loss, int32_t *labels, float *confidence, float *alpha, float *logits,
+                            int32_t *status, void *workspace, size_t workspace_bytes, void *loss_workspace,
+                            size_t loss_bytes, void *stream);
+int vp_splat_loss_backward(const float *means, const float *quats, const float *scales, const float *features, int D,
+                           int64_t row_stride, int64_t n_gaussians, const float *viewmat, float fx, float fy, float cx,
+                           float cy, int W, int H, float eps2d, int64_t capacity, const int32_t *target,
+                           const float *pixel_weight, const float *logits /* NULL = replay */, const double *loss_stats,
+                           int reduction, const float *grad_loss, const float *grad_alpha, float *grad_means,
+                           float *grad_quats, float *grad_scales, float *grad_features, float *grad_opacities,
+                           float *grad_screen, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *bwd_workspace, size_t bwd_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

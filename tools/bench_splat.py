@@ -19,8 +19,13 @@ With --geometry as well, one more splat_geometry_backward_ms_per_view line per l
 vp_splat_rasterize_backward_geometry asking for every gradient (means, quats, scales, features, opacities) beside the
 existing backward on the same view and gradients, timed in alternation, and their ratio (profiles/r10_splat_geometry*).
 
+With --loss, one splat_loss_step_ms line per (G, D, size) instead of the legs above: one refinement step on view 0
+(forward + backward in the features, the intersection count read included) for three arms timed in alternation in one
+process: the fused loss with the replay backward, the fused loss with the saved logits, and the composite
+(splat_autograd.splat_features + F.cross_entropy + backward); torch.cuda.max_memory_allocated of each arm beside it.
+
 python tools/bench_splat.py [--steps K] [--warmup W] [--g 200000 1000000] [--d 13 32] [--size 876x584 1600x1067]
-[--logits off on] [--views V] [--backward [--geometry]]"""
+[--logits off on] [--views V] [--backward [--geometry]] [--loss]"""
 import argparse
 import json
 import os
@@ -60,6 +65,8 @@ def main(argv=None):
                     help="after each logits-on leg, one splat_backward_ms_per_view line: rasterize forward vs backward")
     ap.add_argument("--geometry", action="store_true",
                     help="with --backward: one splat_geometry_backward_ms_per_view line: the fused geometry backward vs the backward")
+    ap.add_argument("--loss", action="store_true",
+                    help="one splat_loss_step_ms line per configuration: a refinement step, fused (replay, saved) vs composite")
     args = ap.parse_args(argv)
     if args.geometry and not args.backward:
         ap.error("--geometry needs --backward")
@@ -75,6 +82,9 @@ def main(argv=None):
             w2c = w2c[::12]
             for D in args.d:
                 feats = lg32[:, :D].contiguous() if D <= 32 else lg32
+                if args.loss:
+                    loss_leg(t, feats, G, W, H, w2c[0], K, args)
+                    continue
                 ws = voxproj_host.SplatWorkspace()
                 for lo in args.logits:
                     want = lo == "on"
@@ -142,6 +152,59 @@ def backward_leg(t, feats, G, W, H, vm, K, ws, cap, args):
                    raster_bwd_ms_runs=[round(ms[0], 4), round(ms[2], 4)], geometry_bwd_ms_runs=[round(ms[1], 4), round(ms[3], 4)],
                    n_isect=cap, geometry_scratch_MB=round(gws.capacity() / 2 ** 20, 1), steps=args.steps, warmup=args.warmup)
         print(json.dumps(res), flush=True)
+
+
+def loss_leg(t, feats, G, W, H, vm, K, args):
+    """--loss: one refinement step (loss forward + backward in the per-Gaussian logits) on one view, three arms."""
+    import splat_autograd
+    D = int(feats.shape[1])
+    dev = feats.device
+    ref = voxproj_host.splat_features(t["means"], t["quats"], t["scales"], t["opacities"], feats, vm, K, W, H, want_alpha=True,
+                                      check=False)
+    target = torch.where(ref.alpha > 0.5, ref.labels, torch.full_like(ref.labels, -1))
+    weight = ref.confidence.clone()
+    mask = (target >= 0).reshape(-1)
+    tl, wl = target.reshape(-1)[mask].long(), weight.reshape(-1)[mask]
+    n_isect = ref.n_isect
+    del ref
+    param = feats.clone().requires_grad_()
+
+    def fused(keep):
+        def fn(i):
+            param.grad = None
+            loss = splat_autograd.splat_cross_entropy(t["means"], t["quats"], t["scales"], t["opacities"], param, vm, K, W, H,
+                                                      target, weight, keep_logits=keep, check=False)[0]
+            loss.backward()
+        return fn
+
+    def composite(i):
+        param.grad = None
+        lg = splat_autograd.splat_features(t["means"], t["quats"], t["scales"], t["opacities"], param, vm, K, W, H,
+                                           check=False)[0]
+        ce = torch.nn.functional.cross_entropy(lg.reshape(D, -1).T[mask], tl, reduction="none")
+        ((ce * wl).sum() / wl.sum()).backward()
+
+    arms = (("replay", fused(False)), ("saved", fused(True)), ("composite", composite))
+    ms = {k: [] for k, _ in arms}
+    peak = {}
+    for rnd in range(2):                               # alternated twice: the two readings show the run-to-run spread
+        for k, fn in arms:
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            ms[k].append(timed(fn, args.steps, args.warmup))
+            peak[k] = torch.cuda.max_memory_allocated() - base
+    best = {k: min(v) for k, v in ms.items()}
+    res = dict(metric="splat_loss_step_ms", G=G, D=D, W=W, H=H, n_isect=n_isect,
+               replay_ms=round(best["replay"], 4), saved_ms=round(best["saved"], 4), composite_ms=round(best["composite"], 4),
+               replay_ms_runs=[round(v, 4) for v in ms["replay"]], saved_ms_runs=[round(v, 4) for v in ms["saved"]],
+               composite_ms_runs=[round(v, 4) for v in ms["composite"]],
+               best_fused_over_composite=round(min(best["replay"], best["saved"]) / best["composite"], 3),
+               replay_peak_MB=round(peak["replay"] / 2 ** 20, 1), saved_peak_MB=round(peak["saved"] / 2 ** 20, 1),
+               composite_peak_MB=round(peak["composite"] / 2 ** 20, 1), two_images_MB=round(2 * D * H * W * 4 / 2 ** 20, 1),
+               valid_pixels=int(mask.sum()), steps=args.steps, warmup=args.warmup)
+    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
