@@ -629,6 +629,61 @@ int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, 
     return VP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Gaussian splatting.  The checks every entry point repeats, each VP_OK or the refusal; none of them needs a GPU, and every
+// entry point makes all of its own before splat_layout (rocprim's scratch sizes depend on the device).
+// ------------------------------------------------------------------------------------------------
+static int splat_check_count(int64_t n_gaussians)
+{
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
+        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
+    return VP_OK;
+}
+
+static int splat_check_image(int W, int H)
+{
+    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
+    return VP_OK;
+}
+
+static int splat_check_rows(int D, int64_t row_stride, int W, int H, int64_t capacity)
+{
+    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
+    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
+    if (int rc = splat_check_image(W, H)) return rc;
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    return VP_OK;
+}
+
+// name: "workspace", "backward workspace" or "loss workspace"
+static int splat_check_buffer(const void *buf, const char *name)
+{
+    if (!buf) return fail(VP_EWORKSPACE, "%s is NULL", name);
+    if ((uintptr_t)buf & 255) return fail(VP_EWORKSPACE, "%s must be 256-byte aligned", name);
+    return VP_OK;
+}
+
+static int splat_check_size(size_t have, size_t need, const char *name)
+{
+    if (have < need) return fail(VP_EWORKSPACE, "%s has %zu bytes, need %zu", name, have, need);
+    return VP_OK;
+}
+
+// the pose and the intrinsics into cam; the planes, eps2d and the image size are the caller's to check and fill
+static int splat_check_camera(const float *viewmat, float fx, float fy, float cx, float cy, SplatCam &cam)
+{
+    if (!viewmat) return fail(VP_EINVAL, "null viewmat");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(viewmat[k])) return fail(VP_EINVAL, "viewmat[%d] is not finite", k);
+    if (!(fx > 0.0f) || !(fy > 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail(VP_EINVAL, "fx, fy must be finite and > 0, cx, cy finite (got %g %g %g %g)", (double)fx, (double)fy,
+                    (double)cx, (double)cy);
+    for (int k = 0; k < 12; ++k) cam.r[k] = viewmat[k];
+    cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy;
+    return VP_OK;
+}
+
 size_t vp_splat_workspace_bytes(int64_t n_gaussians, int W, int H, int64_t capacity)
 {
     if (n_gaussians < 0 || n_gaussians > INT32_MAX || W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH || capacity < 0 ||
@@ -643,31 +698,21 @@ int vp_splat_project(const float *means, const float *quats, const float *scales
                      float far_plane, float eps2d, int64_t *n_isect, int32_t *n_nonfinite, void *workspace,
                      size_t workspace_bytes, void *stream_)
 {
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
-        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
+    if (int rc = splat_check_count(n_gaussians)) return rc;
     if (n_gaussians > 0 && (!means || !quats || !scales || !opacities))
         return fail(VP_EINVAL, "null pointer argument (means, quats, scales or opacities)");
-    if (!viewmat) return fail(VP_EINVAL, "null viewmat");
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
-    for (int k = 0; k < 12; ++k)
-        if (!std::isfinite(viewmat[k])) return fail(VP_EINVAL, "viewmat[%d] is not finite", k);
-    if (!(fx > 0.0f) || !(fy > 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
-        return fail(VP_EINVAL, "fx, fy must be finite and > 0, cx, cy finite (got %g %g %g %g)", (double)fx, (double)fy,
-                    (double)cx, (double)cy);
+    SplatCam cam;
+    if (int rc = splat_check_camera(viewmat, fx, fy, cx, cy, cam)) return rc;
+    if (int rc = splat_check_image(W, H)) return rc;
     if (!(near_plane > 0.0f) || !(far_plane > near_plane) || !(eps2d >= 0.0f) || !std::isfinite(eps2d))
         return fail(VP_EINVAL, "need 0 < near < far and a finite eps2d >= 0 (got %g %g %g)", (double)near_plane,
                     (double)far_plane, (double)eps2d);
-    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    SplatLayout l;   // rocprim's scratch sizes depend on the device: queried after the checks that need no GPU
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    SplatLayout l;
     if (!splat_layout(n_gaussians, W, H, 0, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     char *ws = (char *)workspace;
-    SplatCam cam;
-    for (int k = 0; k < 12; ++k) cam.r[k] = viewmat[k];
-    cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy;
     cam.near_z = near_plane; cam.far_z = far_plane; cam.eps2d = eps2d;
     cam.W = W; cam.H = H; cam.tiles_x = l.tiles_x;
     long long *total = (long long *)(ws + l.total), *offs = (long long *)(ws + l.offs);
@@ -716,40 +761,48 @@ static int splat_sort_tiles(char *ws, const SplatLayout &l, int64_t n_gaussians,
     return VP_OK;
 }
 
+// The forward after the caller's own checks: the shared checks, the tile sort and the blend.  ls: the loss variant's maps and
+// outputs (then loss_stats is summed from its tile pairs), NULL for the plain blend.
+static int splat_forward_impl(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H,
+                              int64_t capacity, int32_t *labels, float *confidence, float *alpha, float *logits,
+                              int32_t *status, void *workspace, size_t workspace_bytes, const SplatLoss *ls,
+                              double *loss_stats, void *stream_)
+{
+    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (int rc = splat_check_rows(D, row_stride, W, H, capacity)) return rc;
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    const long long *total = (const long long *)(ws + l.total);
+    if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
+    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+    splat_with_dt(D, [&](auto dt) {
+        splat_with_flag(ls != nullptr, [&](auto loss) {
+            hipLaunchKernelGGL((k_splat_blend<decltype(dt)::value, decltype(loss)::value>), grid, block, 0, stream,
+                               (const SplatRec *)(ws + l.rec), (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges),
+                               total, (long long)capacity, features, D, (long long)row_stride, W, H, (int *)labels, confidence,
+                               alpha, logits, ls ? *ls : SplatLoss{});
+        });
+    });
+    VP_HIP(hipGetLastError());
+    if (ls) {
+        hipLaunchKernelGGL(k_splat_loss_sum, dim3(1), block, 0, stream, (const double2 *)ls->tile_sums,
+                           (long long)l.tiles_x * l.tiles_y, total, (long long)capacity, loss_stats);
+        VP_HIP(hipGetLastError());
+    }
+    return VP_OK;
+}
+
 int vp_splat_rasterize(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H, int64_t capacity,
                        int32_t *labels, float *confidence, float *alpha, float *logits, int32_t *status, void *workspace,
                        size_t workspace_bytes, void *stream_)
 {
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
-        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
     if (!labels || (n_gaussians > 0 && !features)) return fail(VP_EINVAL, "null pointer argument (labels or features)");
-    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
-    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
-    hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
-    const long long *total = (const long long *)(ws + l.total);
-    const int *v1 = (const int *)(ws + l.vals1);
-    const longlong2 *ranges = (const longlong2 *)(ws + l.ranges);
-    if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-#define VP_SPLAT(DT) hipLaunchKernelGGL((k_splat_blend<DT>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), v1, ranges, \
-                                        total, (long long)capacity, features, D, (long long)row_stride, W, H, (int *)labels, \
-                                        confidence, alpha, logits, SplatLoss{})
-    if (D <= 8) VP_SPLAT(8);
-    else if (D <= 16) VP_SPLAT(16);
-    else if (D <= 32) VP_SPLAT(32);
-    else VP_SPLAT(64);
-#undef VP_SPLAT
-    VP_HIP(hipGetLastError());
-    return VP_OK;
+    return splat_forward_impl(features, D, row_stride, n_gaussians, W, H, capacity, labels, confidence, alpha, logits, status,
+                              workspace, workspace_bytes, nullptr, nullptr, stream_);
 }
 
 size_t vp_splat_backward_workspace_bytes(int64_t capacity, int D)
@@ -758,59 +811,105 @@ size_t vp_splat_backward_workspace_bytes(int64_t capacity, int D)
     return splat_bwd_bytes(capacity, D);
 }
 
+// What the three backward entry points pass to their one implementation: the arguments of
+// vp_splat_rasterize_backward_geometry in their order (the wrappers initialise it positionally), then what tells the calls apart.
+struct SplatBackward {
+    const float *means, *quats, *scales, *features;
+    int D;
+    int64_t row_stride, n_gaussians;
+    const float *viewmat;
+    float fx, fy, cx, cy;
+    int W, H;
+    float eps2d;
+    int64_t capacity;
+    const float *logits;         // the upstream grad_logits; with loss, the forward's logits image (NULL: replay)
+    const float *grad_alpha;
+    float *grad_means, *grad_quats, *grad_scales, *grad_features, *grad_opacities, *grad_screen;
+    int32_t *status;
+    void *workspace;
+    size_t workspace_bytes;
+    void *bwd_workspace;
+    size_t bwd_bytes;
+    void *stream;
+    bool geom;                   // rows with the five screen sums (the geometry sweep and reduce)
+    bool chain;                  // grad_means / grad_quats / grad_scales wanted: needs the Gaussians and the camera
+    bool loss;                   // the upstream gradient is the cross-entropy's, from ls
+    SplatLoss ls;
+};
+
+static int splat_backward_impl(const SplatBackward &a)
+{
+    const int D = a.D;
+    const int64_t n_gaussians = a.n_gaussians, capacity = a.capacity;
+    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (n_gaussians > 0 && !a.features) return fail(VP_EINVAL, "null pointer argument (features)");
+    if (a.chain && n_gaussians > 0 && (!a.means || !a.quats || !a.scales))
+        return fail(VP_EINVAL, "null pointer argument (means, quats or scales, needed by grad_means / grad_quats / grad_scales)");
+    if (int rc = splat_check_rows(D, a.row_stride, a.W, a.H, capacity)) return rc;
+    SplatCam cam = {};
+    if (a.chain) {
+        if (int rc = splat_check_camera(a.viewmat, a.fx, a.fy, a.cx, a.cy, cam)) return rc;
+        if (!(a.eps2d >= 0.0f) || !std::isfinite(a.eps2d))
+            return fail(VP_EINVAL, "need a finite eps2d >= 0 (got %g)", (double)a.eps2d);
+        cam.eps2d = a.eps2d;
+        cam.W = a.W; cam.H = a.H;
+    }
+    if (int rc = splat_check_buffer(a.workspace, "workspace")) return rc;
+    if (int rc = splat_check_buffer(a.bwd_workspace, "backward workspace")) return rc;
+    const size_t bwd_need = a.geom ? splat_geom_bytes(capacity, D) : splat_bwd_bytes(capacity, D);
+    if (int rc = splat_check_size(a.bwd_bytes, bwd_need, "backward workspace")) return rc;
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, a.W, a.H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(a.workspace_bytes, l.bytes, "workspace")) return rc;
+    if (n_gaussians == 0) return VP_OK;                  // no rows to write; nothing can exceed a capacity of 0 either
+    hipStream_t stream = (hipStream_t)a.stream;
+    char *ws = (char *)a.workspace;
+    const long long *total = (const long long *)(ws + l.total);
+    const int *count = (const int *)(ws + l.count);
+    const long long *offs = (const long long *)(ws + l.offs);
+    float *part = (float *)a.bwd_workspace;
+    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+    splat_with_dt(D, [&](auto dt) {
+        splat_with_flag(a.geom, [&](auto geom) {
+            splat_with_flag(a.loss, [&](auto loss) {
+                hipLaunchKernelGGL((k_splat_blend_backward<decltype(dt)::value, decltype(geom)::value, decltype(loss)::value>),
+                                   grid, block, 0, stream, (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), count,
+                                   offs, (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges), total,
+                                   (long long)capacity, a.features, D, (long long)a.row_stride, a.W, a.H, a.logits,
+                                   a.grad_alpha, part, a.ls);
+            });
+        });
+    });
+    VP_HIP(hipGetLastError());
+    // grid-stride over the Gaussians, at most one resident round (2048 workgroups of 4 wavefronts: 32 per CU on 256 CUs)
+    const int gs = splat_reduce_group(a.geom ? D + SPLAT_SCREEN : D);
+    const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / gs - 1) / (256 / gs), 2048LL);
+    splat_with_group(gs, [&](auto group) {
+        splat_with_flag(a.geom, [&](auto geom) {
+            hipLaunchKernelGGL((k_splat_grad_reduce<decltype(group)::value, decltype(geom)::value>), dim3(g_red), dim3(256), 0,
+                               stream, count, offs, (long long)n_gaussians, total, (long long)capacity, part, D,
+                               a.grad_features, a.grad_opacities, a.grad_screen, (int *)a.status);
+        });
+    });
+    VP_HIP(hipGetLastError());
+    if (a.chain) {
+        hipLaunchKernelGGL(k_splat_geom_chain, dim3((unsigned)((n_gaussians + 255) / 256)), dim3(256), 0, stream, a.means,
+                           a.quats, a.scales, (long long)n_gaussians, cam, count, offs, total, (long long)capacity,
+                           (const float *)part, D, a.grad_means, a.grad_quats, a.grad_scales);
+        VP_HIP(hipGetLastError());
+    }
+    return VP_OK;
+}
+
 int vp_splat_rasterize_backward(const float *features, int D, int64_t row_stride, int64_t n_gaussians, int W, int H,
                                 int64_t capacity, const float *grad_logits, const float *grad_alpha, float *grad_features,
                                 float *grad_opacities, int32_t *status, void *workspace, size_t workspace_bytes,
                                 void *bwd_workspace, size_t bwd_bytes, void *stream_)
 {
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
-        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
-    if (n_gaussians > 0 && !features) return fail(VP_EINVAL, "null pointer argument (features)");
-    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
-    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    if (!bwd_workspace) return fail(VP_EWORKSPACE, "backward workspace is NULL");
-    if ((uintptr_t)bwd_workspace & 255) return fail(VP_EWORKSPACE, "backward workspace must be 256-byte aligned");
-    const size_t bwd_need = splat_bwd_bytes(capacity, D);
-    if (bwd_bytes < bwd_need)
-        return fail(VP_EWORKSPACE, "backward workspace has %zu bytes, need %zu", bwd_bytes, bwd_need);
-    SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
-    if (n_gaussians == 0) return VP_OK;                  // no rows to write; nothing can exceed a capacity of 0 either
-    hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
-    const long long *total = (const long long *)(ws + l.total);
-    const int *count = (const int *)(ws + l.count);
-    const long long *offs = (const long long *)(ws + l.offs);
-    float *part = (float *)bwd_workspace;
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-#define VP_SPLAT_BWD(DT) hipLaunchKernelGGL((k_splat_blend_backward<DT, false>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), \
-                                            (const int4 *)(ws + l.box), count, offs, (const int *)(ws + l.vals1),             \
-                                            (const longlong2 *)(ws + l.ranges), total, (long long)capacity, features, D,      \
-                                            (long long)row_stride, W, H, grad_logits, grad_alpha, part, SplatLoss{})
-    if (D <= 8) VP_SPLAT_BWD(8);
-    else if (D <= 16) VP_SPLAT_BWD(16);
-    else if (D <= 32) VP_SPLAT_BWD(32);
-    else VP_SPLAT_BWD(64);
-#undef VP_SPLAT_BWD
-    VP_HIP(hipGetLastError());
-    // grid-stride over the Gaussians, at most one resident round (2048 workgroups of 4 wavefronts: 32 per CU on 256 CUs)
-    const int gs = splat_reduce_group(D);
-    const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / gs - 1) / (256 / gs), 2048LL);
-#define VP_SPLAT_RED(GS) hipLaunchKernelGGL((k_splat_grad_reduce<GS>), dim3(g_red), dim3(256), 0, stream, count, offs, \
-                                            (long long)n_gaussians, total, (long long)capacity, (const float *)part, D,   \
-                                            grad_features, grad_opacities, (int *)status)
-    if (gs == 16) VP_SPLAT_RED(16);
-    else if (gs == 32) VP_SPLAT_RED(32);
-    else VP_SPLAT_RED(64);
-#undef VP_SPLAT_RED
-    VP_HIP(hipGetLastError());
-    return VP_OK;
+    return splat_backward_impl({nullptr, nullptr, nullptr, features, D, row_stride, n_gaussians, nullptr, 0.0f, 0.0f, 0.0f, 0.0f,
+                                W, H, 0.0f, capacity, grad_logits, grad_alpha, nullptr, nullptr, nullptr, grad_features,
+                                grad_opacities, nullptr, status, workspace, workspace_bytes, bwd_workspace, bwd_bytes, stream_,
+                                false, false, false, SplatLoss{}});
 }
 
 size_t vp_splat_geometry_backward_workspace_bytes(int64_t capacity, int D)
@@ -828,74 +927,10 @@ int vp_splat_rasterize_backward_geometry(const float *means, const float *quats,
                                          void *bwd_workspace, size_t bwd_bytes, void *stream_)
 {
     const bool chain = grad_means || grad_quats || grad_scales;
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
-        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
-    if (n_gaussians > 0 && !features) return fail(VP_EINVAL, "null pointer argument (features)");
-    if (chain && n_gaussians > 0 && (!means || !quats || !scales))
-        return fail(VP_EINVAL, "null pointer argument (means, quats or scales, needed by grad_means / grad_quats / grad_scales)");
-    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
-    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    SplatCam cam = {};
-    if (chain) {
-        if (!viewmat) return fail(VP_EINVAL, "null viewmat");
-        for (int k = 0; k < 12; ++k)
-            if (!std::isfinite(viewmat[k])) return fail(VP_EINVAL, "viewmat[%d] is not finite", k);
-        if (!(fx > 0.0f) || !(fy > 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
-            return fail(VP_EINVAL, "fx, fy must be finite and > 0, cx, cy finite (got %g %g %g %g)", (double)fx, (double)fy,
-                        (double)cx, (double)cy);
-        if (!(eps2d >= 0.0f) || !std::isfinite(eps2d)) return fail(VP_EINVAL, "need a finite eps2d >= 0 (got %g)", (double)eps2d);
-        for (int k = 0; k < 12; ++k) cam.r[k] = viewmat[k];
-        cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy; cam.eps2d = eps2d;
-        cam.W = W; cam.H = H;
-    }
-    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    if (!bwd_workspace) return fail(VP_EWORKSPACE, "backward workspace is NULL");
-    if ((uintptr_t)bwd_workspace & 255) return fail(VP_EWORKSPACE, "backward workspace must be 256-byte aligned");
-    const size_t bwd_need = splat_geom_bytes(capacity, D);
-    if (bwd_bytes < bwd_need)
-        return fail(VP_EWORKSPACE, "backward workspace has %zu bytes, need %zu", bwd_bytes, bwd_need);
-    SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
-    if (n_gaussians == 0) return VP_OK;                  // no rows to write; nothing can exceed a capacity of 0 either
-    hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
-    const long long *total = (const long long *)(ws + l.total);
-    const int *count = (const int *)(ws + l.count);
-    const long long *offs = (const long long *)(ws + l.offs);
-    float *part = (float *)bwd_workspace;
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-#define VP_SPLAT_BWD(DT) hipLaunchKernelGGL((k_splat_blend_backward<DT, true>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), \
-                                            (const int4 *)(ws + l.box), count, offs, (const int *)(ws + l.vals1),                  \
-                                            (const longlong2 *)(ws + l.ranges), total, (long long)capacity, features, D,           \
-                                            (long long)row_stride, W, H, grad_logits, grad_alpha, part, SplatLoss{})
-    if (D <= 8) VP_SPLAT_BWD(8);
-    else if (D <= 16) VP_SPLAT_BWD(16);
-    else if (D <= 32) VP_SPLAT_BWD(32);
-    else VP_SPLAT_BWD(64);
-#undef VP_SPLAT_BWD
-    VP_HIP(hipGetLastError());
-    const int gs = splat_reduce_group(D + SPLAT_SCREEN);
-    const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / gs - 1) / (256 / gs), 2048LL);
-#define VP_SPLAT_RED(GS) hipLaunchKernelGGL((k_splat_grad_reduce_geom<GS>), dim3(g_red), dim3(256), 0, stream, count, offs, \
-                                            (long long)n_gaussians, total, (long long)capacity, part, D, grad_features,       \
-                                            grad_opacities, grad_screen, (int *)status)
-    if (gs == 16) VP_SPLAT_RED(16);
-    else if (gs == 32) VP_SPLAT_RED(32);
-    else VP_SPLAT_RED(64);
-#undef VP_SPLAT_RED
-    VP_HIP(hipGetLastError());
-    if (chain) {
-        hipLaunchKernelGGL(k_splat_geom_chain, dim3((unsigned)((n_gaussians + 255) / 256)), dim3(256), 0, stream, means, quats,
-                           scales, (long long)n_gaussians, cam, count, offs, total, (long long)capacity, (const float *)part, D,
-                           grad_means, grad_quats, grad_scales);
-        VP_HIP(hipGetLastError());
-    }
-    return VP_OK;
+    return splat_backward_impl({means, quats, scales, features, D, row_stride, n_gaussians, viewmat, fx, fy, cx, cy, W, H, eps2d,
+                                capacity, grad_logits, grad_alpha, grad_means, grad_quats, grad_scales, grad_features,
+                                grad_opacities, grad_screen, status, workspace, workspace_bytes, bwd_workspace, bwd_bytes,
+                                stream_, true, chain, false, SplatLoss{}});
 }
 
 size_t vp_splat_loss_workspace_bytes(int W, int H)
@@ -911,49 +946,18 @@ int vp_splat_rasterize_loss(const float *features, int D, int64_t row_stride, in
                             int32_t *status, void *workspace, size_t workspace_bytes, void *loss_workspace, size_t loss_bytes,
                             void *stream_)
 {
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
-        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
     if (n_gaussians > 0 && !features) return fail(VP_EINVAL, "null pointer argument (features)");
     if (!target || !loss_stats) return fail(VP_EINVAL, "null pointer argument (target or loss_stats)");
-    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
-    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    if (!loss_workspace) return fail(VP_EWORKSPACE, "loss workspace is NULL");
-    if ((uintptr_t)loss_workspace & 255) return fail(VP_EWORKSPACE, "loss workspace must be 256-byte aligned");
-    const size_t loss_need = vp_splat_loss_workspace_bytes(W, H);
-    if (loss_bytes < loss_need) return fail(VP_EWORKSPACE, "loss workspace has %zu bytes, need %zu", loss_bytes, loss_need);
-    SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
-    hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
-    const long long *total = (const long long *)(ws + l.total);
-    const int *v1 = (const int *)(ws + l.vals1);
-    const longlong2 *ranges = (const longlong2 *)(ws + l.ranges);
-    if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
+    if (int rc = splat_check_image(W, H)) return rc;     // the loss workspace's size needs a valid image
+    if (int rc = splat_check_buffer(loss_workspace, "loss workspace")) return rc;
+    if (int rc = splat_check_size(loss_bytes, vp_splat_loss_workspace_bytes(W, H), "loss workspace")) return rc;
     SplatLoss ls = {};
     ls.target = (const int *)target;
     ls.weight = pixel_weight;
     ls.pixel_loss = pixel_loss;
     ls.tile_sums = (double2 *)loss_workspace;
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-#define VP_SPLAT(DT) hipLaunchKernelGGL((k_splat_blend<DT, true>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec), v1, \
-                                        ranges, total, (long long)capacity, features, D, (long long)row_stride, W, H,        \
-                                        (int *)labels, confidence, alpha, logits, ls)
-    if (D <= 8) VP_SPLAT(8);
-    else if (D <= 16) VP_SPLAT(16);
-    else if (D <= 32) VP_SPLAT(32);
-    else VP_SPLAT(64);
-#undef VP_SPLAT
-    VP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_splat_loss_sum, dim3(1), block, 0, stream, (const double2 *)loss_workspace,
-                       (long long)l.tiles_x * l.tiles_y, total, (long long)capacity, loss_stats);
-    VP_HIP(hipGetLastError());
-    return VP_OK;
+    return splat_forward_impl(features, D, row_stride, n_gaussians, W, H, capacity, labels, confidence, alpha, logits, status,
+                              workspace, workspace_bytes, &ls, loss_stats, stream_);
 }
 
 int vp_splat_loss_backward(const float *means, const float *quats, const float *scales, const float *features, int D,
@@ -965,101 +969,20 @@ int vp_splat_loss_backward(const float *means, const float *quats, const float *
                            int32_t *status, void *workspace, size_t workspace_bytes, void *bwd_workspace, size_t bwd_bytes,
                            void *stream_)
 {
-    const bool chain = grad_means || grad_quats || grad_scales;
-    const bool geom = chain || grad_screen;
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
-        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
-    if (n_gaussians > 0 && !features) return fail(VP_EINVAL, "null pointer argument (features)");
     if (!target || !loss_stats) return fail(VP_EINVAL, "null pointer argument (target or loss_stats)");
     if (reduction != VP_LOSS_SUM && reduction != VP_LOSS_MEAN)
         return fail(VP_EINVAL, "reduction = %d is neither VP_LOSS_SUM nor VP_LOSS_MEAN", reduction);
-    if (chain && n_gaussians > 0 && (!means || !quats || !scales))
-        return fail(VP_EINVAL, "null pointer argument (means, quats or scales, needed by grad_means / grad_quats / grad_scales)");
-    if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
-    if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    SplatCam cam = {};
-    if (chain) {
-        if (!viewmat) return fail(VP_EINVAL, "null viewmat");
-        for (int k = 0; k < 12; ++k)
-            if (!std::isfinite(viewmat[k])) return fail(VP_EINVAL, "viewmat[%d] is not finite", k);
-        if (!(fx > 0.0f) || !(fy > 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
-            return fail(VP_EINVAL, "fx, fy must be finite and > 0, cx, cy finite (got %g %g %g %g)", (double)fx, (double)fy,
-                        (double)cx, (double)cy);
-        if (!(eps2d >= 0.0f) || !std::isfinite(eps2d)) return fail(VP_EINVAL, "need a finite eps2d >= 0 (got %g)", (double)eps2d);
-        for (int k = 0; k < 12; ++k) cam.r[k] = viewmat[k];
-        cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy; cam.eps2d = eps2d;
-        cam.W = W; cam.H = H;
-    }
-    if (!workspace) return fail(VP_EWORKSPACE, "workspace is NULL");
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    if (!bwd_workspace) return fail(VP_EWORKSPACE, "backward workspace is NULL");
-    if ((uintptr_t)bwd_workspace & 255) return fail(VP_EWORKSPACE, "backward workspace must be 256-byte aligned");
-    const size_t bwd_need = geom ? splat_geom_bytes(capacity, D) : splat_bwd_bytes(capacity, D);
-    if (bwd_bytes < bwd_need)
-        return fail(VP_EWORKSPACE, "backward workspace has %zu bytes, need %zu", bwd_bytes, bwd_need);
-    SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (workspace_bytes < l.bytes) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, l.bytes);
-    if (n_gaussians == 0) return VP_OK;                  // no rows to write; nothing can exceed a capacity of 0 either
-    hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
-    const long long *total = (const long long *)(ws + l.total);
-    const int *count = (const int *)(ws + l.count);
-    const long long *offs = (const long long *)(ws + l.offs);
-    float *part = (float *)bwd_workspace;
+    const bool chain = grad_means || grad_quats || grad_scales;
     SplatLoss ls = {};
     ls.target = (const int *)target;
     ls.weight = pixel_weight;
     ls.stats = loss_stats;
     ls.grad_loss = grad_loss;
     ls.mean = reduction == VP_LOSS_MEAN;
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-#define VP_SPLAT_BWD(DT, GEOM) hipLaunchKernelGGL((k_splat_blend_backward<DT, GEOM, true>), grid, block, 0, stream,            \
-                                                  (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), count, offs,     \
-                                                  (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges), total,      \
-                                                  (long long)capacity, features, D, (long long)row_stride, W, H, logits,       \
-                                                  grad_alpha, part, ls)
-    if (geom) {
-        if (D <= 8) VP_SPLAT_BWD(8, true);
-        else if (D <= 16) VP_SPLAT_BWD(16, true);
-        else if (D <= 32) VP_SPLAT_BWD(32, true);
-        else VP_SPLAT_BWD(64, true);
-    } else {
-        if (D <= 8) VP_SPLAT_BWD(8, false);
-        else if (D <= 16) VP_SPLAT_BWD(16, false);
-        else if (D <= 32) VP_SPLAT_BWD(32, false);
-        else VP_SPLAT_BWD(64, false);
-    }
-#undef VP_SPLAT_BWD
-    VP_HIP(hipGetLastError());
-    const int gs = splat_reduce_group(geom ? D + SPLAT_SCREEN : D);
-    const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / gs - 1) / (256 / gs), 2048LL);
-#define VP_SPLAT_RED(GS)                                                                                                       \
-    do {                                                                                                                       \
-        if (geom)                                                                                                              \
-            hipLaunchKernelGGL((k_splat_grad_reduce_geom<GS>), dim3(g_red), dim3(256), 0, stream, count, offs,                 \
-                               (long long)n_gaussians, total, (long long)capacity, part, D, grad_features, grad_opacities,     \
-                               grad_screen, (int *)status);                                                                    \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((k_splat_grad_reduce<GS>), dim3(g_red), dim3(256), 0, stream, count, offs,                      \
-                               (long long)n_gaussians, total, (long long)capacity, (const float *)part, D, grad_features,      \
-                               grad_opacities, (int *)status);                                                                 \
-    } while (0)
-    if (gs == 16) VP_SPLAT_RED(16);
-    else if (gs == 32) VP_SPLAT_RED(32);
-    else VP_SPLAT_RED(64);
-#undef VP_SPLAT_RED
-    VP_HIP(hipGetLastError());
-    if (chain) {
-        hipLaunchKernelGGL(k_splat_geom_chain, dim3((unsigned)((n_gaussians + 255) / 256)), dim3(256), 0, stream, means, quats,
-                           scales, (long long)n_gaussians, cam, count, offs, total, (long long)capacity, (const float *)part, D,
-                           grad_means, grad_quats, grad_scales);
-        VP_HIP(hipGetLastError());
-    }
-    return VP_OK;
+    return splat_backward_impl({means, quats, scales, features, D, row_stride, n_gaussians, viewmat, fx, fy, cx, cy, W, H, eps2d,
+                                capacity, logits, grad_alpha, grad_means, grad_quats, grad_scales, grad_features,
+                                grad_opacities, grad_screen, status, workspace, workspace_bytes, bwd_workspace, bwd_bytes,
+                                stream_, chain || grad_screen, chain, true, ls});
 }
 
 static int read_status(void *workspace, hipStream_t stream, int *st /* [2][ST_WORDS] */)

@@ -7,6 +7,7 @@
 #endif
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <type_traits>
 
 namespace {
 
@@ -14,7 +15,8 @@ namespace {
 // The contract (INTEGRATION.md "Gaussian splatting"; tests/splat_reference.py is its float64 statement):
 //
 // k_splat_project   one thread per Gaussian.  Depth z = ((r20 mx + r21 my) + r22 mz) + t2 in fp32 (no contraction: the
-//   Makefile's -ffp-contract=off), culled when z < near or z > far.  The rest in float64, rounded to fp32 once at the end:
+//   Makefile's -ffp-contract=off), culled when z < near or z > far.  The rest in float64 (splat_chain, which the geometry
+//   backward differentiates), rounded to fp32 once at the end:
 //   Sigma = M M^T with M = R(q/|q|) diag(s), Sigma_c = R_w Sigma R_w^T, the clamped EWA Jacobian, Sigma2 = J Sigma_c J^T +
 //   eps2d I, conic = Sigma2^-1 (culled when det <= 0), mean2d = (fx px/z + cx, fy py/z + cy).  Float64 here keeps the fp32
 //   records within one rounding of the float64 oracle's values, so the blend's decisions differ from it only within the
@@ -29,9 +31,11 @@ namespace {
 // k_splat_ranges    one thread per sorted key: [start, end) of every tile's run.
 // k_splat_blend<DT> one 256-thread workgroup per 16x16 tile, one pixel per thread, DT >= D accumulators in registers.  The
 //   tile's run is staged through LDS in batches of SPLAT_BATCH(DT) Gaussians (records, then the feature rows zero-padded to
-//   DT).  Per visited pair: sigma, one exp, the 1/255 and 1e-4 tests and DT FMAs.  A pixel stops at the first Gaussian that
-//   would take T to <= 1e-4 (that one is not added); the workgroup leaves when every pixel has stopped
-//   (__syncthreads_count).  No atomics: each pixel's sum is in the sorted order, so images are bit-identical run to run.
+//   DT).  Per visited pair: sigma, one exp, the 1/255 and 1e-4 tests (splat_pair, the one statement of them) and DT FMAs
+//   (splat_blend_batch).  A pixel stops at the first Gaussian that would take T to <= 1e-4 (that one is not added); the
+//   workgroup leaves when every pixel has stopped (__syncthreads_count).  No atomics: each pixel's sum is in the sorted
+//   order, so images are bit-identical run to run.  The kernel stages a batch itself (an s_id array and a barrier between
+//   the records and the rows), not through the backward's splat_stage: that would change its LDS.
 //   Epilogue: label = argmax over the D channels (lowest index on ties), confidence = softmax top-1 minus top-2
 //   = (1 - exp(m2 - m1)) / sum_c exp(f_c - m1) (1 when D = 1), alpha = 1 - T; logits planar [D, H, W].  Only the outputs
 //   whose pointer is non-NULL are written.
@@ -61,6 +65,69 @@ struct SplatRec {                // 32 bytes per Gaussian
     int pad;
 };
 
+// The float64 chain from a Gaussian and the camera to its screen-space covariance, written once: k_splat_project takes the
+// record from it and k_splat_geom_chain differentiates it, so both see the same intermediates.  Rq = R(q / |q|), Rw the
+// camera's rotation, p the camera-space mean, S = Sigma_c = V V^T with V = R_w R_q diag(s), u = p.xy / p.z and cu its clamp
+// to the widened frustum, J the EWA Jacobian at the clamped point, JS = J S, Sigma2 = [[s00, s01], [s01, s11]] = J S J^T +
+// eps2d I and its determinant.  False (nothing usable filled) for a zero quaternion.
+struct SplatChain {
+    double qi, w, x, y, zq;      // 1 / |q| and the unit quaternion
+    double Rq[3][3], Rw[3][3], s[3], p[3], S[3][3];
+    double limxp, limxn, limyp, limyn, ux, uy, cux, cuy;
+    double J[2][3], JS[2][3], s00, s01, s11, det;
+};
+
+__device__ inline double splat_quat_norm2(float qw, float qx, float qy, float qz)
+{
+    return (double)qw * qw + (double)qx * qx + (double)qy * qy + (double)qz * qz;
+}
+
+__device__ inline void splat_chain(float mx, float my, float mz, float qw, float qx, float qy, float qz, float sx, float sy,
+                                   float sz, const SplatCam &cam, SplatChain &ch)
+{
+    const float *r = cam.r;
+    const double qi = 1.0 / sqrt(splat_quat_norm2(qw, qx, qy, qz)), w = qw * qi, x = qx * qi, y = qy * qi, zq = qz * qi;
+    ch.qi = qi; ch.w = w; ch.x = x; ch.y = y; ch.zq = zq;
+    const double Rq[3][3] = {{1.0 - 2.0 * (y * y + zq * zq), 2.0 * (x * y - w * zq), 2.0 * (x * zq + w * y)},
+                             {2.0 * (x * y + w * zq), 1.0 - 2.0 * (x * x + zq * zq), 2.0 * (y * zq - w * x)},
+                             {2.0 * (x * zq - w * y), 2.0 * (y * zq + w * x), 1.0 - 2.0 * (x * x + y * y)}};
+    const double s[3] = {sx, sy, sz};
+    double M[3][3], V[3][3];
+    double (&Rw)[3][3] = ch.Rw, (&p)[3] = ch.p, (&S)[3][3] = ch.S, (&J)[2][3] = ch.J, (&JS)[2][3] = ch.JS;
+    for (int a = 0; a < 3; ++a) {
+        ch.s[a] = s[a];
+        for (int c = 0; c < 3; ++c) {
+            ch.Rq[a][c] = Rq[a][c];
+            M[a][c] = Rq[a][c] * s[c];
+            Rw[a][c] = r[4 * a + c];
+        }
+    }
+    for (int a = 0; a < 3; ++a) p[a] = Rw[a][0] * mx + Rw[a][1] * my + Rw[a][2] * mz + (double)r[4 * a + 3];
+    // V = R_w M, Sigma_c = V V^T
+    for (int a = 0; a < 3; ++a)
+        for (int c = 0; c < 3; ++c) V[a][c] = Rw[a][0] * M[0][c] + Rw[a][1] * M[1][c] + Rw[a][2] * M[2][c];
+    for (int a = 0; a < 3; ++a)
+        for (int c = 0; c < 3; ++c) S[a][c] = V[a][0] * V[c][0] + V[a][1] * V[c][1] + V[a][2] * V[c][2];
+    const double zd = p[2], fx = cam.fx, fy = cam.fy, cx = cam.cx, cy = cam.cy;
+    ch.limxp = (cam.W - cx) / fx + 0.3 * (0.5 * cam.W) / fx;
+    ch.limxn = cx / fx + 0.3 * (0.5 * cam.W) / fx;
+    ch.limyp = (cam.H - cy) / fy + 0.3 * (0.5 * cam.H) / fy;
+    ch.limyn = cy / fy + 0.3 * (0.5 * cam.H) / fy;
+    ch.ux = p[0] / zd;
+    ch.uy = p[1] / zd;
+    ch.cux = fmin(fmax(ch.ux, -ch.limxn), ch.limxp);
+    ch.cuy = fmin(fmax(ch.uy, -ch.limyn), ch.limyp);
+    const double tx = zd * ch.cux, ty = zd * ch.cuy;
+    J[0][0] = fx / zd; J[0][1] = 0.0; J[0][2] = -fx * tx / (zd * zd);
+    J[1][0] = 0.0; J[1][1] = fy / zd; J[1][2] = -fy * ty / (zd * zd);
+    for (int a = 0; a < 2; ++a)
+        for (int c = 0; c < 3; ++c) JS[a][c] = J[a][0] * S[0][c] + J[a][1] * S[1][c] + J[a][2] * S[2][c];
+    ch.s00 = JS[0][0] * J[0][0] + JS[0][1] * J[0][1] + JS[0][2] * J[0][2] + cam.eps2d;
+    ch.s01 = JS[0][0] * J[1][0] + JS[0][1] * J[1][1] + JS[0][2] * J[1][2];
+    ch.s11 = JS[1][0] * J[1][0] + JS[1][1] * J[1][1] + JS[1][2] * J[1][2] + cam.eps2d;
+    ch.det = ch.s00 * ch.s11 - ch.s01 * ch.s01;
+}
+
 __global__ __launch_bounds__(256) void k_splat_project(const float *__restrict__ means, const float *__restrict__ quats,
                                                        const float *__restrict__ scales, const float *__restrict__ opac,
                                                        long long n, SplatCam cam, SplatRec *__restrict__ rec,
@@ -79,40 +146,11 @@ __global__ __launch_bounds__(256) void k_splat_project(const float *__restrict__
     if (!finite && n_nonfinite) atomicAdd(n_nonfinite, 1);
     const float *r = cam.r;
     const float z = ((r[8] * mx + r[9] * my) + r[10] * mz) + r[11];
-    const double qn2 = (double)qw * qw + (double)qx * qx + (double)qy * qy + (double)qz * qz;
-    if (finite && z >= cam.near_z && z <= cam.far_z && qn2 > 0.0 && (double)o >= 1.0 / 255.0) {
-        const double qi = 1.0 / sqrt(qn2), w = qw * qi, x = qx * qi, y = qy * qi, zq = qz * qi;
-        const double Rq[3][3] = {{1.0 - 2.0 * (y * y + zq * zq), 2.0 * (x * y - w * zq), 2.0 * (x * zq + w * y)},
-                                 {2.0 * (x * y + w * zq), 1.0 - 2.0 * (x * x + zq * zq), 2.0 * (y * zq - w * x)},
-                                 {2.0 * (x * zq - w * y), 2.0 * (y * zq + w * x), 1.0 - 2.0 * (x * x + y * y)}};
-        const double s[3] = {sx, sy, sz};
-        double M[3][3], Rw[3][3], p[3];
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) {
-                M[a][c] = Rq[a][c] * s[c];
-                Rw[a][c] = r[4 * a + c];
-            }
-        for (int a = 0; a < 3; ++a) p[a] = Rw[a][0] * mx + Rw[a][1] * my + Rw[a][2] * mz + (double)r[4 * a + 3];
-        // V = R_w M, Sigma_c = V V^T
-        double V[3][3], S[3][3];
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) V[a][c] = Rw[a][0] * M[0][c] + Rw[a][1] * M[1][c] + Rw[a][2] * M[2][c];
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) S[a][c] = V[a][0] * V[c][0] + V[a][1] * V[c][1] + V[a][2] * V[c][2];
-        const double zd = p[2], fx = cam.fx, fy = cam.fy, cx = cam.cx, cy = cam.cy;
-        const double limxp = (cam.W - cx) / fx + 0.3 * (0.5 * cam.W) / fx, limxn = cx / fx + 0.3 * (0.5 * cam.W) / fx;
-        const double limyp = (cam.H - cy) / fy + 0.3 * (0.5 * cam.H) / fy, limyn = cy / fy + 0.3 * (0.5 * cam.H) / fy;
-        const double ux = p[0] / zd, uy = p[1] / zd;
-        const double tx = zd * fmin(fmax(ux, -limxn), limxp), ty = zd * fmin(fmax(uy, -limyn), limyp);
-        const double J[2][3] = {{fx / zd, 0.0, -fx * tx / (zd * zd)}, {0.0, fy / zd, -fy * ty / (zd * zd)}};
-        double JS[2][3];
-        for (int a = 0; a < 2; ++a)
-            for (int c = 0; c < 3; ++c) JS[a][c] = J[a][0] * S[0][c] + J[a][1] * S[1][c] + J[a][2] * S[2][c];
-        const double s00 = JS[0][0] * J[0][0] + JS[0][1] * J[0][1] + JS[0][2] * J[0][2] + cam.eps2d;
-        const double s01 = JS[0][0] * J[1][0] + JS[0][1] * J[1][1] + JS[0][2] * J[1][2];
-        const double s11 = JS[1][0] * J[1][0] + JS[1][1] * J[1][1] + JS[1][2] * J[1][2] + cam.eps2d;
-        const double det = s00 * s11 - s01 * s01;
-        const double mxd = fx * ux + cx, myd = fy * uy + cy;
+    if (finite && z >= cam.near_z && z <= cam.far_z && splat_quat_norm2(qw, qx, qy, qz) > 0.0 && (double)o >= 1.0 / 255.0) {
+        SplatChain ch;
+        splat_chain(mx, my, mz, qw, qx, qy, qz, sx, sy, sz, cam, ch);
+        const double s00 = ch.s00, s01 = ch.s01, s11 = ch.s11, det = ch.det;
+        const double mxd = (double)cam.fx * ch.ux + (double)cam.cx, myd = (double)cam.fy * ch.uy + (double)cam.cy;
         if (det > 0.0 && isfinite(det) && isfinite(mxd) && isfinite(myd)) {
             const double ext = 2.0 * fmax(log(255.0 * (double)o), 0.0);
             const double rx = sqrt(ext * s00), ry = sqrt(ext * s11);
@@ -237,6 +275,53 @@ __device__ inline float splat_loss_scale(const SplatLoss &ls)
     return sw > 0.0 ? (float)((double)g / sw) : 0.0f;
 }
 
+// One (pixel, Gaussian) pair of the blend: what every sweep over a tile's run decides, and with which values.  ga = (mx,
+// my, A, B) and gb = (C, o) are the staged record, (sx, sy) the pixel's sample point, T the transmittance in front of the
+// Gaussian.  A pair is skipped (it contributes nothing: false), or it would take T to <= 1e-4, so the pixel ends before it
+// (true), or it is blended with weight a T and leaves Tn: then add(p) runs, and the result is false.  The forward and the
+// three backward sweeps all call this, so a replayed decision is the forward's by construction.  The blended case is a
+// callback, not a third result: the compiler keeps a three-valued result in a register and branches on it again in the
+// hot loop.
+struct SplatPair {
+    float e, raw, a, Tn;         // e^-sigma, o e^-sigma, the clamped alpha, T (1 - a)
+};
+
+template <class Add>
+__device__ inline bool splat_pair(const float4 ga, const float2 gb, float sx, float sy, float T, Add &&add)
+{
+    const float dx = ga.x - sx, dy = ga.y - sy;
+    const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
+    if (sigma < 0.0f) return false;
+    SplatPair p;
+    p.e = __expf(-sigma);
+    p.raw = gb.y * p.e;
+    p.a = fminf(0.999f, p.raw);
+    if (p.a < 1.0f / 255.0f) return false;
+    p.Tn = T * (1.0f - p.a);
+    if (p.Tn <= 1e-4f) return true;
+    add(p);
+    return false;
+}
+
+// The forward's accumulation over one staged batch of nb Gaussians: acc += a T f per added pair, in the batch's order.
+// k_splat_blend and the loss backward's replay both blend through this function: the replayed logits are the forward's bits.
+template <int DT>
+__device__ inline void splat_blend_batch(const float4 *s_ga, const float2 *s_gb, const float *s_f, int nb, float sx, float sy,
+                                         float (&acc)[DT], float &T, bool &done)
+{
+    if (done) return;
+    for (int k = 0; k < nb; ++k) {
+        done = splat_pair(s_ga[k], s_gb[k], sx, sy, T, [&](const SplatPair &p) {
+            const float wgt = p.a * T;
+            const float *f = s_f + k * DT;
+#pragma unroll
+            for (int c = 0; c < DT; ++c) acc[c] = fmaf(f[c], wgt, acc[c]);
+            T = p.Tn;
+        });
+        if (done) break;
+    }
+}
+
 template <int DT, bool LOSS = false>
 __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
     const SplatRec *__restrict__ rec, const int *__restrict__ vals, const longlong2 *__restrict__ ranges,
@@ -277,27 +362,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
             s_f[e] = c < D ? feats[(long long)s_id[k] * stride + c] : 0.0f;
         }
         __syncthreads();
-        if (!done) {
-            for (int k = 0; k < nb; ++k) {
-                const float4 ga = s_ga[k];
-                const float2 gb = s_gb[k];
-                const float dx = ga.x - sx, dy = ga.y - sy;
-                const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
-                if (sigma < 0.0f) continue;
-                const float a = fminf(0.999f, gb.y * __expf(-sigma));
-                if (a < 1.0f / 255.0f) continue;
-                const float Tn = T * (1.0f - a);
-                if (Tn <= 1e-4f) {
-                    done = true;
-                    break;
-                }
-                const float wgt = a * T;
-                const float *f = s_f + k * DT;
-#pragma unroll
-                for (int c = 0; c < DT; ++c) acc[c] = fmaf(f[c], wgt, acc[c]);
-                T = Tn;
-            }
-        }
+        splat_blend_batch<DT>(s_ga, s_gb, s_f, nb, sx, sy, acc, T, done);
     }
     if (!LOSS && !inside) return;
     const long long pix = (long long)py * W + px, hw = (long long)H * W;
@@ -397,8 +462,9 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_loss_sum(const double2 
 //
 // k_splat_blend_backward<DT>  one 256-thread workgroup per 16x16 tile, pixel per thread; the tile's upstream gradient G
 //   [256 x DT] in registers (the thread's own pixel) and in LDS (for the product).
-//   Sweep 1 replays the forward's decisions (the same fp32 operations in the same order) and keeps per pixel T_final and
-//   CG = sum_k w_k (f_k . G_p) in sorted order.
+//   Every sweep stages a batch with splat_stage and takes each pair's decision and values from splat_pair, the function the
+//   forward calls: a replayed decision is the forward's by construction.
+//   Sweep 1 keeps per pixel T_final and CG = sum_k w_k (f_k . G_p) in sorted order.
 //   Sweep 2 replays them again in batches of splat_bwd_batch(DT) Gaussians; per added Gaussian: w = a T, the running prefix
 //   P += w (f . G_p) and the behind-sum S . G_p = CG - P (exactly 0 after the last added Gaussian, since both are the same
 //   fp32 sequence; its error is a few ulp of sum_k w_k |f_k . G_p|), then
@@ -407,9 +473,9 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_loss_sum(const double2 
 //   partial_f[k][c] = sum_p W[k][p] G[p][c] (thread = (channel, group of Gaussians), p ascending, 4 pixels per step) and
 //   partial_o[k] = sum_p Q[k][p] (fixed segment sums, then a fixed xor tree).  Once every pixel has stopped, the rest of
 //   the run gets zero partials.
-// k_splat_grad_reduce<GS>  GS = 16, 32 or 64 lanes per Gaussian, lane = channel (channel D: the opacity), grid-stride over
-//   the Gaussians: its count[g] contiguous slots summed in ascending order.  Gaussians without tiles (culled) get rows of
-//   exactly 0.
+// k_splat_grad_reduce<GS, GEOM>  GS = 16, 32 or 64 lanes per Gaussian, lane = channel (channel D: the opacity; GEOM: then the
+//   five screen sums), grid-stride over the Gaussians: its count[g] contiguous slots summed in ascending order.  Gaussians
+//   without tiles (culled) get rows of exactly 0.
 // k_splat_blend_backward<DT, true> (vp_splat_rasterize_backward_geometry) is the same sweep with rows of D + 1 + 5 floats: the
 //   five screen-space sums of q = dL/da o e^-sigma (0 at the clamp) follow the opacity's,
 //     g_mx = -sum q (A dx + B dy), g_my = -sum q (B dx + C dy), g_A = -sum q dx^2 / 2, g_B = -sum q dx dy, g_C = -sum q dy^2 / 2.
@@ -420,8 +486,9 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_loss_sum(const double2 
 // shuffles' butterfly costs more VALU issue at D = 32 than the product's LDS traffic.
 // k_splat_blend_backward<DT, GEOM, true> (vp_splat_loss_backward) computes its upstream gradient instead of loading it:
 //   G = s w (softmax(C) - onehot(target)) per pixel (splat_loss_grad), with C either read from the logits image the forward
-//   wrote (saved) or blended again in a sweep 0 before sweep 1 (replay: the forward's fp32 operations in its order, gr[] as
-//   the accumulators, so the two arms give the same bits).  s is read on the device (splat_loss_scale).  No LDS is added.
+//   wrote (saved) or blended again in a sweep 0 before sweep 1 (replay: splat_blend_batch, the forward's own accumulation,
+//   with gr[] as the accumulators, so the two arms give the same bits).  s is read on the device (splat_loss_scale).  No
+//   LDS is added.
 // Both kernels write nothing when the device total exceeds the capacity (the reduce raises *status).
 // ------------------------------------------------------------------------------------------------
 // Gaussians per backward batch.  LDS: G (256 DT) + W and Q (2 NB 260) + features (NB DT) floats = 100 KiB at DT 32 and 64
@@ -434,6 +501,39 @@ __device__ inline long long splat_slot(const long long *__restrict__ offs, const
 {
     const int4 b = box[g];
     return offs[g] - count[g] + (long long)((int)blockIdx.y - b.y) * (b.z - b.x + 1) + ((int)blockIdx.x - b.x);
+}
+
+// Stage one batch of a tile's run for a backward sweep: the records and the feature rows (zero past D) of the nb Gaussians
+// from b0 on, with SLOTS also their partial rows' slots (sweep 2 alone writes partials); then the barrier.
+template <int DT, bool SLOTS>
+__device__ inline void splat_stage(const SplatRec *__restrict__ rec, const int4 *__restrict__ box, const int *__restrict__ count,
+                                   const long long *__restrict__ offs, const int *__restrict__ vals, long long b0, int nb,
+                                   const float *__restrict__ feats, int D, long long stride, float4 *s_ga, float2 *s_gb,
+                                   long long *s_slot, float *s_f)
+{
+    const int tid = threadIdx.x;
+    for (int k = tid; k < nb; k += SPLAT_THREADS) {
+        const int g = vals[b0 + k];
+        const SplatRec r = rec[g];
+        s_ga[k] = make_float4(r.mx, r.my, r.A, r.B);
+        s_gb[k] = make_float2(r.C, r.o);
+        if constexpr (SLOTS) s_slot[k] = splat_slot(offs, count, box, g);
+    }
+    for (int e = tid; e < nb * DT; e += SPLAT_THREADS) {
+        const int k = e / DT, c = e % DT;
+        s_f[e] = c < D ? feats[(long long)vals[b0 + k] * stride + c] : 0.0f;
+    }
+    __syncthreads();
+}
+
+// f . G_p over the DT channels, ascending: sweeps 1 and 2 form CG and its prefix P from the same sequence
+template <int DT>
+__device__ inline float splat_dot(const float *f, const float (&gr)[DT])
+{
+    float fg = 0.0f;
+#pragma unroll
+    for (int c = 0; c < DT; ++c) fg = fmaf(f[c], gr[c], fg);
+    return fg;
 }
 
 template <int DT, bool GEOM, bool LOSS = false>
@@ -463,67 +563,32 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
     const long long pix = (long long)py * W + px, hw = (long long)H * W;
     const longlong2 rg = ranges[(long long)blockIdx.y * gridDim.x + blockIdx.x];
     const int D1 = D + (GEOM ? 1 + SPLAT_SCREEN : 1);    // floats per partial row
+    // the pixel's upstream gradient; LOSS: first its logits C, read back (saved) or blended again (replay)
     float gr[DT];
+#pragma unroll
+    for (int c = 0; c < DT; ++c) gr[c] = grad_logits && inside && c < D ? grad_logits[c * hw + pix] : 0.0f;
     if constexpr (LOSS) {
-        // G = s w (softmax(C) - onehot(target)) from the pixel's own logits C: read back (saved) or blended again (replay)
         int t = -1;
         float sw = 0.0f;
         if (inside) {
             t = ls.target[pix];
             if (t >= 0 && t < D) sw = splat_loss_scale(ls) * (ls.weight ? ls.weight[pix] : 1.0f);
         }
-#pragma unroll
-        for (int c = 0; c < DT; ++c) gr[c] = grad_logits && inside && c < D ? grad_logits[c * hw + pix] : 0.0f;
         if (!grad_logits) {
-            // sweep 0: the forward's blend (the same fp32 operations in the same order), gr[] as its accumulators
+            // sweep 0: the forward's own accumulation (splat_blend_batch), gr[] as its accumulators
             float T = 1.0f;
             bool done = !inside;
             for (long long b0 = rg.x; b0 < rg.y; b0 += NB) {
                 if (__syncthreads_count(done) == SPLAT_THREADS) break;
                 const int nb = (int)(rg.y - b0 < NB ? rg.y - b0 : NB);
-                for (int k = tid; k < nb; k += SPLAT_THREADS) {
-                    const SplatRec r = rec[vals[b0 + k]];
-                    s_ga[k] = make_float4(r.mx, r.my, r.A, r.B);
-                    s_gb[k] = make_float2(r.C, r.o);
-                }
-                for (int e = tid; e < nb * DT; e += SPLAT_THREADS) {
-                    const int k = e / DT, c = e % DT;
-                    s_f[e] = c < D ? feats[(long long)vals[b0 + k] * stride + c] : 0.0f;
-                }
-                __syncthreads();
-                if (!done) {
-                    for (int k = 0; k < nb; ++k) {
-                        const float4 ga = s_ga[k];
-                        const float2 gb = s_gb[k];
-                        const float dx = ga.x - sx, dy = ga.y - sy;
-                        const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
-                        if (sigma < 0.0f) continue;
-                        const float a = fminf(0.999f, gb.y * __expf(-sigma));
-                        if (a < 1.0f / 255.0f) continue;
-                        const float Tn = T * (1.0f - a);
-                        if (Tn <= 1e-4f) {
-                            done = true;
-                            break;
-                        }
-                        const float wgt = a * T;
-                        const float *f = s_f + k * DT;
-#pragma unroll
-                        for (int c = 0; c < DT; ++c) gr[c] = fmaf(f[c], wgt, gr[c]);
-                        T = Tn;
-                    }
-                }
+                splat_stage<DT, false>(rec, box, count, offs, vals, b0, nb, feats, D, stride, s_ga, s_gb, s_slot, s_f);
+                splat_blend_batch<DT>(s_ga, s_gb, s_f, nb, sx, sy, gr, T, done);
             }
         }
-        splat_loss_grad<DT>(gr, D, t, sw);
-#pragma unroll
-        for (int c = 0; c < DT; ++c) s_G[tid * DT + c] = gr[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < DT; ++c) {
-            gr[c] = grad_logits && inside && c < D ? grad_logits[c * hw + pix] : 0.0f;
-            s_G[tid * DT + c] = gr[c];
-        }
+        splat_loss_grad<DT>(gr, D, t, sw);       // G = s w (softmax(C) - onehot(target))
     }
+#pragma unroll
+    for (int c = 0; c < DT; ++c) s_G[tid * DT + c] = gr[c];
     const float ga_p = grad_alpha && inside ? grad_alpha[pix] : 0.0f;
 
     // sweep 1: T_final and CG
@@ -532,36 +597,14 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
     for (long long b0 = rg.x; b0 < rg.y; b0 += NB) {
         if (__syncthreads_count(done) == SPLAT_THREADS) break;      // also keeps the last batch's LDS until all read it
         const int nb = (int)(rg.y - b0 < NB ? rg.y - b0 : NB);
-        for (int k = tid; k < nb; k += SPLAT_THREADS) {
-            const SplatRec r = rec[vals[b0 + k]];
-            s_ga[k] = make_float4(r.mx, r.my, r.A, r.B);
-            s_gb[k] = make_float2(r.C, r.o);
-        }
-        for (int e = tid; e < nb * DT; e += SPLAT_THREADS) {
-            const int k = e / DT, c = e % DT;
-            s_f[e] = c < D ? feats[(long long)vals[b0 + k] * stride + c] : 0.0f;
-        }
-        __syncthreads();
+        splat_stage<DT, false>(rec, box, count, offs, vals, b0, nb, feats, D, stride, s_ga, s_gb, s_slot, s_f);
         if (!done) {
             for (int k = 0; k < nb; ++k) {
-                const float4 ga = s_ga[k];
-                const float2 gb = s_gb[k];
-                const float dx = ga.x - sx, dy = ga.y - sy;
-                const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
-                if (sigma < 0.0f) continue;
-                const float a = fminf(0.999f, gb.y * __expf(-sigma));
-                if (a < 1.0f / 255.0f) continue;
-                const float Tn = T * (1.0f - a);
-                if (Tn <= 1e-4f) {
-                    done = true;
-                    break;
-                }
-                const float *f = s_f + k * DT;
-                float fg = 0.0f;
-#pragma unroll
-                for (int c = 0; c < DT; ++c) fg = fmaf(f[c], gr[c], fg);
-                CG = fmaf(a * T, fg, CG);
-                T = Tn;
+                done = splat_pair(s_ga[k], s_gb[k], sx, sy, T, [&](const SplatPair &pr) {
+                    CG = fmaf(pr.a * T, splat_dot<DT>(s_f + k * DT, gr), CG);
+                    T = pr.Tn;
+                });
+                if (done) break;
             }
         }
     }
@@ -582,48 +625,19 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
             break;
         }
         const int nb = (int)(rg.y - b0 < NB ? rg.y - b0 : NB);
-        for (int k = tid; k < nb; k += SPLAT_THREADS) {
-            const int g = vals[b0 + k];
-            const SplatRec r = rec[g];
-            s_ga[k] = make_float4(r.mx, r.my, r.A, r.B);
-            s_gb[k] = make_float2(r.C, r.o);
-            s_slot[k] = splat_slot(offs, count, box, g);
-        }
-        for (int e = tid; e < nb * DT; e += SPLAT_THREADS) {
-            const int k = e / DT, c = e % DT;
-            s_f[e] = c < D ? feats[(long long)vals[b0 + k] * stride + c] : 0.0f;
-        }
-        __syncthreads();
+        splat_stage<DT, true>(rec, box, count, offs, vals, b0, nb, feats, D, stride, s_ga, s_gb, s_slot, s_f);
         for (int k = 0; k < NB; ++k) {
             float wk = 0.0f, qv = 0.0f;
-            if (!done && k < nb) {
-                const float4 ga = s_ga[k];
-                const float2 gb = s_gb[k];
-                const float dx = ga.x - sx, dy = ga.y - sy;
-                const float sigma = 0.5f * (ga.z * dx * dx + gb.x * dy * dy) + ga.w * dx * dy;
-                if (sigma >= 0.0f) {
-                    const float e = __expf(-sigma);
-                    const float raw = gb.y * e;
-                    const float a = fminf(0.999f, raw);
-                    if (a >= 1.0f / 255.0f) {
-                        const float Tn = T * (1.0f - a);
-                        if (Tn <= 1e-4f) {
-                            done = true;
-                        } else {
-                            const float *f = s_f + k * DT;
-                            float fg = 0.0f;
-#pragma unroll
-                            for (int c = 0; c < DT; ++c) fg = fmaf(f[c], gr[c], fg);
-                            wk = a * T;
-                            P = fmaf(wk, fg, P);
-                            const float inv = 1.0f / (1.0f - a);
-                            const float dLda = T * fg - (CG - P) * inv + ga_p * T_final * inv;
-                            qv = raw < 0.999f ? dLda * e : 0.0f;
-                            T = Tn;
-                        }
-                    }
-                }
-            }
+            if (!done && k < nb)
+                done = splat_pair(s_ga[k], s_gb[k], sx, sy, T, [&](const SplatPair &pr) {
+                    const float fg = splat_dot<DT>(s_f + k * DT, gr);
+                    wk = pr.a * T;
+                    P = fmaf(wk, fg, P);
+                    const float inv = 1.0f / (1.0f - pr.a);
+                    const float dLda = T * fg - (CG - P) * inv + ga_p * T_final * inv;
+                    qv = pr.raw < 0.999f ? dLda * pr.e : 0.0f;
+                    T = pr.Tn;
+                });
             s_W[k * SPLAT_BWD_ROW + tid] = wk;
             s_Q[k * SPLAT_BWD_ROW + tid] = qv;
         }
@@ -648,42 +662,45 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
             for (int j = 0; j < KPT; ++j)
                 if (pk0 + j < nb) part[s_slot[pk0 + j] * D1 + pc] = acc[j];
         }
-        float q = 0.0f;
+        // the opacity partial: Q[qk][.] summed in a fixed order, segments by pixel index, then the xor tree.  GEOM: the five
+        // screen sums ride on it, Q[k][p] times a factor of the record and the pixel's offset (recomputed as splat_pair
+        // computes it), through the same segments and tree
+        float q = 0.0f, s5[SPLAT_SCREEN] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        float4 ga = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float2 gb = make_float2(0.0f, 0.0f);
         if constexpr (GEOM) {
-            // the five screen sums ride on the opacity sum: Q[k][p] times a factor of the record and the pixel's offset
-            // (recomputed as sweep 2 computed it), in the same fixed order: segments by pixel index, then the xor tree
-            const float4 ga = s_ga[qk];
-            const float2 gb = s_gb[qk];
-            float s5[SPLAT_SCREEN] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            for (int i = 0; i < NB; ++i) {
-                const int p = qs * NB + i;
-                const float v = s_Q[qk * SPLAT_BWD_ROW + p];
+            ga = s_ga[qk];
+            gb = s_gb[qk];
+        }
+        for (int i = 0; i < NB; ++i) {
+            const int p = qs * NB + i;
+            const float v = s_Q[qk * SPLAT_BWD_ROW + p];
+            q += v;
+            if constexpr (GEOM) {
                 const float dx = ga.x - ((int)blockIdx.x * SPLAT_TILE + (p & (SPLAT_TILE - 1)) + 0.5f);
                 const float dy = ga.y - ((int)blockIdx.y * SPLAT_TILE + p / SPLAT_TILE + 0.5f);
-                q += v;
                 s5[0] += v * (ga.z * dx + ga.w * dy);
                 s5[1] += v * (ga.w * dx + gb.x * dy);
                 s5[2] += v * (0.5f * dx * dx);
                 s5[3] += v * (dx * dy);
                 s5[4] += v * (0.5f * dy * dy);
             }
+        }
 #pragma unroll
-            for (int m = QSEG / 2; m >= 1; m /= 2) {
-                q += __shfl_xor(q, m);
+        for (int m = QSEG / 2; m >= 1; m /= 2) {
+            q += __shfl_xor(q, m);
+            if constexpr (GEOM) {
 #pragma unroll
                 for (int j = 0; j < SPLAT_SCREEN; ++j) s5[j] += __shfl_xor(s5[j], m);
             }
-            if (qs == 0 && qk < nb) {
-                float *row = part + s_slot[qk] * D1 + D;
-                row[0] = q;
+        }
+        if (qs == 0 && qk < nb) {
+            float *row = part + s_slot[qk] * D1 + D;
+            row[0] = q;
+            if constexpr (GEOM) {
 #pragma unroll
                 for (int j = 0; j < SPLAT_SCREEN; ++j) row[1 + j] = -gb.y * s5[j];      // q = Q o, and the sums' sign
             }
-        } else {
-            for (int i = 0; i < NB; ++i) q += s_Q[qk * SPLAT_BWD_ROW + qs * NB + i];
-#pragma unroll
-            for (int m = QSEG / 2; m >= 1; m /= 2) q += __shfl_xor(q, m);
-            if (qs == 0 && qk < nb) part[s_slot[qk] * D1 + D] = q;
         }
     }
 }
@@ -691,25 +708,54 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
 // lanes per Gaussian in the reduce: the smallest of 16, 32, 64 that holds D + 1 channels (D = 64: lane c and c + 64)
 inline int splat_reduce_group(int D) { return D + 1 <= 16 ? 16 : D + 1 <= 32 ? 32 : 64; }
 
+// The kernels are instantiated for DT = 8, 16, 32, 64 accumulators (the smallest that holds D) and for reduce groups of
+// 16, 32, 64 lanes: f gets the choice as a std::integral_constant, and a run-time flag as std::true_type / false_type.
+template <class F>
+inline void splat_with_dt(int D, F &&f)
+{
+    if (D <= 8) f(std::integral_constant<int, 8>{});
+    else if (D <= 16) f(std::integral_constant<int, 16>{});
+    else if (D <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+template <class F>
+inline void splat_with_group(int gs, F &&f)
+{
+    if (gs == 16) f(std::integral_constant<int, 16>{});
+    else if (gs == 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+template <class F>
+inline void splat_with_flag(bool flag, F &&f)
+{
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // GS lanes per Gaussian, grid-stride over the Gaussians; each lane sums its channel over the Gaussian's count[g] contiguous
-// slots in ascending order, four loads in flight
-template <int GS>
+// slots in ascending order, four loads in flight.  GEOM: rows of D + 1 + SPLAT_SCREEN floats, and the five screen sums of a
+// Gaussian with tiles are also written back into its first slot's row, where k_splat_geom_chain reads them (the reduce has
+// no per-Gaussian scratch of its own: the size function knows the capacity, not N).  Each channel of a Gaussian's rows is
+// read and written by one lane only.
+template <int GS, bool GEOM>
 __global__ __launch_bounds__(256) void k_splat_grad_reduce(const int *__restrict__ count, const long long *__restrict__ offs,
                                                            long long n, const long long *total_p, long long capacity,
-                                                           const float *__restrict__ part, int D, float *__restrict__ grad_f,
-                                                           float *__restrict__ grad_o, int *status)
+                                                           float *part, int D, float *__restrict__ grad_f,
+                                                           float *__restrict__ grad_o, float *__restrict__ grad_s, int *status)
 {
     if (*total_p > capacity) {
         if (blockIdx.x == 0 && threadIdx.x == 0 && status) *status = 1;
         return;
     }
     constexpr int GPB = 256 / GS;                       // Gaussians per workgroup and round
-    const int D1 = D + 1, lane = threadIdx.x % GS;
+    const int D1 = D + 1 + (GEOM ? SPLAT_SCREEN : 0), lane = threadIdx.x % GS;
     const long long step = (long long)gridDim.x * GPB;
     for (long long g = (long long)blockIdx.x * GPB + threadIdx.x / GS; g < n; g += step) {
         const long long s1 = offs[g], s0 = s1 - count[g];
         for (int c = lane; c < D1; c += GS) {
-            const float *p = part + c;
+            float *p = part + c;
             float s = 0.0f;
             long long k = s0;
             for (; k + 4 <= s1; k += 4) {
@@ -722,60 +768,19 @@ __global__ __launch_bounds__(256) void k_splat_grad_reduce(const int *__restrict
             for (; k < s1; ++k) s += p[k * D1];
             if (c < D) {
                 if (grad_f) grad_f[g * D + c] = s;
-            } else if (grad_o) {
-                grad_o[g] = s;
-            }
-        }
-    }
-}
-
-// The geometry backward's reduce: as k_splat_grad_reduce over rows of D + 1 + SPLAT_SCREEN floats.  The five screen sums of
-// a Gaussian with tiles are also written back into its first slot's row, where k_splat_geom_chain reads them (the reduce
-// has no per-Gaussian scratch of its own: the size function knows the capacity, not N).  Each channel of a Gaussian's rows
-// is read and written by one lane only.
-template <int GS>
-__global__ __launch_bounds__(256) void k_splat_grad_reduce_geom(const int *__restrict__ count,
-                                                                const long long *__restrict__ offs, long long n,
-                                                                const long long *total_p, long long capacity, float *part, int D,
-                                                                float *__restrict__ grad_f, float *__restrict__ grad_o,
-                                                                float *__restrict__ grad_s, int *status)
-{
-    if (*total_p > capacity) {
-        if (blockIdx.x == 0 && threadIdx.x == 0 && status) *status = 1;
-        return;
-    }
-    constexpr int GPB = 256 / GS;
-    const int DR = D + 1 + SPLAT_SCREEN, lane = threadIdx.x % GS;
-    const long long step = (long long)gridDim.x * GPB;
-    for (long long g = (long long)blockIdx.x * GPB + threadIdx.x / GS; g < n; g += step) {
-        const long long s1 = offs[g], s0 = s1 - count[g];
-        for (int c = lane; c < DR; c += GS) {
-            float *p = part + c;
-            float s = 0.0f;
-            long long k = s0;
-            for (; k + 4 <= s1; k += 4) {
-                const float a0 = p[k * DR], a1 = p[(k + 1) * DR], a2 = p[(k + 2) * DR], a3 = p[(k + 3) * DR];
-                s += a0;
-                s += a1;
-                s += a2;
-                s += a3;
-            }
-            for (; k < s1; ++k) s += p[k * DR];
-            if (c < D) {
-                if (grad_f) grad_f[g * D + c] = s;
             } else if (c == D) {
                 if (grad_o) grad_o[g] = s;
-            } else {
+            } else if constexpr (GEOM) {
                 if (grad_s) grad_s[g * SPLAT_SCREEN + (c - D - 1)] = s;
-                if (s1 > s0) p[s0 * DR] = s;
+                if (s1 > s0) p[s0 * D1] = s;
             }
         }
     }
 }
 
 // The adjoint of k_splat_project's float64 chain, one thread per Gaussian: the five screen sums (fp32, from the first slot's
-// row) to grad_means / grad_quats / grad_scales, rounded to fp32 once.  The forward's intermediates are recomputed from the
-// Gaussian and the camera with the forward's own expressions.  With X = conic, GX = [[g_A, g_B/2], [g_B/2, g_C]]:
+// row) to grad_means / grad_quats / grad_scales, rounded to fp32 once.  The forward's intermediates come from splat_chain, the
+// function k_splat_project calls.  With X = conic, GX = [[g_A, g_B/2], [g_B/2, g_C]]:
 //   G_Sigma2 = -X GX X,  G_S = J^T G_Sigma2 J,  G_J = 2 G_Sigma2 J S,  Hl = U^T G_S U with U = R_w R(n), n = q / |q|
 //   (dL/dSigma in the Gaussian's own frame, where Sigma = diag(s^2)):  grad_s[c] = 2 s_c Hl_cc;  a rotation R -> R exp([d]x)
 //   gives dL/dd = 2 (Hl_12 (s1^2 - s2^2), Hl_02 (s2^2 - s0^2), Hl_01 (s0^2 - s1^2)): exactly 0 between equal scales;
@@ -805,40 +810,13 @@ __global__ __launch_bounds__(256) void k_splat_geom_chain(const float *__restric
             any |= g5[j] != 0.0;
         }
     if (any) {
-        const float *r = cam.r;
-        const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2];
-        const float qw = quats[4 * i], qx = quats[4 * i + 1], qy = quats[4 * i + 2], qz = quats[4 * i + 3];
-        const double qn2 = (double)qw * qw + (double)qx * qx + (double)qy * qy + (double)qz * qz;
-        const double qi = 1.0 / sqrt(qn2), w = qw * qi, x = qx * qi, y = qy * qi, zq = qz * qi;
-        const double Rq[3][3] = {{1.0 - 2.0 * (y * y + zq * zq), 2.0 * (x * y - w * zq), 2.0 * (x * zq + w * y)},
-                                 {2.0 * (x * y + w * zq), 1.0 - 2.0 * (x * x + zq * zq), 2.0 * (y * zq - w * x)},
-                                 {2.0 * (x * zq - w * y), 2.0 * (y * zq + w * x), 1.0 - 2.0 * (x * x + y * y)}};
-        const double s[3] = {scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]};
-        double M[3][3], Rw[3][3], p[3], V[3][3], S[3][3];
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) {
-                M[a][c] = Rq[a][c] * s[c];
-                Rw[a][c] = r[4 * a + c];
-            }
-        for (int a = 0; a < 3; ++a) p[a] = Rw[a][0] * mx + Rw[a][1] * my + Rw[a][2] * mz + (double)r[4 * a + 3];
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) V[a][c] = Rw[a][0] * M[0][c] + Rw[a][1] * M[1][c] + Rw[a][2] * M[2][c];
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) S[a][c] = V[a][0] * V[c][0] + V[a][1] * V[c][1] + V[a][2] * V[c][2];
-        const double zd = p[2], fx = cam.fx, fy = cam.fy, cx = cam.cx, cy = cam.cy;
-        const double limxp = (cam.W - cx) / fx + 0.3 * (0.5 * cam.W) / fx, limxn = cx / fx + 0.3 * (0.5 * cam.W) / fx;
-        const double limyp = (cam.H - cy) / fy + 0.3 * (0.5 * cam.H) / fy, limyn = cy / fy + 0.3 * (0.5 * cam.H) / fy;
-        const double ux = p[0] / zd, uy = p[1] / zd;
-        const double cux = fmin(fmax(ux, -limxn), limxp), cuy = fmin(fmax(uy, -limyn), limyp);
-        const double tx = zd * cux, ty = zd * cuy, iz2 = 1.0 / (zd * zd);
-        const double J[2][3] = {{fx / zd, 0.0, -fx * tx * iz2}, {0.0, fy / zd, -fy * ty * iz2}};
-        double JS[2][3];
-        for (int a = 0; a < 2; ++a)
-            for (int c = 0; c < 3; ++c) JS[a][c] = J[a][0] * S[0][c] + J[a][1] * S[1][c] + J[a][2] * S[2][c];
-        const double s00 = JS[0][0] * J[0][0] + JS[0][1] * J[0][1] + JS[0][2] * J[0][2] + cam.eps2d;
-        const double s01 = JS[0][0] * J[1][0] + JS[0][1] * J[1][1] + JS[0][2] * J[1][2];
-        const double s11 = JS[1][0] * J[1][0] + JS[1][1] * J[1][1] + JS[1][2] * J[1][2] + cam.eps2d;
-        const double det = s00 * s11 - s01 * s01;
+        SplatChain ch;
+        splat_chain(means[3 * i], means[3 * i + 1], means[3 * i + 2], quats[4 * i], quats[4 * i + 1], quats[4 * i + 2],
+                    quats[4 * i + 3], scales[3 * i], scales[3 * i + 1], scales[3 * i + 2], cam, ch);
+        const double qi = ch.qi, w = ch.w, x = ch.x, y = ch.y, zq = ch.zq, zd = ch.p[2], fx = cam.fx, fy = cam.fy;
+        const double ux = ch.ux, uy = ch.uy, cux = ch.cux, cuy = ch.cuy, iz2 = 1.0 / (zd * zd);
+        const double (&Rq)[3][3] = ch.Rq, (&Rw)[3][3] = ch.Rw, (&s)[3] = ch.s, (&J)[2][3] = ch.J, (&JS)[2][3] = ch.JS;
+        const double s00 = ch.s00, s01 = ch.s01, s11 = ch.s11, det = ch.det;
         const double A = s11 / det, B = -s01 / det, C = s00 / det;
         const double gA = g5[2], hB = 0.5 * g5[3], gC = g5[4];
         const double y00 = gA * A + hB * B, y01 = gA * B + hB * C, y10 = hB * A + gC * B, y11 = hB * B + gC * C;
@@ -867,8 +845,8 @@ __global__ __launch_bounds__(256) void k_splat_geom_chain(const float *__restric
         gq[1] = 2.0 * qi * (w * gd[0] - zq * gd[1] + y * gd[2]);
         gq[2] = 2.0 * qi * (zq * gd[0] + w * gd[1] - x * gd[2]);
         gq[3] = 2.0 * qi * (-y * gd[0] + x * gd[1] + w * gd[2]);
-        const double g_ux = g5[0] * fx + (ux > -limxn && ux < limxp ? -GJ[0][2] * fx / zd : 0.0);
-        const double g_uy = g5[1] * fy + (uy > -limyn && uy < limyp ? -GJ[1][2] * fy / zd : 0.0);
+        const double g_ux = g5[0] * fx + (ux > -ch.limxn && ux < ch.limxp ? -GJ[0][2] * fx / zd : 0.0);
+        const double g_uy = g5[1] * fy + (uy > -ch.limyn && uy < ch.limyp ? -GJ[1][2] * fy / zd : 0.0);
         const double g_z = (-GJ[0][0] * fx + GJ[0][2] * fx * cux - GJ[1][1] * fy + GJ[1][2] * fy * cuy) * iz2 -
                            (g_ux * ux + g_uy * uy) / zd;
         const double gp[3] = {g_ux / zd, g_uy / zd, g_z};

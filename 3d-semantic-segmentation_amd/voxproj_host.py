@@ -604,23 +604,94 @@ def _splat_camera(viewmat, K, W, H):
     return (ctypes.c_float * 16)(*vm.tolist()), [float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])]
 
 
+def _splat_gaussians(means, quats, scales, opacities=None, dev=None):
+    """The N x 3 / 4 / 3 (and N) float32 Gaussian tensors on one GPU (``dev``, default the means'): N and contiguous tensors."""
+    import torch
+    named = [(means, "means"), (quats, "quats"), (scales, "scales")] + ([(opacities, "opacities")] if opacities is not None else [])
+    _require_tensors(*((t, name, (torch.float32,)) for t, name in named))
+    N = int(means.shape[0]) if means.dim() == 2 else -1
+    _require(tuple(means.shape) == (N, 3) and N >= 0, "means must be [N, 3]")
+    _require(tuple(quats.shape) == (N, 4), f"quats must be [{N}, 4]")
+    _require(tuple(scales.shape) == (N, 3), f"scales must be [{N}, 3]")
+    _require(opacities is None or tuple(opacities.shape) == (N,), f"opacities must be [{N}]")
+    dev = means.device if dev is None else dev
+    _require(all(t.device == dev for t, _ in named), "the Gaussian tensors must be on one device")
+    return N, [t.contiguous() for t, _ in named]
+
+
+def _splat_rows(features, n=None):
+    """The float32 feature rows [n, D] (any row count when ``n`` is None), 1 <= D <= 64, with a unit channel stride and a
+    row stride >= D (a contiguous copy otherwise): (features, D)."""
+    import torch
+    _require_tensors((features, "features", (torch.float32,)))
+    _require(features.dim() == 2 and (n is None or int(features.shape[0]) == int(n)),
+             f"features must be [{'N' if n is None else n}, D]")
+    D = int(features.shape[1])
+    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
+    if features.stride(1) != 1 or features.stride(0) < D:
+        features = features.contiguous()
+    return features, D
+
+
+def _splat_images(dev, *specs):
+    """(tensor or None, name, shape, dtype) per optional image on the features' device ``dev`` (shape None: one element):
+    the contiguous tensors, None kept."""
+    out = []
+    for t, name, shape, dtype in specs:
+        if t is not None:
+            _require_tensors((t, name, (dtype,)))
+            _require(t.device == dev and (t.numel() == 1 if shape is None else tuple(t.shape) == tuple(int(v) for v in shape)),
+                     f"{name} must be {'one element' if shape is None else list(shape)} on the features' device")
+            t = t.contiguous()
+        out.append(t)
+    return out
+
+
+def _splat_forward_workspace(workspace, n_gaussians, W, H, capacity, dev):
+    """Grow the projection's workspace to ``capacity`` intersections (the projection's bytes kept): its pointer."""
+    L = lib()
+    keep = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), 0))
+    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
+    return workspace.ensure(nbytes, dev, keep=keep)
+
+
+def _splat_backward_workspaces(caller, forward, workspace, bwd_workspace, n_gaussians, W, H, capacity, D, geom, dev):
+    """Check that ``workspace`` is the one a ``forward`` call left, and size the backward scratch (rows with the five
+    screen sums when ``geom``): (the scratch's SplatWorkspace, its pointer)."""
+    L = lib()
+    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= nbytes, f"{caller} needs the workspace of a {forward} call")
+    need = int((L.vp_splat_geometry_backward_workspace_bytes if geom else L.vp_splat_backward_workspace_bytes)(int(capacity), D))
+    _require(need > 0, f"no backward workspace size for capacity {capacity}, D = {D}")
+    bw = bwd_workspace if bwd_workspace is not None else SplatWorkspace()
+    return bw, bw.ensure(need, dev)
+
+
+def _splat_grads(N, D, dev, **want):
+    """The dict of the backward calls' outputs: an empty float32 tensor per gradient asked for, None for the others."""
+    import torch
+    tails = {"means": (3,), "quats": (4,), "scales": (3,), "features": (D,), "opacities": (), "screen": (5,)}
+    return {name: torch.empty((N,) + tail, dtype=torch.float32, device=dev) if want.get(name) else None
+            for name, tail in tails.items()}
+
+
+def _ptr(t):
+    """The device pointer of an optional tensor: NULL for None and for an empty tensor."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
 def splat_project(means, quats, scales, opacities, viewmat, K, W, H, *, near=0.01, far=1e10, eps2d=0.3, workspace=None,
                   n_nonfinite=None):
     """vp_splat_project: screen-space records of every Gaussian into ``workspace`` (a SplatWorkspace; grown to the
     projection's size).  Returns the device int64 [1] intersection count (not read here).  ``n_nonfinite``: optional device
     int32 [1] that counts the Gaussians culled for a non-finite parameter."""
     import torch
-    _require_tensors(*((t, name, (torch.float32,)) for t, name in
-                       ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
-    N = int(means.shape[0]) if means.dim() == 2 else -1
-    _require(tuple(means.shape) == (N, 3) and N >= 0, "means must be [N, 3]")
-    _require(tuple(quats.shape) == (N, 4), f"quats must be [{N}, 4]")
-    _require(tuple(scales.shape) == (N, 3), f"scales must be [{N}, 3]")
-    _require(tuple(opacities.shape) == (N,), f"opacities must be [{N}]")
+    N, (means, quats, scales, opacities) = _splat_gaussians(means, quats, scales, opacities)
     dev = means.device
-    _require(all(t.device == dev for t in (quats, scales, opacities)), "the Gaussian tensors must be on one device")
     vm, (fx, fy, cx, cy) = _splat_camera(viewmat, K, W, H)
-    means, quats, scales, opacities = (t.contiguous() for t in (means, quats, scales, opacities))
     ws = workspace if workspace is not None else SplatWorkspace()
     L = lib()
     nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), 0))
@@ -643,18 +714,9 @@ def splat_rasterize(features, n_gaussians, W, H, capacity, workspace, *, want_lo
     alpha f32 [H,W] or None, logits f32 [D,H,W] or None).  ``status``: optional device int32 [1], set to 1 when the device
     count exceeds ``capacity`` (then no output is written)."""
     import torch
-    _require_tensors((features, "features", (torch.float32,)))
-    _require(features.dim() == 2 and int(features.shape[0]) == int(n_gaussians), f"features must be [{n_gaussians}, D]")
-    D = int(features.shape[1])
-    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
-    if features.stride(1) != 1 or features.stride(0) < D:
-        features = features.contiguous()
+    features, D = _splat_rows(features, n_gaussians)
     dev = features.device
-    L = lib()
-    keep = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), 0))
-    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
-    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
-    ptr = workspace.ensure(nbytes, dev, keep=keep)
+    ptr = _splat_forward_workspace(workspace, n_gaussians, W, H, capacity, dev)
     labels = torch.empty((H, W), dtype=torch.int32, device=dev)
     conf = torch.empty((H, W), dtype=torch.float32, device=dev) if want_confidence else None
     alpha = torch.empty((H, W), dtype=torch.float32, device=dev) if want_alpha else None
@@ -662,9 +724,9 @@ def splat_rasterize(features, n_gaussians, W, H, capacity, workspace, *, want_lo
     p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_splat_rasterize(features.data_ptr(), D, max(int(features.stride(0)), D), int(n_gaussians), int(W), int(H),
-                                       int(capacity), labels.data_ptr(), p(conf), p(alpha), p(logits), p(status), ptr,
-                                       workspace.capacity(), stream.cuda_stream))
+        _check_rc(lib().vp_splat_rasterize(features.data_ptr(), D, max(int(features.stride(0)), D), int(n_gaussians), int(W),
+                                           int(H), int(capacity), labels.data_ptr(), p(conf), p(alpha), p(logits), p(status),
+                                           ptr, workspace.capacity(), stream.cuda_stream))
     return labels, conf, alpha, logits
 
 
@@ -677,40 +739,20 @@ def splat_rasterize_backward(features, n_gaussians, W, H, capacity, workspace, g
     f32 [N,D] or None, grad_opacities f32 [N] or None).  ``status``: optional device int32 [1], set to 1 when the device count
     exceeds ``capacity`` (then nothing is written)."""
     import torch
-    _require_tensors((features, "features", (torch.float32,)))
-    _require(features.dim() == 2 and int(features.shape[0]) == int(n_gaussians), f"features must be [{n_gaussians}, D]")
-    D = int(features.shape[1])
-    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
-    if features.stride(1) != 1 or features.stride(0) < D:
-        features = features.contiguous()
-    dev = features.device
-    for t, name, shape in ((grad_logits, "grad_logits", (D, H, W)), (grad_alpha, "grad_alpha", (H, W))):
-        if t is not None:
-            _require_tensors((t, name, (torch.float32,)))
-            _require(tuple(t.shape) == tuple(int(v) for v in shape) and t.device == dev,
-                     f"{name} must be {list(shape)} on the features' device")
-    grad_logits = grad_logits.contiguous() if grad_logits is not None else None
-    grad_alpha = grad_alpha.contiguous() if grad_alpha is not None else None
-    L = lib()
-    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
-    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-             workspace.capacity() >= nbytes, "splat_rasterize_backward needs the workspace of a splat_rasterize call")
-    need = int(L.vp_splat_backward_workspace_bytes(int(capacity), D))
-    _require(need > 0, f"no backward workspace size for capacity {capacity}, D = {D}")
-    bw = bwd_workspace if bwd_workspace is not None else SplatWorkspace()
-    bptr = bw.ensure(need, dev)
-    N = int(n_gaussians)
-    gf = torch.empty((N, D), dtype=torch.float32, device=dev) if want_features else None
-    go = torch.empty((N,), dtype=torch.float32, device=dev) if want_opacities else None
-    p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    features, D = _splat_rows(features, n_gaussians)
+    dev, N = features.device, int(n_gaussians)
+    grad_logits, grad_alpha = _splat_images(dev, (grad_logits, "grad_logits", (D, H, W), torch.float32),
+                                            (grad_alpha, "grad_alpha", (H, W), torch.float32))
+    bw, bptr = _splat_backward_workspaces("splat_rasterize_backward", "splat_rasterize", workspace, bwd_workspace, N, W, H,
+                                          capacity, D, False, dev)
+    out = _splat_grads(N, D, dev, features=want_features, opacities=want_opacities)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_splat_rasterize_backward(p(features), D, max(int(features.stride(0)), D), N, int(W), int(H),
-                                                int(capacity), p(grad_logits), p(grad_alpha), p(gf), p(go), p(status),
-                                                workspace.ptr(), workspace.capacity(), bptr, bw.capacity(),
-                                                stream.cuda_stream))
-    return gf, go
+        _check_rc(lib().vp_splat_rasterize_backward(
+            _ptr(features), D, max(int(features.stride(0)), D), N, int(W), int(H), int(capacity), _ptr(grad_logits),
+            _ptr(grad_alpha), _ptr(out["features"]), _ptr(out["opacities"]), _ptr(status), workspace.ptr(),
+            workspace.capacity(), bptr, bw.capacity(), stream.cuda_stream))
+    return out["features"], out["opacities"]
 
 
 def splat_rasterize_backward_geometry(means, quats, scales, features, viewmat, K, W, H, capacity, workspace, grad_logits=None,
@@ -727,48 +769,48 @@ def splat_rasterize_backward_geometry(means, quats, scales, features, viewmat, K
     import torch
     _require_tensors(*((t, name, (torch.float32,)) for t, name in
                        ((means, "means"), (quats, "quats"), (scales, "scales"), (features, "features"))))
-    N = int(means.shape[0]) if means.dim() == 2 else -1
-    _require(tuple(means.shape) == (N, 3) and N >= 0, "means must be [N, 3]")
-    _require(tuple(quats.shape) == (N, 4), f"quats must be [{N}, 4]")
-    _require(tuple(scales.shape) == (N, 3), f"scales must be [{N}, 3]")
-    _require(features.dim() == 2 and int(features.shape[0]) == N, f"features must be [{N}, D]")
-    D = int(features.shape[1])
-    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
+    N, (means, quats, scales) = _splat_gaussians(means, quats, scales, dev=features.device)
+    features, D = _splat_rows(features, N)
     dev = features.device
-    _require(all(t.device == dev for t in (means, quats, scales)), "the Gaussian tensors must be on one device")
-    if features.stride(1) != 1 or features.stride(0) < D:
-        features = features.contiguous()
-    means, quats, scales = (t.contiguous() for t in (means, quats, scales))
-    for t, name, shape in ((grad_logits, "grad_logits", (D, H, W)), (grad_alpha, "grad_alpha", (H, W))):
-        if t is not None:
-            _require_tensors((t, name, (torch.float32,)))
-            _require(tuple(t.shape) == tuple(int(v) for v in shape) and t.device == dev,
-                     f"{name} must be {list(shape)} on the features' device")
-    grad_logits = grad_logits.contiguous() if grad_logits is not None else None
-    grad_alpha = grad_alpha.contiguous() if grad_alpha is not None else None
+    grad_logits, grad_alpha = _splat_images(dev, (grad_logits, "grad_logits", (D, H, W), torch.float32),
+                                            (grad_alpha, "grad_alpha", (H, W), torch.float32))
     vm, (fx, fy, cx, cy) = _splat_camera(viewmat, K, W, H)
-    L = lib()
-    nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), int(capacity)))
-    _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}, capacity {capacity}")
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-             workspace.capacity() >= nbytes, "splat_rasterize_backward_geometry needs the workspace of a splat_rasterize call")
-    need = int(L.vp_splat_geometry_backward_workspace_bytes(int(capacity), D))
-    _require(need > 0, f"no backward workspace size for capacity {capacity}, D = {D}")
-    bw = bwd_workspace if bwd_workspace is not None else SplatWorkspace()
-    bptr = bw.ensure(need, dev)
-    out = {name: torch.empty((N,) + tail, dtype=torch.float32, device=dev) if want else None
-           for name, tail, want in (("means", (3,), want_means), ("quats", (4,), want_quats), ("scales", (3,), want_scales),
-                                    ("features", (D,), want_features), ("opacities", (), want_opacities),
-                                    ("screen", (5,), want_screen))}
-    p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    bw, bptr = _splat_backward_workspaces("splat_rasterize_backward_geometry", "splat_rasterize", workspace, bwd_workspace, N,
+                                          W, H, capacity, D, True, dev)
+    out = _splat_grads(N, D, dev, means=want_means, quats=want_quats, scales=want_scales, features=want_features,
+                       opacities=want_opacities, screen=want_screen)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_splat_rasterize_backward_geometry(
-            p(means), p(quats), p(scales), p(features), D, max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy, int(W),
-            int(H), float(eps2d), int(capacity), p(grad_logits), p(grad_alpha), p(out["means"]), p(out["quats"]),
-            p(out["scales"]), p(out["features"]), p(out["opacities"]), p(out["screen"]), p(status), workspace.ptr(),
-            workspace.capacity(), bptr, bw.capacity(), stream.cuda_stream))
+        _check_rc(lib().vp_splat_rasterize_backward_geometry(
+            _ptr(means), _ptr(quats), _ptr(scales), _ptr(features), D, max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy,
+            int(W), int(H), float(eps2d), int(capacity), _ptr(grad_logits), _ptr(grad_alpha), _ptr(out["means"]),
+            _ptr(out["quats"]), _ptr(out["scales"]), _ptr(out["features"]), _ptr(out["opacities"]), _ptr(out["screen"]),
+            _ptr(status), workspace.ptr(), workspace.capacity(), bptr, bw.capacity(), stream.cuda_stream))
     return out
+
+
+def _splat_sized_view(means, quats, scales, opacities, viewmat, K, W, H, near, far, eps2d, workspace):
+    """splat_project, then the one read of the 8-byte intersection count that sizes the sort: (workspace, capacity, the
+    device counter of non-finite Gaussians, the device status word for the rasterize call)."""
+    import torch
+    ws = workspace if workspace is not None else SplatWorkspace()
+    bad = torch.zeros(1, dtype=torch.int32, device=means.device)
+    status = torch.zeros(1, dtype=torch.int32, device=means.device)
+    n_isect = splat_project(means, quats, scales, opacities, viewmat, K, W, H, near=near, far=far, eps2d=eps2d,
+                            workspace=ws, n_nonfinite=bad)
+    cap = int(n_isect.item())
+    _require(cap <= 2 ** 31 - 1, f"{cap} tile intersections: more than 2^31 - 1")
+    return ws, cap, bad, status
+
+
+def _splat_view_check(caller, status, bad, unwritten):
+    """Read the status word and the non-finite counter (one synchronisation) and raise VoxprojError on either."""
+    import torch
+    st, n_bad = (int(v) for v in torch.cat([status, bad]).tolist())
+    if st:
+        raise VoxprojError(f"{caller}: the intersection count outgrew the workspace ({unwritten})")
+    if n_bad:
+        raise VoxprojError(f"{caller}: {n_bad} Gaussian(s) have a non-finite parameter (culled)")
 
 
 def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, *, want_logits=False, want_alpha=False,
@@ -789,21 +831,11 @@ def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, 
     _require_tensors(*((t, name, (torch.float32,)) for t, name in
                        ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"), (features, "features"))))
     _require(features.device == means.device, "features and the Gaussians must be on one device")
-    ws = workspace if workspace is not None else SplatWorkspace()
-    bad = torch.zeros(1, dtype=torch.int32, device=means.device)
-    status = torch.zeros(1, dtype=torch.int32, device=means.device)
-    n_isect = splat_project(means, quats, scales, opacities, viewmat, K, W, H, near=near, far=far, eps2d=eps2d,
-                            workspace=ws, n_nonfinite=bad)
-    cap = int(n_isect.item())
-    _require(cap <= 2 ** 31 - 1, f"{cap} tile intersections: more than 2^31 - 1")
+    ws, cap, bad, status = _splat_sized_view(means, quats, scales, opacities, viewmat, K, W, H, near, far, eps2d, workspace)
     labels, conf, alpha, logits = splat_rasterize(features, int(means.shape[0]), W, H, cap, ws, want_logits=want_logits,
                                                   want_alpha=want_alpha, want_confidence=want_confidence, status=status)
     if check:
-        st, n_bad = (int(v) for v in torch.cat([status, bad]).tolist())
-        if st:
-            raise VoxprojError("splat_features: the intersection count outgrew the workspace (no image written)")
-        if n_bad:
-            raise VoxprojError(f"splat_features: {n_bad} Gaussian(s) have a non-finite parameter (culled)")
+        _splat_view_check("splat_features", status, bad, "no image written")
     return SplatResult(labels, conf, alpha, logits, cap, bad)
 
 
@@ -833,21 +865,12 @@ def splat_rasterize_loss(features, n_gaussians, W, H, capacity, workspace, targe
     logits as splat_rasterize, each None unless asked for).  ``loss_workspace``: a SplatWorkspace for the per-tile sums (a
     fresh one when None)."""
     import torch
-    _require_tensors((features, "features", (torch.float32,)))
-    _require(features.dim() == 2 and int(features.shape[0]) == int(n_gaussians), f"features must be [{n_gaussians}, D]")
-    D = int(features.shape[1])
-    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
-    if features.stride(1) != 1 or features.stride(0) < D:
-        features = features.contiguous()
+    features, D = _splat_rows(features, n_gaussians)
     dev = features.device
     target, pixel_weight = _splat_loss_maps(target, pixel_weight, W, H, dev)
-    L = lib()
-    keep = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), 0))
-    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
-    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
-    ptr = workspace.ensure(nbytes, dev, keep=keep)
+    ptr = _splat_forward_workspace(workspace, n_gaussians, W, H, capacity, dev)
     lw = loss_workspace if loss_workspace is not None else SplatWorkspace()
-    lptr = lw.ensure(int(L.vp_splat_loss_workspace_bytes(int(W), int(H))), dev)
+    lptr = lw.ensure(int(lib().vp_splat_loss_workspace_bytes(int(W), int(H))), dev)
     img = lambda want, dtype, *lead: torch.empty(lead + (H, W), dtype=dtype, device=dev) if want else None  # noqa: E731
     stats = torch.zeros(2, dtype=torch.float64, device=dev)
     ploss = img(want_pixel_loss, torch.float32)
@@ -856,10 +879,10 @@ def splat_rasterize_loss(features, n_gaussians, W, H, capacity, workspace, targe
     p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_splat_rasterize_loss(p(features) if features.numel() else None, D, max(int(features.stride(0)), D),
-                                            int(n_gaussians), int(W), int(H), int(capacity), p(target), p(pixel_weight),
-                                            p(stats), p(ploss), p(labels), p(conf), p(alpha), p(logits), p(status), ptr,
-                                            workspace.capacity(), lptr, lw.capacity(), stream.cuda_stream))
+        _check_rc(lib().vp_splat_rasterize_loss(_ptr(features), D, max(int(features.stride(0)), D), int(n_gaussians), int(W),
+                                                int(H), int(capacity), p(target), p(pixel_weight), p(stats), p(ploss),
+                                                p(labels), p(conf), p(alpha), p(logits), p(status), ptr, workspace.capacity(),
+                                                lptr, lw.capacity(), stream.cuda_stream))
     return stats, ploss, labels, conf, alpha, logits
 
 
@@ -875,13 +898,8 @@ def splat_loss_backward(means, quats, scales, features, viewmat, K, W, H, capaci
     sweep.  Returns the dict of splat_rasterize_backward_geometry."""
     import torch
     _require(reduction in _REDUCTIONS, f"reduction must be 'sum' or 'mean', not {reduction!r}")
-    _require_tensors((features, "features", (torch.float32,)))
-    _require(features.dim() == 2, "features must be [N, D]")
-    N, D = int(features.shape[0]), int(features.shape[1])
-    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
-    dev = features.device
-    if features.stride(1) != 1 or features.stride(0) < D:
-        features = features.contiguous()
+    features, D = _splat_rows(features)
+    N, dev = int(features.shape[0]), features.device
     chain = want_means or want_quats or want_scales
     geom = chain or want_screen
     vm, fx, fy, cx, cy = None, 1.0, 1.0, 0.0, 0.0
@@ -889,43 +907,27 @@ def splat_loss_backward(means, quats, scales, features, viewmat, K, W, H, capaci
         _require_tensors(*((t, name, (torch.float32,)) for t, name in ((means, "means"), (quats, "quats"), (scales, "scales"))))
         _require(tuple(means.shape) == (N, 3) and tuple(quats.shape) == (N, 4) and tuple(scales.shape) == (N, 3),
                  f"means, quats, scales must be [{N}, 3], [{N}, 4], [{N}, 3]")
-        _require(all(t.device == dev for t in (means, quats, scales)), "the Gaussian tensors must be on one device")
-        means, quats, scales = (t.contiguous() for t in (means, quats, scales))
+        _, (means, quats, scales) = _splat_gaussians(means, quats, scales, dev=dev)
         vm, (fx, fy, cx, cy) = _splat_camera(viewmat, K, W, H)
     else:
         means = quats = scales = None
     target, pixel_weight = _splat_loss_maps(target, pixel_weight, W, H, dev)
-    for t, name, shape, dt in ((logits, "logits", (D, H, W), torch.float32), (grad_alpha, "grad_alpha", (H, W), torch.float32),
-                               (grad_loss, "grad_loss", None, torch.float32), (loss_stats, "loss_stats", (2,), torch.float64)):
-        if t is not None:
-            _require_tensors((t, name, (dt,)))
-            _require(t.device == dev and (t.numel() == 1 if shape is None else tuple(t.shape) == tuple(int(v) for v in shape)),
-                     f"{name} must be {'one element' if shape is None else list(shape)} on the features' device")
+    logits, grad_alpha, grad_loss, loss_stats = _splat_images(
+        dev, (logits, "logits", (D, H, W), torch.float32), (grad_alpha, "grad_alpha", (H, W), torch.float32),
+        (grad_loss, "grad_loss", None, torch.float32), (loss_stats, "loss_stats", (2,), torch.float64))
     _require(loss_stats is not None, "loss_stats (the forward's) is required")
-    logits = logits.contiguous() if logits is not None else None
-    grad_alpha = grad_alpha.contiguous() if grad_alpha is not None else None
-    L = lib()
-    nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), int(capacity)))
-    _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}, capacity {capacity}")
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-             workspace.capacity() >= nbytes, "splat_loss_backward needs the workspace of a splat_rasterize_loss call")
-    need = int((L.vp_splat_geometry_backward_workspace_bytes if geom else L.vp_splat_backward_workspace_bytes)(int(capacity), D))
-    _require(need > 0, f"no backward workspace size for capacity {capacity}, D = {D}")
-    bw = bwd_workspace if bwd_workspace is not None else SplatWorkspace()
-    bptr = bw.ensure(need, dev)
-    out = {name: torch.empty((N,) + tail, dtype=torch.float32, device=dev) if want else None
-           for name, tail, want in (("means", (3,), want_means), ("quats", (4,), want_quats), ("scales", (3,), want_scales),
-                                    ("features", (D,), want_features), ("opacities", (), want_opacities),
-                                    ("screen", (5,), want_screen))}
-    p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    bw, bptr = _splat_backward_workspaces("splat_loss_backward", "splat_rasterize_loss", workspace, bwd_workspace, N, W, H,
+                                          capacity, D, geom, dev)
+    out = _splat_grads(N, D, dev, means=want_means, quats=want_quats, scales=want_scales, features=want_features,
+                       opacities=want_opacities, screen=want_screen)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_splat_loss_backward(
-            p(means), p(quats), p(scales), p(features), D, max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy, int(W),
-            int(H), float(eps2d), int(capacity), p(target), p(pixel_weight), p(logits), p(loss_stats), _REDUCTIONS[reduction],
-            p(grad_loss), p(grad_alpha), p(out["means"]), p(out["quats"]), p(out["scales"]), p(out["features"]),
-            p(out["opacities"]), p(out["screen"]), p(status), workspace.ptr(), workspace.capacity(), bptr, bw.capacity(),
-            stream.cuda_stream))
+        _check_rc(lib().vp_splat_loss_backward(
+            _ptr(means), _ptr(quats), _ptr(scales), _ptr(features), D, max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy,
+            int(W), int(H), float(eps2d), int(capacity), _ptr(target), _ptr(pixel_weight), _ptr(logits), _ptr(loss_stats),
+            _REDUCTIONS[reduction], _ptr(grad_loss), _ptr(grad_alpha), _ptr(out["means"]), _ptr(out["quats"]),
+            _ptr(out["scales"]), _ptr(out["features"]), _ptr(out["opacities"]), _ptr(out["screen"]), _ptr(status),
+            workspace.ptr(), workspace.capacity(), bptr, bw.capacity(), stream.cuda_stream))
     return out
 
 
@@ -941,22 +943,12 @@ def splat_loss(means, quats, scales, opacities, features, viewmat, K, W, H, targ
                        ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"), (features, "features"))))
     _require(features.dim() == 2 and features.shape[0] == means.shape[0], "features must be [N, D] with one row per Gaussian")
     _require(features.device == means.device, "features and the Gaussians must be on one device")
-    ws = workspace if workspace is not None else SplatWorkspace()
-    bad = torch.zeros(1, dtype=torch.int32, device=means.device)
-    status = torch.zeros(1, dtype=torch.int32, device=means.device)
-    n_isect = splat_project(means, quats, scales, opacities, viewmat, K, W, H, near=near, far=far, eps2d=eps2d,
-                            workspace=ws, n_nonfinite=bad)
-    cap = int(n_isect.item())
-    _require(cap <= 2 ** 31 - 1, f"{cap} tile intersections: more than 2^31 - 1")
+    ws, cap, bad, status = _splat_sized_view(means, quats, scales, opacities, viewmat, K, W, H, near, far, eps2d, workspace)
     out = splat_rasterize_loss(features, int(means.shape[0]), W, H, cap, ws, target, pixel_weight,
                                want_pixel_loss=want_pixel_loss, want_labels=want_labels, want_confidence=want_confidence,
                                want_alpha=want_alpha, want_logits=want_logits, loss_workspace=loss_workspace, status=status)
     if check:
-        st, n_bad = (int(v) for v in torch.cat([status, bad]).tolist())
-        if st:
-            raise VoxprojError("splat_loss: the intersection count outgrew the workspace (nothing written)")
-        if n_bad:
-            raise VoxprojError(f"splat_loss: {n_bad} Gaussian(s) have a non-finite parameter (culled)")
+        _splat_view_check("splat_loss", status, bad, "nothing written")
     return SplatLossResult(*out, cap, bad)
 
 

@@ -93,7 +93,7 @@ def compare(s, vm, K, W, H, r, min_good_frac=0.8, min_reached=1, **kw):
     return o, good
 
 
-@pytest.mark.parametrize("D", [1, 3, 13, 32, 33, 64])
+@pytest.mark.parametrize("D", [1, 3, 8, 9, 13, 16, 17, 32, 33, 64])
 @pytest.mark.parametrize("seed", [0, 1])
 def test_random_scenes(D, seed):
     W, H = 61, 47

@@ -74,7 +74,7 @@ def compare(s, vm, K, W, H, G, Ga, gf, go, min_nonzero=1):
 
 
 @pytest.mark.parametrize("mode", ["logits", "alpha", "both"])
-@pytest.mark.parametrize("D", [1, 3, 13, 16, 32, 33, 64])
+@pytest.mark.parametrize("D", [1, 3, 8, 9, 13, 16, 17, 32, 33, 64])
 def test_random_scenes(D, mode):
     W, H = 61, 47
     s = scene(400, D, D)

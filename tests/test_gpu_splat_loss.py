@@ -124,7 +124,7 @@ def compare(name, s, r, g, e, grad_alpha=None, min_nonzero=1, geometry=False):
 # ------------------------------------------------------------------------------------------------ 1. random scenes
 @pytest.mark.parametrize("reduction", ["sum", "mean"])
 @pytest.mark.parametrize("weights", [False, True])
-@pytest.mark.parametrize("D", [1, 3, 13, 16, 32, 33, 64])
+@pytest.mark.parametrize("D", [1, 3, 8, 9, 13, 16, 17, 32, 33, 64])
 def test_random_scenes(D, weights, reduction):
     W, H = 61, 47
     s = scene(400, D, D)
