@@ -31,6 +31,7 @@
 //   vp_render.h  the transpose: every pixel copies the row of its first-hit voxel (k_render_walk, k_render_small)
 //   vp_query.h   text query of a feature table: cosine logits, argmax label, softmax margin on the matrix cores (k_query)
 //   vp_splat.h   tile-based Gaussian splatting of D-channel features with a fused label / confidence epilogue (stage 5.2)
+//   vp_eval.h    scoring label maps against ground truth: confusion matrix, boundary band, boundary counts (all integers)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 #include <hip/hip_runtime.h>
@@ -59,6 +60,7 @@
 #include "vp_render.h"
 #include "vp_query.h"
 #include "vp_splat.h"
+#include "vp_eval.h"
 
 // ------------------------------------------------------------------------------------------------
 // host helpers
@@ -1276,6 +1278,78 @@ int vp_aggregate_view_f16(float *view_sum, int32_t *view_count, void *run16, int
     hipLaunchKernelGGL(k_aggregate_view_f16, dim3((unsigned)((n_rows - 1 + 3) / 4)), dim3(256), 0, (hipStream_t)stream_, view_sum,
                        (int *)view_count, (_Float16 *)run16, (int *)views, (int *)first_view, view_index, (int *)nonfinite_dev,
                        (long long)n_rows, C);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Scoring label maps (vp_eval.h).  Every check is host arithmetic and comes before the first launch.
+// ------------------------------------------------------------------------------------------------
+size_t vp_label_scores_workspace_bytes(int W, int H)
+{
+    if (W < 1 || W > EVAL_MAX_WH || H < 1 || H > EVAL_MAX_WH) return 0;
+    // the prediction's band | the target's band | the row pass's ok map, one byte per pixel each
+    return 3 * align256((size_t)W * H);
+}
+
+static int eval_check_image(int W, int H)
+{
+    if (W < 1 || W > EVAL_MAX_WH || H < 1 || H > EVAL_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, EVAL_MAX_WH);
+    return VP_OK;
+}
+
+static int eval_check_workspace(const void *workspace, size_t workspace_bytes, int W, int H)
+{
+    const size_t need = vp_label_scores_workspace_bytes(W, H);
+    if (!workspace || workspace_bytes < need)
+        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    return VP_OK;
+}
+
+int vp_label_boundary(const int32_t *labels, int W, int H, int radius, uint8_t *band, void *workspace, size_t workspace_bytes,
+                      void *stream_)
+{
+    if (!labels || !band) return fail(VP_EINVAL, "null pointer argument (labels or band)");
+    if (int rc = eval_check_image(W, H)) return rc;
+    if (radius < 1 || radius > EVAL_MAX_RADIUS) return fail(VP_EINVAL, "radius = %d outside [1, %d]", radius, EVAL_MAX_RADIUS);
+    if (int rc = eval_check_workspace(workspace, workspace_bytes, W, H)) return rc;
+    unsigned char *ok = (unsigned char *)workspace + 2 * align256((size_t)W * H);
+    eval_launch_band((const int *)labels, W, H, radius, (unsigned char *)band, ok, (hipStream_t)stream_);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_label_scores(const int32_t *pred, const int32_t *target, int W, int H, int P, int radius, int64_t *confusion,
+                    int64_t *skipped, int64_t *bnd_inter, int64_t *bnd_union, void *workspace, size_t workspace_bytes,
+                    void *stream_)
+{
+    if (!pred || !target || !confusion || !skipped) return fail(VP_EINVAL, "null pointer argument (pred, target, confusion or skipped)");
+    if (int rc = eval_check_image(W, H)) return rc;
+    if (P < 1 || P > EVAL_MAX_P) return fail(VP_EINVAL, "P = %d outside [1, %d]", P, EVAL_MAX_P);
+    if (radius < 0 || radius > EVAL_MAX_RADIUS) return fail(VP_EINVAL, "radius = %d outside [0, %d]", radius, EVAL_MAX_RADIUS);
+    if (radius > 0 && (!bnd_inter || !bnd_union)) return fail(VP_EINVAL, "radius > 0 needs bnd_inter and bnd_union");
+    if (radius > 0)
+        if (int rc = eval_check_workspace(workspace, workspace_bytes, W, H)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long n = (long long)W * H;
+    unsigned char *pband = nullptr, *tband = nullptr;
+    if (radius > 0) {
+        const size_t plane = align256((size_t)n);
+        pband = (unsigned char *)workspace;
+        tband = pband + plane;
+        unsigned char *ok = tband + plane;
+        eval_launch_band((const int *)pred, W, H, radius, pband, ok, stream);
+        eval_launch_band((const int *)target, W, H, radius, tband, ok, stream);
+    }
+    // (radius = 0: the boundary pointers are not touched, whatever they are)
+    const dim3 grid((unsigned)std::min<long long>((n + 255) / 256, EVAL_SCORE_BLOCKS));
+#define VP_EVAL_SCORES(LDS) hipLaunchKernelGGL((k_eval_scores<LDS>), grid, dim3(256), 0, stream, (const int *)pred, (const int *)target, n, \
+        P, (const unsigned char *)pband, (const unsigned char *)tband, (unsigned long long *)confusion,                              \
+        (unsigned long long *)skipped, (unsigned long long *)bnd_inter, (unsigned long long *)bnd_union)
+    if (P <= EVAL_LDS_P) VP_EVAL_SCORES(true); else VP_EVAL_SCORES(false);
+#undef VP_EVAL_SCORES
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

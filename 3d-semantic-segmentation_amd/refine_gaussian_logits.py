@@ -3,7 +3,7 @@ the per-Gaussian logits and the per-view labels) and ``render_semantics_logits.p
 
   refine_gaussian_logits.py --gaussians_ply point_cloud.ply --logit_path X.npz --cam_params camera_params.json
       --targets_dir DIR [--views NAME ...] [--max_images N] [--downsample_factor F] [--principal_point center|camera]
-      [--weight confidence|none] [--steps 200] [--views_per_step 4] [--lr 0.1] [--seed 0] --out REFINED.npz
+      [--weight confidence|none] [--steps 200] [--views_per_step 4] [--lr 0.1] [--seed 0] [--report_miou] --out REFINED.npz
 
 Inputs: the 3DGS point cloud and the .npz of ``query_voxel_features.py gaussians`` ('logits' [N, P], 'prompts'), as
 render_semantics_logits.py reads them, with its cameras and image sizes; the targets ``DIR/<name>_labels.npy`` (int16 [H,W],
@@ -14,7 +14,8 @@ differs from the view's render size is an error.
 Training: the P real channels of 'logits' (no padding) are the parameters of torch Adam; each step draws --views_per_step
 views with a seeded generator and takes the mean of their weighted cross-entropies, each one fused call
 (splat_autograd.splat_cross_entropy: no logits image, no gradient image).  Before and after, the mean loss and the share of
-labelled pixels whose rendered label agrees with the target are printed over all views.  Every kernel on the path is
+labelled pixels whose rendered label agrees with the target are printed over all views; with --report_miou also the mIoU
+and fwIoU of the rendered labels against the targets (one confusion over all views, voxproj_host.label_scores).  Every kernel on the path is
 deterministic, so two runs with the same arguments write byte-identical logits.
 
 Output: --out, an .npz with the input's schema: 'labels' int16 [N] (argmax of the refined logits), 'logits' f32 [N, P],
@@ -77,6 +78,7 @@ def build_parser():
     ap.add_argument("--views_per_step", type=int, default=4)
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--report_miou", action="store_true", help="add mIoU / fwIoU against the targets to the before / after lines")
     ap.add_argument("--out", required=True, help="the refined .npz")
     return ap
 
@@ -127,20 +129,37 @@ def main(argv=None):
         return splat_autograd.splat_cross_entropy(g["means"], g["quats"], g["scales"], g["opacities"], param, vm, K, W, H,
                                                   target, w, reduction="mean", check=False)
 
+    scores = None
+    if args.report_miou:
+        import label_metrics
+        import voxproj_host
+        scores = voxproj_host.LabelScores(P, dev)
+
     def evaluate():
         with torch.no_grad():
             loss, agree, total = 0.0, 0, 0
+            if scores is not None:
+                scores.zero_()
             for v in views:
                 ce, labels, _, _ = view_loss(v)
                 valid = v[4] >= 0
                 loss += float(ce)
                 agree += int((labels[valid] == v[4][valid]).sum())
                 total += int(valid.sum())
-        return loss / len(views), agree / max(total, 1), total
+                if scores is not None:
+                    voxproj_host.label_scores(labels, v[4], P, out=scores)
+        m = label_metrics.metrics(scores.numpy()[0]) if scores is not None else None
+        return loss / len(views), agree / max(total, 1), total, m
 
-    l0, a0, total = evaluate()
+    def miou_text(m):
+        if m is None:
+            return ""
+        fmt = lambda x: "null" if x is None else f"{x:.4f}"  # noqa: E731
+        return f", mIoU {fmt(m['miou'])}, fwIoU {fmt(m['fwiou'])}"
+
+    l0, a0, total, m0 = evaluate()
     print(f"[REFINE] {len(views)} view(s), {total} labelled pixels, {P} classes, {raw.shape[0]} Gaussians")
-    print(f"[REFINE] before: mean loss {l0:.6f}, pixel agreement {a0:.4f}")
+    print(f"[REFINE] before: mean loss {l0:.6f}, pixel agreement {a0:.4f}{miou_text(m0)}")
     gen = torch.Generator().manual_seed(args.seed)
     k = min(args.views_per_step, len(views))
     for _ in range(args.steps):
@@ -151,12 +170,15 @@ def main(argv=None):
             loss = loss + view_loss(views[i])[0] / k
         loss.backward()
         opt.step()
-    l1, a1, _ = evaluate()
-    print(f"[REFINE] after {args.steps} step(s): mean loss {l1:.6f}, pixel agreement {a1:.4f}")
+    l1, a1, _, m1 = evaluate()
+    print(f"[REFINE] after {args.steps} step(s): mean loss {l1:.6f}, pixel agreement {a1:.4f}{miou_text(m1)}")
     prompts = d["prompts"] if "prompts" in d else None
     save_refined(args.out, param.detach().cpu().numpy(), prompts, d["colors"] if "colors" in d else None)
     print(f"[REFINE] -> {args.out}")
-    return dict(loss_before=l0, loss_after=l1, agreement_before=a0, agreement_after=a1)
+    res = dict(loss_before=l0, loss_after=l1, agreement_before=a0, agreement_after=a1)
+    if scores is not None:
+        res.update(miou_before=m0["miou"], miou_after=m1["miou"], fwiou_before=m0["fwiou"], fwiou_after=m1["fwiou"])
+    return res
 
 
 if __name__ == "__main__":

@@ -57,6 +57,7 @@ EXPORTS = [
     "vp_splat_backward_workspace_bytes", "vp_splat_rasterize_backward",
     "vp_splat_geometry_backward_workspace_bytes", "vp_splat_rasterize_backward_geometry",
     "vp_splat_loss_workspace_bytes", "vp_splat_rasterize_loss", "vp_splat_loss_backward",
+    "vp_label_scores_workspace_bytes", "vp_label_boundary", "vp_label_scores",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -210,6 +211,12 @@ def lib():
                                                  ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
                 [ctypes.c_int] * 2 + [ctypes.c_float, ctypes.c_int64] + [vp] * 4 + [ctypes.c_int] + [vp] * 10 + \
                 [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+            L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
+            L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+            L.vp_label_boundary.restype = ctypes.c_int
+            L.vp_label_boundary.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]
+            L.vp_label_scores.restype = ctypes.c_int
+            L.vp_label_scores.argtypes = [vp, vp] + [ctypes.c_int] * 4 + [vp] * 5 + [ctypes.c_size_t, vp]
             if L.vp_abi_version() != VP_ABI_VERSION:
                 raise VoxprojError(f"{LIB_PATH} has ABI version {L.vp_abi_version()}, this package needs {VP_ABI_VERSION}: rebuild it")
             _lib = L
@@ -953,6 +960,93 @@ def splat_loss(means, quats, scales, opacities, features, viewmat, K, W, H, targ
 
 
 _check_rc = check
+
+
+class LabelScores:
+    """The four device tensors vp_label_scores accumulates into: confusion i64 [P,P] (rows = ground truth), skipped i64 [2]
+    ({target not valid, target valid under a prediction that is not}), bnd_inter and bnd_union i64 [P]."""
+
+    def __init__(self, P, device):
+        import torch
+        _require(1 <= int(P) <= 256, f"P = {P} outside [1, 256]")
+        self.P = int(P)
+        self.confusion = torch.zeros(self.P, self.P, dtype=torch.int64, device=device)
+        self.skipped = torch.zeros(2, dtype=torch.int64, device=device)
+        self.bnd_inter = torch.zeros(self.P, dtype=torch.int64, device=device)
+        self.bnd_union = torch.zeros(self.P, dtype=torch.int64, device=device)
+
+    def zero_(self):
+        for t in (self.confusion, self.skipped, self.bnd_inter, self.bnd_union):
+            t.zero_()
+        return self
+
+    def numpy(self):
+        """(confusion, skipped, bnd_inter, bnd_union) as numpy int64 arrays (one synchronising download each)."""
+        return tuple(t.cpu().numpy() for t in (self.confusion, self.skipped, self.bnd_inter, self.bnd_union))
+
+
+def _label_map(t, name, dev=None, shape=None):
+    """A [H,W] CUDA tensor of any integer dtype as contiguous int32 (the conversion is plumbing; int32 passes untouched).
+    An int64 value outside int32 becomes -1: a label that is not valid, instead of wrapping into a class."""
+    import torch
+    _require(isinstance(t, torch.Tensor) and t.is_cuda, f"{name} must be a CUDA tensor")
+    _require(not t.dtype.is_floating_point and not t.dtype.is_complex and t.dtype != torch.bool,
+             f"{name} must have an integer dtype, not {t.dtype}")
+    _require(t.dim() == 2 and t.numel() > 0, f"{name} must be [H, W]")
+    _require(dev is None or t.device == dev, f"{name} must be on the other map's device")
+    _require(shape is None or tuple(t.shape) == tuple(shape), f"{name} must be {list(shape) if shape else ''} like the other map")
+    if t.dtype == torch.int64:
+        t = torch.where((t < -(1 << 31)) | (t >= (1 << 31)), torch.full_like(t, -1), t)
+    return t.to(torch.int32).contiguous()
+
+
+def _label_workspace(workspace, W, H, dev):
+    ws = workspace if workspace is not None else SplatWorkspace()
+    nbytes = int(lib().vp_label_scores_workspace_bytes(int(W), int(H)))
+    _require(nbytes > 0, f"image size {W} x {H} outside [1, 32768]")
+    return ws, ws.ensure(nbytes, dev)
+
+
+def label_boundary(labels, radius, workspace=None):
+    """vp_label_boundary: the u8 [H,W] boundary band of an integer label map for ``radius`` in [1, 4096] (1 where the
+    (2 radius + 1)^2 window leaves the image or holds another label).  ``workspace``: a SplatWorkspace to reuse."""
+    import torch
+    labels = _label_map(labels, "labels")
+    H, W = (int(v) for v in labels.shape)
+    dev = labels.device
+    ws, ptr = _label_workspace(workspace, W, H, dev)
+    band = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check_rc(lib().vp_label_boundary(labels.data_ptr(), W, H, int(radius), band.data_ptr(), ptr, ws.capacity(),
+                                          torch.cuda.current_stream(dev).cuda_stream))
+    return band
+
+
+def label_scores(pred, target, P, radius=0, out=None, workspace=None):
+    """vp_label_scores: add one view to ``out`` (a LabelScores; a fresh, zeroed one when None) and return it.  pred, target:
+    CUDA tensors [H,W] of any integer dtype (int64 values outside int32 count as -1); a label is valid when 0 <= v < P.
+    radius = 0: confusion and skipped only;
+    radius > 0: the boundary counts too, through ``workspace`` (a SplatWorkspace, reused and grown as splat_loss does; a
+    fresh one when None).  Nothing is read back here."""
+    import torch
+    pred = _label_map(pred, "pred")
+    target = _label_map(target, "target", pred.device, pred.shape)
+    H, W = (int(v) for v in pred.shape)
+    dev = pred.device
+    if out is None:
+        out = LabelScores(P, dev)
+    _require(isinstance(out, LabelScores) and out.P == int(P) and out.confusion.device == dev,
+             f"out must be a LabelScores of {P} classes on the maps' device")
+    radius = int(radius)
+    ws, ptr = (None, None)
+    if radius > 0:
+        ws, ptr = _label_workspace(workspace, W, H, dev)
+    with torch.cuda.device(dev):
+        _check_rc(lib().vp_label_scores(pred.data_ptr(), target.data_ptr(), W, H, int(P), radius, out.confusion.data_ptr(),
+                                        out.skipped.data_ptr(), out.bnd_inter.data_ptr() if radius > 0 else None,
+                                        out.bnd_union.data_ptr() if radius > 0 else None, ptr,
+                                        ws.capacity() if ws is not None else 0, torch.cuda.current_stream(dev).cuda_stream))
+    return out
 
 
 def counters(ws, device):

@@ -613,6 +613,53 @@ int vp_splat_loss_backward(const float *means, const float *quats, const float *
                            float *grad_screen, int32_t *status, void *workspace, size_t workspace_bytes,
                            void *bwd_workspace, size_t bwd_bytes, void *stream);
 
+/*
+ * Scoring label maps against ground truth: the confusion matrix of a predicted and a target label map, the boundary band
+ * of a label map and the per-class boundary intersections and unions, from which the host forms mIoU, fwIoU, pixel accuracy
+ * and boundary IoU.  Added after VP_ABI_VERSION 4 without changing it or any existing entry point; detect the three
+ * functions by symbol.  Everything computed is an integer: results are exact and bit-identical from run to run (integer
+ * atomics, whose sum does not depend on order).  tests/label_scores_reference.py states the contract in numpy.
+ *
+ * The contract, for maps of n = W x H pixels (i32, row-major [H,W]) and P classes:
+ *   Valid: a label v is valid when 0 <= v < P; every other value (-1, 255, ...) is not.
+ *   Confusion (device i64 [P,P], rows are ground truth): a pixel with a valid target t and a valid prediction p adds 1 to
+ *     confusion[t * P + p].  A pixel whose target is not valid adds 1 to skipped[0]; one with a valid target and a
+ *     prediction that is not valid adds 1 to skipped[1] (device i64 [2]).
+ *   Boundary band (u8 [H,W]) of one map for a radius r: band[y,x] = 1 iff some (x', y') with |x' - x| <= r and |y' - y| <= r
+ *     lies outside the image or holds a label different from labels[y,x]; 0 otherwise.  Labels that are not valid take part
+ *     as labels of their own.  For every class c, band & (labels == c) is what r iterations of a 3 x 3 erosion of the
+ *     zero-padded mask labels == c remove from it: a mask the image border truncates is boundary there.
+ *   Boundary counts (device i64 [P] each), over the pixels with a valid target, with pband / tband the bands of the
+ *     prediction and the target:
+ *       bnd_inter[c] += [pred == c and pband and target == c and tband]
+ *       bnd_union[c] += [(pred == c and pband) or (target == c and tband)]
+ *     A pixel with pred = a != b = target and both in their bands counts in bnd_union[a] and in bnd_union[b]; a valid target
+ *     under a prediction that is not valid contributes its target side only.
+ *   Accumulation: confusion, skipped, bnd_inter and bnd_union are added to (+=), never cleared: a caller adds view after
+ *     view and zeroes the buffers when it wants a per-view result.
+ *
+ * vp_label_scores_workspace_bytes: bytes of the scratch of either call, three 256-byte rounded planes of W x H bytes (the
+ *   two bands and the row pass's map); 0 when W or H is outside [1, 32768].  Needs no GPU.
+ *
+ * vp_label_boundary: writes `band` for `labels` and `radius` in [1, 4096]; correct for a radius that exceeds W, H or both.
+ *   Asynchronous on `stream`, no allocation, no host synchronisation.  VP_EINVAL on the host for a NULL labels or band, W or
+ *   H outside [1, 32768] and a radius outside [1, 4096]; VP_EWORKSPACE for a workspace that is NULL, not 256-byte aligned or
+ *   smaller than vp_label_scores_workspace_bytes.  A refused call writes nothing.
+ *
+ * vp_label_scores: adds one view to confusion and skipped and, with radius > 0, to bnd_inter and bnd_union (the bands of
+ *   both maps are taken into the workspace first).  radius = 0 means confusion only: bnd_inter, bnd_union and the workspace
+ *   are not touched and may be NULL.  Asynchronous on `stream`, no allocation, no host synchronisation.  VP_EINVAL on the
+ *   host for a NULL pred, target, confusion or skipped; W or H outside [1, 32768]; P outside [1, 256]; radius outside
+ *   [0, 4096]; radius > 0 with a NULL bnd_inter or bnd_union.  VP_EWORKSPACE, when radius > 0, as vp_label_boundary.  A
+ *   refused call writes nothing.
+ */
+size_t vp_label_scores_workspace_bytes(int W, int H);
+int vp_label_boundary(const int32_t *labels, int W, int H, int radius, uint8_t *band, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int vp_label_scores(const int32_t *pred, const int32_t *target, int W, int H, int P, int radius, int64_t *confusion,
+                    int64_t *skipped, int64_t *bnd_inter, int64_t *bnd_union, void *workspace, size_t workspace_bytes,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

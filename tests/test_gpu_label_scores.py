@@ -1,0 +1,316 @@
+"""vp_label_boundary and vp_label_scores (voxproj_host.label_boundary / label_scores) on the GPU against the numpy reference
+of tests/label_scores_reference.py.  Everything computed is an integer: every comparison is exact equality.
+
+The dispatcher has one threshold: P <= 64 keeps the confusion in LDS (k_eval_scores<true>), P > 64 counts through grouped
+global atomics (k_eval_scores<false>); the sweep holds 64 and 65.  The band kernels cut rows into segments of
+max(256, r + 1 rounded up to 64) pixels and columns into segments of max(64, r + 1) rows, and a sweep starts r + 1 pixels
+(rounded up to 64 along a row) before its segment:
+  r < 64, segments at their least size, several of them:   257 x 19 r = 7 and 300 x 150 r = 3 (rows), 800 x 533 r = 19 (both)
+  64 <= r < 256, column segments stretched to r + 1, a row halo of two chunks, row segments still 256:   700 x 300 r = 70
+  r >= 256, row segments stretched too (320 pixels), column segments of 257 rows:   1400 x 800 r = 256
+The last two are maps with pixels outside the band on both sides of segment edges along both axes (asserted below), so
+their expected band is not all ones.  100 x 70 r = 40, 64 x 48 r = 64 and 130 x 200 r = 70 have a window larger than the
+image: every pixel is band, which checks the border rule, not the sweeps.
+
+Every test here fails on a library without the three vp_label_* symbols."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+PKG = os.path.join(ROOT, "3d-semantic-segmentation_amd")
+for p in (HERE, ROOT, PKG):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import label_metrics  # noqa: E402
+import label_scores_reference as lref  # noqa: E402
+import voxproj_host  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+
+def dev(a, dtype=torch.int32):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dtype)
+
+
+def gpu_band(m, r):
+    return voxproj_host.label_boundary(dev(m), r).cpu().numpy()
+
+
+def gpu_scores(pred, target, P, radius=0, out=None, workspace=None, dtype=torch.int32):
+    return voxproj_host.label_scores(dev(pred, dtype), dev(target, dtype), P, radius, out=out, workspace=workspace)
+
+
+def assert_scores(got, conf, skipped, inter=None, union=None):
+    c, s, bi, bu = got.numpy()
+    assert np.array_equal(c, conf), f"confusion differs in {int((c != conf).sum())} cell(s)"
+    assert np.array_equal(s, skipped), (s, skipped)
+    if inter is not None:
+        assert np.array_equal(bi, inter), (bi, inter)
+        assert np.array_equal(bu, union), (bu, union)
+
+
+# ------------------------------------------------------------------------------------------------ 1. the band
+BAND_SHAPES = [(1, 1, 1), (1, 9, 1), (1, 9, 3), (9, 1, 1), (9, 1, 3), (37, 23, 1), (37, 23, 2), (37, 23, 5), (100, 70, 40),
+               (64, 48, 64), (257, 19, 7), (300, 150, 3), (130, 200, 70)]
+
+
+@pytest.mark.parametrize("W,H,r", BAND_SHAPES, ids=[f"{w}x{h}-r{r}" for w, h, r in BAND_SHAPES])
+def test_band_matches_the_window_definition(W, H, r):
+    m = lref.make_map(W, H, 5, seed=1000 * W + H + r, n_rects=6, n_dots=4)
+    want = lref.band_by_window(m, r)
+    got = gpu_band(m, r)
+    assert got.dtype == np.uint8 and np.array_equal(got, want), f"{int((got != want).sum())} pixel(s) differ"
+    if 2 * r + 1 > W or 2 * r + 1 > H:
+        assert got.all()
+    print(f"band {W}x{H} r={r}: {int(want.sum())} of {want.size} pixels in the band")
+
+
+LARGE_RADII = [(700, 300, 70), (1400, 800, 256)]
+
+
+@pytest.mark.parametrize("W,H,r", LARGE_RADII, ids=[f"{w}x{h}-r{r}" for w, h, r in LARGE_RADII])
+def test_band_with_a_large_radius_inside_a_larger_image(W, H, r):
+    """Both axes exceed 2r + 1 and span several segments: the sweeps' halo, the carry across chunks and the stretched
+    segments decide pixels that are NOT all band."""
+    m = lref.sparse_map(W, H, r)
+    want = lref.band_by_window(m, r)
+    seg, cseg = max(256, (r + 1 + 63) // 64 * 64), max(64, r + 1)
+    both = lambda a, b: all((v == k).any() for v in (a, b) for k in (0, 1))  # noqa: E731
+    row_edges = [e for e in range(seg, W, seg) if both(want[:, e - 1], want[:, e])]
+    col_edges = [e for e in range(cseg, H, cseg) if both(want[e - 1], want[e])]
+    assert len(row_edges) >= 2 and len(col_edges) >= 2, (row_edges, col_edges)
+    assert 0.05 < 1 - want.mean()
+    got = gpu_band(m, r)
+    assert np.array_equal(got, want), f"{int((got != want).sum())} pixel(s) differ"
+    print(f"band {W}x{H} r={r}: {int(want.sum())} of {want.size} in the band; segment edges with both kinds on both sides: "
+          f"x = {row_edges}, y = {col_edges}")
+
+
+def test_band_of_a_uniform_map_is_the_frame():
+    m = np.full((17, 33), 4, np.int32)
+    frame = np.ones((17, 33), np.uint8)
+    frame[3:-3, 3:-3] = 0
+    assert np.array_equal(lref.band_by_window(m, 3), frame)
+    assert np.array_equal(gpu_band(m, 3), frame)
+
+
+def test_band_of_a_checkerboard_is_everything():
+    y, x = np.mgrid[:23, :41]
+    m = ((x + y) & 1).astype(np.int32)
+    got = gpu_band(m, 1)
+    assert np.array_equal(got, lref.band_by_window(m, 1)) and got.all()
+    # single pixels in a uniform field: each one puts its 5 x 5 neighbourhood (r = 2) into the band
+    m = np.zeros((40, 90), np.int32)
+    m[10, 20] = m[25, 70] = 1
+    got = gpu_band(m, 2)
+    assert np.array_equal(got, lref.band_by_window(m, 2))
+    assert got[8:13, 18:23].all() and not got[13, 18:23].any() and not got[8:13, 23].any()
+
+
+def test_band_treats_unlabelled_regions_as_labels_of_their_own():
+    m = np.zeros((48, 80), np.int32)
+    m[10:30, 15:40] = -1
+    m[20:44, 50:70] = 255
+    m[12:14, 60:62] = 3
+    for r in (1, 4):
+        got = gpu_band(m, r)
+        assert np.array_equal(got, lref.band_by_window(m, r))
+        assert np.array_equal(got, lref.band_by_erosion(m, r))
+    inside = gpu_band(m, 4)[15:25, 20:35]
+    assert not inside.any()                    # deep inside the -1 region: a label like any other
+    assert gpu_band(m, 4)[10:30, 11:15].all()  # its neighbours within 4 pixels are boundary
+
+
+# ------------------------------------------------------------------------------------------------ 2. the scores
+def sweep_maps(P, seed):
+    target = lref.make_map(61, 45, P, seed=seed, invalid=0.1, invalid_values=(-1, 255) if P < 255 else (-1, 256, 1000))
+    pred = lref.perturb(target, P, seed=seed + 1, bad_values=(-1, P, 1 << 20))
+    return pred, target
+
+
+@pytest.mark.parametrize("P", [1, 2, 13, 32, 33, 64, 65, 256])
+def test_scores_p_sweep(P):
+    pred, target = sweep_maps(P, 7 * P)
+    conf, skipped = lref.confusion(pred, target, P)
+    share = skipped[0] / target.size
+    assert 0.05 <= share <= 0.25 and skipped[1] > 0, (share, skipped)
+    r = 2
+    inter, union = lref.boundary_counts(pred, target, P, r) if P <= 64 else lref.boundary_counts_from_bands(
+        pred, target, P, lref.band_by_window(pred, r), lref.band_by_window(target, r))
+    assert_scores(gpu_scores(pred, target, P, r), conf, skipped, inter, union)
+    assert_scores(gpu_scores(pred, target, P), conf, skipped, np.zeros(P, np.int64), np.zeros(P, np.int64))
+    print(f"scores P={P}: {int(conf.sum())} counted, skipped {skipped.tolist()}, {int((conf > 0).sum())} non-zero cells")
+
+
+@pytest.mark.parametrize("P", [64, 65])
+def test_scores_with_many_classes_per_wavefront(P):
+    """Both sides of the dispatcher's threshold on maps where neighbouring pixels differ: every wavefront holds many keys."""
+    rng = np.random.default_rng(P)
+    target = rng.integers(-1, P + 1, (45, 61)).astype(np.int32)
+    pred = rng.integers(-1, P + 1, (45, 61)).astype(np.int32)
+    conf, skipped = lref.confusion(pred, target, P)
+    assert (conf > 0).sum() > 1000
+    assert_scores(gpu_scores(pred, target, P), conf, skipped)
+
+
+def test_any_integer_dtype_is_accepted():
+    pred, target = sweep_maps(13, 5)
+    conf, skipped = lref.confusion(pred, target, 13)
+    assert_scores(gpu_scores(pred, target, 13, dtype=torch.int64), conf, skipped)
+    p16, t16 = np.clip(pred, -1, 255).astype(np.int16), np.clip(target, -1, 255).astype(np.int16)
+    c16, s16 = lref.confusion(p16, t16, 13)
+    assert_scores(gpu_scores(p16, t16, 13, dtype=torch.int16), c16, s16)
+    with pytest.raises(ValueError, match="integer dtype"):
+        voxproj_host.label_scores(dev(pred).float(), dev(target), 13)
+    # int64 values beyond int32 are labels that are not valid, never wrapped into [0, P)
+    p64, t64 = pred.astype(np.int64), target.astype(np.int64)
+    p64[0, :5] = [1 << 32, (1 << 32) + 3, -(1 << 32), (1 << 31), -(1 << 31) - 1]
+    t64[1, :4] = [1 << 32, (1 << 40) + 2, -(1 << 33) + 1, 1 << 31]
+    c64, s64 = lref.confusion(p64, t64, 13)
+    assert not np.array_equal(c64, conf) or not np.array_equal(s64, skipped)
+    assert_scores(gpu_scores(p64, t64, 13, dtype=torch.int64), c64, s64)
+    wide = np.zeros((40, 60), np.int64)
+    wide[:, 30:] = 1 << 32                      # would wrap to 0 and erase the boundary
+    assert np.array_equal(voxproj_host.label_boundary(dev(wide, torch.int64), 2).cpu().numpy(),
+                          lref.band_by_window(np.where(wide == 0, 0, -1), 2))
+
+
+# ------------------------------------------------------------------------------------------------ 3. accumulation
+def test_two_views_accumulate_and_radius_zero_leaves_the_same_confusion():
+    P, r = 13, 3
+    views = [sweep_maps(P, 100), sweep_maps(P, 200)]
+    ws = voxproj_host.SplatWorkspace()
+    total = voxproj_host.LabelScores(P, DEV)
+    want = [np.zeros((P, P), np.int64), np.zeros(2, np.int64), np.zeros(P, np.int64), np.zeros(P, np.int64)]
+    for pred, target in views:
+        separate = gpu_scores(pred, target, P, r, workspace=ws)
+        ref = lref.confusion(pred, target, P) + lref.boundary_counts(pred, target, P, r)
+        assert_scores(separate, *ref)
+        assert gpu_scores(pred, target, P, r, out=total, workspace=ws) is total
+        for acc, part in zip(want, ref):
+            acc += part
+    assert_scores(total, *want)
+    assert not np.array_equal(lref.confusion(*views[0], P)[0], lref.confusion(*views[1], P)[0])
+    # confusion only, with NULL boundary pointers and no workspace: the same confusion, boundary counts untouched
+    only = voxproj_host.LabelScores(P, DEV)
+    for pred, target in views:
+        gpu_scores(pred, target, P, 0, out=only)
+    assert_scores(only, want[0], want[1], np.zeros(P, np.int64), np.zeros(P, np.int64))
+    assert int(total.zero_().confusion.sum()) == 0
+
+
+# ------------------------------------------------------------------------------------------------ 4. boundary counts
+@pytest.mark.parametrize("r", [3, 12])
+def test_boundary_counts_match_the_per_class_erosion(r):
+    P, W, H = 5, 100, 70
+    target = lref.make_map(W, H, P, seed=31, n_rects=7, invalid=0.08)
+    pred = lref.perturb(target, P, seed=32, n_rects=5, n_bad=4, bad_values=(-1, 255, P, 1 << 20))
+    pb, tb = lref.band_by_window(pred, r).astype(bool), lref.band_by_window(target, r).astype(bool)
+    tv, pv = (target >= 0) & (target < P), (pred >= 0) & (pred < P)
+    assert (tv & pv & (pred != target) & pb & tb).sum() > 20          # counted in two classes' unions
+    assert (tv & ~pv & tb).sum() > 0 and (tv & ~pv).sum() > 0         # the target side alone
+    inter, union = lref.boundary_counts(pred, target, P, r)
+    assert inter.sum() > 0 and (union > inter).any()
+    conf, skipped = lref.confusion(pred, target, P)
+    assert_scores(gpu_scores(pred, target, P, r), conf, skipped, inter, union)
+
+
+# ------------------------------------------------------------------------------------------------ 5. the hand-off
+def test_splatted_label_map_goes_straight_into_the_scores():
+    import splat_scenes as sc
+    c = sc.camera_scene("anisotropic", D=8)
+    t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(DEV) for k, v in c["s"].items()}
+    W, H, P = c["W"], c["H"], 8
+    res = voxproj_host.splat_features(t["means"], t["quats"], t["scales"], t["opacities"], t["features"], c["vm"], c["K"], W, H)
+    labels = res.labels
+    assert labels.dtype == torch.int32 and tuple(labels.shape) == (H, W)
+    target = lref.make_map(W, H, P, seed=77, invalid=0.1)
+    r = label_metrics.boundary_radius(W, H)
+    got = voxproj_host.label_scores(labels, dev(target), P, r)
+    down = labels.cpu().numpy()
+    assert len(np.unique(down)) >= 4
+    assert_scores(got, *(lref.confusion(down, target, P) + lref.boundary_counts(down, target, P, r)))
+    # against itself: diagonal, IoU 1 for every class present, intersections = unions
+    own = voxproj_host.label_scores(labels, labels, P, r)
+    conf, skipped, inter, union = own.numpy()
+    assert np.array_equal(conf, np.diag(np.diag(conf))) and conf.sum() + skipped.sum() == W * H and skipped[1] == 0
+    assert np.array_equal(inter, union) and inter.sum() > 0
+    m = label_metrics.metrics(conf, inter, union)
+    present = [cl for cl in range(P) if m["row"][cl] > 0]
+    assert present and all(m["iou"][cl] == 1.0 and m["biou"][cl] == 1.0 for cl in present)
+    assert all(m["iou"][cl] is None for cl in range(P) if cl not in present)
+    assert m["miou"] == 1.0 and m["fwiou"] == 1.0 and m["pixel_accuracy"] == 1.0 and m["mbiou"] == 1.0
+
+
+# ------------------------------------------------------------------------------------------------ 6. one larger view
+def test_one_larger_view():
+    W, H, P = 800, 533, 13
+    r = label_metrics.boundary_radius(W, H)
+    assert r == 19
+    target = lref.make_map(W, H, P, seed=5, n_rects=14, n_dots=30, invalid=0.1)
+    pred = lref.perturb(target, P, seed=6, n_rects=8, n_bad=5)
+    pb, tb = lref.band_by_window(pred, r), lref.band_by_window(target, r)
+    assert 0.05 < tb.mean() < 0.95
+    assert np.array_equal(gpu_band(pred, r), pb) and np.array_equal(gpu_band(target, r), tb)
+    conf, skipped = lref.confusion(pred, target, P)
+    inter, union = lref.boundary_counts_from_bands(pred, target, P, pb, tb)
+    assert_scores(gpu_scores(pred, target, P, r), conf, skipped, inter, union)
+
+
+# ------------------------------------------------------------------------------------------------ 7. refusals
+def test_host_refusals_return_their_code_and_write_nothing():
+    lib = voxproj_host.lib()
+    W, H, P = 40, 30, 5
+    pred, target = dev(lref.make_map(W, H, P, 1)), dev(lref.make_map(W, H, P, 2))
+    out = voxproj_host.LabelScores(P, DEV)
+    band = torch.full((H, W), 7, dtype=torch.uint8, device=DEV)
+    ws = voxproj_host.SplatWorkspace()
+    nbytes = int(lib.vp_label_scores_workspace_bytes(W, H))
+    assert nbytes == 3 * ((W * H + 255) // 256 * 256) and lib.vp_label_scores_workspace_bytes(0, H) == 0
+    assert lib.vp_label_scores_workspace_bytes(W, 32769) == 0
+    ptr = ws.ensure(nbytes, DEV)
+    base = dict(pred=pred.data_ptr(), target=target.data_ptr(), W=W, H=H, P=P, radius=2, confusion=out.confusion.data_ptr(),
+                skipped=out.skipped.data_ptr(), bi=out.bnd_inter.data_ptr(), bu=out.bnd_union.data_ptr(), ws=ptr, bytes=nbytes)
+
+    def scores(**kw):
+        a = dict(base, **kw)
+        return lib.vp_label_scores(a["pred"], a["target"], a["W"], a["H"], a["P"], a["radius"], a["confusion"], a["skipped"],
+                                   a["bi"], a["bu"], a["ws"], a["bytes"], None)
+
+    EINVAL, EWORKSPACE = -1, -2
+    cases = [(dict(pred=None), EINVAL), (dict(target=None), EINVAL), (dict(confusion=None), EINVAL), (dict(skipped=None), EINVAL),
+             (dict(W=0), EINVAL), (dict(W=32769), EINVAL), (dict(H=0), EINVAL), (dict(H=32769), EINVAL),
+             (dict(P=0), EINVAL), (dict(P=257), EINVAL), (dict(radius=-1), EINVAL), (dict(radius=4097), EINVAL),
+             (dict(bi=None), EINVAL), (dict(bu=None), EINVAL),
+             (dict(ws=None), EWORKSPACE), (dict(bytes=nbytes - 1), EWORKSPACE), (dict(ws=ptr + 16), EWORKSPACE)]
+    for kw, rc in cases:
+        assert scores(**kw) == rc, kw
+        assert lib.vp_last_error()
+    bcases = [(dict(labels=None), EINVAL), (dict(band=None), EINVAL), (dict(W=0), EINVAL), (dict(H=32769), EINVAL),
+              (dict(radius=0), EINVAL), (dict(radius=4097), EINVAL), (dict(ws=None), EWORKSPACE),
+              (dict(bytes=nbytes - 1), EWORKSPACE), (dict(ws=ptr + 16), EWORKSPACE)]
+    for kw, rc in bcases:
+        a = dict(dict(labels=pred.data_ptr(), band=band.data_ptr(), W=W, H=H, radius=2, ws=ptr, bytes=nbytes), **kw)
+        assert lib.vp_label_boundary(a["labels"], a["W"], a["H"], a["radius"], a["band"], a["ws"], a["bytes"], None) == rc, kw
+    torch.cuda.synchronize()
+    assert all(int(t.abs().sum()) == 0 for t in (out.confusion, out.skipped, out.bnd_inter, out.bnd_union))
+    assert bool((band == 7).all())
+    # and the accepted calls: radius 0 needs neither boundary pointers nor a workspace
+    assert scores(radius=0, bi=None, bu=None, ws=None, bytes=0) == 0
+    assert scores() == 0 and lib.vp_label_boundary(pred.data_ptr(), W, H, 2, band.data_ptr(), ptr, nbytes, None) == 0
+    torch.cuda.synchronize()
+    assert int(out.confusion.sum() + out.skipped.sum()) == 2 * W * H and bool((band <= 1).all())
+    # the wrapper's own checks
+    with pytest.raises(ValueError, match="like the other map"):
+        voxproj_host.label_scores(pred, target[:, :-1], P)
+    with pytest.raises(ValueError, match="CUDA tensor"):
+        voxproj_host.label_scores(pred.cpu(), target, P)
+    with pytest.raises(voxproj_host.VoxprojError, match="radius"):
+        voxproj_host.label_boundary(pred, 0)
