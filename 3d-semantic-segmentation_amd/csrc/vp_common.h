@@ -1,6 +1,6 @@
 // vp_common.h -- host-side plumbing shared by every part of libvoxproj: error text, HIP call checking, optional
 // per-kernel timing (HIP events), the per-workspace state record (streams/events of VP_FLAG_PIPELINE, table shape, options), kernel parameters and
-// the workspace layout.  Included by voxproj.hip only (one translation unit).
+// the workspace layout.  Included by voxproj.hip only (one translation unit), behind vp_plan.h.
 #pragma once
 
 namespace {
@@ -84,8 +84,21 @@ struct PipeState {
     hipEvent_t call_done[2] = {nullptr, nullptr};    // everything of the call that used set q finished (caller's stream)
     bool used[2] = {false, false};
     long long calls = 0;
-    int last_q = 0;
     bool ok = false;
+};
+// What VP_FLAG_GATHER_ONLY compares and takes up: the arguments of the last call that queued all of its launches.  The call
+// repeats that call's phase 2 on another row range, from the first-hit image and histogram its march left.
+struct LastCall {
+    const void *feats = nullptr, *out = nullptr, *count = nullptr, *vmi = nullptr;
+    int B = 0, V = 0, H = 0, W = 0, C = 0;
+    bool f16 = false;
+    bool ranged = false;              // the call had a row range (VP_OPT_ROW_BEGIN / _END); not compared
+    PlanArgs plan = {};               // its thresholds, which the repeated phase 2 keeps; not compared
+    bool matches(const LastCall &o) const
+    {
+        return feats == o.feats && out == o.out && count == o.count && vmi == o.vmi && B == o.B && V == o.V && H == o.H &&
+               W == o.W && C == o.C && f16 == o.f16;
+    }
 };
 struct WsState {
     unsigned gen = 0;                 // this record's generation (also in the workspace header once a call has run)
@@ -108,12 +121,13 @@ struct WsState {
     long long opt_one_view = -1;                        // VP_OPT_ONE_VIEW_GATHER: 0 = one-view calls through k_gather (A/B arm)
     long long opt_part_px = -1;                         // VP_OPT_PART_PIXELS: pixels per part of a split voxel (-1: default)
     long long opt_one_view_split = -1;                  // VP_OPT_ONE_VIEW_SPLIT: one-view calls cut voxels above this many pixels into parts (0: never)
-    // arguments of the last vp_project_features call (VP_FLAG_GATHER_ONLY repeats its phase 2 on another row range)
-    int last_B = 0, last_V = 0, last_H = 0, last_W = 0, last_C = 0, last_q = 0;
-    bool last_f16 = false, last_ranged = false;
-    int last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // PlanArgs of the last call, as ints
+    LastCall last;                                      // what VP_FLAG_GATHER_ONLY takes up; valid while has_hit
+    // The buffer set the last call ran on: vp_workspace_counters reads that set's status block, VP_FLAG_GATHER_ONLY runs on it.
+    // One word serves both: a gather-only call reads it only while has_hit, i.e. straight after a call that queued all of its
+    // launches and wrote its own set here; a failed call leaves the word and withdraws has_hit; a march-only call
+    // (vp_first_hit_ids) writes 0, the set its counters are in, and withdraws has_hit.
+    int last_q = 0;
     unsigned split_seq = 0;                             // sequence number of the last blocking one-view call that polled ST_HOST_NSPLIT
-    const void *last_feats = nullptr, *last_out = nullptr, *last_count = nullptr, *last_vmi = nullptr;
     // first-hit image of the last call (vp_copy_hit_image)
     bool has_hit = false;
     size_t hit_off = 0;
@@ -302,30 +316,7 @@ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 // `capacity` = bytes of the caller's workspace (0 = compute the minimum).  The two per-call buffer sets sit
 // at offsets that depend only on (B, n_rows, grid dims, capacity), never on V/H/W, so that consecutive
 // pipelined calls of different V on one workspace cannot alias each other's buffers.
-// Part slots of one buffer set (split voxels, vp_gather.h): a voxel above the heavy threshold is summed as P parts, each
-// part's C-wide partial row in a slot.  The number of slots bounds how finely a call can be cut: with part_px >= 2*B*V*H*W /
-// slots and heavy_t >= part_px the parts of a call can never outnumber the slots (project_impl raises both to that bound).
-// 65536 slots -- parts of 2048 pixels for calls of up to 67 M pixels (126 views of 968x548: the 100-108 views a call of fp16 maps
-// holds; round 5's 32768 slots forced parts of 3238-3373 pixels on those calls: R2T fp16 25.3 -> 24.9 ms, A1 fp16 14.9 -> 13.9 ms
-// per pass, profiles/r06_f16_part_slots.log) --, fewer when the rows are wide (128 MiB of partial rows per set at most) or the
-// call is small.
-#ifndef VP_MAX_SLOTS
-#define VP_MAX_SLOTS 65536
-#endif
-#ifndef VP_ONE_VIEW_SLOTS
-#define VP_ONE_VIEW_SLOTS 8192
-#endif
-inline long long part_slot_cap(int B, int V, int H, int W, int C)
-{
-    const long long px2 = 2ll * B * V * (long long)H * W;
-    const long long by_bytes = std::max<long long>(1024, ((long long)VP_MAX_SLOTS * 2048) / (std::max(C, 1) * 4ll));
-    long long cap = std::max<long long>(64, std::min<long long>(VP_MAX_SLOTS, std::min(px2, by_bytes)));
-    // a call of ONE view cuts voxels into parts of 256 pixels by default (128 at the least for a view of 524 k pixels): 8192 slots
-    // (16 MiB at C = 512) -- the drop-in module's scratch buffer should not carry 2 x 128 MiB it never touches
-    if ((long long)B * V == 1) cap = std::min<long long>(cap, VP_ONE_VIEW_SLOTS);
-    return cap;
-}
-
+// Part slots per set: part_slot_cap, vp_plan.h.
 Layout make_layout(int B, int V, int H, int W, int C, long long n_rows, int dimz, int dimy, int dimx, size_t capacity = 0)
 {
     Layout l;

@@ -242,41 +242,10 @@ struct GatherArgs {
 
 constexpr int GW_MERGED = 4;     // wavefronts of a workgroup that share one voxel: k_combine_parts, its whole-image redo, and the A/B arm of k_gather_one
 constexpr int COMBINE_BLOCKS = 512; // grid of k_combine_parts (a workgroup per split voxel at a time)
-// One-view calls size their parts on the device, from the number of pixels the view's rays hit (k_worklist): the smallest part,
-// and how many parts' worth of pixels a voxel must exceed to be cut (VP_OPT_PART_PIXELS / VP_OPT_ONE_VIEW_SPLIT fix them)
-#ifndef VP_ONE_VIEW_PART_MIN
-#define VP_ONE_VIEW_PART_MIN 32
-#endif
-#ifndef VP_ONE_VIEW_T_RATIO
-#define VP_ONE_VIEW_T_RATIO 2
-#endif
-#ifndef VP_ONE_VIEW_T_FLOOR_SMALL
-#define VP_ONE_VIEW_T_FLOOR_SMALL 256
-#endif
-constexpr int ONE_VIEW_PART_MIN = VP_ONE_VIEW_PART_MIN, ONE_VIEW_T_RATIO = VP_ONE_VIEW_T_RATIO, ONE_VIEW_T_FLOOR_SMALL = VP_ONE_VIEW_T_FLOOR_SMALL;
-
-// What k_worklist plans with.  Calls of more than one view: heavy_t == part_t and part_px are the host's (project_impl).
-// One-view calls that split (round 6): no voxel is shared by a workgroup any more, heavy_t == part_t again, and both numbers may
-// be left to the device: dyn_px_min > 0 -> part_px = max(dyn_px_min, 2 * hits / slots), with `hits` the pixels of the view whose
-// ray hit a voxel (counted by the march, ST_NHIT) -- about one part per wavefront the machine holds on a frame that is all large
-// voxels, parts of 32 pixels on a frame that is mostly misses, where the longest single item IS the launch (a wavefront alone
-// pulls ~5 GB/s: 320 rows of 2 KiB last 128 us); dyn_t_ratio > 0 -> part_t = heavy_t = max(dyn_t_ratio * part_px, dyn_t_floor): a
-// voxel is worth cutting only when one wavefront would need a good part of the launch's duration for it -- ~26 us are 64 pixels
-// with 4 rows in flight per wavefront, and views of up to 262144 pixels (8 rows in flight; a quarter-resolution frame is ten
-// thousand voxels of a dozen pixels, bounded by round trips per voxel, not by its longest voxel) gain nothing below 256.
-struct PlanArgs {
-    int heavy_t, part_t, part_px;
-    int count_heavy;      // add the split voxels to ST_NHEAVY (0: the march counts the voxels above heavy_t, one-view calls without parts)
-    int dyn_px_min, dyn_t_ratio, dyn_t_floor;
-    int cell_in_item;     // parts[].w = the voxel's cell in batch 0 instead of its first slot (one-view calls: B == 1)
-};
-
-// Views whose first ID tile is fetched together by the one-wavefront gather (template argument G of k_gather; 1 = one view
-// at a time).  fp16 rows: 4 (-1 % pipelined, round 2).  fp32 rows: 4 for small images (a voxel of R1's 484x274 views gathers
-// half the rows per view an R2 voxel does, so the dependent tile fetch in front of them weighs twice as much: -1.4 % per
-// pipelined R1 call), 1 otherwise (968x548: equal alone, +0.3 % pipelined) -- profiles/r03_ab_id_tile_grouping_fp32.log.
+// (the split plan's numbers -- PlanArgs, ONE_VIEW_*, GATHER_G32_SMALL_IMAGE, the part slots -- are host arithmetic: vp_plan.h)
+// Views whose first ID tile is fetched together by the one-wavefront gather on fp16 rows (template argument G of k_gather): 4
+// (-1 % pipelined, round 2); fp32 rows: GATHER_G32_SMALL_IMAGE, vp_plan.h
 constexpr int GATHER_G16 = 4;
-constexpr long long GATHER_G32_SMALL_IMAGE = 262144;     // pixels per view up to which fp32 calls use G = 4
 
 // Output rows are read once and written once per call by the wavefront that owns the voxel: no reuse inside a launch.
 // The finished row is stored WRITE-THROUGH (buffer_store_dwordx4 with the sc0 sc1 cache-policy bits): stores that leave
@@ -760,7 +729,7 @@ constexpr int WL_PER_THREAD = 16;   // IDs per lane of k_worklist: a 256-thread 
 // part_px > 0: the launch also PLANS the split voxels (see "Split voxels" above): a voxel with more than part_t pixels
 // gets P = ceil(c / part_px) consecutive part slots and an entry in the split list; slots and entries are handed out per
 // workgroup (LDS counters, two global atomics per workgroup).  part_px and part_t >= part_px are such that the parts of a
-// call cannot outnumber slot_cap (project_impl; PlanArgs for the numbers derived here); the guard below only keeps a broken
+// call cannot outnumber slot_cap (plan_split, vp_plan.h; PlanArgs for the numbers derived here); the guard below only keeps a broken
 // promise from writing out of bounds, and the consumers clamp what they walk to slot_cap.
 // One-view calls without parts (VP_OPT_ONE_VIEW_SPLIT = 0): the voxels above heavy_t are in the march's heavy list (a workgroup
 // of k_gather_one sums each) and stay out of this list, ST_NHEAVY is the march's count.  part_px == 0: nothing is split.

@@ -3,7 +3,7 @@ its neighbours -- not only the ones the production shapes reach.  Each case name
 it (file:line in csrc/voxproj.hip unless another file is named).
 
   A  the scalar fp32 projector path (K = 4, VEC = 1: a pass of 256 channels as ch = k*64 + lane), which vec_ok == 0 selects
-     (voxproj.hip:422): C % 4 != 0, or feats / out not 16-byte aligned.  Against the oracle: hit image and counts exact, sums
+     (project_gather, vp_project.h): C % 4 != 0, or feats / out not 16-byte aligned.  Against the oracle: hit image and counts exact, sums
      bit-exact when serial, tests/sum_criteria.py when split; misaligned rows give the aligned run's bytes.
   B  k_aggregate_view_f16 (vp_aggregate.h) at every width class, against oracle.aggregate_views bit for bit.
   C  k_upsample_hwc<TS, TD, VEC, NV> for every register-window size (VP_UPS, voxproj.hip:793-800) and both transposes, against
@@ -95,10 +95,10 @@ def _oracle_one_view_calls(oracle_mod, s, feats):
 @pytest.mark.parametrize("C", WIDE)
 @pytest.mark.parametrize("V", [3, 9])
 def test_scalar_rows_multi_view_calls(oracle_mod, V, C):
-    """k_gather<4,1,4,1>: VP_DISPATCH_GATHER's last arm (voxproj.hip:77), taken when vec_ok == 0 (voxproj.hip:422, C % 4 != 0).
-    V = 9 on this small image is the small_image branch (voxproj.hip:424,481, G32 = 4), V = 3 the other (G32 = 1): the scalar arm
+    """k_gather<4,1,4,1>: project_with_rows' last arm (vp_project.h), taken when vec_ok == 0 (project_gather, C % 4 != 0).
+    V = 9 on this small image is the small-image branch (project_gather_views, G32 = 4), V = 3 the other (G32 = 1): the scalar arm
     pins G = 1 in both.  Serial sums: the oracle's bits.  Heavy threshold 6: the voxels above part_t are summed in parts by the
-    same kernel and added by k_combine_parts<4,1,4> (VP_DISPATCH_KVU's last arm, voxproj.hip:68, launched at :485-491)."""
+    same kernel and added by k_combine_parts<4,1,4> (the same arm, project_combine)."""
     import voxproj_host
     dev = torch.device(DEV)
     s, feats = _scene(V, C, seed=500 + V + C)
@@ -130,10 +130,10 @@ def test_scalar_rows_multi_view_calls(oracle_mod, V, C):
 @pytest.mark.parametrize("C", WIDE)
 def test_scalar_rows_one_view_calls(oracle_mod, C):
     """Three one-view calls accumulating into the same outputs, in each of the three roles a one-view call can give a voxel:
-    - serial: k_gather_one<4,1,4> (VP_DISPATCH_GATHER_ONE's last arm, voxproj.hip:90, one_view at :301), the oracle's bits;
-    - split: VP_OPT_ONE_VIEW_SPLIT = 12, VP_OPT_PART_PIXELS = 5 (one_split, voxproj.hip:313,320-332): parts summed by
-      k_gather_one<4,1,4>, added by k_combine_parts<4,1,4> (voxproj.hip:467-473);
-    - workgroup: the A/B arm VP_OPT_ONE_VIEW_SPLIT = 0 with heavy threshold 6 (voxproj.hip:333-335,442): the voxels the march
+    - serial: k_gather_one<4,1,4> (project_with_rows' last arm in project_gather_one, vp_project.h; one_view: plan_split, vp_plan.h), the oracle's bits;
+    - split: VP_OPT_ONE_VIEW_SPLIT = 12, VP_OPT_PART_PIXELS = 5 (one_split, plan_split): parts summed by
+      k_gather_one<4,1,4>, added by k_combine_parts<4,1,4> (project_combine);
+    - workgroup: the A/B arm VP_OPT_ONE_VIEW_SPLIT = 0 with heavy threshold 6 (plan_split; heavy_blocks in project_gather_one): the voxels the march
       enlists are summed by a workgroup of k_gather_one (gather_voxel_block<4,1,4,GW_MERGED>, vp_gather.h).
     Counts and views-hit exact in all three; rows no voxel role split keep the oracle's bits; the others by sum_criteria."""
     import voxproj_host
@@ -193,8 +193,8 @@ def _drop_in(front):
 @pytest.mark.parametrize("V", [1, 3])
 def test_misaligned_rows_take_the_scalar_path_with_the_aligned_bits(oracle_mod, heavy_threshold, front, C, V):
     """C % 4 == 0, but ``feats`` or ``out`` is a contiguous view 4 bytes off a 16-byte boundary: the drop-in module accepts it
-    (VP_CHECK_INPUT checks device and contiguity only, project_features_ext.cpp:25-27), and vec_ok == 0 (voxproj.hip:422)
-    sends the call to k_gather_one<4,1,4> (V = 1, voxproj.hip:90) or k_gather<4,1,4,1> (V = 3, :77), and its parts to
+    (VP_CHECK_INPUT checks device and contiguity only, project_features_ext.cpp:25-27), and vec_ok == 0 (project_gather)
+    sends the call to k_gather_one<4,1,4> (V = 1) or k_gather<4,1,4,1> (V = 3), and its parts to
     k_combine_parts<4,1,4> (:68).  The summation order -- (view, y, x) per wavefront, parts in slot order -- and the part plan
     (k_worklist: pixel counts and part_px, vp_gather.h) do not depend on the row width class, so both misaligned runs leave the
     aligned run's bytes, serial and split alike; no byte around the misaligned ``out`` is written."""
@@ -245,7 +245,7 @@ def test_misaligned_rows_take_the_scalar_path_with_the_aligned_bits(oracle_mod, 
 
 def test_scalar_rows_in_job_mode_with_a_gather_only_range(oracle_mod):
     """C = 257 (k_gather<4,1,4,1>) in a pipelined sequence: a VP_FLAG_PIPELINE call on rows [0, h), the gather-only call for
-    [h, n_rows) (VP_FLAG_GATHER_ONLY, voxproj.hip:167-179,352-356: the previous call's march and plan), then a whole pipelined
+    [h, n_rows) (VP_FLAG_GATHER_ONLY, project_check and project_relist: the previous call's march and plan), then a whole pipelined
     call, all accumulating into the same outputs: the oracle called twice, bit for bit."""
     import voxproj_host
     dev = torch.device(DEV)

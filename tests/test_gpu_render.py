@@ -35,7 +35,7 @@ def _scene_args(s, views, B=1):
 @pytest.mark.parametrize("exact", [False, True])
 def test_first_hit_ids_equal_the_oracle_and_the_forward_calls_hit_image(oracle_mod, case, exact):
     import voxproj_host as vh
-    # "one_view" cases: B*V == 1, the one-view plan of project_impl -- the path render_voxel_features.py takes for every view
+    # "one_view" cases: B*V == 1, the one-view plan of plan_split (vp_plan.h) -- the path render_voxel_features.py takes for every view
     if case.startswith("trajectory"):
         s = make_scene(6000, 40, 80, 60, seed=4, trajectory=True)
         views, B = ([0] if case == "trajectory_one_view" else [0, 1, 2]), 1    # the first frames of the path: its first close-up dwell

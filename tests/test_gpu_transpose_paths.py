@@ -13,7 +13,7 @@
      between guard words: no byte outside it is written.
   B  past the grid cap (RENDER_MAX_BLOCKS = 2^20 blocks of 4 tiles, :547,558): 2^28 + 837 pixels, so blocks 0-3 take a second
      tile in the grid-stride loop (vp_render.h:78,153) and the last tile holds 5 pixels.
-  C  vp_first_hit_ids (:534, project_impl's march-only branch, :124,368-371,404): batched calls with a different grid per
+  C  vp_first_hit_ids (voxproj.hip; project_march of vp_project.h without a plan or a work list): batched calls with a different grid per
      batch, up to 70 views, both march modes, against the oracle's hit image; then on a workspace whose pipelined forward
      calls (VP_FLAG_PIPELINE) are still in flight.
   D  project_features_autograd.ProjectFeatures: the gradient against g[oracle_hits] ("sum") or g / max(oracle_count, 1)
@@ -403,7 +403,7 @@ def _feats(B, V, H, W, C, dtype, seed):
 def test_autograd_multi_view_against_the_oracle(oracle_mod, C, dtype, reduce):
     """Six views, default heavy threshold (min(256 + 64*B*V, 2048) = 640): the large voxels of the close views are split into
     parts.  Backward: fp16 C = 512 -> k_render_walk<8,1,_Float16> (voxproj.hip:568), the LSeg production case; fp32 C = 67 ->
-    the scalar forward (vec_ok == 0, voxproj.hip:422) and <1,4,float> (:574); C = 64, 1024 -> <4,2,float> (:573)."""
+    the scalar forward (vec_ok == 0, project_gather) and <1,4,float> (:574); C = 64, 1024 -> <4,2,float> (:573)."""
     s, occ, c2w, intr = _room(6, 96, 72, 1000, seed=61, room=(3.0, 2.5, 2.0))     # 12 voxels above 640 pixels
     feats = _feats(1, 6, 72, 96, C, dtype, seed=C)
     ctr = _grad_case(oracle_mod, feats, occ, c2w, intr, s.opts(), s.grid_origin, s.voxel_size, s.n_vox + 1, reduce, seed=C)
