@@ -16,7 +16,13 @@
 //                          read-modify-write of the output row; hit count by ballot/popcount.
 //                          The box is only a search hint: the per-call histogram of phase 1 is the
 //                          ground truth, and a voxel whose box scan finds fewer pixels than phase 1
-//                          counted is rescanned over the whole image.
+//                          counted is rescanned over the whole image.  A voxel above the call's split
+//                          threshold is cut into PARTS: each part is an item of the same work list, one
+//                          wavefront sums it into a partial row, and k_combine_parts, next on the stream,
+//                          adds a voxel's partial rows to its row in a fixed order.  One-view calls have
+//                          k_gather_one: a fixed grid of wavefronts dealt the parts and the size-ordered
+//                          list (a workgroup of four wavefronts per large voxel only as the A/B arm,
+//                          VP_OPT_ONE_VIEW_SPLIT = 0).
 //
 // No float atomics (deterministic sums), no MFMA (the path is gather/accumulate, HBM-bound).
 //
@@ -25,7 +31,7 @@
 //   vp_common.h  error text, timing spans, VP_FLAG_PIPELINE stream state, Params, workspace Layout
 //   vp_tables.h  arithmetic contract helpers, occupancy-derived tables, view table
 //   vp_march.h   phase 1 (k_first_hit)
-//   vp_gather.h  work list and phase 2 (k_worklist, k_gather: one wavefront per voxel, one workgroup per heavy voxel)
+//   vp_gather.h  work list and phase 2 (k_worklist; k_gather, k_gather_one: one wavefront per voxel or per part of a split voxel; k_combine_parts)
 //   vp_aux.h     RGB projection, nearest-voxel map, streaming-read probe
 //   vp_prep.h    feature-map up-sampler (PTD:119-127), occupancy builder (BSO:30-53)
 //   vp_aggregate.h  the aggregator's per-view fp16 accumulate over the hit rows (AGG:307-313)

@@ -1,63 +1,123 @@
-// vp_gather.h -- phase 2: one wavefront per voxel gathers and sums the feature rows of the pixels that first-hit it
-// (k_gather).  A voxel that collected more pixels than the heavy threshold in the call is cut into PARTS (round 5): each
-// part is an item of the same work list, summed by one wavefront into a partial row, and a small follow-up kernel
-// (k_combine_parts) adds the partial rows to the voxel's row in a fixed order.  One-view calls have a kernel of their
-// own (k_gather_one): a fixed grid of wavefronts dealt the parts and the size-ordered list (round 6: parts sized on the device
-// from the view's hit total; round 5's path -- a workgroup of four wavefronts per large voxel -- is kept as the A/B arm).
+// vp_gather.h -- the work list and phase 2: the feature rows of the pixels that first-hit a voxel are gathered and summed.
+//   k_worklist       bins the voxels a call touched by size and plans the PARTS of the voxels above the split threshold;
+//   k_gather         calls with more than one view: wavefront w takes item w of the work list -- a part (gather_part_wave:
+//                    a partial row into the part's slot) or a whole voxel (gather_voxel_wave: the oracle's order and bits);
+//   k_gather_one     one-view calls: a fixed grid of wavefronts dealt the parts (gather_part_one) and the size-ordered
+//                    list; with VP_OPT_ONE_VIEW_SPLIT = 0 (the A/B arm) workgroups of four wavefronts take the march's
+//                    heavy voxels first (gather_voxel_block);
+//   k_combine_parts  follows either gather on the stream: adds the partial rows of each split voxel to its row in a fixed
+//                    order, and redoes over whole images (gather_voxel_block) a voxel whose parts came up short.
+// The pieces every role is made of are written once, in this order: a lane's share of a row (Row, scan_box, acc_*), the
+// pixel box of a voxel (voxel_box, only_view_box), the walk over a voxel's views (for_view_groups, for_views), the
+// whole-image redo of a wavefront (redo_whole_images), the meeting of four wavefronts in LDS (lds_meet).
 // Included by voxproj.hip only.
 #pragma once
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// phase 2: one wavefront per voxel
+// A lane's share of a row
 // ------------------------------------------------------------------------------------------------
 template <int K, int VEC>
 struct Acc {
     float a[K * VEC];
 };
 
-// VEC == 8 selects the fp16 feature-map mode (8 halves = 16 B per lane per chunk; values are widened exactly and
-// summed in fp32 in the same order, so the outputs equal the fp32 path's on the same data).  Feature pointers are
-// carried as `const float *`; this advances one by `elems` ELEMENTS of the mode's input type.
+typedef _Float16 v8h_ __attribute__((ext_vector_type(8)));
+typedef float v4f_ __attribute__((ext_vector_type(4)));
+
+// One pass covers the channels cb .. cb + CB of a row.  A lane holds K CHUNKS of it, chunk k = the VEC channels from
+// (k * 64 + lane) * VEC on, in acc.a[k * VEC ...]: one 16-byte load per chunk from the feature map (VEC == 8 selects the
+// fp16 feature-map mode: 8 halves; values are widened exactly and summed in fp32 in the same order, so the outputs equal
+// the fp32 path's on the same data).  Towards fp32 memory (the output row, a part's row, LDS) a chunk is VEC / PW PIECES of
+// PW floats, PW = 4 (a float4) or 1: piece i of the lane's NP is acc.a[i * PW ...].  A chunk is inside the row or outside
+// it as a whole.  Every loop over a lane's registers of a row takes its channels from here.
+template <int PW> struct piece_type { typedef float4 type; };
+template <> struct piece_type<1> { typedef float type; };
+template <int K, int VEC>
+struct Row {
+    static constexpr int CB = 64 * K * VEC;
+    static constexpr int PW = VEC == 1 ? 1 : 4;
+    static constexpr int NP = K * VEC / PW;
+    typedef typename piece_type<PW>::type piece_t;
+    // first channel, within the pass, of chunk k / of piece i
+    static __device__ __forceinline__ int chunk_ch(int k, int lane) { return (k * 64 + lane) * VEC; }
+    static __device__ __forceinline__ int piece_ch(int i, int lane) { return chunk_ch(i * PW / VEC, lane) + i * PW % VEC; }
+    static __device__ __forceinline__ bool piece_in(int i, int lane, int cb, int C) { return cb + chunk_ch(i * PW / VEC, lane) < C; }
+};
+
+// a piece between acc.a and fp32 memory: P = float4 or float
+template <class P> __device__ __forceinline__ P piece_of(const float *a);
+template <> __device__ __forceinline__ float4 piece_of<float4>(const float *a) { return make_float4(a[0], a[1], a[2], a[3]); }
+template <> __device__ __forceinline__ float piece_of<float>(const float *a) { return a[0]; }
+__device__ __forceinline__ void piece_to(float *a, float4 v) { a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w; }
+__device__ __forceinline__ void piece_to(float *a, float v) { a[0] = v; }
+
+// Feature pointers are carried as `const float *`; this advances one by `elems` ELEMENTS of the mode's input type.
 template <int VEC>
 __device__ __forceinline__ const float *feat_ptr(const float *base, long long elems)
 {
     return reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + elems * (VEC == 8 ? 2 : 4));
 }
 
-// Scan the pixel box [x0,x1]x[y0,y1] of one view's ID image for pixels whose first hit is `id`, in
-// raster order, and add their feature rows (channels cb .. cb+64*K*VEC) to acc.  64 lanes cover a
-// tile of tw x (64/tw) pixels, tw = smallest power of two >= box width (capped at 64), so tiles
-// and the lanes inside a tile are visited in raster order.
-// ID of the pixel this lane covers in the FIRST 64-pixel tile of the box (0 outside the box): the load scan_box would
-// issue for that tile, split off so that a caller can have the first tiles of several views in flight at once
-__device__ __forceinline__ int first_tile_id(const int *__restrict__ hv, int W, int x0, int y0, int x1, int y1, int lane)
+// The chunk at element `elem` of a feature map, as it stays in flight: 8 halves in 4 registers (widened when added --
+// what keeps k_gather<1, 8, 4, 4> at its register count), 4 floats or 1 float.  Feature rows are read exactly once:
+// non-temporal loads keep them out of L2/MALL (+12 % gather bandwidth measured against plain loads).
+template <int VEC>
+__device__ __forceinline__ auto ld_feat(const float *fv, long long elem)
 {
-    const int bw = x1 - x0 + 1;
+    if constexpr (VEC == 8) return __builtin_nontemporal_load(reinterpret_cast<const v8h_ *>(feat_ptr<8>(fv, elem)));
+    else if constexpr (VEC == 4) return __builtin_nontemporal_load(reinterpret_cast<const v4f_ *>(fv + elem));
+    else return fv[elem];
+}
+template <class T> __device__ __forceinline__ float feat_elem(const T &r, int e) { return (float)r[e]; }
+__device__ __forceinline__ float feat_elem(float r, int) { return r; }
+
+// inclusive pixel box.  Passed BY VALUE everywhere: as `const Box &` into scan_box it cost k_gather_one 19-56 VGPRs and a
+// wavefront per SIMD in <2,4,4> and <2,4,8> (profiles/r16_gather_refactor.txt, section 1)
+struct Box {
+    int x0, y0, x1, y1;
+};
+
+// 64 lanes cover a tile of tw x th pixels of a box, tw = smallest power of two >= box width (capped at 64), th = 64 / tw:
+// lane `lane` covers the pixel (lx, ly) of the tile.
+struct TileShape {
+    int tw, th, lx, ly;
+};
+__device__ __forceinline__ TileShape tile_shape(const Box bx, int lane)
+{
+    const int bw = bx.x1 - bx.x0 + 1;
     const int lg = bw >= 64 ? 6 : (bw <= 1 ? 0 : 32 - __builtin_clz(bw - 1));
-    const int px = x0 + (lane & ((1 << lg) - 1)), py = y0 + (lane >> lg);
-    return ((px <= x1) && (py <= y1)) ? hv[py * W + px] : 0;
+    return {1 << lg, 64 >> lg, lane & ((1 << lg) - 1), lane >> lg};
 }
 
+// ID of the pixel this lane covers in the FIRST 64-pixel tile of the box (0 outside the box): the load scan_box would
+// issue for that tile, split off so that a caller can have the first tiles of several views in flight at once
+__device__ __forceinline__ int first_tile_id(const int *__restrict__ hv, int W, const Box bx, int lane)
+{
+    const TileShape t = tile_shape(bx, lane);
+    const int px = bx.x0 + t.lx, py = bx.y0 + t.ly;
+    return ((px <= bx.x1) && (py <= bx.y1)) ? hv[py * W + px] : 0;
+}
+
+// Scan the pixel box bx of one view's ID image for pixels whose first hit is `id`, in raster order, and add their
+// feature rows (channels cb .. cb + CB) to acc: tiles (tile_shape) and the lanes inside a tile are visited in raster
+// order, the hit pixels of a tile U at a time -- U rows in flight, added pixel after pixel, chunk after chunk, element
+// after element.  have_first: the caller fetched the first tile's IDs (first_tile_id) into h_first.
 template <int K, int VEC, int U>
-__device__ __forceinline__ void scan_box(const float *__restrict__ fv, const int *__restrict__ hv,
-                                         int W, int C, int id, int x0, int y0, int x1, int y1,
-                                         int cb, int lane, Acc<K, VEC> &acc, int &found,
+__device__ __forceinline__ void scan_box(const float *__restrict__ fv, const int *__restrict__ hv, int W, int C, int id,
+                                         const Box bx, int cb, int lane, Acc<K, VEC> &acc, int &found,
                                          bool have_first = false, int h_first = 0)
 {
-    const int bw = x1 - x0 + 1;
-    const int lg = bw >= 64 ? 6 : (bw <= 1 ? 0 : 32 - __builtin_clz(bw - 1));
-    const int tw = 1 << lg, th = 64 >> lg;
-    const int lx = lane & (tw - 1), ly = lane >> lg;
-    for (int ty = y0; ty <= y1; ty += th) {
-        const int py = ty + ly;
-        for (int tx = x0; tx <= x1; tx += tw) {
-            const int px = tx + lx;
-            const bool inb = (px <= x1) && (py <= y1);
+    const TileShape t = tile_shape(bx, lane);
+    for (int ty = bx.y0; ty <= bx.y1; ty += t.th) {
+        const int py = ty + t.ly;
+        for (int tx = bx.x0; tx <= bx.x1; tx += t.tw) {
+            const int px = tx + t.lx;
+            const bool inb = (px <= bx.x1) && (py <= bx.y1);
             const int pix = py * W + px;
             int h;
-            if (have_first && ty == y0 && tx == x0) h = h_first;     // prefetched by the caller (first_tile_id)
+            if (have_first && ty == bx.y0 && tx == bx.x0) h = h_first;
             else h = inb ? hv[pix] : 0;
             unsigned long long m = __ballot(h == id);
             found += __popcll(m);
@@ -74,78 +134,25 @@ __device__ __forceinline__ void scan_box(const float *__restrict__ fv, const int
                         n = j + 1;
                     }
                 }
-                if constexpr (VEC == 8) {
-                    typedef _Float16 v8h_ __attribute__((ext_vector_type(8)));
-                    v8h_ r[U][K];
+                decltype(ld_feat<VEC>(fv, 0)) r[U][K];
 #pragma unroll
-                    for (int j = 0; j < U; j++)
-                        if (j < n) {
+                for (int j = 0; j < U; j++)
+                    if (j < n) {
 #pragma unroll
-                            for (int k = 0; k < K; k++) {
-                                const int ch = (k * 64 + lane) * 8;
-                                if (cb + ch < C)
-                                    r[j][k] = __builtin_nontemporal_load(reinterpret_cast<const v8h_ *>(
-                                        reinterpret_cast<const char *>(fv) + (off[j] + ch) * 2));
-                                else
-                                    r[j][k] = (v8h_)(_Float16)0;
-                            }
+                        for (int k = 0; k < K; k++) {
+                            const int ch = Row<K, VEC>::chunk_ch(k, lane);
+                            if (cb + ch < C) r[j][k] = ld_feat<VEC>(fv, off[j] + ch);
+                            else r[j][k] = {};
                         }
+                    }
 #pragma unroll
-                    for (int j = 0; j < U; j++)
-                        if (j < n) {
+                for (int j = 0; j < U; j++)
+                    if (j < n) {
 #pragma unroll
-                            for (int k = 0; k < K; k++)
+                        for (int k = 0; k < K; k++)
 #pragma unroll
-                                for (int e = 0; e < 8; e++) acc.a[k * 8 + e] += (float)r[j][k][e];
-                        }
-                } else if constexpr (VEC == 4) {
-                    float4 r[U][K];
-#pragma unroll
-                    for (int j = 0; j < U; j++)
-                        if (j < n) {
-#pragma unroll
-                            for (int k = 0; k < K; k++) {
-                                const int ch = (k * 64 + lane) * 4;
-                                // feature rows are read exactly once: non-temporal loads keep them out of L2/MALL
-                                // (+12 % gather bandwidth measured against plain loads)
-                                typedef float v4f_ __attribute__((ext_vector_type(4)));
-                                if (cb + ch < C) {
-                                    const v4f_ t_ = __builtin_nontemporal_load(reinterpret_cast<const v4f_ *>(fv + off[j] + ch));
-                                    r[j][k] = make_float4(t_.x, t_.y, t_.z, t_.w);
-                                } else {
-                                    r[j][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                                }
-                            }
-                        }
-#pragma unroll
-                    for (int j = 0; j < U; j++)
-                        if (j < n) {
-#pragma unroll
-                            for (int k = 0; k < K; k++) {
-                                acc.a[k * 4 + 0] += r[j][k].x;
-                                acc.a[k * 4 + 1] += r[j][k].y;
-                                acc.a[k * 4 + 2] += r[j][k].z;
-                                acc.a[k * 4 + 3] += r[j][k].w;
-                            }
-                        }
-                } else {
-                    float r[U][K];
-#pragma unroll
-                    for (int j = 0; j < U; j++)
-                        if (j < n) {
-#pragma unroll
-                            for (int k = 0; k < K; k++) {
-                                const int ch = k * 64 + lane;
-                                r[j][k] = (cb + ch < C) ? fv[off[j] + ch] : 0.f;
-                            }
-                        }
-#pragma unroll
-                    for (int j = 0; j < U; j++)
-                        if (j < n) {
-#pragma unroll
-                            for (int k = 0; k < K; k++) acc.a[k] += r[j][k];
-                        }
-                }
+                            for (int e = 0; e < VEC; e++) acc.a[k * VEC + e] += feat_elem(r[j][k], e);
+                    }
             }
         }
     }
@@ -258,15 +265,9 @@ constexpr int GATHER_G16 = 4;
 typedef int v4i_ __attribute__((ext_vector_type(4)));
 constexpr int OUT_ST_POLICY = 0x11;     // aux bits of the raw buffer store on gfx940+: sc0 (bit 0) | sc1 (bit 4)
 
-__device__ __forceinline__ float4 ld_out4(const float *p)
-{
-    return *reinterpret_cast<const float4 *>(p);
-}
-
 // store 16 bytes at row + byte_off, row wave-uniform (one buffer descriptor per row chunk: base = the row, no bound)
 __device__ __forceinline__ void st_out4(__amdgpu_buffer_rsrc_t row, int byte_off, float4 v)
 {
-    typedef float v4f_ __attribute__((ext_vector_type(4)));
     const v4f_ t = {v.x, v.y, v.z, v.w};
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i_, t), row, byte_off, 0, OUT_ST_POLICY);
 }
@@ -277,26 +278,37 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t out_row_rsrc(float *orow)
     return __builtin_amdgcn_make_buffer_rsrc(orow, 0, 0x7fffffff, 0x00020000);
 }
 
+// the piece at channel ch of the row: written through (float4 pieces only; the row's descriptor is made once per row, the
+// compiler merges the copies) or plainly
+template <bool WT>
+__device__ __forceinline__ void st_piece(float *orow, int ch, float4 v)
+{
+    if constexpr (WT) st_out4(out_row_rsrc(orow), ch * 4, v);
+    else *reinterpret_cast<float4 *>(orow + ch) = v;
+}
+template <bool WT>
+__device__ __forceinline__ void st_piece(float *orow, int ch, float v)
+{
+    orow[ch] = v;
+}
+
+template <int K, int VEC>
+__device__ __forceinline__ void acc_zero(Acc<K, VEC> &acc)
+{
+#pragma unroll
+    for (int i = 0; i < K * VEC; i++) acc.a[i] = 0.f;
+}
+
+// orow: the row's channel cb (as everywhere below); channels beyond the row read as zero
 template <int K, int VEC>
 __device__ __forceinline__ void acc_load(Acc<K, VEC> &acc, const float *orow, int cb, int C, int lane)
 {
+    typedef Row<K, VEC> R;
+    typedef typename R::piece_t P;
 #pragma unroll
-    for (int k = 0; k < K; k++) {
-        if constexpr (VEC == 8) {
-            const int ch = (k * 64 + lane) * 8;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const float4 o = (cb + ch < C) ? ld_out4(orow + ch + h * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc.a[k * 8 + h * 4 + 0] = o.x; acc.a[k * 8 + h * 4 + 1] = o.y; acc.a[k * 8 + h * 4 + 2] = o.z; acc.a[k * 8 + h * 4 + 3] = o.w;
-            }
-        } else if constexpr (VEC == 4) {
-            const int ch = (k * 64 + lane) * 4;
-            const float4 o = (cb + ch < C) ? ld_out4(orow + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
-            acc.a[k * 4 + 0] = o.x; acc.a[k * 4 + 1] = o.y; acc.a[k * 4 + 2] = o.z; acc.a[k * 4 + 3] = o.w;
-        } else {
-            const int ch = k * 64 + lane;
-            acc.a[k] = (cb + ch < C) ? orow[ch] : 0.f;
-        }
+    for (int i = 0; i < R::NP; i++) {
+        const P *src = reinterpret_cast<const P *>(orow + R::piece_ch(i, lane));
+        piece_to(acc.a + i * R::PW, R::piece_in(i, lane, cb, C) ? *src : P{});
     }
 }
 
@@ -305,61 +317,36 @@ __device__ __forceinline__ void acc_load(Acc<K, VEC> &acc, const float *orow, in
 template <int K, int VEC, bool WT>
 __device__ __forceinline__ void acc_store(const Acc<K, VEC> &acc, float *orow, int cb, int C, int lane)
 {
-    if constexpr (!WT) {
+    typedef Row<K, VEC> R;
+    typedef typename R::piece_t P;
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-            if constexpr (VEC == 8) {
-                const int ch = (k * 64 + lane) * 8;
-                if (cb + ch < C) {
-#pragma unroll
-                    for (int h = 0; h < 2; h++)
-                        *reinterpret_cast<float4 *>(orow + ch + h * 4) = make_float4(acc.a[k * 8 + h * 4 + 0], acc.a[k * 8 + h * 4 + 1], acc.a[k * 8 + h * 4 + 2], acc.a[k * 8 + h * 4 + 3]);
-                }
-            } else if constexpr (VEC == 4) {
-                const int ch = (k * 64 + lane) * 4;
-                if (cb + ch < C)
-                    *reinterpret_cast<float4 *>(orow + ch) = make_float4(acc.a[k * 4 + 0], acc.a[k * 4 + 1], acc.a[k * 4 + 2], acc.a[k * 4 + 3]);
-            } else {
-                const int ch = k * 64 + lane;
-                if (cb + ch < C) orow[ch] = acc.a[k];
-            }
-        }
-        return;
-    }
-    const __amdgpu_buffer_rsrc_t row = out_row_rsrc(orow);
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        if constexpr (VEC == 8) {
-            const int ch = (k * 64 + lane) * 8;
-            if (cb + ch < C) {
-#pragma unroll
-                for (int h = 0; h < 2; h++)
-                    st_out4(row, (ch + h * 4) * 4, make_float4(acc.a[k * 8 + h * 4 + 0], acc.a[k * 8 + h * 4 + 1], acc.a[k * 8 + h * 4 + 2], acc.a[k * 8 + h * 4 + 3]));
-            }
-        } else if constexpr (VEC == 4) {
-            const int ch = (k * 64 + lane) * 4;
-            if (cb + ch < C)
-                st_out4(row, ch * 4, make_float4(acc.a[k * 4 + 0], acc.a[k * 4 + 1], acc.a[k * 4 + 2], acc.a[k * 4 + 3]));
-        } else {
-            const int ch = k * 64 + lane;
-            if (cb + ch < C) orow[ch] = acc.a[k];
-        }
-    }
+    for (int i = 0; i < R::NP; i++)
+        if (R::piece_in(i, lane, cb, C)) st_piece<WT>(orow, R::piece_ch(i, lane), piece_of<P>(acc.a + i * R::PW));
 }
 
-// world-space centre of voxel `id` in batch b; false if the grid of batch b does not hold the ID
-__device__ __forceinline__ bool voxel_centre(const GatherArgs &g, const Params &p, int b, int id,
-                                             float &cxw, float &cyw, float &czw)
+// the lane's registers to their channels of an LDS row of CB floats
+template <int K, int VEC>
+__device__ __forceinline__ void acc_stage(const Acc<K, VEC> &acc, float *dst, int lane)
 {
-    const int cell = g.cell_of_id[(long long)b * p.n_rows + id];
-    if (cell < 0) return false;
-    const int czi = cell / (p.dimy * p.dimx);
-    const int rem = cell - czi * (p.dimy * p.dimx);
-    const int cyi = rem / p.dimx, cxi = rem - cyi * p.dimx;
-    cxw = p.ox + (float)cxi * p.vs; cyw = p.oy + (float)cyi * p.vs; czw = p.oz + (float)czi * p.vs;
-    return true;
+    typedef Row<K, VEC> R;
+    typedef typename R::piece_t P;
+#pragma unroll
+    for (int i = 0; i < R::NP; i++) *reinterpret_cast<P *>(dst + R::piece_ch(i, lane)) = piece_of<P>(acc.a + i * R::PW);
 }
 
+// scan_box on view bv (= b * V + v) of the call
+template <int K, int VEC, int U>
+__device__ __forceinline__ void scan_view(const GatherArgs &g, const Params &p, long long bv, int id, const Box bx, int cb,
+                                          int lane, Acc<K, VEC> &acc, int &found, bool have_first = false, int h_first = 0)
+{
+    const long long HW = (long long)p.height * p.width;
+    scan_box<K, VEC, U>(feat_ptr<VEC>(g.feats, bv * HW * p.C), g.hit + bv * HW, p.width, p.C, id, bx, cb, lane, acc, found,
+                        have_first, h_first);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The pixel box of a voxel, the walk over a voxel's views
+// ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float box_half_edge(const Params &p)
 {
     return 0.5f * fabsf(p.vs) * 1.02f +
@@ -374,90 +361,167 @@ __device__ __forceinline__ float near_plane(const Params &p)
     return (zn > 1e-6f && zn < 1e30f) ? zn : 1e-6f;
 }
 
+// world-space centre of grid cell `cell`
+__device__ __forceinline__ void cell_centre(const Params &p, int cell, float &cxw, float &cyw, float &czw)
+{
+    const int czi = cell / (p.dimy * p.dimx);
+    const int rem = cell - czi * (p.dimy * p.dimx);
+    const int cyi = rem / p.dimx, cxi = rem - cyi * p.dimx;
+    cxw = p.ox + (float)cxi * p.vs; cyw = p.oy + (float)cyi * p.vs; czw = p.oz + (float)czi * p.vs;
+}
+
+// One-view calls: the pixel box, in the call's only view, of the voxel in `cell`; x1 < x0 if there is no cell (< 0) or no box
+__device__ __forceinline__ Box only_view_box(const GatherArgs &g, const Params &p, int cell)
+{
+    Box bx = {0, 0, -1, -1};
+    if (cell >= 0) {
+        float cxw, cyw, czw;
+        cell_centre(p, cell, cxw, cyw, czw);
+        int a0, a1, a2, a3;
+        if (voxel_box(g.viewtab[0], g.intr[0], g.intr[1], g.intr[2], g.intr[3], cxw, cyw, czw, box_half_edge(p), near_plane(p),
+                      p.width, p.height, a0, a1, a2, a3))
+            bx = {a0, a1, a2, a3};
+    }
+    return bx;
+}
+
+// The boxes of one voxel in the views vbase .. vbase + 63 of batch b, the box of view vbase + lane on lane `lane`: `mine` =
+// this lane's view exists and its box is not empty, mask = the ballot of `mine`.
+struct ViewGroup {
+    int b, vbase;
+    Box bx;
+    bool mine;
+    unsigned long long mask;
+};
+
+// view vbase + l's box, to every lane
+__device__ __forceinline__ Box box_of(const ViewGroup &vg, int l)
+{
+    return {__builtin_amdgcn_readlane(vg.bx.x0, l), __builtin_amdgcn_readlane(vg.bx.y0, l),
+            __builtin_amdgcn_readlane(vg.bx.x1, l), __builtin_amdgcn_readlane(vg.bx.y1, l)};
+}
+
+// THE view walk: for each batch whose grid holds voxel `id` (its cell -> world centre, the batch's intrinsics), for each
+// group of 64 views, one view per lane through voxel_box: f(group), while go().  whole_image: every view of every batch,
+// the box the whole image -- correctness never depends on the boxes.
+template <class Go, class F>
+__device__ __forceinline__ void for_view_groups(const GatherArgs &g, const Params &p, int id, int lane, bool whole_image, Go &&go,
+                                                F &&f)
+{
+    const int W = p.width, H = p.height;
+    const float hh = box_half_edge(p);
+    const float zn = near_plane(p);
+    for (int b = 0; b < p.B && go(); b++) {
+        float cxw = 0.f, cyw = 0.f, czw = 0.f;
+        if (!whole_image) {
+            const int cell = g.cell_of_id[(long long)b * p.n_rows + id];
+            if (cell < 0) continue;      // the grid of batch b does not hold the ID
+            cell_centre(p, cell, cxw, cyw, czw);
+        }
+        const float fx = g.intr[b * 4 + 0], fy = g.intr[b * 4 + 1], mx = g.intr[b * 4 + 2], my = g.intr[b * 4 + 3];
+        for (int vbase = 0; vbase < p.V && go(); vbase += 64) {
+            const int v = vbase + lane;
+            ViewGroup vg = {b, vbase, {0, 0, W - 1, H - 1}, v < p.V, 0ull};
+            if (vg.mine && !whole_image) {
+                Box &bx = vg.bx;
+                vg.mine = voxel_box(g.viewtab[b * p.V + v], fx, fy, mx, my, cxw, cyw, czw, hh, zn, W, H, bx.x0, bx.y0, bx.x1, bx.y1);
+            }
+            vg.mask = __ballot(vg.mine);   // identical in every wavefront of a workgroup
+            f(vg);
+        }
+    }
+}
+
+// ... one view at a time: f(bv = b * V + v, the view's box), in view order, while go()
+template <class Go, class F>
+__device__ __forceinline__ void for_views(const GatherArgs &g, const Params &p, int id, int lane, bool whole_image, Go &&go, F &&f)
+{
+    for_view_groups(g, p, id, lane, whole_image, go, [&](const ViewGroup &vg) {
+        for (unsigned long long vm = vg.mask; vm && go(); vm &= vm - 1) {
+            const int l = __builtin_ctzll(vm);
+            f((long long)vg.b * p.V + vg.vbase + l, box_of(vg, l));
+        }
+    });
+}
+
+// The whole-image redo of the one-wavefront roles: the search box(es) missed pixels of voxel `id` (an ID labelling several
+// cells, a degenerate pose ...), so its n_bv views are summed again over whole images, on top of the row the caller has put
+// back into acc.  Correctness never depends on the boxes.
+template <int K, int VEC, int U>
+__device__ __forceinline__ void redo_whole_images(const GatherArgs &g, const Params &p, int id, long long n_bv, int cb, int lane,
+                                                  Acc<K, VEC> &acc, int &found, int &nviews)
+{
+    if (lane == 0 && cb == 0) atomicAdd(&g.status[ST_BOXMISS], 1);
+    found = 0;
+    nviews = 0;
+    for (long long bv = 0; bv < n_bv; bv++) {
+        const int before = found;
+        scan_view<K, VEC, U>(g, p, bv, id, Box{0, 0, p.width - 1, p.height - 1}, cb, lane, acc, found);
+        nviews += found > before;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Normal role: one wavefront sums all pixels of one voxel, in (b, v, y, x) order, starting from the
 // row already in `out` -- bit-identical to the oracle's serial accumulation.
+// ------------------------------------------------------------------------------------------------
 template <int K, int VEC, int U, int G, bool WT>
 __device__ __forceinline__ void gather_voxel_wave(const GatherArgs &g, const Params &p, int id, int expected, int lane)
 {
-    const int W = p.width, H = p.height, C = p.C;
-    const long long HW = (long long)H * W;
-    const float hh = box_half_edge(p);
-    const float zn = near_plane(p);
-    constexpr int CB = 64 * K * VEC;
-    for (int cb = 0; cb < C; cb += CB) {
+    const int W = p.width, C = p.C;
+    const long long HW = (long long)p.height * W;
+    for (int cb = 0; cb < C; cb += Row<K, VEC>::CB) {
         Acc<K, VEC> acc;
         float *orow = g.out + (long long)id * C + cb;
         acc_load<K, VEC>(acc, orow, cb, C, lane);
         const Acc<K, VEC> acc0 = acc;
         int found = 0, nviews = 0;
-        for (int b = 0; b < p.B && found < expected; b++) {
-            float cxw, cyw, czw;
-            if (!voxel_centre(g, p, b, id, cxw, cyw, czw)) continue;
-            const float fx = g.intr[b * 4 + 0], fy = g.intr[b * 4 + 1], mx = g.intr[b * 4 + 2], my = g.intr[b * 4 + 3];
-            for (int vbase = 0; vbase < p.V && found < expected; vbase += 64) {
-                const int v = vbase + lane;
-                int x0 = 0, y0 = 0, x1 = -1, y1 = -1;
-                bool ne = false;
-                if (v < p.V) ne = voxel_box(g.viewtab[b * p.V + v], fx, fy, mx, my, cxw, cyw, czw, hh, zn, W, H, x0, y0, x1, y1);
-                unsigned long long vm = __ballot(ne);
-                // Views are taken G at a time: the ID-image loads of the first tile of all G views go out together (one
-                // memory latency instead of G dependent ones -- most boxes are a single 64-pixel tile, and many views of
-                // a voxel yield no pixel at all), then the views are summed one after the other, in order.
-                while (vm && found < expected) {
-                    // the group: the lowest G set bits of vm
-                    unsigned long long mg = 0ull;
+        const auto go = [&] { return found < expected; };
+        for_view_groups(g, p, id, lane, false, go, [&](const ViewGroup &vg) {
+            unsigned long long vm = vg.mask;
+            const long long bv0 = (long long)vg.b * p.V + vg.vbase;
+            // Views are taken G at a time: the ID-image loads of the first tile of all G views go out together (one
+            // memory latency instead of G dependent ones -- most boxes are a single 64-pixel tile, and many views of
+            // a voxel yield no pixel at all), then the views are summed one after the other, in order.
+            while (vm && go()) {
+                // the group: the lowest G set bits of vm
+                unsigned long long mg = 0ull;
 #pragma unroll
-                    for (int q = 0; q < G; q++)
-                        if (vm) { mg |= vm & (~vm + 1ull); vm &= vm - 1; }
-                    int gh[G];
-                    if constexpr (G > 1) {
-                        unsigned long long t = mg;
+                for (int q = 0; q < G; q++)
+                    if (vm) { mg |= vm & (~vm + 1ull); vm &= vm - 1; }
+                int gh[G];
+                if constexpr (G > 1) {
+                    unsigned long long t = mg;
 #pragma unroll
-                        for (int q = 0; q < G; q++) {
-                            gh[q] = 0;
-                            if (t) {
-                                const int l = __builtin_ctzll(t);
-                                t &= t - 1;
-                                gh[q] = first_tile_id(g.hit + ((long long)b * p.V + vbase + l) * HW, W, __builtin_amdgcn_readlane(x0, l),
-                                                      __builtin_amdgcn_readlane(y0, l), __builtin_amdgcn_readlane(x1, l),
-                                                      __builtin_amdgcn_readlane(y1, l), lane);
-                            }
+                    for (int q = 0; q < G; q++) {
+                        gh[q] = 0;
+                        if (t) {
+                            const int l = __builtin_ctzll(t);
+                            t &= t - 1;
+                            gh[q] = first_tile_id(g.hit + (bv0 + l) * HW, W, box_of(vg, l), lane);
                         }
-                    }
-                    int q = 0;
-#pragma unroll 1
-                    for (unsigned long long t = mg; t && found < expected; q++) {
-                        const int l = __builtin_ctzll(t);
-                        t &= t - 1;
-                        const int bx0 = __builtin_amdgcn_readlane(x0, l), by0 = __builtin_amdgcn_readlane(y0, l);
-                        const int bx1 = __builtin_amdgcn_readlane(x1, l), by1 = __builtin_amdgcn_readlane(y1, l);
-                        int hq = 0;
-                        if constexpr (G > 1) {
-                            hq = gh[0];
-#pragma unroll
-                            for (int k = 1; k < G; k++) hq = (q == k) ? gh[k] : hq;
-                        }
-                        const long long bv = (long long)b * p.V + vbase + l;
-                        const int before = found;
-                        scan_box<K, VEC, U>(feat_ptr<VEC>(g.feats, bv * HW * C), g.hit + bv * HW, W, C, id, bx0, by0, bx1, by1, cb, lane,
-                                            acc, found, G > 1, hq);
-                        nviews += found > before;
                     }
                 }
+                int q = 0;
+#pragma unroll 1
+                for (unsigned long long t = mg; t && go(); q++) {
+                    const int l = __builtin_ctzll(t);
+                    t &= t - 1;
+                    int hq = 0;
+                    if constexpr (G > 1) {
+                        hq = gh[0];
+#pragma unroll
+                        for (int k = 1; k < G; k++) hq = (q == k) ? gh[k] : hq;
+                    }
+                    const int before = found;
+                    scan_view<K, VEC, U>(g, p, bv0 + l, id, box_of(vg, l), cb, lane, acc, found, G > 1, hq);
+                    nviews += found > before;
+                }
             }
-        }
+        });
         if (found != expected) {
-            // the search boxes missed pixels (an ID labelling several cells, a degenerate pose...):
-            // redo this voxel over whole images.  Correctness never depends on the boxes.
-            if (lane == 0 && cb == 0) atomicAdd(&g.status[ST_BOXMISS], 1);
             acc = acc0;
-            found = 0;
-            nviews = 0;
-            for (long long bv = 0; bv < (long long)p.B * p.V; bv++) {
-                const int before = found;
-                scan_box<K, VEC, U>(feat_ptr<VEC>(g.feats, bv * HW * C), g.hit + bv * HW, W, C, id, 0, 0, W - 1, H - 1, cb, lane, acc, found);
-                nviews += found > before;
-            }
+            redo_whole_images<K, VEC, U>(g, p, id, (long long)p.B * p.V, cb, lane, acc, found, nviews);
         }
         acc_store<K, VEC, WT>(acc, orow, cb, C, lane);
         if (cb == 0 && lane == 0) {
@@ -504,72 +568,40 @@ __device__ __forceinline__ void gather_part_wave(const GatherArgs &g, const Para
 {
     const int4 it = g.parts[slot];
     const int id = it.x, part = it.y, P = it.z;
-    const int W = p.width, H = p.height, C = p.C;
-    const long long HW = (long long)H * W;
-    const float hh = box_half_edge(p);
-    const float zn = near_plane(p);
-    constexpr int CB = 64 * K * VEC;
+    const int C = p.C;
     // pass 1: the voxel's total box area over the call's views
     long long A = 0;
-    for (int b = 0; b < p.B; b++) {
-        float cxw, cyw, czw;
-        if (!voxel_centre(g, p, b, id, cxw, cyw, czw)) continue;
-        const float fx = g.intr[b * 4 + 0], fy = g.intr[b * 4 + 1], mx = g.intr[b * 4 + 2], my = g.intr[b * 4 + 3];
-        for (int vbase = 0; vbase < p.V; vbase += 64) {
-            const int v = vbase + lane;
-            int x0 = 0, y0 = 0, x1 = -1, y1 = -1, area = 0;
-            if (v < p.V && voxel_box(g.viewtab[b * p.V + v], fx, fy, mx, my, cxw, cyw, czw, hh, zn, W, H, x0, y0, x1, y1))
-                area = (x1 - x0 + 1) * (y1 - y0 + 1);
-            A += wave_sum_nonneg(area);
-        }
-    }
+    for_view_groups(g, p, id, lane, false, [] { return true; }, [&](const ViewGroup &vg) {
+        A += wave_sum_nonneg(vg.mine ? (vg.bx.x1 - vg.bx.x0 + 1) * (vg.bx.y1 - vg.bx.y0 + 1) : 0);
+    });
     const long long lo = A * part / P, hi = A * (part + 1) / P;      // A < 2^47, P <= 2^15
     int found0 = 0, nviews = 0, first_v = -1, last_v = -1;
-    for (int cb = 0; cb < C; cb += CB) {
+    for (int cb = 0; cb < C; cb += Row<K, VEC>::CB) {
         Acc<K, VEC> acc;
-#pragma unroll
-        for (int i = 0; i < K * VEC; i++) acc.a[i] = 0.f;
+        acc_zero(acc);
         int found = 0;
         long long a0 = 0;      // area of the boxes in front of the current view
-        for (int b = 0; b < p.B && a0 < hi; b++) {
-            float cxw, cyw, czw;
-            if (!voxel_centre(g, p, b, id, cxw, cyw, czw)) continue;
-            const float fx = g.intr[b * 4 + 0], fy = g.intr[b * 4 + 1], mx = g.intr[b * 4 + 2], my = g.intr[b * 4 + 3];
-            for (int vbase = 0; vbase < p.V && a0 < hi; vbase += 64) {
-                const int v = vbase + lane;
-                int x0 = 0, y0 = 0, x1 = -1, y1 = -1;
-                bool ne = false;
-                if (v < p.V) ne = voxel_box(g.viewtab[b * p.V + v], fx, fy, mx, my, cxw, cyw, czw, hh, zn, W, H, x0, y0, x1, y1);
-                unsigned long long vm = __ballot(ne);
-                while (vm && a0 < hi) {
-                    const int l = __builtin_ctzll(vm);
-                    vm &= vm - 1;
-                    const int bx0 = __builtin_amdgcn_readlane(x0, l), by0 = __builtin_amdgcn_readlane(y0, l);
-                    const int bx1 = __builtin_amdgcn_readlane(x1, l), by1 = __builtin_amdgcn_readlane(y1, l);
-                    const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
-                    const long long av = (long long)bw * bh;
-                    // rows r of this box with lo <= a0 + r*bw < hi.  A box that ends before lo owns none of them -- most views of a
-                    // part in the middle of a long voxel: no division for those; the others divide 32-bit numbers (lo - a0, hi - a0
-                    // < av < 2^31; two 64-bit divisions per view and part were a third of a part's instructions)
-                    const long long a1 = a0 + av;
-                    const long long b0 = a0;
-                    a0 = a1;
-                    if (a1 <= lo) continue;
-                    const int r_lo = lo > b0 ? (int)(((unsigned)(lo - b0) + (unsigned)bw - 1u) / (unsigned)bw) : 0;
-                    const int r_hi = hi < a1 ? (int)(((unsigned)(hi - b0) + (unsigned)bw - 1u) / (unsigned)bw) : bh;
-                    if (r_lo >= r_hi) continue;
-                    const long long bv = (long long)b * p.V + vbase + l;
-                    const int before = found;
-                    scan_box<K, VEC, U>(feat_ptr<VEC>(g.feats, bv * HW * C), g.hit + bv * HW, W, C, id, bx0, by0 + r_lo, bx1,
-                                        by0 + r_hi - 1, cb, lane, acc, found);
-                    if (cb == 0 && found > before) {
-                        nviews++;
-                        if (first_v < 0) first_v = (int)bv;
-                        last_v = (int)bv;
-                    }
-                }
+        for_views(g, p, id, lane, false, [&] { return a0 < hi; }, [&](long long bv, const Box bx) {
+            const int bw = bx.x1 - bx.x0 + 1, bh = bx.y1 - bx.y0 + 1;
+            const long long av = (long long)bw * bh;
+            // rows r of this box with lo <= a0 + r*bw < hi.  A box that ends before lo owns none of them -- most views of a
+            // part in the middle of a long voxel: no division for those; the others divide 32-bit numbers (lo - a0, hi - a0
+            // < av < 2^31; two 64-bit divisions per view and part were a third of a part's instructions)
+            const long long a1 = a0 + av;
+            const long long b0 = a0;
+            a0 = a1;
+            if (a1 <= lo) return;
+            const int r_lo = lo > b0 ? (int)(((unsigned)(lo - b0) + (unsigned)bw - 1u) / (unsigned)bw) : 0;
+            const int r_hi = hi < a1 ? (int)(((unsigned)(hi - b0) + (unsigned)bw - 1u) / (unsigned)bw) : bh;
+            if (r_lo >= r_hi) return;
+            const int before = found;
+            scan_view<K, VEC, U>(g, p, bv, id, Box{bx.x0, bx.y0 + r_lo, bx.x1, bx.y0 + r_hi - 1}, cb, lane, acc, found);
+            if (cb == 0 && found > before) {
+                nviews++;
+                if (first_v < 0) first_v = (int)bv;
+                last_v = (int)bv;
             }
-        }
+        });
         acc_store<K, VEC, false>(acc, g.prow + (long long)slot * C + cb, cb, C, lane);
         if (cb == 0) found0 = found;
     }
@@ -586,129 +618,110 @@ __device__ __forceinline__ void gather_part_one(const GatherArgs &g, const Param
 {
     const int4 it = g.parts[slot];
     const int id = it.x, part = it.y, P = it.z, cell = it.w;
-    const int W = p.width, H = p.height, C = p.C;
-    constexpr int CB = 64 * K * VEC;
-    int x0 = 0, y0 = 0, x1 = -1, y1 = -1;
-    if (cell >= 0) {
-        const int czi = cell / (p.dimy * p.dimx);
-        const int rem = cell - czi * (p.dimy * p.dimx);
-        const int cyi = rem / p.dimx, cxi = rem - cyi * p.dimx;
-        int a0, a1, a2, a3;
-        if (voxel_box(g.viewtab[0], g.intr[0], g.intr[1], g.intr[2], g.intr[3], p.ox + (float)cxi * p.vs, p.oy + (float)cyi * p.vs,
-                      p.oz + (float)czi * p.vs, box_half_edge(p), near_plane(p), W, H, a0, a1, a2, a3)) { x0 = a0; y0 = a1; x1 = a2; y1 = a3; }
-    }
-    const int bh = y1 - y0 + 1;
+    const int C = p.C;
+    const Box bx = only_view_box(g, p, cell);
+    const int bh = bx.y1 - bx.y0 + 1;
     int r_lo = 0, r_hi = 0;
-    if (bh > 0 && x1 >= x0) {
+    if (bh > 0 && bx.x1 >= bx.x0) {
         const unsigned up = (unsigned)P;
         r_lo = (int)(((unsigned long long)(unsigned)bh * (unsigned)part + up - 1u) / up);
         r_hi = (int)(((unsigned long long)(unsigned)bh * ((unsigned)part + 1u) + up - 1u) / up);
     }
     int found0 = 0;
-    for (int cb = 0; cb < C; cb += CB) {
+    for (int cb = 0; cb < C; cb += Row<K, VEC>::CB) {
         Acc<K, VEC> acc;
-#pragma unroll
-        for (int i = 0; i < K * VEC; i++) acc.a[i] = 0.f;
+        acc_zero(acc);
         int found = 0;
-        if (r_lo < r_hi) scan_box<K, VEC, U>(g.feats, g.hit, W, C, id, x0, y0 + r_lo, x1, y0 + r_hi - 1, cb, lane, acc, found);
+        if (r_lo < r_hi) scan_view<K, VEC, U>(g, p, 0, id, Box{bx.x0, bx.y0 + r_lo, bx.x1, bx.y0 + r_hi - 1}, cb, lane, acc, found);
         acc_store<K, VEC, false>(acc, g.prow + (long long)slot * C + cb, cb, C, lane);
         if (cb == 0) found0 = found;
     }
     if (lane == 0) g.pmeta[slot] = make_int4(found0, found0 > 0 ? 1 : 0, found0 > 0 ? 0 : -1, found0 > 0 ? 0 : -1);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Four wavefronts, one voxel: the meeting in LDS
+// ------------------------------------------------------------------------------------------------
+// The channels of a pass as the GW * 64 threads of a workgroup hold them: thread tid has channel tid + r * GW * 64 in v[r].
+template <int CB, int GW>
+struct Run {
+    static constexpr int R = (CB + GW * 64 - 1) / (GW * 64);
+    float v[R];
+    // f(r, channel within the pass), for the thread's channels inside the pass
+    template <class F>
+    static __device__ __forceinline__ void channels(F &&f)
+    {
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const int c = (int)threadIdx.x + r * GW * 64;
+            if (c < CB) f(r, c);
+        }
+    }
+    __device__ __forceinline__ void load(const float *orow, int cb, int C)
+    {
+#pragma unroll
+        for (int r = 0; r < R; r++) v[r] = 0.f;
+        channels([&](int r, int c) { if (cb + c < C) v[r] = orow[c]; });
+    }
+    __device__ __forceinline__ void store(float *orow, int cb, int C) const
+    {
+        channels([&](int r, int c) { if (cb + c < C) orow[c] = v[r]; });
+    }
+};
+
+// The GW wavefronts of a workgroup meet: each stages its lanes' sums in its LDS row, and after the barrier every thread adds
+// the GW rows to its channels of `run` in wavefront order -- a fixed summation tree.  The caller's next barrier frees `part`.
+template <int K, int VEC, int GW>
+__device__ __forceinline__ void lds_meet(const Acc<K, VEC> &acc, float (*part)[64 * K * VEC], Run<64 * K * VEC, GW> &run)
+{
+    acc_stage(acc, part[threadIdx.x >> 6], threadIdx.x & 63);
+    __syncthreads();
+    run.channels([&](int r, int c) {
+#pragma unroll
+        for (int ww = 0; ww < GW; ww++) run.v[r] += part[ww][c];
+    });
+}
+
 // Workgroup role: the GW wavefronts of a workgroup share one voxel.  Used by k_combine_parts to redo a split voxel whose parts came
 // up short (whole images) and by k_gather_one's A/B arm (VP_OPT_ONE_VIEW_SPLIT = 0: every voxel above heavy_t pixels in the call).  Per view the box rows are cut into GW contiguous ranges,
 // each wavefront sums its range in raster order, and the partial rows are combined through LDS in
 // wavefront order -- a fixed summation tree, so results are reproducible run to run (they differ from
-// the serial order in the last bits only, well inside the 1e-4 bar).
+// the serial order in the last bits only, well inside the 1e-4 bar).  false: the boxes missed pixels and the caller redoes the
+// voxel with whole_image; nothing has been stored then, because every channel pass finds the same pixels, so the shortfall
+// shows in the first pass, before any store.
 template <int K, int VEC, int U, int GW>
 __device__ bool gather_voxel_block(const GatherArgs &g, const Params &p, int id, int expected,
                                    float (*part)[64 * K * VEC], int *part_found, bool whole_image)
 {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tid = threadIdx.x;
-    const int W = p.width, H = p.height, C = p.C;
-    const long long HW = (long long)H * W;
-    const float hh = box_half_edge(p);
-    const float zn = near_plane(p);
-    constexpr int CB = 64 * K * VEC;
-    constexpr int R = (CB + GW * 64 - 1) / (GW * 64);   // running-sum channels per thread
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int C = p.C;
     int found_total = 0, nviews = 0;
-    for (int cb = 0; cb < C; cb += CB) {
-        float run[R];
+    for (int cb = 0; cb < C; cb += Row<K, VEC>::CB) {
+        Run<Row<K, VEC>::CB, GW> run;
         float *orow = g.out + (long long)id * C + cb;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int c = tid + r * GW * 64;
-            run[r] = (c < CB && cb + c < C) ? orow[c] : 0.f;
-        }
+        run.load(orow, cb, C);
         found_total = 0;
         nviews = 0;
-        for (int b = 0; b < p.B && found_total < expected; b++) {
-            float cxw = 0.f, cyw = 0.f, czw = 0.f;
-            if (!whole_image && !voxel_centre(g, p, b, id, cxw, cyw, czw)) continue;
-            const float fx = g.intr[b * 4 + 0], fy = g.intr[b * 4 + 1], mx = g.intr[b * 4 + 2], my = g.intr[b * 4 + 3];
-            for (int vbase = 0; vbase < p.V && found_total < expected; vbase += 64) {
-                const int v = vbase + lane;
-                int x0 = 0, y0 = 0, x1 = W - 1, y1 = H - 1;
-                bool ne = v < p.V;
-                if (ne && !whole_image) ne = voxel_box(g.viewtab[b * p.V + v], fx, fy, mx, my, cxw, cyw, czw, hh, zn, W, H, x0, y0, x1, y1);
-                unsigned long long vm = __ballot(ne);   // identical in every wavefront of the workgroup
-                while (vm && found_total < expected) {
-                    const int l = __builtin_ctzll(vm);
-                    vm &= vm - 1;
-                    const int bx0 = __builtin_amdgcn_readlane(x0, l), by0 = __builtin_amdgcn_readlane(y0, l);
-                    const int bx1 = __builtin_amdgcn_readlane(x1, l), by1 = __builtin_amdgcn_readlane(y1, l);
-                    const long long bv = (long long)b * p.V + vbase + l;
-                    const int per = (by1 - by0 + GW) / GW;
-                    const int ry0 = by0 + w * per, ry1 = min(by1, ry0 + per - 1);
-                    Acc<K, VEC> acc;
+        for_views(g, p, id, lane, whole_image, [&] { return found_total < expected; }, [&](long long bv, const Box bx) {
+            const int per = (bx.y1 - bx.y0 + GW) / GW;
+            const int ry0 = bx.y0 + w * per, ry1 = min(bx.y1, ry0 + per - 1);
+            Acc<K, VEC> acc;
+            acc_zero(acc);
+            int f = 0;
+            if (ry0 <= ry1) scan_view<K, VEC, U>(g, p, bv, id, Box{bx.x0, ry0, bx.x1, ry1}, cb, lane, acc, f);
+            if (lane == 0) part_found[w] = f;
+            lds_meet<K, VEC, GW>(acc, part, run);
+            int fview = 0;
 #pragma unroll
-                    for (int i = 0; i < K * VEC; i++) acc.a[i] = 0.f;
-                    int f = 0;
-                    if (ry0 <= ry1)
-                        scan_box<K, VEC, U>(feat_ptr<VEC>(g.feats, bv * HW * C), g.hit + bv * HW, W, C, id, bx0, ry0, bx1, ry1, cb, lane, acc, f);
-#pragma unroll
-                    for (int k = 0; k < K; k++) {
-                        if constexpr (VEC == 8) {
-#pragma unroll
-                            for (int h = 0; h < 2; h++)
-                                *reinterpret_cast<float4 *>(&part[w][(k * 64 + lane) * 8 + h * 4]) =
-                                    make_float4(acc.a[k * 8 + h * 4 + 0], acc.a[k * 8 + h * 4 + 1], acc.a[k * 8 + h * 4 + 2], acc.a[k * 8 + h * 4 + 3]);
-                        } else if constexpr (VEC == 4) {
-                            *reinterpret_cast<float4 *>(&part[w][(k * 64 + lane) * 4]) =
-                                make_float4(acc.a[k * 4 + 0], acc.a[k * 4 + 1], acc.a[k * 4 + 2], acc.a[k * 4 + 3]);
-                        } else {
-                            part[w][k * 64 + lane] = acc.a[k];
-                        }
-                    }
-                    if (lane == 0) part_found[w] = f;
-                    __syncthreads();
-#pragma unroll
-                    for (int r = 0; r < R; r++) {
-                        const int c = tid + r * GW * 64;
-                        if (c < CB) {
-#pragma unroll
-                            for (int ww = 0; ww < GW; ww++) run[r] += part[ww][c];
-                        }
-                    }
-                    int fview = 0;
-#pragma unroll
-                    for (int ww = 0; ww < GW; ww++) fview += part_found[ww];
-                    found_total += fview;
-                    nviews += fview > 0;
-                    __syncthreads();
-                }
-            }
-        }
-        if (found_total != expected) return false;   // caller retries over whole images; nothing stored yet
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int c = tid + r * GW * 64;
-            if (c < CB && cb + c < C) orow[c] = run[r];
-        }
+            for (int ww = 0; ww < GW; ww++) fview += part_found[ww];
+            found_total += fview;
+            nviews += fview > 0;
+            __syncthreads();
+        });
+        if (found_total != expected) return false;
+        run.store(orow, cb, C);
     }
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         g.count[id] += found_total;
         if (g.views_hit) g.views_hit[id] += nviews;
     }
@@ -836,6 +849,18 @@ __global__ __launch_bounds__(256) void k_worklist(const int *__restrict__ cnt_ca
     }
 }
 
+// Entry w of the size-ordered list: the classes are walked from the largest down (n[k] = voxels of class k); 0 beyond its end
+__device__ __forceinline__ int work_item(const GatherArgs &g, const Params &p, long long w, const int *n)
+{
+    int id = 0;
+#pragma unroll
+    for (int k = WORK_CLASSES - 1; k >= 0; k--) {
+        if (id == 0 && w < n[k]) id = g.work[(long long)k * p.n_rows + w];
+        w -= n[k];
+    }
+    return id;
+}
+
 // The gather of every call with more than one view.  Wavefront w of the grid takes item w of the call's work list: first
 // the parts of the split voxels (the longest items), then the voxels of the size classes from the largest class down --
 // long items start first, short ones fill the tail.  104-112 VGPRs allocated = 4 wavefronts per SIMD -- in pipelined mode a
@@ -851,31 +876,38 @@ __global__ __launch_bounds__(256) void k_gather(GatherArgs g, Params p)
     // march waves of the next call that share the SIMD in pipelined mode.
     __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x & 63;
-    long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int n_parts = min(g.work_n[WORK_CLASSES], g.slot_cap);
     if (w < n_parts) {
         gather_part_wave<K, VEC, U>(g, p, (int)w, lane);
         return;
     }
-    w -= n_parts;
-    int id = 0;
-#pragma unroll
-    for (int k = WORK_CLASSES - 1; k >= 0; k--) {
-        const int n = g.work_n[k];
-        if (id == 0 && w < n) id = g.work[(long long)k * p.n_rows + w];
-        w -= n;
-    }
+    const int id = work_item(g, p, w - n_parts, g.work_n);
     if (id == 0) return;
-    const int expected = g.cnt_call[id];
-    gather_voxel_wave<K, VEC, U, G, true>(g, p, id, expected, lane);
+    gather_voxel_wave<K, VEC, U, G, true>(g, p, id, g.cnt_call[id], lane);
 }
+
+// pixels found, distinct views, first and last contributing view of a run of parts.  Parts cover ascending, contiguous
+// stretches of the view sequence, so only the boundary views of two neighbours can repeat: such a view is counted once.
+struct PartMeta {
+    int found = 0, nviews = 0, first = -1, last = -1;
+    __device__ __forceinline__ void fold(int f, int nv, int first_v, int last_v)
+    {
+        found += f;
+        if (nv > 0) {
+            nviews += nv - (first_v == last ? 1 : 0);
+            if (first < 0) first = first_v;
+            last = last_v;
+        }
+    }
+};
 
 // After k_gather on the same stream: one workgroup per split voxel at a time adds the voxel's partial rows to its row in
 // `out`, in slot order.  The four wavefronts take four consecutive runs of the P slots (U rows in flight each), their
-// sums meet in LDS and are added to the old row in wavefront order: a fixed tree for a given P.  Pixel counts add exactly;
-// a view that two neighbouring parts share is counted once (parts cover ascending, contiguous stretches of the view
-// sequence, so only the boundary views can repeat).  Parts that found fewer pixels than the march counted: the search
-// boxes missed some (an ID labelling several cells, a degenerate pose) -- the voxel is redone over whole images.
+// sums meet in LDS and are added to the old row in wavefront order: a fixed tree for a given P.  Pixel counts add exactly,
+// views by PartMeta's rule, over a wavefront's slots and then over the wavefronts.  Parts that found fewer pixels than the
+// march counted: the search boxes missed some (an ID labelling several cells, a degenerate pose) -- the voxel is redone
+// over whole images.
 template <int K, int VEC, int U>
 __global__ __launch_bounds__(256) void k_combine_parts(GatherArgs g, Params p)
 {
@@ -885,50 +917,30 @@ __global__ __launch_bounds__(256) void k_combine_parts(GatherArgs g, Params p)
     const int n_split = min(g.work_n[WORK_CLASSES + 1], g.slot_cap);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tid = threadIdx.x;
     const int C = p.C;
-    constexpr int CB = 64 * K * VEC;
-    constexpr int R = (CB + GW_MERGED * 64 - 1) / (GW_MERGED * 64);
     for (int j = blockIdx.x; j < n_split; j += gridDim.x) {
         const int4 sp = g.split[j];
         const int id = sp.x, base = sp.y, P = sp.z, expected = sp.w;
         if (base < 0 || P <= 0 || (long long)base + P > g.slot_cap) continue;      // never written by k_worklist (its guard fired: ST_BADID is up)
         const int q0 = (int)((long long)P * w / GW_MERGED), q1 = (int)((long long)P * (w + 1) / GW_MERGED);
-        {   // this wavefront's run of slots: pixels found, distinct views, first and last contributing view
-            int f = 0, nv = 0, first = -1, last = -1;
-            for (int q = q0; q < q1; q++) {
-                const int4 m = g.pmeta[base + q];
-                f += m.x;
-                if (m.y > 0) {
-                    nv += m.y - (m.z == last ? 1 : 0);
-                    if (first < 0) first = m.z;
-                    last = m.w;
-                }
-            }
-            if (lane == 0) { meta[w][0] = f; meta[w][1] = nv; meta[w][2] = first; meta[w][3] = last; }
+        PartMeta mine, all;
+        for (int q = q0; q < q1; q++) {      // this wavefront's run of slots
+            const int4 m = g.pmeta[base + q];
+            mine.fold(m.x, m.y, m.z, m.w);
         }
+        if (lane == 0) { meta[w][0] = mine.found; meta[w][1] = mine.nviews; meta[w][2] = mine.first; meta[w][3] = mine.last; }
         __syncthreads();
-        int found = 0, nviews = 0;
-        {
-            int last = -1;
 #pragma unroll
-            for (int ww = 0; ww < GW_MERGED; ww++) {
-                found += meta[ww][0];
-                if (meta[ww][1] > 0) {
-                    nviews += meta[ww][1] - (meta[ww][2] == last ? 1 : 0);
-                    last = meta[ww][3];
-                }
-            }
-        }
+        for (int ww = 0; ww < GW_MERGED; ww++) all.fold(meta[ww][0], meta[ww][1], meta[ww][2], meta[ww][3]);
         __syncthreads();
-        if (found != expected) {
+        if (all.found != expected) {
             if (tid == 0) atomicAdd(&g.status[ST_BOXMISS], 1);
             gather_voxel_block<K, VEC, U, GW_MERGED>(g, p, id, expected, part, part_found, true);      // count / views_hit included
             __syncthreads();
             continue;
         }
-        for (int cb = 0; cb < C; cb += CB) {
+        for (int cb = 0; cb < C; cb += Row<K, VEC>::CB) {
             Acc<K, VEC> acc;
-#pragma unroll
-            for (int i = 0; i < K * VEC; i++) acc.a[i] = 0.f;
+            acc_zero(acc);
             for (int q = q0; q < q1; q += U) {
                 Acc<K, VEC> r[U];
 #pragma unroll
@@ -941,37 +953,16 @@ __global__ __launch_bounds__(256) void k_combine_parts(GatherArgs g, Params p)
                         for (int i = 0; i < K * VEC; i++) acc.a[i] += r[u].a[i];
                     }
             }
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                if constexpr (VEC == 8) {
-#pragma unroll
-                    for (int h = 0; h < 2; h++)
-                        *reinterpret_cast<float4 *>(&part[w][(k * 64 + lane) * 8 + h * 4]) =
-                            make_float4(acc.a[k * 8 + h * 4 + 0], acc.a[k * 8 + h * 4 + 1], acc.a[k * 8 + h * 4 + 2], acc.a[k * 8 + h * 4 + 3]);
-                } else if constexpr (VEC == 4) {
-                    *reinterpret_cast<float4 *>(&part[w][(k * 64 + lane) * 4]) =
-                        make_float4(acc.a[k * 4 + 0], acc.a[k * 4 + 1], acc.a[k * 4 + 2], acc.a[k * 4 + 3]);
-                } else {
-                    part[w][k * 64 + lane] = acc.a[k];
-                }
-            }
-            __syncthreads();
+            Run<Row<K, VEC>::CB, GW_MERGED> run;
             float *orow = g.out + (long long)id * C + cb;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const int c = tid + r * GW_MERGED * 64;
-                if (c < CB && cb + c < C) {
-                    float run = orow[c];
-#pragma unroll
-                    for (int ww = 0; ww < GW_MERGED; ww++) run += part[ww][c];
-                    orow[c] = run;
-                }
-            }
+            run.load(orow, cb, C);
+            lds_meet<K, VEC, GW_MERGED>(acc, part, run);
+            run.store(orow, cb, C);
             __syncthreads();
         }
         if (tid == 0) {
-            g.count[id] += found;
-            if (g.views_hit) g.views_hit[id] += nviews;
+            g.count[id] += all.found;
+            if (g.views_hit) g.views_hit[id] += all.nviews;
         }
     }
 }
@@ -1037,65 +1028,50 @@ __global__ __launch_bounds__(256) void k_gather_one(GatherArgs g, Params p)
 #pragma unroll
     for (int k = 0; k < WORK_CLASSES; k++) { n[k] = g.work_n[k]; total += n[k]; }
     const int W = p.width, H = p.height, C = p.C;
-    constexpr int CB = 64 * K * VEC;
-    const float *fv = g.feats;
-    const int *hv = g.hit;
     for (long long base = first; base < total; base += 64 * NW) {
-        // lane j: the j-th entry of this wavefront in this batch -- ID, box, pixel count
-        long long r = base + (long long)lane * NW;
-        int id_l = 0;
-        if (r < total) {
-#pragma unroll
-            for (int k = WORK_CLASSES - 1; k >= 0; k--) {
-                if (id_l == 0 && r < n[k]) id_l = g.work[(long long)k * p.n_rows + r];
-                r -= n[k];
-            }
-        }
-        int bx0_l = 0, by0_l = 0, bx1_l = -1, by1_l = -1, cnt_l = 0;      // x1 < x0: no box, scan the whole image
+        // lane j: the j-th entry of this wavefront in this batch -- ID, box (x1 < x0: none, scan the whole image), pixel count
+        const long long r = base + (long long)lane * NW;
+        const int id_l = r < total ? work_item(g, p, r, n) : 0;
+        Box bx_l = {0, 0, -1, -1};
+        int cnt_l = 0;
         if (id_l != 0) {
             cnt_l = g.cnt_call[id_l];
-            float cxw, cyw, czw;
-            if (voxel_centre(g, p, 0, id_l, cxw, cyw, czw)) {
-                int a0, a1, a2, a3;
-                if (voxel_box(g.viewtab[0], g.intr[0], g.intr[1], g.intr[2], g.intr[3], cxw, cyw, czw, box_half_edge(p), near_plane(p),
-                              W, H, a0, a1, a2, a3)) { bx0_l = a0; by0_l = a1; bx1_l = a2; by1_l = a3; }
-            }
+            bx_l = only_view_box(g, p, g.cell_of_id[id_l]);
         }
         const int nv = __popcll(__ballot(id_l != 0));      // the entries of a wavefront fill its lanes from 0 upwards
         // the first voxel's ID tile and output row
-        int id = 0, x0 = 0, y0 = 0, x1 = -1, y1 = -1, expected = 0, tile = 0;
+        int id = 0, expected = 0, tile = 0;
+        Box bx = {0, 0, -1, -1};
         Acc<K, VEC> acc;
         auto fetch = [&](int j) {
             id = __builtin_amdgcn_readlane(id_l, j);
             expected = __builtin_amdgcn_readlane(cnt_l, j);
-            x0 = __builtin_amdgcn_readlane(bx0_l, j); y0 = __builtin_amdgcn_readlane(by0_l, j);
-            x1 = __builtin_amdgcn_readlane(bx1_l, j); y1 = __builtin_amdgcn_readlane(by1_l, j);
-            if (x1 < x0 || y1 < y0) { x0 = 0; y0 = 0; x1 = W - 1; y1 = H - 1; }      // no box: the whole image
-            tile = first_tile_id(hv, W, x0, y0, x1, y1, lane);
+            bx = {__builtin_amdgcn_readlane(bx_l.x0, j), __builtin_amdgcn_readlane(bx_l.y0, j),
+                  __builtin_amdgcn_readlane(bx_l.x1, j), __builtin_amdgcn_readlane(bx_l.y1, j)};
+            if (bx.x1 < bx.x0 || bx.y1 < bx.y0) bx = {0, 0, W - 1, H - 1};      // no box: the whole image
+            tile = first_tile_id(g.hit, W, bx, lane);
             acc_load<K, VEC>(acc, g.out + (long long)id * C, 0, C, lane);
         };
         if (nv > 0) fetch(0);
         for (int j = 0; j < nv; j++) {
-            const int cid = id, cx0 = x0, cy0 = y0, cx1 = x1, cy1 = y1, cexp = expected, ctile = tile;
+            const int cid = id, cexp = expected, ctile = tile;
+            const Box cbx = bx;
             Acc<K, VEC> cacc = acc;
             if (j + 1 < nv) fetch(j + 1);       // in flight while this voxel's rows stream
-            for (int cb = 0; cb < C; cb += CB) {
+            for (int cb = 0; cb < C; cb += Row<K, VEC>::CB) {
                 float *orow = g.out + (long long)cid * C + cb;
                 if (cb > 0) acc_load<K, VEC>(cacc, orow, cb, C, lane);
                 int found = 0;
-                scan_box<K, VEC, U>(fv, hv, W, C, cid, cx0, cy0, cx1, cy1, cb, lane, cacc, found, cb == 0, ctile);
-                if (found != cexp) {
-                    // the box missed pixels (an ID labelling several cells, a degenerate pose ...): redo over the whole
-                    // image from the row as it still is in memory.  Correctness never depends on the boxes.
-                    if (lane == 0 && cb == 0) atomicAdd(&g.status[ST_BOXMISS], 1);
+                scan_view<K, VEC, U>(g, p, 0, cid, cbx, cb, lane, cacc, found, cb == 0, ctile);
+                int nviews = found > 0;
+                if (found != cexp) {      // redo from the row as it still is in memory
                     acc_load<K, VEC>(cacc, orow, cb, C, lane);
-                    found = 0;
-                    scan_box<K, VEC, U>(fv, hv, W, C, cid, 0, 0, W - 1, H - 1, cb, lane, cacc, found);
+                    redo_whole_images<K, VEC, U>(g, p, cid, 1, cb, lane, cacc, found, nviews);
                 }
                 acc_store<K, VEC, false>(cacc, orow, cb, C, lane);
                 if (cb == 0 && lane == 0) {
                     g.count[cid] += found;
-                    if (g.views_hit) g.views_hit[cid] += found > 0;
+                    if (g.views_hit) g.views_hit[cid] += nviews;
                 }
             }
         }
