@@ -38,6 +38,7 @@
 //   vp_render.h  the transpose: every pixel copies the row of its first-hit voxel (k_render_walk, k_render_small)
 //   vp_query.h   text query of a feature table: cosine logits, argmax label, softmax margin on the matrix cores (k_query)
 //   vp_splat.h   tile-based Gaussian splatting of D-channel features with a fused label / confidence epilogue (stage 5.2)
+//   vp_lift.h    lifting a 2D feature map onto the Gaussians: the splatter's transpose on the matrix cores (k_splat_lift)
 //   vp_eval.h    scoring label maps against ground truth: confusion matrix, boundary band, boundary counts (all integers)
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
@@ -70,6 +71,7 @@
 #include "vp_render.h"
 #include "vp_query.h"
 #include "vp_splat.h"
+#include "vp_lift.h"
 #include "vp_eval.h"
 #include "vp_project.h"
 
@@ -593,6 +595,64 @@ int vp_splat_loss_backward(const float *means, const float *quats, const float *
                                 capacity, logits, grad_alpha, grad_means, grad_quats, grad_scales, grad_features,
                                 grad_opacities, grad_screen, status, workspace, workspace_bytes, bwd_workspace, bwd_bytes,
                                 stream_, chain || grad_screen, chain, true, ls});
+}
+
+size_t vp_splat_lift_workspace_bytes(int64_t capacity, int C)
+{
+    if (capacity < 0 || capacity > INT32_MAX || C < 1 || C > LIFT_MAX_C) return 0;
+    return lift_bytes(capacity, C);
+}
+
+int vp_splat_lift(const void *feats_f16, int C, int64_t pix_stride, const float *pixel_weight, int64_t n_gaussians, int W, int H,
+                  int64_t capacity, int sorted, float *sum, int64_t sum_stride, float *wsum, int32_t *status, void *workspace,
+                  size_t workspace_bytes, void *lift_workspace, size_t lift_bytes_, void *stream_)
+{
+    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (!feats_f16 || !sum) return fail(VP_EINVAL, "null pointer argument (feats_f16 or sum)");
+    if (C < 1 || C > LIFT_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, LIFT_MAX_C);
+    if (pix_stride < C) return fail(VP_EINVAL, "pix_stride %lld < C = %d", (long long)pix_stride, C);
+    if (sum_stride < C) return fail(VP_EINVAL, "sum_stride %lld < C = %d", (long long)sum_stride, C);
+    if (sorted != 0 && sorted != 1) return fail(VP_EINVAL, "sorted = %d is neither 0 nor 1", sorted);
+    if (int rc = splat_check_image(W, H)) return rc;
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    if (int rc = splat_check_buffer(lift_workspace, "lift workspace")) return rc;
+    if (int rc = splat_check_size(lift_bytes_, lift_bytes(capacity, C), "lift workspace")) return rc;
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    if (!sorted)
+        if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
+    if (n_gaussians == 0) return VP_OK;                  // no rows to add to; nothing can exceed a capacity of 0 either
+    const long long *total = (const long long *)(ws + l.total);
+    const int *count = (const int *)(ws + l.count);
+    const long long *offs = (const long long *)(ws + l.offs);
+    const _Float16 *feats = (const _Float16 *)feats_f16;
+    float *part = (float *)lift_workspace, *wpart = (float *)((char *)lift_workspace + lift_part_bytes(capacity, C));
+    const bool vec = C % 8 == 0 && pix_stride % 8 == 0 && ((uintptr_t)feats_f16 & 15) == 0;
+    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+    splat_with_flag(C > 16, [&](auto wide) {
+        constexpr int CC = decltype(wide)::value ? 64 : 16;
+        static_assert(lift_chunk(decltype(wide)::value ? 17 : 16) == CC, "the pass width is lift_chunk's");
+        // grid-stride over the Gaussians, at most one resident round (as the backward's reduce)
+        const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / CC - 1) / (256 / CC), 2048LL);
+        for (int c0 = 0; c0 < C; c0 += CC) {
+            float *wp = c0 == 0 && wsum ? wpart : nullptr;
+            splat_with_flag(vec, [&](auto v) {
+                hipLaunchKernelGGL((k_splat_lift<CC, decltype(v)::value>), grid, block, 0, stream,
+                                   (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), count, offs,
+                                   (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges), total, (long long)capacity,
+                                   feats, C, (long long)pix_stride, c0, pixel_weight, W, H, part, wp);
+            });
+            hipLaunchKernelGGL((k_splat_lift_reduce<CC>), dim3(g_red), dim3(256), 0, stream, count, offs,
+                               (long long)n_gaussians, total, (long long)capacity, (const float *)part, (const float *)wp,
+                               std::min(CC, C - c0), c0, sum, (long long)sum_stride, wsum, (int *)status);
+        }
+    });
+    VP_HIP(hipGetLastError());
+    return VP_OK;
 }
 
 static int read_status(void *workspace, hipStream_t stream, int *st /* [2][ST_WORDS] */)

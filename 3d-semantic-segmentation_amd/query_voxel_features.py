@@ -13,6 +13,10 @@ Sub-commands (all take --text_emb FILE --prompt NAME ... [--logit_scale S]; one 
   gaussians  --vox ALL_*.pt --gauss centres.npy [--map g2v.npy] --out X.npz: per Gaussian labels int16 [M], logits f32 [M,P],
              prompts and X_colored_gaussians.ply; the Gaussian -> voxel map is read from --map or computed with
              voxel_to_gaussian_map.map_gaussians_to_voxels (the 1-NN voxel).
+             --gauss_feats LIFTED.pt (lift_gaussian_features.py: xyz, avg_feats f16 [M,C], weight) instead of --vox / --gauss /
+             --map: the Gaussians' own rows are queried directly; a Gaussian with weight 0 or a row of zeros (below the
+             lift's --min_weight, or a mean that rounds to zeros in fp16) gets label -1 and zero logits.  The .npz has the
+             same schema either way.
   views      the camera / grid / view arguments of render_voxel_features.py: per view <name>_labels.npy int16 [H,W] (-1 where
              the ray hits nothing or hits an occupied voxel without a feature row), <name>_confidence.npy f32 [H,W] (0 where the
              label is -1) and with --save_logits <name>_logits.npy f16 [P,H,W] (the layout logit_confidence_map.py reads; zeros
@@ -135,7 +139,33 @@ def _cmd_voxels(args, text, dev):
     summary(lab, lg, args.prompt)
 
 
+def lifted_labels(feats, weight, labels, logits):
+    """Labels and logits of directly lifted rows: a Gaussian without a feature gets -1 and zero logits.  It has none when its
+    weight is 0 or its row is all zeros: lift_gaussian_features.py zeroes the rows below --min_weight, and a mean that rounds
+    to zeros in fp16 (tiny or cancelling features) has no direction to compare with a text embedding either."""
+    valid = ((feats != 0).any(dim=1) & (weight > 0)).to(labels.device)
+    return (torch.where(valid, labels, torch.full_like(labels, -1)),
+            torch.where(valid[:, None], logits, torch.zeros((), dtype=logits.dtype, device=logits.device)))
+
+
+def _cmd_gaussians_lifted(args, text, dev):
+    import lift_gaussian_features
+    mu, feats, weight = lift_gaussian_features.load_lifted(args.gauss_feats)
+    labels, logits, _ = query(feats, text, args.logit_scale, dev)
+    labels, logits = lifted_labels(feats, weight, labels, logits)
+    lab, lg = labels.cpu().numpy(), logits.cpu().numpy()
+    colors = label_colors(lab, len(args.prompt))
+    write_npz(args.out, lab, lg, args.prompt)
+    ply = _stem(args.out) + "_colored_gaussians.ply"
+    write_ply(ply, mu.numpy(), colors)
+    print(f"[QUERY] {len(lab)} Gaussian labels and logits from lifted rows ({int((lab < 0).sum())} without a feature) -> "
+          f"{args.out}; coloured Gaussians -> {ply}")
+    summary(lab, lg, args.prompt)
+
+
 def _cmd_gaussians(args, text, dev):
+    if args.gauss_feats:
+        return _cmd_gaussians_lifted(args, text, dev)
     xyz, feats, _ = load_voxels(args.vox)
     mu = torch.from_numpy(np.load(args.gauss)).float()
     if mu.dim() != 2 or mu.shape[1] != 3:
@@ -241,9 +271,12 @@ def build_parser():
     v.add_argument("--out", required=True, help="output .npz")
     g = sub.add_parser("gaussians", help="label every Gaussian through its 1-NN voxel (voxeltoGaussian_logits.py query)")
     common(g)
-    g.add_argument("--vox", required=True)
-    g.add_argument("--gauss", required=True, help="Gaussian centres [M, 3] (.npy)")
+    g.add_argument("--vox", default=None, help="ALL_nonzero_voxel_features_*.pt of the aggregator (with --gauss)")
+    g.add_argument("--gauss", default=None, help="Gaussian centres [M, 3] (.npy)")
     g.add_argument("--map", default=None, help="Gaussian -> voxel index [M] (.npy); computed when absent")
+    g.add_argument("--gauss_feats", default=None,
+                   help="LIFTED.pt of lift_gaussian_features.py: query the Gaussians' own rows (instead of --vox / --gauss / --map); "
+                        "weight 0 or an all-zero row: label -1")
     g.add_argument("--out", required=True)
     w = sub.add_parser("views", help="semantic segmentation of camera views from the voxel grid")
     common(w)
@@ -266,6 +299,11 @@ def main(argv=None):
     text = load_text(args.text_emb)
     if len(args.prompt) != text.shape[0]:
         ap.error(f"{len(args.prompt)} prompts for {text.shape[0]} embedding rows in {args.text_emb}")
+    if args.cmd == "gaussians":
+        if args.gauss_feats and (args.vox or args.map or args.gauss):
+            ap.error("--gauss_feats cannot be combined with --vox / --gauss / --map")
+        if not args.gauss_feats and not (args.vox and args.gauss):
+            ap.error("gaussians needs --vox and --gauss, or --gauss_feats")
     if not (args.logit_scale > 0 and np.isfinite(args.logit_scale)):
         ap.error(f"--logit_scale must be finite and > 0, not {args.logit_scale}")
     if not torch.cuda.is_available():

@@ -58,6 +58,7 @@ EXPORTS = [
     "vp_splat_geometry_backward_workspace_bytes", "vp_splat_rasterize_backward_geometry",
     "vp_splat_loss_workspace_bytes", "vp_splat_rasterize_loss", "vp_splat_loss_backward",
     "vp_label_scores_workspace_bytes", "vp_label_boundary", "vp_label_scores",
+    "vp_splat_lift_workspace_bytes", "vp_splat_lift",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -211,6 +212,13 @@ def lib():
                                                  ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
                 [ctypes.c_int] * 2 + [ctypes.c_float, ctypes.c_int64] + [vp] * 4 + [ctypes.c_int] + [vp] * 10 + \
                 [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+            if hasattr(L, "vp_splat_lift"):      # added after ABI version 4: detected by symbol (splat_lift raises without it)
+                L.vp_splat_lift_workspace_bytes.restype = ctypes.c_size_t
+                L.vp_splat_lift_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
+                L.vp_splat_lift.restype = ctypes.c_int
+                L.vp_splat_lift.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_size_t, vp,
+                                            ctypes.c_size_t, vp]
             L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
             L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
             L.vp_label_boundary.restype = ctypes.c_int
@@ -957,6 +965,116 @@ def splat_loss(means, quats, scales, opacities, features, viewmat, K, W, H, targ
     if check:
         _splat_view_check("splat_loss", status, bad, "nothing written")
     return SplatLossResult(*out, cap, bad)
+
+
+def _lift_lib():
+    L = lib()
+    if not hasattr(L, "vp_splat_lift"):
+        raise VoxprojError(f"{LIB_PATH} has no vp_splat_lift: rebuild it (there is no fallback)")
+    return L
+
+
+def splat_lift_workspace_bytes(capacity, C):
+    """vp_splat_lift_workspace_bytes: bytes of the lift's scratch for ``capacity`` intersections and C channels (0 when
+    either is out of range).  Needs no GPU."""
+    return int(_lift_lib().vp_splat_lift_workspace_bytes(int(capacity), int(C)))
+
+
+def splat_lift(feats, n_gaussians, W, H, capacity, workspace, sum, wsum, pixel_weight=None, sorted=False, status=None,
+               lift_workspace=None):
+    """vp_splat_lift after splat_project on ``workspace``: add one view's blend-weighted feature sums to the Gaussians.
+    feats f16 [H,W,C] channels-last (unit channel stride, any pixel stride >= C; what upsample_features(keep_dtype=True)
+    returns), sum f32 [N,C] (unit channel stride) and wsum f32 [N] or None, all on one GPU; both accumulate and are never
+    cleared.  pixel_weight f32 [H,W] or None (1).  ``sorted``: False sorts ``capacity`` keys first (valid directly after
+    splat_project; the workspace grows as for splat_rasterize), True reuses the sort a splat_rasterize / splat_rasterize_loss
+    call with the same capacity left.  ``lift_workspace``: a SplatWorkspace for the partial rows (a fresh one when None).
+    ``status``: optional device int32 [1], set to 1 when the device count exceeds ``capacity`` (then nothing is added)."""
+    import torch
+    L = _lift_lib()
+    _require(isinstance(sorted, (bool, int)) and int(sorted) in (0, 1), "sorted must be False or True")
+    _require_tensors((feats, "feats", (torch.float16,)), (sum, "sum", (torch.float32,)))
+    dev, N = feats.device, int(n_gaussians)
+    _require(feats.dim() == 3 and tuple(feats.shape[:2]) == (int(H), int(W)), f"feats must be [{H}, {W}, C]")
+    C = int(feats.shape[2])
+    _require(1 <= C <= 4096, f"C = {C} outside [1, 4096]")
+    if feats.stride(2) != 1 or feats.stride(1) < C or feats.stride(0) != int(W) * feats.stride(1):
+        feats = feats.contiguous()
+    _require(sum.dim() == 2 and tuple(sum.shape) == (N, C) and sum.device == dev and (N == 0 or sum.stride(1) == 1) and
+             (N <= 1 or sum.stride(0) >= C), f"sum must be float32 [{N}, {C}] with a unit channel stride on the map's device")
+    if wsum is not None:
+        _require_tensors((wsum, "wsum", (torch.float32,)))
+        _require(tuple(wsum.shape) == (N,) and wsum.device == dev and wsum.is_contiguous(),
+                 f"wsum must be contiguous float32 [{N}] on the map's device")
+    (pixel_weight,) = _splat_images(dev, (pixel_weight, "pixel_weight", (H, W), torch.float32))
+    if sorted:
+        nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), int(capacity)))
+        _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}, capacity {capacity}")
+        _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+                 workspace.capacity() >= nbytes, "splat_lift(sorted=True) needs the workspace of a splat_rasterize call")
+        ptr = workspace.ptr()
+    else:
+        ptr = _splat_forward_workspace(workspace, N, W, H, capacity, dev)
+    need = int(L.vp_splat_lift_workspace_bytes(int(capacity), C))
+    _require(need > 0, f"no lift workspace size for capacity {capacity}, C = {C}")
+    lw = lift_workspace if lift_workspace is not None else SplatWorkspace()
+    lptr = lw.ensure(need, dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_splat_lift(feats.data_ptr(), C, int(feats.stride(1)), _ptr(pixel_weight), N, int(W), int(H),
+                                  int(capacity), int(sorted), sum.data_ptr() if N else lptr, max(int(sum.stride(0)), C) if N else C,
+                                  _ptr(wsum), _ptr(status), ptr, workspace.capacity(), lptr, lw.capacity(), stream.cuda_stream))
+
+
+def splat_lift_view(means, quats, scales, opacities, feats, viewmat, K, W, H, sum, wsum, pixel_weight=None, *, near=0.01,
+                    far=1e10, eps2d=0.3, workspace=None, lift_workspace=None, check=True):
+    """Lift one view's fp16 feature map onto the Gaussians (vp_splat_project + vp_splat_lift), as splat_features splats:
+    reads the 8-byte intersection count once to size the sort and the scratch.  ``sum`` / ``wsum`` accumulate.  Returns
+    (n_isect int, n_nonfinite device int32 [1]).  With ``check`` the call synchronises once more and raises VoxprojError when
+    a Gaussian had a non-finite parameter (it is culled)."""
+    import torch
+    _require_tensors(*((t, name, (torch.float32,)) for t, name in
+                       ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
+    _require(isinstance(feats, torch.Tensor) and feats.device == means.device, "feats and the Gaussians must be on one device")
+    ws, cap, bad, status = _splat_sized_view(means, quats, scales, opacities, viewmat, K, W, H, near, far, eps2d, workspace)
+    splat_lift(feats, int(means.shape[0]), W, H, cap, ws, sum, wsum, pixel_weight, sorted=False, status=status,
+               lift_workspace=lift_workspace)
+    if check:
+        _splat_view_check("splat_lift_view", status, bad, "nothing added")
+    return cap, bad
+
+
+class GaussianFeatureLifter:
+    """Blend-weighted mean of the pixel features every Gaussian contributed to, over any number of views:
+    F_g = sum_views sum_p m_p w_g(p) feat_v(p) / sum_views sum_p m_p w_g(p).  ``add_view`` accumulates one view's sums
+    (splat_lift_view), ``finish`` divides."""
+
+    def __init__(self, n, C, device):
+        import torch
+        self.n, self.C, self.device = int(n), int(C), torch.device(device)
+        self.sum = torch.zeros((self.n, self.C), dtype=torch.float32, device=self.device)
+        self.wsum = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        self.views = 0
+        self._ws = self._lw = None
+        if self.device.type == "cuda":
+            self._ws, self._lw = SplatWorkspace(), SplatWorkspace()
+
+    def add_view(self, means, quats, scales, opacities, feats, viewmat, K, W, H, pixel_weight=None, **kw):
+        """One view's map f16 [H,W,C] into the sums; returns splat_lift_view's (n_isect, n_nonfinite)."""
+        _require(int(means.shape[0]) == self.n and int(feats.shape[-1]) == self.C,
+                 f"add_view needs {self.n} Gaussians and a map of {self.C} channels")
+        out = splat_lift_view(means, quats, scales, opacities, feats, viewmat, K, W, H, self.sum, self.wsum, pixel_weight,
+                              workspace=self._ws, lift_workspace=self._lw, **kw)
+        self.views += 1
+        return out
+
+    def finish(self, min_weight=1e-3):
+        """(avg_feats f16 [n,C], weight f32 [n], valid bool [n]): sum / weight where weight >= min_weight (and > 0), rows of
+        zeros elsewhere."""
+        import torch
+        valid = (self.wsum >= float(min_weight)) & (self.wsum > 0)
+        avg = torch.where(valid[:, None], self.sum / self.wsum.clamp_min(torch.finfo(torch.float32).tiny)[:, None],
+                          torch.zeros((), dtype=torch.float32, device=self.device))
+        return avg.to(torch.float16), self.wsum.clone(), valid
 
 
 _check_rc = check

@@ -614,6 +614,54 @@ int vp_splat_loss_backward(const float *means, const float *quats, const float *
                            void *bwd_workspace, size_t bwd_bytes, void *stream);
 
 /*
+ * Lifting a 2D feature map onto the Gaussians: the transpose of the splatter for one view, accumulated into per-Gaussian
+ * sums.  Added after VP_ABI_VERSION 4 without changing it or any existing entry point; detect the two functions by symbol.
+ * tests/splat_lift_reference.py states the contract in float64.
+ *
+ * The contract: with w_g(p) = a T the weight vp_splat_rasterize blends Gaussian g into pixel p with, decision for decision
+ * (Gaussians in ascending (fp32 z, index) order; skipped when sigma < 0 or a < 1/255; the pixel stops before the Gaussian that
+ * would take T to <= 1e-4, which is not added), and m_p the pixel's weight,
+ *   sum[g * sum_stride + c] += sum_p m_p w_g(p) feat[p, c]      wsum[g] += sum_p m_p w_g(p).
+ * The outputs accumulate and are never cleared: a caller adds view after view and divides at the end.  A sum of exactly 0 is
+ * not added, so the rows of a culled Gaussian, and of one that no pixel added, keep their bits.  w_g(p) is fp32 and is
+ * not rounded to binary16: the product runs on the matrix cores with the weight split into two binary16 terms that carry 22
+ * bits of it (when the weights m_p of one 16x16 tile differ by more than 2^7 the smallest w_g(p) at the smallest m_p keep
+ * fewer).  No float atomics: per-(tile, Gaussian) partials go to the pair's emission slot and are summed per Gaussian in
+ * ascending slot order, so results are bit-identical from run to run.
+ *
+ * The map: feats_f16 is binary16, channels-last [H,W,C]: pixel p = y W + x starts at feats_f16 + p * pix_stride elements,
+ *   pix_stride >= C, unit channel stride (what vp_upsample_features writes with dst_is_f16).  C in [1, 4096].  16-byte loads
+ *   are used when C and pix_stride are multiples of 8 and the base is 16-byte aligned; any other layout is read element by
+ *   element.  pixel_weight f32 [H,W] or NULL (read as 1), finite; a value that is not > 0 is read as 0.
+ *   A pixel with m_p = 0 contributes nothing whatever its map holds (NaN included).  At every other pixel the map must be
+ *   finite: a non-finite element there leaves channel c of `sum` unspecified for every Gaussian with a tile over that pixel
+ *   (in a matrix product 0 * Inf is NaN, so Gaussians that never blended into the pixel are affected too).
+ *
+ * The workspace: the call runs after vp_splat_project on `workspace` with the same n_gaussians, W, H and stream.
+ *   vp_splat_project leaves the records, the tile boxes, the counts, their scan and the device total; the sort
+ *   (vp_splat_rasterize, vp_splat_rasterize_loss, or this call with sorted = 0) emits `capacity` keys, sorts them and writes
+ *   the sorted values and every tile's run, which stay valid until the next vp_splat_project on the workspace.
+ *   sorted = 0: the call sorts first, exactly as vp_splat_rasterize does; valid directly after vp_splat_project.
+ *   sorted = 1: a vp_splat_rasterize or vp_splat_rasterize_loss call with the same capacity already sorted this workspace
+ *     (the backward's precondition); the workspace is only read.  Any other value: VP_EINVAL.
+ *
+ * vp_splat_lift_workspace_bytes: bytes of the lift's own scratch; with Cc = 16 when C <= 16, else 64 (the channels of one
+ *   pass) and n = max(capacity, 1):  round256(n * Cc * 4) + round256(n * 4)  -- one partial row of Cc floats and one weight
+ *   partial per intersection.  0 when capacity is outside [0, 2^31 - 1] or C outside [1, 4096].  Needs no GPU.  Channels are
+ *   processed in ceil(C / Cc) passes over this scratch; a larger lift_bytes is accepted and not used.
+ *
+ * vp_splat_lift: when the device count exceeds `capacity` nothing is written and *status (device i32, may be NULL; not
+ *   reset) is set to 1.  wsum may be NULL.  Asynchronous on `stream`, no allocation, no host synchronisation, 64-bit offsets.
+ *   VP_EINVAL: NULL feats_f16 or sum, C outside [1, 4096], pix_stride < C, sum_stride < C, a bad `sorted`, n_gaussians or
+ *   capacity outside [0, 2^31 - 1], W or H outside [1, 32768].  VP_EWORKSPACE for either workspace: NULL, not 256-byte
+ *   aligned, or smaller than its size function.  A refused call writes nothing.
+ */
+size_t vp_splat_lift_workspace_bytes(int64_t capacity, int C);
+int vp_splat_lift(const void *feats_f16, int C, int64_t pix_stride, const float *pixel_weight, int64_t n_gaussians, int W,
+                  int H, int64_t capacity, int sorted, float *sum, int64_t sum_stride, float *wsum, int32_t *status,
+                  void *workspace, size_t workspace_bytes, void *lift_workspace, size_t lift_bytes, void *stream);
+
+/*
  * Scoring label maps against ground truth: the confusion matrix of a predicted and a target label map, the boundary band
  * of a label map and the per-class boundary intersections and unions, from which the host forms mIoU, fwIoU, pixel accuracy
  * and boundary IoU.  Added after VP_ABI_VERSION 4 without changing it or any existing entry point; detect the three

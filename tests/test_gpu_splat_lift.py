@@ -1,0 +1,476 @@
+"""Lifting a feature map onto the Gaussians (vp_splat_lift, voxproj_host.splat_lift / splat_lift_view / GaussianFeatureLifter)
+on the GPU against the float64 reference of tests/splat_lift_reference.py.
+
+Bound: |got - ref| <= 1e-4 M + 1e-6 max|G| for every element of sum and wsum (splat_grad_reference.grad_bound, the bar the
+backward's grad_features meets), with G = [m feat^T ; m] the reference's upstream and the fp16 map converted exactly.  Pixels
+the oracle marks fragile get m = 0, so a threshold decision that fp32 may take the other way cannot reach a sum.  Every case
+asserts a minimum number of nonzero reference entries.  The calls go through voxproj_host.splat_lift, which raises when the
+library has no vp_splat_lift: nothing here skips.
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (HERE, ROOT, os.path.join(ROOT, "3d-semantic-segmentation_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import splat_grad_reference as gref  # noqa: E402
+import splat_lift_reference as lref  # noqa: E402
+import splat_scenes  # noqa: E402
+import voxproj_host  # noqa: E402
+from test_gpu_splat import camera, scene  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+GEO = ("means", "quats", "scales", "opacities")
+
+
+def tens(s):
+    return {k: torch.from_numpy(np.ascontiguousarray(s[k])).to(DEV) for k in GEO}
+
+
+def make_map(W, H, C, seed, scale=1.0):
+    return (scale * np.random.default_rng(seed + 500).normal(size=(H, W, C))).astype(np.float16)
+
+
+def safe_weight(s, vm, K, W, H, seed=None, cap=0.01, **kw):
+    """Pixel weights f32 [H,W]: 1 (or, with a seed, uniform in [0.25, 1]) and 0 on the oracle's fragile pixels, whose share
+    of the image may not exceed ``cap`` (1 % unless the scene states its own), so a case cannot be hollowed out unnoticed."""
+    m = np.ones((H, W), np.float32) if seed is None else np.random.default_rng(seed).uniform(0.25, 1.0, (H, W)).astype(np.float32)
+    fragile = lref.fragile_pixels(s["means"], s["quats"], s["scales"], s["opacities"], vm, K, W, H, **kw)
+    assert fragile.mean() <= cap, f"{fragile.mean():.4f} of the pixels are fragile"
+    m[fragile] = 0.0
+    return m
+
+
+def run_lift(s, vm, K, W, H, feats, m=None, sum_=None, wsum=None, feats_t=None, **kw):
+    """splat_lift_view of one view into (new zeroed, or the given) sums; feats fp16 numpy [H,W,C] unless feats_t is given."""
+    t = tens(s)
+    ft = feats_t if feats_t is not None else torch.from_numpy(feats).to(DEV)
+    N, C = len(s["means"]), ft.shape[2]
+    sum_ = torch.zeros((N, C), device=DEV) if sum_ is None else sum_
+    wsum = torch.zeros(N, device=DEV) if wsum is None else wsum
+    mt = torch.from_numpy(m).to(DEV) if m is not None else None
+    n_isect, _ = voxproj_host.splat_lift_view(t["means"], t["quats"], t["scales"], t["opacities"], ft, vm, K, W, H, sum_, wsum,
+                                              mt, check=False, **kw)
+    torch.cuda.synchronize()
+    return sum_, wsum, n_isect
+
+
+def compare(s, vm, K, W, H, feats, m, got_sum, got_wsum, min_nonzero=200, r=None, **kw):
+    r = r if r is not None else lref.lift64(s["means"], s["quats"], s["scales"], s["opacities"], feats, vm, K, W, H,
+                                            pixel_weight=m, **kw)
+    bs, bw = gref.grad_bound(r["M_sum"], [r["G"]]), gref.grad_bound(r["M_wsum"], [r["G"]])
+    es = np.abs(got_sum.cpu().numpy().astype(np.float64) - r["sum"])
+    ew = np.abs(got_wsum.cpu().numpy().astype(np.float64) - r["wsum"])
+    nz = int((r["sum"] != 0).sum() + (r["wsum"] != 0).sum())
+    print(f"lift: {nz} nonzero reference entries; worst error / bound: sum {(es / bs).max():.3f}, wsum {(ew / bw).max():.3f}")
+    assert nz >= min_nonzero, f"only {nz} nonzero reference entries"
+    assert (es <= bs).all(), f"sum error {es.max():.3e} over its bound at {np.unravel_index((es - bs).argmax(), es.shape)}"
+    assert (ew <= bw).all(), f"wsum error {ew.max():.3e} over its bound at {(ew - bw).argmax()}"
+    return r
+
+
+@pytest.mark.parametrize("C", [1, 8, 13, 64, 96])
+def test_channel_counts(C):
+    # C = 1, 8, 13: the 16-channel pass (13 and 1 element by element); 64: one MFMA pass; 96: a ragged second pass
+    W, H = 61, 47
+    s = scene(400, 1, C)
+    vm, K = camera(W, H)
+    feats, m = make_map(W, H, C, C), safe_weight(s, vm, K, W, H)
+    got = run_lift(s, vm, K, W, H, feats, m)
+    compare(s, vm, K, W, H, feats, m, got[0], got[1])
+
+
+def test_512_channels():
+    """Eight passes.  The float64 reference of 513 upstream channels takes ten seconds, so the map is built from 16 base
+    channels: channel c is base channel c % 16 times +-2^e (exact in binary16), and the reference of channel c is that of
+    its base channel times the same factor -- exactly, since the lift is linear and a power of two rounds nothing."""
+    W, H, C = 61, 47, 512
+    s = scene(400, 1, 512)
+    vm, K = camera(W, H)
+    rng = np.random.default_rng(512)
+    base, m = make_map(W, H, 16, 512), safe_weight(s, vm, K, W, H, seed=513)
+    factor = rng.choice([-1.0, 1.0], C) * 2.0 ** rng.integers(0, 5, C)
+    feats = (base.astype(np.float64)[:, :, np.arange(C) % 16] * factor).astype(np.float16)
+    assert np.array_equal(feats.astype(np.float64), base.astype(np.float64)[:, :, np.arange(C) % 16] * factor)
+    r = lref.lift64(s["means"], s["quats"], s["scales"], s["opacities"], base, vm, K, W, H, pixel_weight=m)
+    G = lref.upstream(feats, m)
+    r = dict(r, sum=r["sum"][:, np.arange(C) % 16] * factor, M_sum=r["M_sum"][:, np.arange(C) % 16] * np.abs(factor), G=G)
+    got = run_lift(s, vm, K, W, H, feats, m)
+    compare(s, vm, K, W, H, feats, m, got[0], got[1], min_nonzero=100000, r=r)
+
+
+@pytest.mark.parametrize("C,pix_stride,sum_stride", [(13, 20, 16), (64, 72, 80), (64, 70, 64), (24, 24, 30)])
+def test_pixel_and_sum_strides(C, pix_stride, sum_stride):
+    # (64, 72): 16-byte loads with a padded pixel; (64, 70) and (13, 20): the element path; the padding holds NaN and is never read
+    W, H = 61, 47
+    s = scene(400, 1, 31)
+    vm, K = camera(W, H)
+    feats, m = make_map(W, H, C, 7), safe_weight(s, vm, K, W, H, seed=8)
+    wide = torch.full((H, W, pix_stride), float("nan"), dtype=torch.float16, device=DEV)
+    wide[:, :, :C] = torch.from_numpy(feats).to(DEV)
+    sums = torch.full((400, sum_stride), -3.0, device=DEV)
+    sums[:, :C] = 0.0
+    got = run_lift(s, vm, K, W, H, feats, m, sum_=sums[:, :C], feats_t=wide[:, :, :C])
+    compare(s, vm, K, W, H, feats, m, got[0], got[1])
+    assert (sums[:, C:] == -3.0).all(), "the lift wrote past C in a row of sum"
+
+
+@pytest.mark.parametrize("size", [(37, 23), (1, 1)])
+def test_odd_sizes(size):
+    W, H = size
+    s = scene(300, 1, 3, spread=0.3 if W == 1 else 1.2, scale=0.4 if W == 1 else 0.05)
+    vm, K = camera(W, H)
+    C = 40 if W == 1 else 5              # one pixel adds nine Gaussians: 41 entries each reach the floor of 200
+    feats, m = make_map(W, H, C, 3), safe_weight(s, vm, K, W, H)
+    got = run_lift(s, vm, K, W, H, feats, m)
+    compare(s, vm, K, W, H, feats, m, got[0], got[1])
+
+
+def test_misaligned_map_base():
+    # C and the pixel stride are multiples of 8 but the map starts 2 bytes into its allocation: the element path
+    W, H, C = 61, 47, 64
+    s = scene(400, 1, 33)
+    vm, K = camera(W, H)
+    feats, m = make_map(W, H, C, 33), safe_weight(s, vm, K, W, H)
+    buf = torch.full((H * W * C + 1,), float("nan"), dtype=torch.float16, device=DEV)
+    view = buf[1:].view(H, W, C)
+    view.copy_(torch.from_numpy(feats).to(DEV))
+    assert view.data_ptr() % 16 == 2 and view.is_contiguous()
+    got = run_lift(s, vm, K, W, H, feats, m, feats_t=view)
+    compare(s, vm, K, W, H, feats, m, got[0], got[1])
+    aligned = run_lift(s, vm, K, W, H, feats, m)
+    assert torch.equal(got[0], aligned[0]) and torch.equal(got[1], aligned[1]), "the two load paths must give the same bits"
+
+
+def test_no_gaussians_and_all_culled():
+    W, H, C = 40, 33, 24
+    vm, K = camera(W, H)
+    feats = make_map(W, H, C, 5)
+    empty = dict(means=np.zeros((0, 3), np.float32), quats=np.zeros((0, 4), np.float32), scales=np.zeros((0, 3), np.float32),
+                 opacities=np.zeros(0, np.float32))
+    got = run_lift(empty, vm, K, W, H, feats)
+    assert got[0].shape == (0, C) and got[1].shape == (0,) and got[2] == 0
+    culled = dict(scene(200, 1, 2), means=np.tile(np.float32([[0, 0, -2.0]]), (200, 1)))
+    sum_, wsum = torch.full((200, C), -7.0, device=DEV), torch.full((200,), -7.0, device=DEV)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    t = tens(culled)
+    ws = voxproj_host.SplatWorkspace()
+    total = int(voxproj_host.splat_project(t["means"], t["quats"], t["scales"], t["opacities"], vm, K, W, H, workspace=ws).item())
+    voxproj_host.splat_lift(torch.from_numpy(feats).to(DEV), 200, W, H, total, ws, sum_, wsum, status=status)
+    torch.cuda.synchronize()
+    assert total == 0 and int(status.item()) == 0 and (sum_ == -7).all() and (wsum == -7).all()
+
+
+def test_tile_with_more_gaussians_than_one_batch():
+    W, H = 32, 32
+    rng = np.random.default_rng(11)
+    n = 3000
+    s = scene(n, 1, 11)
+    s["means"] = np.stack([rng.uniform(-0.2, 0.2, n), rng.uniform(-0.2, 0.2, n), rng.uniform(1.5, 3.0, n)], 1).astype(np.float32)
+    s["scales"] = np.full((n, 3), 0.3, np.float32)
+    s["opacities"] = rng.uniform(0.01, 0.03, n).astype(np.float32)
+    vm, K = np.eye(4, dtype=np.float32), np.array([[30, 0, 16], [0, 30, 16], [0, 0, 1]], np.float32)
+    feats, m = make_map(W, H, 24, 11), safe_weight(s, vm, K, W, H)
+    got = run_lift(s, vm, K, W, H, feats, m)
+    r = compare(s, vm, K, W, H, feats, m, got[0], got[1], min_nonzero=2000)
+    assert r["visits"].max() > 2 * 256
+
+
+def test_saturating_stack_and_zeroed_slots():
+    # 40 opaque Gaussians stacked on the axis: pixels stop after a few, the tiles leave early, and the Gaussians behind every
+    # stop must get zero partials: the lift's scratch starts as NaN, so a slot left unwritten would poison their rows
+    W, H = 40, 30
+    n = 40
+    rng = np.random.default_rng(4)
+    s = dict(means=np.stack([rng.uniform(-0.05, 0.05, n), rng.uniform(-0.05, 0.05, n), np.linspace(2.0, 4.0, n)], 1).astype(np.float32),
+             quats=np.tile(np.float32([[1, 0, 0, 0]]), (n, 1)), scales=np.full((n, 3), 3.0, np.float32),
+             opacities=np.where(np.arange(n) < 3, 1.0, 0.95).astype(np.float32))
+    vm, K = np.eye(4, dtype=np.float32), np.array([[20, 0, 20], [0, 20, 15], [0, 0, 1]], np.float32)
+    feats, m = make_map(W, H, 70, 4), safe_weight(s, vm, K, W, H)
+    lw = voxproj_host.SplatWorkspace()
+    lw.ensure(voxproj_host.splat_lift_workspace_bytes(4096, 70), DEV)
+    lw.buf.fill_(255)
+    sum_ = torch.full((n, 70), 5.0, device=DEV)
+    wsum = torch.full((n,), 5.0, device=DEV)
+    got = run_lift(s, vm, K, W, H, feats, m, sum_=sum_, wsum=wsum, lift_workspace=lw)
+    assert got[2] <= 4096
+    r = compare(s, vm, K, W, H, feats, m, got[0] - 5.0, got[1] - 5.0)
+    behind = r["added"] == 0
+    assert behind.sum() >= 10
+    assert (got[0].cpu().numpy()[behind] == 5.0).all() and (got[1].cpu().numpy()[behind] == 5.0).all()
+
+
+def test_depth_ties():
+    sc = splat_scenes.ties_scene()
+    s, vm, K, W, H = sc["s"], sc["vm"], sc["K"], sc["W"], sc["H"]
+    feats, m = make_map(W, H, 20, 9), safe_weight(s, vm, K, W, H)
+    got = run_lift(s, vm, K, W, H, feats, m)
+    compare(s, vm, K, W, H, feats, m, got[0], got[1], min_nonzero=2000)
+
+
+def test_masked_pixels_may_hold_nan_and_the_largest_half():
+    W, H = 61, 47
+    s = scene(400, 1, 12)
+    vm, K = camera(W, H)
+    rng = np.random.default_rng(12)
+    feats, m = make_map(W, H, 64, 12), safe_weight(s, vm, K, W, H, seed=13)
+    off = rng.uniform(size=(H, W)) < 0.3
+    m[off] = 0.0
+    feats[off] = np.where(rng.uniform(size=(int(off.sum()), 64)) < 0.5, np.float16(np.nan), np.float16(65504.0))
+    feats[off & (rng.uniform(size=(H, W)) < 0.2)] = np.float16(np.inf)
+    assert off.sum() > 500 and (m > 0).sum() > 1500
+    got = run_lift(s, vm, K, W, H, feats, m)
+    assert torch.isfinite(got[0]).all() and torch.isfinite(got[1]).all()
+    compare(s, vm, K, W, H, feats, m, got[0], got[1])
+
+
+def test_subnormal_map_values():
+    W, H = 61, 47
+    s = scene(400, 1, 14)
+    vm, K = camera(W, H)
+    feats, m = make_map(W, H, 13, 14, scale=2.0 ** -17), safe_weight(s, vm, K, W, H)
+    f64 = np.abs(feats.astype(np.float64))
+    assert ((f64 > 0) & (f64 < 2.0 ** -14)).mean() > 0.9, "the map is meant to be fp16 subnormals"
+    got = run_lift(s, vm, K, W, H, feats, m)
+    compare(s, vm, K, W, H, feats, m, got[0], got[1])
+    # the wsum entries dominate max|G| here; hold the sums to their relative part alone as well
+    r = lref.lift64(s["means"], s["quats"], s["scales"], s["opacities"], feats, vm, K, W, H, pixel_weight=m)
+    es = np.abs(got[0].cpu().numpy().astype(np.float64) - r["sum"])
+    assert (es <= 1e-4 * r["M_sum"] + 1e-6 * f64.max()).all()
+
+
+def test_weights_below_the_half_precision_normal_range():
+    # two nearly opaque sheets in front (T falls to a few 1e-4), faint Gaussians behind: their added weights a T lie below
+    # 6e-5, the smallest normal binary16; asserted from the reference, so the weight's staging is exercised there
+    W, H = 61, 47
+    rng = np.random.default_rng(21)
+    s = scene(300, 1, 21, z=(2.0, 4.0))
+    s["opacities"] = rng.uniform(0.05, 0.2, 300).astype(np.float32)
+    front = dict(means=np.float32([[0, 0, 1.0], [0, 0, 1.1]]), quats=np.float32([[1, 0, 0, 0]] * 2),
+                 scales=np.full((2, 3), 5.0, np.float32), opacities=np.float32([0.98, 0.98]))
+    s = {k: np.concatenate([front[k], s[k]]) for k in GEO}
+    vm, K = camera(W, H)
+    feats, m = make_map(W, H, 32, 21), safe_weight(s, vm, K, W, H)
+    px = np.argwhere(m > 0)[::7]
+    w = lref.added_weights(s["means"], s["quats"], s["scales"], s["opacities"], vm, K, W, H, px)
+    assert (w < 6e-5).sum() >= 200 and w[w > 0].min() < 2e-5, f"{(w < 6e-5).sum()} small weights, min {w.min():.2e}"
+    got = run_lift(s, vm, K, W, H, feats, m)
+    r = compare(s, vm, K, W, H, feats, m, got[0], got[1])
+    # the faint Gaussians alone, relative to their own magnitude (no absolute term)
+    faint = np.arange(len(s["means"])) >= 2
+    ew = np.abs(got[1].cpu().numpy().astype(np.float64) - r["wsum"])[faint]
+    assert (r["wsum"][faint] > 0).sum() >= 100 and (ew <= 1e-4 * r["M_wsum"][faint]).all()
+
+
+def test_culled_nan_and_never_added_rows_keep_their_bits():
+    W, H = 61, 47
+    s = scene(300, 1, 4)
+    s["means"][3, 1] = np.nan
+    s["scales"][10, 0] = np.inf
+    s["opacities"][20] = np.nan
+    s["means"][30] = (0, 0, -2.0)                       # behind the camera
+    s["quats"][40] = 0.0
+    s["opacities"][50] = 0.001
+    s["means"][60] = (0.0, 0.0, 3.9)                    # hidden behind three opaque blobs: has tiles, is never added
+    s["scales"][60] = 0.01
+    for k, z in ((61, 1.0), (62, 1.05), (63, 1.1)):
+        s["means"][k], s["scales"][k], s["opacities"][k], s["quats"][k] = (0.0, 0.0, z), 0.6, 1.0, (1, 0, 0, 0)
+    vm, K = camera(W, H)
+    feats, m = make_map(W, H, 40, 4), safe_weight(s, vm, K, W, H)
+    rng = np.random.default_rng(40)
+    pre = rng.normal(size=(300, 40)).astype(np.float32)
+    pre[:, ::5] = -0.0
+    prew = rng.normal(size=300).astype(np.float32)
+    prew[::2] = -0.0
+    got = run_lift(s, vm, K, W, H, feats, m, sum_=torch.from_numpy(pre).to(DEV), wsum=torch.from_numpy(prew).to(DEV))
+    r = lref.lift64(s["means"], s["quats"], s["scales"], s["opacities"], feats, vm, K, W, H, pixel_weight=m)
+    keep = r["added"] == 0
+    assert keep[[3, 10, 20, 30, 40, 50, 60]].all() and keep.sum() >= 8 and (~keep).sum() >= 5
+    gs, gw = got[0].cpu().numpy(), got[1].cpu().numpy()
+    assert gs[keep].tobytes() == pre[keep].tobytes() and gw[keep].tobytes() == prew[keep].tobytes()
+    changed = r["wsum"] > 0
+    assert changed.sum() >= 100 and (gw[changed] != prew[changed]).all()
+
+
+def test_two_views_accumulate():
+    W, H = 61, 47
+    s = scene(400, 1, 15)
+    cams = [camera(W, H), camera(W, H, yaw=-0.2, pitch=0.1, t=(-0.1, 0.05, 0.3))]
+    maps = [make_map(W, H, 48, 15), make_map(W, H, 48, 16)]
+    ms = [safe_weight(s, vm, K, W, H) for vm, K in cams]
+    sum_, wsum = torch.zeros((400, 48), device=DEV), torch.zeros(400, device=DEV)
+    refs = []
+    for (vm, K), f, m in zip(cams, maps, ms):
+        run_lift(s, vm, K, W, H, f, m, sum_=sum_, wsum=wsum)
+        refs.append(lref.lift64(s["means"], s["quats"], s["scales"], s["opacities"], f, vm, K, W, H, pixel_weight=m))
+    both = dict(sum=refs[0]["sum"] + refs[1]["sum"], wsum=refs[0]["wsum"] + refs[1]["wsum"],
+                M_sum=refs[0]["M_sum"] + refs[1]["M_sum"], M_wsum=refs[0]["M_wsum"] + refs[1]["M_wsum"],
+                G=np.concatenate([refs[0]["G"], refs[1]["G"]]))
+    assert ((refs[0]["wsum"] > 0) & (refs[1]["wsum"] > 0)).sum() >= 100
+    compare(s, None, None, W, H, None, None, sum_, wsum, r=both)
+    # the same view twice into one buffer is exactly twice one call from zero
+    one = run_lift(s, *cams[0], W, H, maps[0], ms[0])
+    two = run_lift(s, *cams[0], W, H, maps[0], ms[0], sum_=one[0].clone(), wsum=one[1].clone())
+    assert torch.equal(two[0], 2 * one[0]) and torch.equal(two[1], 2 * one[1]) and (one[0] != 0).sum() > 1000
+
+
+def test_sorted_flag_gives_the_same_bits():
+    W, H = 61, 47
+    s = scene(400, 5, 17)
+    vm, K = camera(W, H)
+    t = tens(s)
+    feats = torch.from_numpy(make_map(W, H, 96, 17)).to(DEV)
+    a = run_lift(s, vm, K, W, H, None, feats_t=feats)                     # project, then sorted = 0
+    ws = voxproj_host.SplatWorkspace()
+    r = voxproj_host.splat_features(t["means"], t["quats"], t["scales"], t["opacities"],
+                                    torch.from_numpy(s["features"]).to(DEV), vm, K, W, H, workspace=ws)
+    b = torch.zeros((400, 96), device=DEV), torch.zeros(400, device=DEV)
+    before = ws.buf.clone()
+    voxproj_host.splat_lift(feats, 400, W, H, r.n_isect, ws, b[0], b[1], sorted=True)
+    torch.cuda.synchronize()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and (a[0] != 0).sum() > 1000
+    assert torch.equal(before, ws.buf), "sorted = 1 must only read the workspace"
+    with pytest.raises(ValueError, match="sorted"):
+        voxproj_host.splat_lift(feats, 400, W, H, r.n_isect, ws, b[0], b[1], sorted=2)
+
+
+def test_bit_identical_runs():
+    W, H = 61, 47
+    s = scene(400, 1, 18)
+    vm, K = camera(W, H)
+    feats = torch.from_numpy(make_map(W, H, 512, 18)).to(DEV)
+    m = np.random.default_rng(18).uniform(0.0, 1.0, (H, W)).astype(np.float32)
+    a = run_lift(s, vm, K, W, H, None, m, feats_t=feats)
+    b = run_lift(s, vm, K, W, H, None, m, feats_t=feats)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and (a[0] != 0).sum() > 10000
+
+
+def _direct(feats0, W0, H0, cap0, ws0, sum0, wsum0, lw0, **over):
+    """vp_splat_lift through ctypes with any argument replaced (the refusals)."""
+    L = voxproj_host.lib()
+    N, C = sum0.shape
+    a = dict(feats_ptr=feats0.data_ptr(), C=C, pix_stride=C, weight=None, n=N, W=W0, H=H0, cap=cap0, sorted=0,
+             sum=sum0.data_ptr(), sum_stride=C, wsum=wsum0.data_ptr(), status=None, ws=ws0.ptr(), ws_bytes=ws0.capacity(),
+             lw=lw0.ptr(), lw_bytes=lw0.capacity())
+    assert set(over) <= set(a), over
+    a.update(over)
+    return L.vp_splat_lift(a["feats_ptr"], a["C"], a["pix_stride"], a["weight"], a["n"], a["W"], a["H"], a["cap"], a["sorted"],
+                           a["sum"], a["sum_stride"], a["wsum"], a["status"], a["ws"], a["ws_bytes"], a["lw"], a["lw_bytes"],
+                           torch.cuda.current_stream().cuda_stream)
+
+
+def test_too_small_capacity_writes_nothing():
+    W, H = 61, 47
+    s = scene(400, 1, 1)
+    vm, K = camera(W, H)
+    t = tens(s)
+    ws = voxproj_host.SplatWorkspace()
+    total = int(voxproj_host.splat_project(t["means"], t["quats"], t["scales"], t["opacities"], vm, K, W, H, workspace=ws).item())
+    assert total > 10
+    feats = torch.from_numpy(make_map(W, H, 64, 1)).to(DEV)
+    sum_, wsum = torch.full((400, 64), -7.0, device=DEV), torch.full((400,), -7.0, device=DEV)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    voxproj_host.splat_lift(feats, 400, W, H, total - 1, ws, sum_, wsum, status=status)
+    torch.cuda.synchronize()
+    assert int(status.item()) == 1
+    assert (sum_ == -7).all() and (wsum == -7).all(), "a too-small capacity must not add anything"
+    status.zero_()
+    voxproj_host.splat_lift(feats, 400, W, H, total, ws, sum_, wsum, status=status)
+    torch.cuda.synchronize()
+    assert int(status.item()) == 0 and (sum_ != -7).sum() > 1000
+
+
+def test_refusals_write_nothing():
+    W, H = 61, 47
+    s = scene(200, 1, 2)
+    vm, K = camera(W, H)
+    t = tens(s)
+    ws = voxproj_host.SplatWorkspace()
+    total = int(voxproj_host.splat_project(t["means"], t["quats"], t["scales"], t["opacities"], vm, K, W, H, workspace=ws).item())
+    L = voxproj_host.lib()
+    ws.ensure(L.vp_splat_workspace_bytes(200, W, H, total), DEV, keep=L.vp_splat_workspace_bytes(200, W, H, 0))
+    C = 24
+    feats = torch.from_numpy(make_map(W, H, C, 2)).to(DEV)
+    sum_, wsum = torch.full((200, C), -7.0, device=DEV), torch.full((200,), -7.0, device=DEV)
+    lw = voxproj_host.SplatWorkspace()
+    need = voxproj_host.splat_lift_workspace_bytes(total, C)
+    lw.ensure(need, DEV)
+    lw.buf.fill_(9)
+    snap_ws, snap_lw = ws.buf.clone(), lw.buf.clone()
+    EINVAL, EWORKSPACE = -1, -2                          # VP_EINVAL, VP_EWORKSPACE of include/voxproj.h
+    cases = [(EINVAL, dict(feats_ptr=None)), (EINVAL, dict(sum=None)), (EINVAL, dict(C=0)), (EINVAL, dict(C=4097, pix_stride=4097, sum_stride=4097)),
+             (EINVAL, dict(pix_stride=C - 1)), (EINVAL, dict(sum_stride=C - 1)), (EINVAL, dict(sorted=2)), (EINVAL, dict(sorted=-1)),
+             (EINVAL, dict(n=-1)), (EINVAL, dict(n=2 ** 31)), (EINVAL, dict(W=0)), (EINVAL, dict(H=32769)), (EINVAL, dict(cap=-1)),
+             (EINVAL, dict(cap=2 ** 31)),
+             (EWORKSPACE, dict(ws=None)), (EWORKSPACE, dict(ws=ws.ptr() + 16)), (EWORKSPACE, dict(ws_bytes=ws.capacity() // 4)),
+             (EWORKSPACE, dict(lw=None)), (EWORKSPACE, dict(lw=lw.ptr() + 16)), (EWORKSPACE, dict(lw_bytes=need - 1))]
+    for rc, over in cases:
+        assert _direct(feats, W, H, total, ws, sum_, wsum, lw, **over) == rc, over
+        assert voxproj_host.last_error()
+    torch.cuda.synchronize()
+    assert (sum_ == -7).all() and (wsum == -7).all()
+    assert torch.equal(ws.buf, snap_ws) and torch.equal(lw.buf, snap_lw), "a refused call wrote into a workspace"
+    assert _direct(feats, W, H, total, ws, sum_, wsum, lw) == voxproj_host.VP_OK        # and the same arguments are accepted
+    assert _direct(feats, W, H, total, ws, sum_, wsum, lw, wsum=None, sorted=1) == voxproj_host.VP_OK
+    torch.cuda.synchronize()
+    assert (sum_ != -7).sum() > 500
+    # the Python wrapper's own checks
+    with pytest.raises(ValueError, match="float16"):
+        voxproj_host.splat_lift(feats.float(), 200, W, H, total, ws, sum_, wsum)
+    with pytest.raises(ValueError, match="sum must be"):
+        voxproj_host.splat_lift(feats, 200, W, H, total, ws, sum_[:, :5], wsum)
+
+
+@pytest.mark.parametrize("D", [13, 64])
+def test_adjoint_and_telescoping_on_the_device(D):
+    """<lift(F), X> against <F, splat(X)> and sum(wsum) against sum(alpha), both sides from the device (they take the same
+    decisions, so no pixel is masked): each side is within 1e-4 of the magnitude sum_{g,c,p} w |F| |X| by its own contract."""
+    W, H = 61, 47
+    s = scene(400, D, D + 40)
+    vm, K = camera(W, H)
+    t = tens(s)
+    F = make_map(W, H, D, D)
+    X = torch.from_numpy(s["features"]).to(DEV)
+    ws = voxproj_host.SplatWorkspace()
+    r = voxproj_host.splat_features(t["means"], t["quats"], t["scales"], t["opacities"], X, vm, K, W, H, want_logits=True,
+                                    want_alpha=True, workspace=ws)
+    sum_, wsum = torch.zeros((400, D), device=DEV), torch.zeros(400, device=DEV)
+    voxproj_host.splat_lift(torch.from_numpy(F).to(DEV), 400, W, H, r.n_isect, ws, sum_, wsum, sorted=True)
+    torch.cuda.synchronize()
+    ref_ = lref.lift64(s["means"], s["quats"], s["scales"], s["opacities"], F, vm, K, W, H)
+    lhs = float((sum_.double() * X.double()).sum())
+    rhs = float((torch.from_numpy(F.astype(np.float64)).to(DEV).permute(2, 0, 1) * r.logits.double()).sum())
+    mag = float((ref_["M_sum"] * np.abs(s["features"].astype(np.float64))).sum())
+    print(f"adjoint D={D}: lift {lhs:.9g}, splat {rhs:.9g}, |difference| {abs(lhs - rhs):.3e}, tolerance {2e-4 * mag:.3e}")
+    assert mag > 100 and abs(lhs - rhs) <= 2e-4 * mag
+    tw, ta, wmag = float(wsum.double().sum()), float(r.alpha.double().sum()), float(ref_["M_wsum"].sum())
+    print(f"telescoping: sum wsum {tw:.9g}, sum alpha {ta:.9g}, tolerance {2e-4 * wmag:.3e}")
+    assert wmag > 100 and abs(tw - ta) <= 2e-4 * wmag
+
+
+def test_end_to_end_lifting_recovers_the_classes():
+    sc = lref.class_scene()
+    s, W, H = sc["s"], lref.CLASS_W, lref.CLASS_H
+    t = tens(s)
+    lifter = voxproj_host.GaussianFeatureLifter(len(s["means"]), lref.CLASS_C, DEV)
+    for (vm, K), mp in zip(sc["views"], sc["maps"]):
+        lifter.add_view(t["means"], t["quats"], t["scales"], t["opacities"], torch.from_numpy(mp).to(DEV), vm, K, W, H)
+    avg, weight, valid = lifter.finish(lref.CLASS_MIN_WEIGHT)
+    assert lifter.views == 2 and avg.dtype == torch.float16 and avg.shape == (len(s["means"]), lref.CLASS_C)
+    tot, wt = lref.class_reference(sc)
+    _, valid64 = lref.finish64(tot, wt, lref.CLASS_MIN_WEIGHT)
+    valid = valid.cpu().numpy()
+    share, share64 = 1.0 - valid.mean(), 1.0 - valid64.mean()
+    print(f"end to end: {share:.4f} of the Gaussians invalid on the device, {share64:.4f} in the float64 reference")
+    assert share64 < 0.2 and share <= share64
+    got = (avg.float().cpu().numpy() @ lref.class_vectors().T).argmax(1)
+    assert valid.sum() >= 150 and (got[valid] == sc["cls"][valid]).all()
+    assert not avg[~torch.from_numpy(valid).to(DEV)].any() and weight.shape == (len(s["means"]),)
