@@ -39,6 +39,7 @@
 //   vp_query.h   text query of a feature table: cosine logits, argmax label, softmax margin on the matrix cores (k_query)
 //   vp_splat.h   tile-based Gaussian splatting of D-channel features with a fused label / confidence epilogue (stage 5.2)
 //   vp_lift.h    lifting a 2D feature map onto the Gaussians: the splatter's transpose on the matrix cores (k_splat_lift)
+//   vp_splat_render.h  rendering wide feature rows into a view: the splatter's forward on the matrix cores (k_splat_render)
 //   vp_eval.h    scoring label maps against ground truth: confusion matrix, boundary band, boundary counts (all integers)
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
@@ -72,6 +73,7 @@
 #include "vp_query.h"
 #include "vp_splat.h"
 #include "vp_lift.h"
+#include "vp_splat_render.h"
 #include "vp_eval.h"
 #include "vp_project.h"
 
@@ -651,6 +653,55 @@ int vp_splat_lift(const void *feats_f16, int C, int64_t pix_stride, const float 
                                std::min(CC, C - c0), c0, sum, (long long)sum_stride, wsum, (int *)status);
         }
     });
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_splat_render(const void *rows, int rows_is_f16, int C, int64_t row_stride, int64_t n_gaussians, int W, int H,
+                    int64_t capacity, int sorted, void *out, int out_is_f16, int64_t pix_stride, float *alpha, int32_t *status,
+                    void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (!rows || !out) return fail(VP_EINVAL, "null pointer argument (rows or out)");
+    if (C < 1 || C > RENDER_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, RENDER_MAX_C);
+    if (row_stride < C) return fail(VP_EINVAL, "row_stride %lld < C = %d", (long long)row_stride, C);
+    if (pix_stride < C) return fail(VP_EINVAL, "pix_stride %lld < C = %d", (long long)pix_stride, C);
+    if (sorted != 0 && sorted != 1) return fail(VP_EINVAL, "sorted = %d is neither 0 nor 1", sorted);
+    if (rows_is_f16 != 0 && rows_is_f16 != 1) return fail(VP_EINVAL, "rows_is_f16 = %d is neither 0 nor 1", rows_is_f16);
+    if (out_is_f16 != 0 && out_is_f16 != 1) return fail(VP_EINVAL, "out_is_f16 = %d is neither 0 nor 1", out_is_f16);
+    if (int rc = splat_check_image(W, H)) return rc;
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    if (!sorted)
+        if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
+    // n_gaussians == 0 still launches: every tile's run is empty, and every pixel gets its zeros
+    const int epl = rows_is_f16 ? 8 : 4;                 // elements of one 16-byte load
+    const bool vec = C % epl == 0 && row_stride % epl == 0 && ((uintptr_t)rows & 15) == 0;
+    const int CC = render_chunk(C);
+    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+    auto launch = [&](auto nt) {
+        splat_with_flag(!rows_is_f16, [&](auto f32) {
+            splat_with_flag(vec, [&](auto v) {
+                splat_with_flag(out_is_f16 != 0, [&](auto o16) {
+                    for (int c0 = 0; c0 < C; c0 += CC)
+                        hipLaunchKernelGGL(
+                            (k_splat_render<decltype(nt)::value, decltype(f32)::value, decltype(v)::value, decltype(o16)::value>),
+                            grid, block, 0, stream, (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box),
+                            (const int *)(ws + l.count), (const long long *)(ws + l.offs), (const int *)(ws + l.vals1),
+                            (const longlong2 *)(ws + l.ranges), (const long long *)(ws + l.total), (long long)capacity, rows, C,
+                            (long long)row_stride, c0, W, H, out, (long long)pix_stride, c0 == 0 ? alpha : nullptr,
+                            (int *)status);
+                });
+            });
+        });
+    };
+    if (CC == 16) launch(std::integral_constant<int, 1>{});
+    else launch(std::integral_constant<int, 4>{});
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

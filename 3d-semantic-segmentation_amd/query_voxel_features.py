@@ -255,6 +255,50 @@ def _cmd_views(args, text, dev):
             print(f"  {(args.prompt[i] if i >= 0 else 'unlabelled'):20s} (idx={i}): count={c}")
 
 
+def rendered_labels(img, alpha, labels, margin, logits=None):
+    """Labels, confidence and logits of a rendered view: a pixel without a feature gets label -1, confidence 0 and zero
+    logits.  It has none where alpha is 0 (no Gaussian reaches it) or its rendered row [C] is all zeros -- the rule
+    ``lifted_labels`` applies to the Gaussians.  img [H,W,C], alpha [H,W], labels / margin [H*W], logits [H*W,P] or None."""
+    H, W = alpha.shape
+    valid = ((img != 0).any(dim=2) & (alpha > 0)).reshape(-1)
+    zero = torch.zeros((), dtype=torch.float32, device=labels.device)
+    lab = torch.where(valid, labels, torch.full_like(labels, -1)).reshape(H, W)
+    conf = torch.where(valid & (labels >= 0), margin, zero).reshape(H, W)
+    if logits is not None:
+        logits = torch.where((valid & (labels >= 0))[:, None], logits, zero).reshape(H, W, -1)
+    return lab, conf, logits
+
+
+def _cmd_gaussian_views(args, text, dev):
+    import render_gaussian_features as rgf
+    g, rows = rgf.load_scene(args, dev)
+    if rows.shape[1] != text.shape[1]:
+        raise ValueError(f"the rows have {rows.shape[1]} channels, the text embeddings {text.shape[1]}")
+    os.makedirs(args.out_dir, exist_ok=True)
+    ws = voxproj_host.SplatWorkspace()
+    t = text.to(dev)
+    all_labels = []
+    for name, vm, K, W, H in rgf.iter_views(args):
+        # the view channels-last in fp16, then the query on the [H W, C] map in place: cosine normalisation per pixel,
+        # after the blend
+        img, alpha, _, _ = voxproj_host.splat_render_view(g["means"], g["quats"], g["scales"], g["opacities"], rows, vm, K, W, H,
+                                                          dtype=torch.float16, want_alpha=True, workspace=ws, check=False)
+        labels, logits, margin = voxproj_host.query_features(img.view(H * W, -1), t, args.logit_scale,
+                                                             want_logits=args.save_logits, check=False)
+        lab_img, conf_img, logit_img = rendered_labels(img, alpha, labels, margin, logits)
+        stem = os.path.join(args.out_dir, name)
+        np.save(stem + "_labels.npy", lab_img.to(torch.int16).cpu().numpy())
+        np.save(stem + "_confidence.npy", conf_img.cpu().numpy())
+        if args.save_logits:
+            np.save(stem + "_logits.npy", logit_img.permute(2, 0, 1).contiguous().to(torch.float16).cpu().numpy())
+        all_labels.append(lab_img.reshape(-1).cpu().numpy())
+        print(f"[QUERY] {name}: {W}x{H}, {int((lab_img >= 0).sum())} labelled pixels -> {stem}_labels.npy")
+    pix = np.concatenate(all_labels)
+    print("\n[SUMMARY] Pixel labels over the views (-1: no rendered feature):")
+    for i, c in zip(*np.unique(pix, return_counts=True)):
+        print(f"  {(args.prompt[i] if i >= 0 else 'unlabelled'):20s} (idx={i}): count={c}")
+
+
 def build_parser():
     import aggregate_voxel_features_onthefly as agg
     ap = argparse.ArgumentParser(description="Score voxel features against text embeddings (GPU)")
@@ -290,6 +334,20 @@ def build_parser():
     w.add_argument("--out_dir", default="semantic_views")
     w.add_argument("--save_logits", action="store_true", help="also write <name>_logits.npy f16 [P,H,W]")
     w.add_argument("--save_ids", action="store_true", help="also write <name>_ids.npy: the first-hit voxel ID image")
+    # the arguments of render_gaussian_features.add_view_arguments, written out: building this parser imports nothing the
+    # other sub-commands do not need (tests/test_splat_render_cpu.py holds the two lists together)
+    r = sub.add_parser("gaussian_views", help="semantic segmentation of camera views from the Gaussians' own rendered rows")
+    common(r)
+    r.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
+    r.add_argument("--gauss_feats", required=True, help="LIFTED.pt of lift_gaussian_features.py: one feature row per Gaussian")
+    r.add_argument("--cam_params", required=True, help="camera_params.json")
+    r.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
+    r.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
+    r.add_argument("--max_images", type=int, default=None)
+    r.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
+    r.add_argument("--principal_point", choices=("center", "camera"), default="center")
+    r.add_argument("--out_dir", required=True)
+    r.add_argument("--save_logits", action="store_true", help="also write <name>_logits.npy f16 [P,H,W]")
     return ap
 
 
@@ -309,7 +367,8 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise RuntimeError("query_voxel_features runs on the GPU: there is no CPU path")
     dev = torch.device("cuda", torch.cuda.current_device())
-    {"voxels": _cmd_voxels, "gaussians": _cmd_gaussians, "views": _cmd_views}[args.cmd](args, text, dev)
+    {"voxels": _cmd_voxels, "gaussians": _cmd_gaussians, "views": _cmd_views,
+     "gaussian_views": _cmd_gaussian_views}[args.cmd](args, text, dev)
 
 
 if __name__ == "__main__":

@@ -8,6 +8,8 @@ the gradient.  ``splat_gaussians`` is differentiable in the means, the quaternio
 vp_splat_rasterize_backward_geometry (one fused tile sweep for every gradient asked for).  No gradient for the camera, no
 double backward.  ``splat_cross_entropy`` is the fused softmax cross-entropy of the splatted logits against a per-pixel target
 map (vp_splat_rasterize_loss / vp_splat_loss_backward): no logits or gradient image crosses torch.
+``splat_wide_features`` renders rows of up to 4096 channels channels-last (vp_splat_render) and is differentiable in the rows
+only, with the lift (vp_splat_lift) as its backward.
 
 Each call keeps its own SplatWorkspace until its backward has run (the backward reads the forward's sorted intersections),
 so calls from several threads or views share no state.  The workspace is freed after the backward, or with the graph.
@@ -17,7 +19,8 @@ from torch.autograd.function import once_differentiable
 
 import voxproj_host as _host
 
-__all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians", "splat_cross_entropy", "SplatCrossEntropy"]
+__all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians", "splat_cross_entropy", "SplatCrossEntropy",
+           "splat_wide_features", "SplatWideFeatures", "quantize_gradient_map"]
 
 
 class SplatFeatures(torch.autograd.Function):
@@ -191,3 +194,69 @@ def splat_cross_entropy(means, quats, scales, opacities, features, viewmat, K, W
                               (features, "features"))))
     return SplatCrossEntropy.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), target, pixel_weight,
                                    reduction, bool(keep_logits), float(near), float(far), float(eps2d), bool(check))
+
+
+def quantize_gradient_map(G):
+    """The rule that brings an fp32 gradient map to the binary16 map the lift reads: with m = max |G|,
+    s = 2^(14 - ceil(log2 m)) and Gq = f16(G s), so the largest element lands in (2^13, 2^14] whatever the loss's scale and
+    the small gradients of a mean loss stay out of the binary16 subnormals; s is a power of two, so G s is exact in fp32 and
+    the only rounding is the one to binary16.  The exponent is capped at 126 (m below 2^-112), and an all-zero map gives
+    s = 1 and a zero Gq.  Returns (Gq f16, k int32 0-dim with s = 2^k), both on G's device; no host synchronisation."""
+    _host._require(isinstance(G, torch.Tensor) and G.dtype == torch.float32, "the gradient map must be a torch.float32 tensor")
+    m = G.abs().max() if G.numel() else G.new_zeros(())
+    mant, ex = torch.frexp(m)                                # m = mant 2^ex with mant in [0.5, 1)
+    ceil_log2 = torch.where(mant == 0.5, ex - 1, ex)
+    k = torch.where(m > 0, (14 - ceil_log2).clamp(max=126), torch.zeros_like(ex)).to(torch.int32)
+    return torch.ldexp(G, k).to(torch.float16), k
+
+
+class SplatWideFeatures(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, means, quats, scales, opacities, viewmat, K, W, H, dtype, near, far, eps2d, check):
+        ws = _host.SplatWorkspace()
+        out, alpha, cap, _ = _host.splat_render_view(means.detach(), quats.detach(), scales.detach(), opacities.detach(),
+                                                     rows.detach(), viewmat, K, W, H, dtype=dtype, want_alpha=True, near=near,
+                                                     far=far, eps2d=eps2d, workspace=ws, check=check)
+        ctx.ws = ws
+        ctx.shape = (int(W), int(H), int(cap), int(rows.shape[0]), int(rows.shape[1]), rows.dtype)
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_alpha):
+        ws, ctx.ws = ctx.ws, None
+        W, H, cap, N, C, dtype = ctx.shape
+        if not ctx.needs_input_grad[0] or grad_out is None:
+            return (None,) * 14
+        Gq, k = quantize_gradient_map(grad_out.float())
+        total = torch.zeros((N, C), dtype=torch.float32, device=grad_out.device)
+        _host.splat_lift(Gq, N, W, H, cap, ws, total, None, sorted=True)
+        return (torch.ldexp(total, -k).to(dtype),) + (None,) * 13
+
+
+def splat_wide_features(means, quats, scales, opacities, rows, viewmat, K, W, H, *, dtype=torch.float32, near=0.01, far=1e10,
+                        eps2d=0.3, check=True):
+    """Differentiable rendering of wide per-Gaussian feature rows into one W x H view, channels-last (vp_splat_render).
+
+      means f32 [N,3], quats f32 [N,4], scales f32 [N,3], opacities f32 [N]   on the GPU; must not require grad
+      rows f16 or f32 [N,C], 1 <= C <= 4096, on the same GPU                  may require grad
+      viewmat [4,4] world-to-camera, K [3,3]                                  any device, read on the host
+
+    Returns (out ``dtype`` [H,W,C], alpha f32 [H,W]), bit-identical to voxproj_host.splat_render_view's.  Differentiable IN
+    THE ROWS ONLY: alpha is not differentiable, and a call whose geometry or opacities require grad raises instead of
+    dropping the gradient (use ``splat_gaussians`` for <= 64 channels).
+
+    The backward is the lift (vp_splat_lift with sorted = 1 on the forward's workspace), which reads a binary16 map: the
+    upstream gradient G [H,W,C] is brought to binary16 by ``quantize_gradient_map`` (s = 2^(14 - ceil(log2 max|G|)),
+    Gq = f16(G s)) and the lifted sums are divided by s.  The gradient returned is therefore the exact adjoint of the forward
+    applied to Gq / s (every element of G rounded to 11 bits relative to the map's largest, not to its own magnitude), within
+    the lift's stated accuracy.  An all-zero G gives zero gradients.  No double backward."""
+    for t, name in ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities")):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError(f"{name} requires grad, but splat_wide_features is differentiable in the rows only (detach it)")
+    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
+                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
+    _host._require_tensors((rows, "rows", (torch.float16, torch.float32)))
+    return SplatWideFeatures.apply(rows, means, quats, scales, opacities, viewmat, K, int(W), int(H), dtype, float(near),
+                                   float(far), float(eps2d), bool(check))

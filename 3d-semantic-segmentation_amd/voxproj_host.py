@@ -58,7 +58,7 @@ EXPORTS = [
     "vp_splat_geometry_backward_workspace_bytes", "vp_splat_rasterize_backward_geometry",
     "vp_splat_loss_workspace_bytes", "vp_splat_rasterize_loss", "vp_splat_loss_backward",
     "vp_label_scores_workspace_bytes", "vp_label_boundary", "vp_label_scores",
-    "vp_splat_lift_workspace_bytes", "vp_splat_lift",
+    "vp_splat_lift_workspace_bytes", "vp_splat_lift", "vp_splat_render",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -219,6 +219,11 @@ def lib():
                 L.vp_splat_lift.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_size_t, vp,
                                             ctypes.c_size_t, vp]
+            if hasattr(L, "vp_splat_render"):    # added after ABI version 4: detected by symbol (splat_render raises without it)
+                L.vp_splat_render.restype = ctypes.c_int
+                L.vp_splat_render.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int64, vp,
+                                              vp, vp, ctypes.c_size_t, vp]
             L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
             L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
             L.vp_label_boundary.restype = ctypes.c_int
@@ -1075,6 +1080,89 @@ class GaussianFeatureLifter:
         avg = torch.where(valid[:, None], self.sum / self.wsum.clamp_min(torch.finfo(torch.float32).tiny)[:, None],
                           torch.zeros((), dtype=torch.float32, device=self.device))
         return avg.to(torch.float16), self.wsum.clone(), valid
+
+
+def _render_lib():
+    L = lib()
+    if not hasattr(L, "vp_splat_render"):
+        raise VoxprojError(f"{LIB_PATH} has no vp_splat_render: rebuild it (there is no fallback)")
+    return L
+
+
+def splat_render(rows, n_gaussians, W, H, capacity, workspace, *, out=None, dtype=None, want_alpha=False, sorted=False,
+                 status=None, check=True):
+    """vp_splat_render after splat_project on ``workspace``: blend the Gaussians' wide rows into one view,
+    out[y, x, c] = sum_g w_g(p) rows[g, c], with the weights vp_splat_rasterize blends with.  rows f16 or f32 [N,C] (unit
+    channel stride, any row stride >= C), 1 <= C <= 4096.  ``out``: a f16 or f32 [H,W,C] tensor on the rows' GPU with a unit
+    channel stride and any pixel stride >= C (elements C.. of a pixel are not touched), or None for a fresh contiguous one
+    of ``dtype``.  The default ``dtype=None`` stands for torch.float16 (the fp32 sums rounded once; above 65504 they become
+    Inf): this module imports torch inside its functions, so the default cannot name torch.float16, and None also lets
+    ``out=`` alone decide the format.  ``sorted``: False sorts
+    ``capacity`` keys first (valid directly after splat_project; the workspace grows as for splat_rasterize), True reuses
+    the sort a splat_rasterize / splat_rasterize_loss / splat_lift / splat_render call with the same capacity left.
+    ``status``: optional device int32 [1], set to 1 when the device count exceeds ``capacity`` (then nothing is written).
+    With ``check`` the call reads the status word (one synchronisation) and raises VoxprojError when it is set.
+    Returns (out, alpha f32 [H,W] or None); alpha is bit-identical to splat_rasterize's."""
+    import torch
+    L = _render_lib()
+    _require(isinstance(sorted, (bool, int)) and int(sorted) in (0, 1), "sorted must be False or True")
+    _require_tensors((rows, "rows", (torch.float16, torch.float32)))
+    dev, N = rows.device, int(n_gaussians)
+    _require(rows.dim() == 2 and int(rows.shape[0]) == N, f"rows must be [{N}, C]")
+    C = int(rows.shape[1])
+    _require(1 <= C <= 4096, f"C = {C} outside [1, 4096]")
+    if N and (rows.stride(1) != 1 or (N > 1 and rows.stride(0) < C)):
+        rows = rows.contiguous()
+    if out is None:
+        out = torch.empty((int(H), int(W), C), dtype=torch.float16 if dtype is None else dtype, device=dev)
+    else:
+        _require(dtype is None or out.dtype == dtype, "out and dtype disagree")
+    _require_tensors((out, "out", (torch.float16, torch.float32)))
+    _require(out.device == dev and tuple(out.shape) == (int(H), int(W), C) and out.stride(2) == 1 and out.stride(1) >= C and
+             out.stride(0) == int(W) * out.stride(1),
+             f"out must be [{H}, {W}, {C}] on the rows' device, channels-last with one pixel stride >= C")
+    if status is None and check:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if status is not None:
+        _require_tensors((status, "status", (torch.int32,)))
+        _require(status.numel() == 1 and status.device == dev, "status must be one int32 on the rows' device")
+    if sorted:
+        nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), int(capacity)))
+        _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}, capacity {capacity}")
+        _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+                 workspace.capacity() >= nbytes, "splat_render(sorted=True) needs the workspace of a splat_rasterize call")
+        ptr = workspace.ptr()
+    else:
+        ptr = _splat_forward_workspace(workspace, N, W, H, capacity, dev)
+    alpha = torch.empty((int(H), int(W)), dtype=torch.float32, device=dev) if want_alpha else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        _check_rc(L.vp_splat_render(rows.data_ptr() if N else ptr, int(rows.dtype == torch.float16), C,
+                                    max(int(rows.stride(0)), C) if N > 1 else C, N, int(W), int(H), int(capacity), int(sorted),
+                                    out.data_ptr(), int(out.dtype == torch.float16), int(out.stride(1)), _ptr(alpha),
+                                    _ptr(status), ptr, workspace.capacity(), stream.cuda_stream))
+    if check and int(status.item()):
+        raise VoxprojError("splat_render: the intersection count outgrew the workspace (nothing written)")
+    return out, alpha
+
+
+def splat_render_view(means, quats, scales, opacities, rows, viewmat, K, W, H, *, out=None, dtype=None, want_alpha=False,
+                      near=0.01, far=1e10, eps2d=0.3, workspace=None, check=True):
+    """Render the Gaussians' wide rows into one view (vp_splat_project + vp_splat_render), as splat_features splats logits:
+    reads the 8-byte intersection count once to size the sort.  Returns (out [H,W,C], alpha f32 [H,W] or None, n_isect int,
+    n_nonfinite device int32 [1]); ``out`` / ``dtype`` as in splat_render.  With ``check`` the call synchronises once more
+    and raises VoxprojError when a Gaussian had a non-finite parameter (it is culled)."""
+    import torch
+    _render_lib()
+    _require_tensors(*((t, name, (torch.float32,)) for t, name in
+                       ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
+    _require(isinstance(rows, torch.Tensor) and rows.device == means.device, "rows and the Gaussians must be on one device")
+    ws, cap, bad, status = _splat_sized_view(means, quats, scales, opacities, viewmat, K, W, H, near, far, eps2d, workspace)
+    out, alpha = splat_render(rows, int(means.shape[0]), W, H, cap, ws, out=out, dtype=dtype, want_alpha=want_alpha,
+                              sorted=False, status=status, check=False)
+    if check:
+        _splat_view_check("splat_render_view", status, bad, "nothing written")
+    return out, alpha, cap, bad
 
 
 _check_rc = check

@@ -662,6 +662,59 @@ int vp_splat_lift(const void *feats_f16, int C, int64_t pix_stride, const float 
                   void *workspace, size_t workspace_bytes, void *lift_workspace, size_t lift_bytes, void *stream);
 
 /*
+ * Rendering wide per-Gaussian feature rows into a view: the splatter's forward for rows of up to 4096 channels, the
+ * operation vp_splat_lift is the transpose of.  Added after VP_ABI_VERSION 4 without changing it or any existing entry
+ * point; detect the function by symbol.  tests/splat_reference.py (splat64, any number of channels) states the contract in
+ * float64.
+ *
+ * The contract: with w_g(p) = a T exactly the weight vp_splat_rasterize blends Gaussian g into pixel p with, decision for
+ * decision (Gaussians in ascending (fp32 z, index) order; skipped when sigma < 0 or a < 1/255; the pixel stops before the
+ * Gaussian that would take T to <= 1e-4, which is not added),
+ *   out[p * pix_stride + c] = sum_g w_g(p) row[g, c]   for c < C,      alpha[p] = 1 - T.
+ * Elements C .. pix_stride - 1 of a pixel are never touched.  A pixel nothing reaches gets C zeros (and alpha 0): every
+ * pixel of the image is written by every accepted call.  alpha is f32 [H,W], may be NULL, and is bit-identical to the alpha
+ * vp_splat_rasterize writes from the same workspace: it is the same fp32 chain.
+ * w_g(p) is fp32 and is not rounded to binary16: the product runs on the matrix cores (v_mfma_f32_16x16x32_f16, the
+ * Gaussians of a tile's run as the k dimension, fp32 accumulators held for the whole run and written once) with the
+ * weight split into two binary16 terms that carry 22 bits of it, as vp_splat_lift stages it.  No float atomics, a fixed
+ * order of every sum: results are bit-identical from run to run.  No scratch beyond the splat workspace.
+ *
+ * The rows: binary16 (rows_is_f16 = 1) or f32 (0), row g at rows + g * row_stride elements, row_stride >= C, unit channel
+ *   stride; C in [1, 4096].  binary16 rows enter the product as they stand.  f32 rows are split into two binary16 terms as
+ *   well, after an exact power-of-two scaling chosen per channel and per batch of 32 Gaussians of a run, so that any finite
+ *   f32 value is representable and a small channel beside a large one keeps its own precision.  16-byte loads are used when
+ *   C and row_stride are multiples of 8 (binary16) or 4 (f32) and the base is 16-byte aligned; any other layout is read
+ *   element by element, with the same bits as the result.
+ *   Rows of Gaussians that are in no tile's run (culled, or with an opacity below 1/255) are never read.  Every other row
+ *   must be finite: a non-finite element in a row that is staged leaves channel c of `out` unspecified for every pixel of
+ *   the tiles the Gaussian covers (in a matrix product 0 * Inf is NaN, so pixels that never blended the Gaussian are
+ *   affected too).  Whether a row behind every pixel's stop is staged is not specified.
+ *
+ * The image: out is channels-last [H,W,C], pixel p = y W + x at out + p * pix_stride elements, pix_stride >= C, f32
+ *   (out_is_f16 = 0) or binary16 (1): the fp32 result rounded once, to nearest even (torch's .half() of the f32 image, bit
+ *   for bit); a magnitude above 65504 becomes Inf.  A [H W, C] binary16 image with its pixel stride is what
+ *   vp_query_features takes as rows.
+ *
+ * Accuracy: for finite rows, on pixels where no decision lies within the oracle's fragile band (a relative 1e-5 of a
+ *   threshold), every f32 output element is within  1e-4 * max_g |row[g, c]| + 1e-6 * max |row|  of the float64 value: the
+ *   forward's bound (tests/test_gpu_splat.py), taken per channel.  Measured: 0.01 of that bound.
+ *
+ * The workspace: as for vp_splat_lift.  The call runs after vp_splat_project on `workspace` with the same n_gaussians, W, H
+ *   and stream.  sorted = 0: the call sorts first, exactly as vp_splat_rasterize does; valid directly after
+ *   vp_splat_project.  sorted = 1: vp_splat_rasterize, vp_splat_rasterize_loss, vp_splat_lift with sorted = 0 or this call
+ *   with sorted = 0 already sorted this workspace with the same capacity; the workspace is only read.
+ *
+ * When the device count exceeds `capacity` nothing is written and *status (device i32, may be NULL; not reset) is set to
+ *   1.  Asynchronous on `stream`, no allocation, no host synchronisation, 64-bit offsets.  n_gaussians = 0 is valid (zeros).
+ *   VP_EINVAL: NULL rows or out, C outside [1, 4096], row_stride < C, pix_stride < C, sorted, rows_is_f16 or out_is_f16
+ *   neither 0 nor 1, n_gaussians or capacity outside [0, 2^31 - 1], W or H outside [1, 32768].  VP_EWORKSPACE: a workspace
+ *   that is NULL, not 256-byte aligned, or smaller than vp_splat_workspace_bytes.  A refused call writes nothing.
+ */
+int vp_splat_render(const void *rows, int rows_is_f16, int C, int64_t row_stride, int64_t n_gaussians, int W, int H,
+                    int64_t capacity, int sorted, void *out, int out_is_f16, int64_t pix_stride, float *alpha,
+                    int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Scoring label maps against ground truth: the confusion matrix of a predicted and a target label map, the boundary band
  * of a label map and the per-class boundary intersections and unions, from which the host forms mIoU, fwIoU, pixel accuracy
  * and boundary IoU.  Added after VP_ABI_VERSION 4 without changing it or any existing entry point; detect the three
