@@ -41,6 +41,7 @@
 //   vp_lift.h    lifting a 2D feature map onto the Gaussians: the splatter's transpose on the matrix cores (k_splat_lift)
 //   vp_splat_render.h  rendering wide feature rows into a view: the splatter's forward on the matrix cores (k_splat_render)
 //   vp_eval.h    scoring label maps against ground truth: confusion matrix, boundary band, boundary counts (all integers)
+//   vp_feature_loss.h  cosine / L2 loss of a rendered feature image against a 2D feature map, and its binary16 gradient image
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -75,6 +76,7 @@
 #include "vp_lift.h"
 #include "vp_splat_render.h"
 #include "vp_eval.h"
+#include "vp_feature_loss.h"
 #include "vp_project.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1069,6 +1071,106 @@ int vp_label_scores(const int32_t *pred, const int32_t *target, int W, int H, in
         (unsigned long long *)skipped, (unsigned long long *)bnd_inter, (unsigned long long *)bnd_union)
     if (P <= EVAL_LDS_P) VP_EVAL_SCORES(true); else VP_EVAL_SCORES(false);
 #undef VP_EVAL_SCORES
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The feature loss (vp_feature_loss.h).  Every check is host arithmetic and comes before the first launch.
+// ------------------------------------------------------------------------------------------------
+size_t vp_feature_loss_workspace_bytes(int W, int H)
+{
+    if (W < 1 || W > FLOSS_MAX_WH || H < 1 || H > FLOSS_MAX_WH) return 0;
+    return floss_bytes((long long)W * H);
+}
+
+static int floss_check_maps(const void *image, int image_is_f16, int64_t pix_stride, const void *target_f16, int64_t tgt_stride,
+                            int C, int W, int H, const void *workspace, size_t workspace_bytes)
+{
+    if (!image || !target_f16) return fail(VP_EINVAL, "null pointer argument (image or target_f16)");
+    if (image_is_f16 != 0 && image_is_f16 != 1) return fail(VP_EINVAL, "image_is_f16 = %d is neither 0 nor 1", image_is_f16);
+    if (C < 1 || C > FLOSS_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, FLOSS_MAX_C);
+    if (W < 1 || W > FLOSS_MAX_WH || H < 1 || H > FLOSS_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, FLOSS_MAX_WH);
+    if (pix_stride < C) return fail(VP_EINVAL, "pix_stride %lld < C = %d", (long long)pix_stride, C);
+    if (tgt_stride < C) return fail(VP_EINVAL, "tgt_stride %lld < C = %d", (long long)tgt_stride, C);
+    const size_t need = floss_bytes((long long)W * H);
+    if (!workspace || workspace_bytes < need)
+        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    return VP_OK;
+}
+
+// 16-byte loads: whole chunks of 8 channels, every pixel's row 16-byte aligned in both maps
+static bool floss_vec(const void *image, int image_is_f16, int64_t pix_stride, const void *target_f16, int64_t tgt_stride, int C)
+{
+    return C % 8 == 0 && tgt_stride % 8 == 0 && ((uintptr_t)target_f16 & 15) == 0 && pix_stride % (image_is_f16 ? 8 : 4) == 0 &&
+           ((uintptr_t)image & 15) == 0;
+}
+
+int vp_feature_loss(const void *image, int image_is_f16, int64_t pix_stride, const void *target_f16, int64_t tgt_stride, int C,
+                    int W, int H, const float *pixel_weight, const float *alpha, float min_alpha, int kind, double *loss_stats,
+                    float *pixel_loss, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!loss_stats) return fail(VP_EINVAL, "null pointer argument (loss_stats)");
+    if (kind != VP_FEATURE_LOSS_COSINE && kind != VP_FEATURE_LOSS_L2)
+        return fail(VP_EINVAL, "kind = %d is neither VP_FEATURE_LOSS_COSINE nor VP_FEATURE_LOSS_L2", kind);
+    if (int rc = floss_check_maps(image, image_is_f16, pix_stride, target_f16, tgt_stride, C, W, H, workspace, workspace_bytes))
+        return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long n = (long long)W * H, blocks = floss_blocks(n);
+    char *ws = (char *)workspace;
+    unsigned *max_bits = (unsigned *)ws;
+    double2 *sums = (double2 *)(ws + FLOSS_HEADER);
+    float4 *coef = (float4 *)(ws + FLOSS_HEADER + floss_sums_bytes(n));
+    VP_HIP(hipMemsetAsync(ws, 0, FLOSS_HEADER, stream));
+    const bool vec = floss_vec(image, image_is_f16, pix_stride, target_f16, tgt_stride, C);
+    floss_with_nch(C, [&](auto nch) {
+        splat_with_flag(vec, [&](auto v) {
+            splat_with_flag(image_is_f16 != 0, [&](auto f16) {
+                splat_with_flag(kind == VP_FEATURE_LOSS_COSINE, [&](auto cosine) {
+                    hipLaunchKernelGGL(
+                        (k_feature_loss<decltype(nch)::value, decltype(v)::value, decltype(f16)::value, decltype(cosine)::value>),
+                        dim3((unsigned)blocks), dim3(FLOSS_THREADS), 0, stream, image, (long long)pix_stride,
+                        (const _Float16 *)target_f16, (long long)tgt_stride, C, n, pixel_weight, alpha, min_alpha, coef, sums,
+                        max_bits, pixel_loss);
+                });
+            });
+        });
+    });
+    hipLaunchKernelGGL(k_feature_loss_sum, dim3(1), dim3(FLOSS_THREADS), 0, stream, (const double2 *)sums, blocks, loss_stats);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_feature_loss_gradient(const void *image, int image_is_f16, int64_t pix_stride, const void *target_f16, int64_t tgt_stride,
+                             int C, int W, int H, const double *loss_stats, int reduction, const float *grad_loss, void *grad_f16,
+                             int64_t grad_stride, int32_t *grad_exponent, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!loss_stats || !grad_f16 || !grad_exponent)
+        return fail(VP_EINVAL, "null pointer argument (loss_stats, grad_f16 or grad_exponent)");
+    if (reduction != VP_LOSS_SUM && reduction != VP_LOSS_MEAN)
+        return fail(VP_EINVAL, "reduction = %d is neither VP_LOSS_SUM nor VP_LOSS_MEAN", reduction);
+    if (grad_stride < C) return fail(VP_EINVAL, "grad_stride %lld < C = %d", (long long)grad_stride, C);
+    if (int rc = floss_check_maps(image, image_is_f16, pix_stride, target_f16, tgt_stride, C, W, H, workspace, workspace_bytes))
+        return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long n = (long long)W * H, blocks = floss_blocks(n);
+    const char *ws = (const char *)workspace;
+    const float4 *coef = (const float4 *)(ws + FLOSS_HEADER + floss_sums_bytes(n));
+    const bool vec = floss_vec(image, image_is_f16, pix_stride, target_f16, tgt_stride, C) && grad_stride % 8 == 0 &&
+                     ((uintptr_t)grad_f16 & 15) == 0;
+    floss_with_nch(C, [&](auto nch) {
+        splat_with_flag(vec, [&](auto v) {
+            splat_with_flag(image_is_f16 != 0, [&](auto f16) {
+                hipLaunchKernelGGL((k_feature_loss_gradient<decltype(nch)::value, decltype(v)::value, decltype(f16)::value>),
+                                   dim3((unsigned)blocks), dim3(FLOSS_THREADS), 0, stream, image, (long long)pix_stride,
+                                   (const _Float16 *)target_f16, (long long)tgt_stride, C, n, coef, (const unsigned *)ws, loss_stats,
+                                   (int)(reduction == VP_LOSS_MEAN), grad_loss, (_Float16 *)grad_f16, (long long)grad_stride,
+                                   (int *)grad_exponent);
+            });
+        });
+    });
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

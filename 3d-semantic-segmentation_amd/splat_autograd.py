@@ -9,7 +9,9 @@ vp_splat_rasterize_backward_geometry (one fused tile sweep for every gradient as
 double backward.  ``splat_cross_entropy`` is the fused softmax cross-entropy of the splatted logits against a per-pixel target
 map (vp_splat_rasterize_loss / vp_splat_loss_backward): no logits or gradient image crosses torch.
 ``splat_wide_features`` renders rows of up to 4096 channels channels-last (vp_splat_render) and is differentiable in the rows
-only, with the lift (vp_splat_lift) as its backward.
+only, with the lift (vp_splat_lift) as its backward.  ``splat_feature_loss`` is the fused cosine / L2 loss of that render
+against a 2D feature map (vp_feature_loss / vp_feature_loss_gradient): the gradient image is written in binary16 once, and no
+fp32 gradient image or torch reduction over an image appears on the path.
 
 Each call keeps its own SplatWorkspace until its backward has run (the backward reads the forward's sorted intersections),
 so calls from several threads or views share no state.  The workspace is freed after the backward, or with the graph.
@@ -20,7 +22,7 @@ from torch.autograd.function import once_differentiable
 import voxproj_host as _host
 
 __all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians", "splat_cross_entropy", "SplatCrossEntropy",
-           "splat_wide_features", "SplatWideFeatures", "quantize_gradient_map"]
+           "splat_wide_features", "SplatWideFeatures", "quantize_gradient_map", "splat_feature_loss", "SplatFeatureLoss"]
 
 
 class SplatFeatures(torch.autograd.Function):
@@ -260,3 +262,68 @@ def splat_wide_features(means, quats, scales, opacities, rows, viewmat, K, W, H,
     _host._require_tensors((rows, "rows", (torch.float16, torch.float32)))
     return SplatWideFeatures.apply(rows, means, quats, scales, opacities, viewmat, K, int(W), int(H), dtype, float(near),
                                    float(far), float(eps2d), bool(check))
+
+
+class SplatFeatureLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, means, quats, scales, opacities, viewmat, K, W, H, target, pixel_weight, kind, reduction, min_alpha,
+                dtype, near, far, eps2d, check):
+        ws = _host.SplatWorkspace()
+        image, alpha, cap, _ = _host.splat_render_view(means.detach(), quats.detach(), scales.detach(), opacities.detach(),
+                                                       rows.detach(), viewmat, K, W, H, dtype=dtype, want_alpha=True, near=near,
+                                                       far=far, eps2d=eps2d, workspace=ws, check=check)
+        stats, _, lws = _host.feature_loss(image, target, pixel_weight, alpha, kind=kind, min_alpha=min_alpha)
+        total, weight = stats[0], stats[1]
+        loss = torch.where(weight > 0, total / weight, torch.zeros_like(total)) if reduction == "mean" else total
+        ctx.ws, ctx.lws = ws, lws
+        ctx.maps = (image, target, stats)
+        ctx.shape = (int(W), int(H), int(cap), int(rows.shape[0]), int(rows.shape[1]), rows.dtype, reduction)
+        ctx.mark_non_differentiable(alpha)
+        return loss.float(), alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_alpha):
+        ws, ctx.ws = ctx.ws, None
+        lws, ctx.lws = ctx.lws, None
+        (image, target, stats), ctx.maps = ctx.maps, None
+        W, H, cap, N, C, dtype, reduction = ctx.shape
+        if not ctx.needs_input_grad[0] or grad_loss is None:
+            return (None,) * 19
+        # the scale stays on the device: the kernel reads it, and writes the exponent the lifted sums are divided by
+        Gq, k = _host.feature_loss_gradient(image, target, stats, lws, reduction=reduction,
+                                            grad_loss=grad_loss.float().reshape(1).contiguous())
+        total = torch.zeros((N, C), dtype=torch.float32, device=Gq.device)
+        _host.splat_lift(Gq, N, W, H, cap, ws, total, None, sorted=True)
+        return (torch.ldexp(total, -k).to(dtype),) + (None,) * 18
+
+
+def splat_feature_loss(means, quats, scales, opacities, rows, viewmat, K, W, H, target, pixel_weight=None, *, kind="cosine",
+                       reduction="mean", min_alpha=0.0, dtype=torch.float16, near=0.01, far=1e10, eps2d=0.3, check=True):
+    """The cosine or L2 loss between the wide rows rendered into one W x H view and a 2D feature map, fused
+    (include/voxproj.h states the contract of vp_feature_loss and vp_feature_loss_gradient).
+
+      means, quats, scales, opacities, rows, viewmat, K   as ``splat_wide_features``: differentiable IN THE ROWS ONLY
+      target f16 [H,W,C] on the GPU, channels-last         the view's feature map (upsample_features(keep_dtype=True))
+      pixel_weight f32 [H,W] or None                       per-pixel weights (None: 1; not > 0 excludes the pixel)
+      kind "cosine" (1 - cos per pixel) or "l2" (mean squared difference per pixel)
+      reduction "mean" (sum m l / sum m; 0 when sum m = 0) or "sum"
+      min_alpha   pixels whose rendered alpha is below it are excluded: a near-empty pixel has a tiny rendered row, and its
+                  cosine gradient, proportional to 1 / |row|, would set the one exponent the binary16 gradient map has
+      dtype       of the rendered image the loss reads: torch.float16 (half the traffic) or torch.float32
+
+    Returns (loss f32 0-dim, alpha f32 [H,W]); only the loss is differentiable.  Forward: vp_splat_render into a ``dtype``
+    image, then vp_feature_loss.  Backward: vp_feature_loss_gradient (the upstream scalar is read on the device) writes the
+    binary16 gradient map and its exponent k, vp_splat_lift (sorted = 1, on the forward's workspace) lifts it, and the sums
+    are divided by 2^k.  No double backward."""
+    _host._require(kind in _host.FEATURE_LOSS_KINDS, f"kind must be 'cosine' or 'l2', not {kind!r}")
+    _host._require(reduction in ("mean", "sum"), f"reduction must be 'mean' or 'sum', not {reduction!r}")
+    _host._require(dtype in (torch.float16, torch.float32), "dtype must be torch.float16 or torch.float32")
+    for t, name in ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities")):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError(f"{name} requires grad, but splat_feature_loss is differentiable in the rows only (detach it)")
+    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
+                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
+    _host._require_tensors((rows, "rows", (torch.float16, torch.float32)), (target, "target", (torch.float16,)))
+    return SplatFeatureLoss.apply(rows, means, quats, scales, opacities, viewmat, K, int(W), int(H), target, pixel_weight, kind,
+                                  reduction, float(min_alpha), dtype, float(near), float(far), float(eps2d), bool(check))

@@ -59,6 +59,7 @@ EXPORTS = [
     "vp_splat_loss_workspace_bytes", "vp_splat_rasterize_loss", "vp_splat_loss_backward",
     "vp_label_scores_workspace_bytes", "vp_label_boundary", "vp_label_scores",
     "vp_splat_lift_workspace_bytes", "vp_splat_lift", "vp_splat_render",
+    "vp_feature_loss_workspace_bytes", "vp_feature_loss", "vp_feature_loss_gradient",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -70,6 +71,8 @@ VP_OPT_PART_PIXELS = 6
 VP_OPT_ONE_VIEW_SPLIT = 7
 VP_LOSS_SUM = 0
 VP_LOSS_MEAN = 1
+VP_FEATURE_LOSS_COSINE = 0
+VP_FEATURE_LOSS_L2 = 1
 
 
 class VoxprojError(RuntimeError):
@@ -224,6 +227,16 @@ def lib():
                 L.vp_splat_render.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int64, vp,
                                               vp, vp, ctypes.c_size_t, vp]
+            if hasattr(L, "vp_feature_loss"):    # added after ABI version 4: detected by symbol (feature_loss raises without it)
+                L.vp_feature_loss_workspace_bytes.restype = ctypes.c_size_t
+                L.vp_feature_loss_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+                L.vp_feature_loss.restype = ctypes.c_int
+                L.vp_feature_loss.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, vp, vp, ctypes.c_float, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]
+                L.vp_feature_loss_gradient.restype = ctypes.c_int
+                L.vp_feature_loss_gradient.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int,
+                                                       ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp,
+                                                       vp, ctypes.c_size_t, vp]
             L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
             L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
             L.vp_label_boundary.restype = ctypes.c_int
@@ -1163,6 +1176,102 @@ def splat_render_view(means, quats, scales, opacities, rows, viewmat, K, W, H, *
     if check:
         _splat_view_check("splat_render_view", status, bad, "nothing written")
     return out, alpha, cap, bad
+
+
+def _feature_loss_lib():
+    L = lib()
+    if not hasattr(L, "vp_feature_loss"):
+        raise VoxprojError(f"{LIB_PATH} has no vp_feature_loss: rebuild it (there is no fallback)")
+    return L
+
+
+FEATURE_LOSS_KINDS = {"cosine": VP_FEATURE_LOSS_COSINE, "l2": VP_FEATURE_LOSS_L2}
+_LOSS_REDUCTIONS = {"sum": VP_LOSS_SUM, "mean": VP_LOSS_MEAN}
+
+
+def feature_loss_workspace_bytes(W, H):
+    """vp_feature_loss_workspace_bytes: bytes of the feature loss's workspace for a W x H view (0 when out of range).  Needs
+    no GPU."""
+    return int(_feature_loss_lib().vp_feature_loss_workspace_bytes(int(W), int(H)))
+
+
+def _feature_maps(caller, image, target):
+    """The image f16 / f32 [H,W,C] and the map f16 [H,W,C] of the feature loss on one GPU, channels-last with a unit channel
+    stride and one pixel stride >= C each (a contiguous copy otherwise): (image, target, H, W, C)."""
+    import torch
+    _require_tensors((image, "image", (torch.float16, torch.float32)), (target, "target", (torch.float16,)))
+    _require(image.dim() == 3 and image.numel() > 0, "image must be [H, W, C]")
+    H, W, C = (int(v) for v in image.shape)
+    _require(1 <= C <= 4096, f"C = {C} outside [1, 4096]")
+    _require(1 <= W <= 32768 and 1 <= H <= 32768, f"image size {W} x {H} outside [1, 32768]")
+    _require(tuple(target.shape) == (H, W, C) and target.device == image.device,
+             f"{caller}: target must be float16 [{H}, {W}, {C}] on the image's device")
+
+    def layout(t):
+        return t if t.stride(2) == 1 and t.stride(1) >= C and t.stride(0) == W * t.stride(1) else t.contiguous()
+    return layout(image), layout(target), H, W, C
+
+
+def feature_loss(image, target, pixel_weight=None, alpha=None, *, kind="cosine", min_alpha=0.0, want_pixel_loss=False,
+                 workspace=None):
+    """vp_feature_loss: the cosine or L2 loss of a rendered feature image against a 2D feature map, per pixel and summed.
+    image f16 or f32 [H,W,C] (what splat_render writes), target f16 [H,W,C] (what upsample_features(keep_dtype=True) returns
+    for an f16 map), both channels-last with a unit channel stride and any pixel stride >= C, on one GPU.  pixel_weight f32
+    [H,W] or None (1; a value that is not > 0 reads as 0), alpha f32 [H,W] or None with ``min_alpha``: a pixel is valid when
+    its weight is > 0, alpha >= min_alpha and, for "cosine", neither row is all zeros.  ``workspace``: a SplatWorkspace that
+    the call fills for feature_loss_gradient (a fresh one when None).
+    Returns (loss_stats f64 [2] = {sum m l, sum m}, pixel_loss f32 [H,W] or None, workspace); nothing is read back here."""
+    import torch
+    L = _feature_loss_lib()
+    _require(kind in FEATURE_LOSS_KINDS, f"kind must be 'cosine' or 'l2', not {kind!r}")
+    image, target, H, W, C = _feature_maps("feature_loss", image, target)
+    dev = image.device
+    pixel_weight, alpha = _splat_images(dev, (pixel_weight, "pixel_weight", (H, W), torch.float32),
+                                        (alpha, "alpha", (H, W), torch.float32))
+    ws = workspace if workspace is not None else SplatWorkspace()
+    ptr = ws.ensure(int(L.vp_feature_loss_workspace_bytes(W, H)), dev)
+    stats = torch.empty(2, dtype=torch.float64, device=dev)
+    pixel_loss = torch.empty((H, W), dtype=torch.float32, device=dev) if want_pixel_loss else None
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_feature_loss(image.data_ptr(), int(image.dtype == torch.float16), int(image.stride(1)), target.data_ptr(),
+                                    int(target.stride(1)), C, W, H, _ptr(pixel_weight), _ptr(alpha), float(min_alpha),
+                                    FEATURE_LOSS_KINDS[kind], stats.data_ptr(), _ptr(pixel_loss), ptr, ws.capacity(),
+                                    torch.cuda.current_stream(dev).cuda_stream))
+    return stats, pixel_loss, ws
+
+
+def feature_loss_gradient(image, target, loss_stats, workspace, *, reduction="mean", grad_loss=None, out=None):
+    """vp_feature_loss_gradient after feature_loss on ``workspace`` with the same image and target: the gradient image of the
+    loss in binary16 with one exponent for the map, the form splat_lift reads.  ``reduction`` "mean" (the scalar is
+    grad_loss / sum m, formed on the device from ``loss_stats``; sum m = 0 gives zeros) or "sum"; ``grad_loss``: a device f32
+    [1] (None: 1).  ``out``: a f16 [H,W,C] tensor with a unit channel stride and one pixel stride >= C (elements C.. of a
+    pixel are not touched), or None for a fresh contiguous one.
+    Returns (Gq f16 [H,W,C], k int32 [1] on the device): the gradient is Gq / 2^k; nothing is read back here."""
+    import torch
+    L = _feature_loss_lib()
+    _require(reduction in _LOSS_REDUCTIONS, f"reduction must be 'mean' or 'sum', not {reduction!r}")
+    image, target, H, W, C = _feature_maps("feature_loss_gradient", image, target)
+    dev = image.device
+    _require_tensors((loss_stats, "loss_stats", (torch.float64,)))
+    _require(loss_stats.numel() == 2 and loss_stats.device == dev and loss_stats.is_contiguous(),
+             "loss_stats must be the float64 [2] tensor feature_loss returned")
+    (grad_loss,) = _splat_images(dev, (grad_loss, "grad_loss", None, torch.float32))
+    need = int(L.vp_feature_loss_workspace_bytes(W, H))
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= need, "feature_loss_gradient needs the workspace of a feature_loss call")
+    if out is None:
+        out = torch.empty((H, W, C), dtype=torch.float16, device=dev)
+    _require_tensors((out, "out", (torch.float16,)))
+    _require(out.device == dev and tuple(out.shape) == (H, W, C) and out.stride(2) == 1 and out.stride(1) >= C and
+             out.stride(0) == W * out.stride(1), f"out must be float16 [{H}, {W}, {C}], channels-last with one pixel stride >= C")
+    k = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_feature_loss_gradient(image.data_ptr(), int(image.dtype == torch.float16), int(image.stride(1)),
+                                             target.data_ptr(), int(target.stride(1)), C, W, H, loss_stats.data_ptr(),
+                                             _LOSS_REDUCTIONS[reduction], _ptr(grad_loss), out.data_ptr(), int(out.stride(1)),
+                                             k.data_ptr(), workspace.ptr(), workspace.capacity(),
+                                             torch.cuda.current_stream(dev).cuda_stream))
+    return out, k
 
 
 _check_rc = check

@@ -761,6 +761,78 @@ int vp_label_scores(const int32_t *pred, const int32_t *target, int W, int H, in
                     int64_t *skipped, int64_t *bnd_inter, int64_t *bnd_union, void *workspace, size_t workspace_bytes,
                     void *stream);
 
+/*
+ * The loss between a rendered feature image and a 2D feature map, and its gradient image in the binary16 form vp_splat_lift
+ * reads: the two calls between vp_splat_render and vp_splat_lift that train per-Gaussian rows against feature maps.  Added
+ * after VP_ABI_VERSION 4 without changing it or any existing entry point; detect the three functions by symbol.
+ * tests/feature_loss_reference.py states the contract in float64.
+ *
+ * The maps, n = W x H pixels, pixel p = y W + x, unit channel stride, C in [1, 4096], W and H in [1, 32768], 64-bit offsets:
+ *   image       channels-last [H,W,C], binary16 (image_is_f16 = 1) or f32 (0), pixel p at image + p * pix_stride elements,
+ *               pix_stride >= C: what vp_splat_render writes.  Row o of a pixel below.
+ *   target_f16  binary16 channels-last, pixel p at target_f16 + p * tgt_stride elements, tgt_stride >= C: what
+ *               vp_upsample_features writes with dst_is_f16 and vp_splat_lift reads.  Row t of a pixel below.
+ *   pixel_weight f32 [H,W] or NULL (read as 1): m_p; a value that is not > 0 (0, -0, negative, NaN) is read as 0.
+ *   alpha       f32 [H,W] or NULL, with min_alpha: see validity.
+ *   Elements C .. stride - 1 of a pixel are never read and never written.  16-byte loads and stores are used when C and
+ *   the binary16 strides are multiples of 8, an f32 image's stride is a multiple of 4 and the bases are 16-byte aligned; any
+ *   other layout is read and written element by element and gives the same bits.
+ *
+ * Validity: pixel p is valid when m_p > 0, and alpha is NULL or alpha[p] >= min_alpha, and, for the cosine kind, the fp32
+ *   sums a = sum_c o_c^2 and b = sum_c t_c^2 are both > 0.  An invalid pixel has loss 0, weight 0 and a gradient row of exact
+ *   zeros whatever its image or map holds, NaN included (vp_splat_lift's rule for m_p = 0); when the weight or alpha
+ *   decides, its rows are not read at all.  At a valid pixel both rows must be finite.
+ *
+ * Per-pixel loss, fp32, with d = sum_c o_c t_c:
+ *   VP_FEATURE_LOSS_COSINE   l_p = 1 - d / (sqrtf(a) sqrtf(b))
+ *   VP_FEATURE_LOSS_L2       l_p = (sum_c (o_c - t_c)^2) / C
+ *   Each sum is taken per lane over the lane's channels (lane L of 64 holds channels 512 j + 8 L .. + 7, j ascending) and
+ *   then over the lanes in a butterfly: a fixed order, the same in every run and for both load paths.
+ *   loss_stats (device f64 [2]) = {sum_p m_p l_p, sum_p m_p} over the valid pixels: the fp32 values m_p l_p and m_p summed in
+ *     float64 in a fixed order (a halving tree over a workgroup's 256 consecutive pixels, then the workgroups in ascending
+ *     index).  No float atomics: bit-identical from run to run (vp_splat_rasterize_loss's rule).
+ *   pixel_loss (f32 [H,W], optional) = m_p l_p, 0 where invalid.
+ *
+ * Gradient of the image: s = grad_loss (device f32 [1], NULL = 1) for VP_LOSS_SUM, and s = (float)(grad_loss / sum m) (the
+ *   quotient in float64, sum m = loss_stats[1] read on the device) for VP_LOSS_MEAN; sum m = 0 gives s = 0, an all-zero
+ *   gradient, and the mean loss is defined as 0: exactly vp_splat_loss_backward's scalar.  For both kinds the row is a
+ *   combination of the two rows,  G[p,c] = (s m_p) (A_p t_c + B_p o_c)  in fp32 as written, with
+ *     cosine:  A = -1 / (|o| |t|),  B = cos / |o|^2  (|o| |t| = sqrtf(a) sqrtf(b), |o|^2 = a)        L2:  B = 2 / C,  A = -B.
+ *   vp_feature_loss leaves {m_p (0 when invalid), A_p, B_p, m_p max_c |A_p t_c + B_p o_c|} per pixel in the workspace and the
+ *   largest of the last over the map in its header (an integer atomic max over the bit patterns of these non-negative
+ *   floats: the result does not depend on the order of arrival).
+ *   vp_feature_loss_gradient derives the exponent on the device, by splat_autograd.quantize_gradient_map's rule:
+ *   k = 14 - ceil(log2(|s| max)), at most 126; k = 0 and an image of zeros when |s| max is 0 (or not finite).  It writes
+ *   grad_f16[p * grad_stride + c] = f16(G[p,c] 2^k) (grad_stride >= C; the product with 2^k is exact, the one rounding is the
+ *   one to binary16, to nearest even) and *grad_exponent = k (device i32).  The image is vp_splat_lift's feats_f16 as it
+ *   stands; the caller divides the lifted sums by 2^k.  The largest element lands in (2^13, 2^14] up to the last bit of
+ *   (s m) v against s (m v).
+ *   Scale hazard: with one exponent per map every element is rounded to 11 bits relative to the map's largest.  A near-empty
+ *   pixel with a tiny |o| has a cosine gradient proportional to 1 / |o| and would take the exponent, flushing the rows of
+ *   every other pixel towards zero.  alpha and min_alpha exist to exclude such pixels (pass vp_splat_render's alpha).
+ *
+ * vp_feature_loss_workspace_bytes: 256 + round256(16 ceil(W H / 256)) + round256(16 W H); 0 when W or H is outside
+ *   [1, 32768].  Needs no GPU.
+ * vp_feature_loss: writes loss_stats, pixel_loss when given, and the workspace.  Asynchronous on `stream`, no allocation,
+ *   no host synchronisation.
+ * vp_feature_loss_gradient: after vp_feature_loss on this workspace with the same image, target, C, W, H and stream (the
+ *   kind, the weights and alpha reach it through the workspace, which it only reads).  loss_stats (the forward's) is read
+ *   only for VP_LOSS_MEAN.  Writes C elements of every pixel of grad_f16, and grad_exponent.
+ * Refused on the host, no GPU needed, nothing written: VP_EINVAL for a NULL image, target_f16 or loss_stats (and grad_f16 or
+ *   grad_exponent), an unknown kind, reduction or image_is_f16, C, W or H out of range, a stride < C; VP_EWORKSPACE for a
+ *   workspace that is NULL, not 256-byte aligned or smaller than vp_feature_loss_workspace_bytes.
+ */
+#define VP_FEATURE_LOSS_COSINE 0
+#define VP_FEATURE_LOSS_L2     1
+size_t vp_feature_loss_workspace_bytes(int W, int H);
+int vp_feature_loss(const void *image, int image_is_f16, int64_t pix_stride, const void *target_f16, int64_t tgt_stride, int C,
+                    int W, int H, const float *pixel_weight, const float *alpha, float min_alpha, int kind, double *loss_stats,
+                    float *pixel_loss, void *workspace, size_t workspace_bytes, void *stream);
+int vp_feature_loss_gradient(const void *image, int image_is_f16, int64_t pix_stride, const void *target_f16,
+                             int64_t tgt_stride, int C, int W, int H, const double *loss_stats, int reduction,
+                             const float *grad_loss, void *grad_f16, int64_t grad_stride, int32_t *grad_exponent,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
