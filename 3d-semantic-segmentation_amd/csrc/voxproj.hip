@@ -42,6 +42,7 @@
 //   vp_splat_render.h  rendering wide feature rows into a view: the splatter's forward on the matrix cores (k_splat_render)
 //   vp_eval.h    scoring label maps against ground truth: confusion matrix, boundary band, boundary counts (all integers)
 //   vp_feature_loss.h  cosine / L2 loss of a rendered feature image against a 2D feature map, and its binary16 gradient image
+//   vp_proto_loss.h    prototype-contrastive loss of a rendered identity image against an instance mask, and its gradient image
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -77,6 +78,7 @@
 #include "vp_splat_render.h"
 #include "vp_eval.h"
 #include "vp_feature_loss.h"
+#include "vp_proto_loss.h"
 #include "vp_project.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1170,6 +1172,101 @@ int vp_feature_loss_gradient(const void *image, int image_is_f16, int64_t pix_st
                                    (int *)grad_exponent);
             });
         });
+    });
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The prototype-contrastive loss (vp_proto_loss.h).  Every check is host arithmetic and comes before the first launch.
+// ------------------------------------------------------------------------------------------------
+size_t vp_proto_contrast_workspace_bytes(int D, int W, int H)
+{
+    if (D < 1 || D > PROTO_MAX_D || W < 1 || W > PROTO_MAX_WH || H < 1 || H > PROTO_MAX_WH) return 0;
+    return proto_carve(nullptr, D, (long long)W * H).bytes;
+}
+
+static int proto_check(const float *image, int D, int W, int H, const int32_t *ids, const void *workspace, size_t workspace_bytes)
+{
+    if (!image || !ids) return fail(VP_EINVAL, "null pointer argument (image or ids)");
+    if (D < 1 || D > PROTO_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, PROTO_MAX_D);
+    if (W < 1 || W > PROTO_MAX_WH || H < 1 || H > PROTO_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, PROTO_MAX_WH);
+    const size_t need = vp_proto_contrast_workspace_bytes(D, W, H);
+    if (!workspace || workspace_bytes < need)
+        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    return VP_OK;
+}
+
+int vp_proto_contrast(const float *image, int D, int W, int H, const int32_t *ids, const int32_t *count, int ignore_id,
+                      int min_count, float phi_scale, float phi_min, float phi_max, double *stats, float *pixel_loss,
+                      float *own_prob, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!stats) return fail(VP_EINVAL, "null pointer argument (stats)");
+    if (min_count < 0) return fail(VP_EINVAL, "min_count = %d is negative", min_count);
+    if (!std::isfinite(phi_scale) || !std::isfinite(phi_min) || !std::isfinite(phi_max) || !(phi_min > 0.0f) || phi_max < phi_min)
+        return fail(VP_EINVAL, "temperatures: need finite phi_scale = %g and 0 < phi_min = %g <= phi_max = %g", (double)phi_scale,
+                    (double)phi_min, (double)phi_max);
+    if (int rc = proto_check(image, D, W, H, ids, workspace, workspace_bytes)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long n = (long long)W * H;
+    const int G = proto_grid(n);
+    const ProtoWs w = proto_carve(workspace, D, n);
+    const size_t lds = (size_t)PROTO_IDS * D * sizeof(float);
+    hipError_t attr_rc = hipSuccess;
+    proto_with_dp(D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        // with the static tiles the two accumulating kernels pass 64 KiB of the CU's 160 at large D: said once per variant
+        static hipError_t lds_attr = [] {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_proto_sums<DP>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, PROTO_IDS * DP * (int)sizeof(float));
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_proto_loss<DP>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, PROTO_IDS * DP * (int)sizeof(float));
+            return e;
+        }();
+        if (lds_attr != hipSuccess) {
+            attr_rc = lds_attr;
+            return;
+        }
+        hipLaunchKernelGGL(k_proto_sums<DP>, dim3(G), dim3(PROTO_THREADS), lds, stream, image, D, n, ids, count, ignore_id,
+                           w.s_part, w.cnt_part, w.norm_part);
+        hipLaunchKernelGGL(k_proto_means, dim3(PROTO_IDS), dim3(PROTO_COMBINE), 0, stream, D, G, (const float *)w.s_part,
+                           (const unsigned long long *)w.cnt_part, (const double *)w.norm_part, w.n_id, w.u_id, stats);
+        hipLaunchKernelGGL(k_proto_spread<DP>, dim3(G), dim3(PROTO_THREADS), 0, stream, image, D, n, ids, count, ignore_id,
+                           min_count, (const unsigned long long *)w.n_id, (const float *)w.u_id, w.a_part);
+        hipLaunchKernelGGL(k_proto_temps, dim3(1), dim3(PROTO_COMBINE), 0, stream, D, G, min_count, phi_scale, phi_min, phi_max,
+                           (const float *)w.a_part, (const unsigned long long *)w.n_id, (const float *)w.u_id, w.hdr, w.slot_of_id,
+                           w.inv_phi, w.n_slot, w.utab, stats);
+        hipLaunchKernelGGL(k_proto_loss<DP>, dim3(G), dim3(PROTO_THREADS), lds, stream, image, D, n, ids, count,
+                           (const ProtoHeader *)w.hdr, (const int *)w.slot_of_id, (const float *)w.utab, pixel_loss, own_prob,
+                           w.s_part, w.loss_part);
+        hipLaunchKernelGGL(k_proto_protos, dim3(PROTO_IDS), dim3(PROTO_COMBINE), 0, stream, D, G, (const ProtoHeader *)w.hdr,
+                           (const float *)w.s_part, (const double *)w.loss_part, (const float *)w.inv_phi,
+                           (const float *)w.n_slot, w.gn, stats);
+    });
+    VP_HIP(attr_rc);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_proto_contrast_gradient(const float *image, int D, int W, int H, const int32_t *ids, const int32_t *count,
+                               float weight_contrast, float weight_norm, const float *grad_loss, float *grad_image,
+                               void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!grad_image) return fail(VP_EINVAL, "null pointer argument (grad_image)");
+    if (!std::isfinite(weight_contrast) || !std::isfinite(weight_norm))
+        return fail(VP_EINVAL, "weights %g and %g must be finite", (double)weight_contrast, (double)weight_norm);
+    if (int rc = proto_check(image, D, W, H, ids, workspace, workspace_bytes)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long n = (long long)W * H;
+    const ProtoWs w = proto_carve(workspace, D, n);
+    proto_with_dp(D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        hipLaunchKernelGGL(k_proto_gradient<DP>, dim3((unsigned)proto_tiles(n)), dim3(PROTO_THREADS), 0, stream, image, D, n, ids,
+                           count, (const ProtoHeader *)w.hdr, (const int *)w.slot_of_id, (const float *)w.utab,
+                           (const float *)w.gn, weight_contrast, weight_norm, grad_loss, grad_image);
     });
     VP_HIP(hipGetLastError());
     return VP_OK;

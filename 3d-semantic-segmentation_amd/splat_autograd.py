@@ -11,7 +11,9 @@ map (vp_splat_rasterize_loss / vp_splat_loss_backward): no logits or gradient im
 ``splat_wide_features`` renders rows of up to 4096 channels channels-last (vp_splat_render) and is differentiable in the rows
 only, with the lift (vp_splat_lift) as its backward.  ``splat_feature_loss`` is the fused cosine / L2 loss of that render
 against a 2D feature map (vp_feature_loss / vp_feature_loss_gradient): the gradient image is written in binary16 once, and no
-fp32 gradient image or torch reduction over an image appears on the path.
+fp32 gradient image or torch reduction over an image appears on the path.  ``splat_contrastive`` is the prototype-contrastive
+loss of the splatted identity features against one view's instance mask (vp_proto_contrast / vp_proto_contrast_gradient
+between the rasterizer and its backward): no torch pass over an image.
 
 Each call keeps its own SplatWorkspace until its backward has run (the backward reads the forward's sorted intersections),
 so calls from several threads or views share no state.  The workspace is freed after the backward, or with the graph.
@@ -22,7 +24,8 @@ from torch.autograd.function import once_differentiable
 import voxproj_host as _host
 
 __all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians", "splat_cross_entropy", "SplatCrossEntropy",
-           "splat_wide_features", "SplatWideFeatures", "quantize_gradient_map", "splat_feature_loss", "SplatFeatureLoss"]
+           "splat_wide_features", "SplatWideFeatures", "quantize_gradient_map", "splat_feature_loss", "SplatFeatureLoss",
+           "splat_contrastive", "SplatContrastive"]
 
 
 class SplatFeatures(torch.autograd.Function):
@@ -327,3 +330,74 @@ def splat_feature_loss(means, quats, scales, opacities, rows, viewmat, K, W, H, 
     _host._require_tensors((rows, "rows", (torch.float16, torch.float32)), (target, "target", (torch.float16,)))
     return SplatFeatureLoss.apply(rows, means, quats, scales, opacities, viewmat, K, int(W), int(H), target, pixel_weight, kind,
                                   reduction, float(min_alpha), dtype, float(near), float(far), float(eps2d), bool(check))
+
+
+class SplatContrastive(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, quats, scales, opacities, features, viewmat, K, W, H, ids, count, weights, proto, near, far, eps2d,
+                check):
+        ws = _host.SplatWorkspace()
+        m, q, s, f = means.detach(), quats.detach(), scales.detach(), features.detach()
+        r = _host.splat_features(m, q, s, opacities.detach(), f, viewmat, K, W, H, want_logits=True, want_alpha=False,
+                                 want_confidence=False, near=near, far=far, eps2d=eps2d, workspace=ws, check=check)
+        stats, _, _, lws = _host.proto_contrast(r.logits, ids, count, **proto)
+        # four numbers, on the device: weight_contrast (sum m l) / K (0 when K = 0) + weight_norm (sum (r - 1)^2) / (W H)
+        contrast = torch.where(stats[1] > 0, stats[0] / stats[1].clamp(min=1.0), torch.zeros_like(stats[0]))
+        loss = weights[0] * contrast + weights[1] * stats[2] / float(int(W) * int(H))
+        ctx.ws, ctx.lws = ws, lws
+        ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect), weights)
+        ctx.maps = (r.logits, ids, count)
+        ctx.save_for_backward(m, q, s, f)
+        ctx.mark_non_differentiable(stats)
+        return loss.float(), stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        m, q, s, f = ctx.saved_tensors
+        ws, ctx.ws = ctx.ws, None
+        lws, ctx.lws = ctx.lws, None
+        (image, ids, count), ctx.maps = ctx.maps, None
+        viewmat, K, W, H, eps2d, cap, weights = ctx.view
+        want_m, want_q, want_s, want_o, want_f = ctx.needs_input_grad[:5]
+        g = dict(means=None, quats=None, scales=None, opacities=None, features=None)
+        if want_m or want_q or want_s or want_o or want_f:
+            # the scale stays on the device: the kernel reads it
+            G = _host.proto_contrast_gradient(image, ids, count, lws, weight_contrast=weights[0], weight_norm=weights[1],
+                                              grad_loss=grad_loss.float().reshape(1).contiguous())
+            if want_m or want_q or want_s:
+                g = _host.splat_rasterize_backward_geometry(m, q, s, f, viewmat, K, W, H, cap, ws, G, None, eps2d=eps2d,
+                                                            want_means=want_m, want_quats=want_q, want_scales=want_s,
+                                                            want_features=want_f, want_opacities=want_o)
+            else:
+                g["features"], g["opacities"] = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws, grad_logits=G,
+                                                                               grad_alpha=None, want_features=want_f,
+                                                                               want_opacities=want_o)
+        return (g["means"], g["quats"], g["scales"], g["opacities"], g["features"]) + (None,) * 12
+
+
+def splat_contrastive(means, quats, scales, opacities, features, viewmat, K, W, H, ids, count=None, *, weight_contrast=1.0,
+                      weight_norm=1.0, min_count=20, ignore_id=-1, phi_scale=10.0, phi_min=0.5, phi_max=1.0, near=0.01, far=1e10,
+                      eps2d=0.3, check=True):
+    """The prototype-contrastive loss of the splatted identity features of one W x H view against the view's instance mask,
+    whose ids mean nothing in any other view (include/voxproj.h states the contract of vp_proto_contrast).
+
+      means, quats, scales, opacities, features, viewmat, K   as ``splat_gaussians``; any of the five tensors may require grad
+      ids int32 [H,W] on the GPU      the mask; ids outside [0, 256) and ``ignore_id`` are left out
+      count int32 [H,W] or None       how many times each pixel was drawn (torch.bincount of a draw with replacement); None: once
+      min_count, phi_*                an id takes part with more than min_count drawn pixels; its temperature is
+                                      clip(phi_scale spread, phi_min, phi_max)
+
+    Returns (loss f32 0-dim = weight_contrast (sum m l) / K + weight_norm mean (|f| - 1)^2, stats f64 [4] = {sum m l, K,
+    sum (|f| - 1)^2, sum m}, detached).  Forward: vp_splat_project, vp_splat_rasterize (the image is kept), vp_proto_contrast.
+    Backward: vp_proto_contrast_gradient writes the gradient image (the upstream scalar is read on the device), then
+    vp_splat_rasterize_backward_geometry, or vp_splat_rasterize_backward when no geometry gradient is asked for.  No torch
+    pass over an image, no double backward, no gradient for the camera."""
+    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
+                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
+                              (features, "features"))))
+    weights = (float(weight_contrast), float(weight_norm))
+    proto = dict(ignore_id=int(ignore_id), min_count=int(min_count), phi_scale=float(phi_scale), phi_min=float(phi_min),
+                 phi_max=float(phi_max))
+    return SplatContrastive.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), ids, count, weights,
+                                  proto, float(near), float(far), float(eps2d), bool(check))

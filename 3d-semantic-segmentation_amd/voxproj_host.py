@@ -60,6 +60,7 @@ EXPORTS = [
     "vp_label_scores_workspace_bytes", "vp_label_boundary", "vp_label_scores",
     "vp_splat_lift_workspace_bytes", "vp_splat_lift", "vp_splat_render",
     "vp_feature_loss_workspace_bytes", "vp_feature_loss", "vp_feature_loss_gradient",
+    "vp_proto_contrast_workspace_bytes", "vp_proto_contrast", "vp_proto_contrast_gradient",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -237,6 +238,15 @@ def lib():
                 L.vp_feature_loss_gradient.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int,
                                                        ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp,
                                                        vp, ctypes.c_size_t, vp]
+            if hasattr(L, "vp_proto_contrast"):  # added after ABI version 4: detected by symbol (proto_contrast raises without it)
+                L.vp_proto_contrast_workspace_bytes.restype = ctypes.c_size_t
+                L.vp_proto_contrast_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+                L.vp_proto_contrast.restype = ctypes.c_int
+                L.vp_proto_contrast.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, vp]
+                L.vp_proto_contrast_gradient.restype = ctypes.c_int
+                L.vp_proto_contrast_gradient.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_float,
+                                                         ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]
             L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
             L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
             L.vp_label_boundary.restype = ctypes.c_int
@@ -1272,6 +1282,84 @@ def feature_loss_gradient(image, target, loss_stats, workspace, *, reduction="me
                                              k.data_ptr(), workspace.ptr(), workspace.capacity(),
                                              torch.cuda.current_stream(dev).cuda_stream))
     return out, k
+
+
+def _proto_lib():
+    L = lib()
+    if not hasattr(L, "vp_proto_contrast"):
+        raise VoxprojError(f"{LIB_PATH} has no vp_proto_contrast: rebuild it (there is no fallback)")
+    return L
+
+
+VP_PROTO_MAX_IDS = 256
+
+
+def proto_contrast_workspace_bytes(D, W, H):
+    """vp_proto_contrast_workspace_bytes: bytes of the prototype-contrastive loss's workspace for a D-channel W x H image
+    (0 when out of range).  Needs no GPU."""
+    return int(_proto_lib().vp_proto_contrast_workspace_bytes(int(D), int(W), int(H)))
+
+
+def _proto_maps(caller, image, ids, count):
+    """The image f32 [D,H,W], the mask i32 [H,W] and the multiplicity map i32 [H,W] or None, contiguous on one GPU."""
+    import torch
+    _require_tensors((image, "image", (torch.float32,)), (ids, "ids", (torch.int32,)))
+    _require(image.dim() == 3 and image.numel() > 0, "image must be [D, H, W]")
+    D, H, W = (int(v) for v in image.shape)
+    _require(1 <= D <= 64, f"D = {D} outside [1, 64]")
+    _require(1 <= W <= 32768 and 1 <= H <= 32768, f"image size {W} x {H} outside [1, 32768]")
+    dev = image.device
+    _require(tuple(ids.shape) == (H, W) and ids.device == dev, f"{caller}: ids must be int32 [{H}, {W}] on the image's device")
+    (count,) = _splat_images(dev, (count, "count", (H, W), torch.int32))
+    return image.contiguous(), ids.contiguous(), count, D, H, W
+
+
+def proto_contrast(image, ids, count=None, *, ignore_id=-1, min_count=20, phi_scale=10.0, phi_min=0.5, phi_max=1.0,
+                   want_pixel_loss=False, want_own_prob=False, workspace=None):
+    """vp_proto_contrast: the prototype-contrastive loss of a rendered identity image against one view's instance mask.
+    image f32 [D,H,W] (splat_features' logits), ids int32 [H,W], count int32 [H,W] or None (every pixel drawn once), on one
+    GPU.  The defaults are the loss's parameters; phi_scale 0.1, phi_min 0.1, min_count 0 are the confidence map's.
+    ``workspace``: a SplatWorkspace the call fills for proto_contrast_gradient (a fresh one when None).
+    Returns (stats f64 [4] = {sum m l, K, sum (r - 1)^2, sum m}, pixel_loss f32 [H,W] or None, own_prob f32 [H,W] or None,
+    workspace); nothing is read back here."""
+    import torch
+    L = _proto_lib()
+    image, ids, count, D, H, W = _proto_maps("proto_contrast", image, ids, count)
+    dev = image.device
+    ws = workspace if workspace is not None else SplatWorkspace()
+    ptr = ws.ensure(int(L.vp_proto_contrast_workspace_bytes(D, W, H)), dev)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    pixel_loss = torch.empty((H, W), dtype=torch.float32, device=dev) if want_pixel_loss else None
+    own_prob = torch.empty((H, W), dtype=torch.float32, device=dev) if want_own_prob else None
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_proto_contrast(image.data_ptr(), D, W, H, ids.data_ptr(), _ptr(count), int(ignore_id), int(min_count),
+                                      float(phi_scale), float(phi_min), float(phi_max), stats.data_ptr(), _ptr(pixel_loss),
+                                      _ptr(own_prob), ptr, ws.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+    return stats, pixel_loss, own_prob, ws
+
+
+def proto_contrast_gradient(image, ids, count, workspace, *, weight_contrast=1.0, weight_norm=1.0, grad_loss=None, out=None):
+    """vp_proto_contrast_gradient after proto_contrast on ``workspace`` with the same image, ids and count: the gradient
+    image f32 [D,H,W] of  weight_contrast (sum m l) / K + weight_norm (sum (r - 1)^2) / (W H), times ``grad_loss`` (a device
+    f32 [1]; None: 1).  ``out``: a contiguous f32 [D,H,W] tensor, or None for a fresh one.  Nothing is read back here."""
+    import torch
+    L = _proto_lib()
+    image, ids, count, D, H, W = _proto_maps("proto_contrast_gradient", image, ids, count)
+    dev = image.device
+    (grad_loss,) = _splat_images(dev, (grad_loss, "grad_loss", None, torch.float32))
+    need = int(L.vp_proto_contrast_workspace_bytes(D, W, H))
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= need, "proto_contrast_gradient needs the workspace of a proto_contrast call")
+    if out is None:
+        out = torch.empty((D, H, W), dtype=torch.float32, device=dev)
+    _require_tensors((out, "out", (torch.float32,)))
+    _require(out.device == dev and tuple(out.shape) == (D, H, W) and out.is_contiguous(),
+             f"out must be a contiguous float32 [{D}, {H}, {W}] tensor on the image's device")
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_proto_contrast_gradient(image.data_ptr(), D, W, H, ids.data_ptr(), _ptr(count), float(weight_contrast),
+                                               float(weight_norm), _ptr(grad_loss), out.data_ptr(), workspace.ptr(),
+                                               workspace.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+    return out
 
 
 _check_rc = check

@@ -833,6 +833,56 @@ int vp_feature_loss_gradient(const void *image, int image_is_f16, int64_t pix_st
                              const float *grad_loss, void *grad_f16, int64_t grad_stride, int32_t *grad_exponent,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The prototype-contrastive loss between a rendered identity image and one view's instance mask, and its gradient image:
+ * the two calls between vp_splat_rasterize and vp_splat_rasterize_backward(_geometry) that train per-Gaussian identity rows
+ * against masks whose ids mean nothing across views.  Added after VP_ABI_VERSION 4 without changing it or any existing
+ * entry point; detect the three functions by symbol.  tests/proto_loss_reference.py states the contract in float64.
+ *
+ *   image, grad_image  f32 planar [D,H,W], contiguous: vp_splat_rasterize's logits and the backward's grad_logits as they
+ *               stand.  D in [1, 64], W and H in [1, 32768], 64-bit offsets.  Row f_p of pixel p = y W + x below.
+ *   ids         i32 [H,W]: the mask.        count  i32 [H,W] or NULL (read as 1): m_p, how many times pixel p was drawn.
+ *
+ * Samples: pixel p is a sample when m_p > 0, 0 <= ids[p] < VP_PROTO_MAX_IDS and ids[p] != ignore_id (-1: none).  Id k is
+ *   active when n_k = sum_{p in k} m_p > min_count (integers); a sample of an inactive id is not valid; K = active ids.
+ * Per pixel, fp32:  r_p = sqrtf(sum_c f_pc^2),  s_p = f_p / (r_p + 1e-6)  (the divisor is a constant for the gradient).
+ * Per active id:    u_k = (sum_{p in k} m_p s_p) / n_k,
+ *                   phi_k = clip(phi_scale sum_{p in k} m_p |s_p - u_k| / (n_k logf(n_k + 10)), phi_min, phi_max), a constant
+ *                   for the gradient.
+ * Loss:  z_pk = s_p . (u_k / phi_k) over the active k, c = the pixel's own id,  l_p = logf(sum_k expf(z_pk) + 1e-6) - z_pc,
+ *   own_prob[p] = expf(z_pc) / (sum_k expf(z_pk) + 1e-6),  pixel_loss[p] = m_p l_p  (both optional, both exactly 0 at a pixel
+ *   that is not a valid sample).
+ *   stats (device f64 [4]) = {sum_p m_p l_p, K, sum_p (r_p - 1)^2 over ALL W H pixels, sum m_p over the valid samples}.
+ * Order: no float atomics.  Every sum over pixels runs over tiles of 256 consecutive pixels; workgroup b of
+ *   G = min(tiles, 768) takes tiles b, b + G, ..., adds a tile's samples in ascending pixel order, and the workgroups' sums
+ *   are added in one fixed shape: 16 chunks of 48 consecutive workgroups, each in ascending b, then the 16 chunk sums in
+ *   ascending order (a workgroup at or beyond G adds nothing).  The two statistics are fp32 terms added in float64: a halving tree over the
+ *   workgroup's 256 threads, then a halving tree over 1024 slots, one per workgroup.  Every output is bit-identical from run to run.
+ * Gradient of  L = weight_contrast (sum_p m_p l_p) / K + weight_norm (sum_p (r_p - 1)^2) / (W H), times grad_loss (device f32
+ *   [1], NULL = 1), through the prototypes:  with P_pk the softmax above (its 1e-6 included), q_pk = P_pk - [k = c_p] at a
+ *   valid sample and 0 elsewhere, g_k = (sum_p m_p q_pk s_p) / phi_k,
+ *     dL/ds_p = (weight_contrast / K) m_p (sum_k q_pk u_k / phi_k + g_c / n_c),
+ *     grad_image[c,p] = grad_loss (dL/ds_pc / (r_p + 1e-6) + (weight_norm / (W H)) 2 (r_p - 1) f_pc / r_p),
+ *   the norm term 0 where r_p = 0, the contrastive part exactly 0 when K = 0.  Every element of grad_image is written.
+ *
+ * vp_proto_contrast_workspace_bytes: host arithmetic, 0 when D, W or H is out of range.  At most 18 KiB + 3 KiB D + 768 (3 KiB + 1 KiB D).
+ * vp_proto_contrast: three reads of the image (the second and third of valid samples' rows only).  Leaves u / phi, g / n, K
+ *   and the active list in the workspace.  Asynchronous on `stream`, no allocation, no host synchronisation.
+ * vp_proto_contrast_gradient: after vp_proto_contrast on this workspace with the same image, D, W, H, ids, count and
+ *   stream; it only reads the workspace (ignore_id and min_count reach it through the active list).  One read, one write.
+ * Refused on the host, no GPU needed, nothing written: VP_EINVAL for a NULL image, ids, stats or grad_image, D, W or H out
+ *   of range, min_count < 0, a non-finite phi_*, phi_min <= 0, phi_max < phi_min, a non-finite weight; VP_EWORKSPACE for a
+ *   workspace that is NULL, not 256-byte aligned or smaller than vp_proto_contrast_workspace_bytes.
+ */
+#define VP_PROTO_MAX_IDS 256
+size_t vp_proto_contrast_workspace_bytes(int D, int W, int H);
+int vp_proto_contrast(const float *image, int D, int W, int H, const int32_t *ids, const int32_t *count, int ignore_id,
+                      int min_count, float phi_scale, float phi_min, float phi_max, double *stats, float *pixel_loss,
+                      float *own_prob, void *workspace, size_t workspace_bytes, void *stream);
+int vp_proto_contrast_gradient(const float *image, int D, int W, int H, const int32_t *ids, const int32_t *count,
+                               float weight_contrast, float weight_norm, const float *grad_loss, float *grad_image,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
