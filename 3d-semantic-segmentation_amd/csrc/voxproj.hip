@@ -43,6 +43,7 @@
 //   vp_eval.h    scoring label maps against ground truth: confusion matrix, boundary band, boundary counts (all integers)
 //   vp_feature_loss.h  cosine / L2 loss of a rendered feature image against a 2D feature map, and its binary16 gradient image
 //   vp_proto_loss.h    prototype-contrastive loss of a rendered identity image against an instance mask, and its gradient image
+//   vp_codebook.h      a code book of global instance labels: the id-by-code score matrix, the loss and its gradients on the matrix cores
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -79,6 +80,7 @@
 #include "vp_eval.h"
 #include "vp_feature_loss.h"
 #include "vp_proto_loss.h"
+#include "vp_codebook.h"
 #include "vp_project.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1268,6 +1270,91 @@ int vp_proto_contrast_gradient(const float *image, int D, int W, int H, const in
                            count, (const ProtoHeader *)w.hdr, (const int *)w.slot_of_id, (const float *)w.utab,
                            (const float *)w.gn, weight_contrast, weight_norm, grad_loss, grad_image);
     });
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The code book of global instance labels (vp_codebook.h).  Every check is host arithmetic and comes before the first launch.
+// ------------------------------------------------------------------------------------------------
+size_t vp_codebook_workspace_bytes(int D, int K, int W, int H)
+{
+    if (D < 1 || D > CB_MAX_D || K < 1 || K > CB_MAX_K || W < 1 || W > CB_MAX_WH || H < 1 || H > CB_MAX_WH) return 0;
+    // sized for min(tiles, 256) workgroups, which the plan never exceeds: the size does not shrink when the image grows
+    return cb_carve(nullptr, D, K, (int)std::min<long long>(cb_plan(W, H).tiles, CB_GRID)).bytes;
+}
+
+static int cb_check(const float *image, int D, int W, int H, const int32_t *ids, const float *codebook, int K,
+                    const void *workspace, size_t workspace_bytes)
+{
+    if (!image || !ids || !codebook) return fail(VP_EINVAL, "null pointer argument (image, ids or codebook)");
+    if (D < 1 || D > CB_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, CB_MAX_D);
+    if (K < 1 || K > CB_MAX_K) return fail(VP_EINVAL, "K = %d outside [1, %d]", K, CB_MAX_K);
+    if (W < 1 || W > CB_MAX_WH || H < 1 || H > CB_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, CB_MAX_WH);
+    const size_t need = vp_codebook_workspace_bytes(D, K, W, H);
+    if (!workspace || workspace_bytes < need)
+        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    return VP_OK;
+}
+
+int vp_codebook_assoc(const float *image, int D, int W, int H, const int32_t *ids, int ignore_id, const float *codebook, int K,
+                      double *score, int32_t *id_pixels, int32_t *pred, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!score || !id_pixels) return fail(VP_EINVAL, "null pointer argument (score or id_pixels)");
+    if (int rc = cb_check(image, D, W, H, ids, codebook, K, workspace, workspace_bytes)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const CbPlan plan = cb_plan(W, H);
+    const CbWs w = cb_carve(workspace, D, K, plan.G);
+    hipError_t attr_rc = hipSuccess;
+    cb_with_dp(D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        // code book and probability tile pass 64 KiB of the CU's 160: said once per variant
+        static hipError_t lds_attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_codebook_assoc<DP>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)cb_assoc_lds(DP, CB_MAX_K));
+        if (lds_attr != hipSuccess) {
+            attr_rc = lds_attr;
+            return;
+        }
+        hipLaunchKernelGGL(k_codebook_assoc<DP>, dim3(plan.G), dim3(CB_THREADS), cb_assoc_lds(DP, K), stream, image, D, plan.n, ids,
+                           ignore_id, codebook, K, plan.tiles, plan.per, w.tab, w.touched, w.cnt, pred);
+        hipLaunchKernelGGL(k_codebook_score, dim3(CB_IDS), dim3(CB_THREADS), 0, stream, K, plan.G, (const float *)w.tab,
+                           (const int *)w.touched, (const int *)w.cnt, score, id_pixels);
+    });
+    VP_HIP(attr_rc);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_codebook_loss(const float *image, int D, int W, int H, const int32_t *ids, int ignore_id, const float *conf,
+                     float conf_min, const float *codebook, int K, const int32_t *assign, double *stats, float *grad_cls,
+                     float *grad_cluster, float *pixel_loss, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!assign || !stats || !grad_cls || !grad_cluster)
+        return fail(VP_EINVAL, "null pointer argument (assign, stats, grad_cls or grad_cluster)");
+    if (!std::isfinite(conf_min)) return fail(VP_EINVAL, "conf_min = %g must be finite", (double)conf_min);
+    if (int rc = cb_check(image, D, W, H, ids, codebook, K, workspace, workspace_bytes)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const CbPlan plan = cb_plan(W, H);
+    const CbWs w = cb_carve(workspace, D, K, plan.G);
+    hipError_t attr_rc = hipSuccess;
+    cb_with_dp(D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        static hipError_t lds_attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_codebook_loss<DP>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)cb_loss_lds(DP, CB_MAX_K));
+        if (lds_attr != hipSuccess) {
+            attr_rc = lds_attr;
+            return;
+        }
+        hipLaunchKernelGGL(k_codebook_loss<DP>, dim3(plan.G), dim3(CB_THREADS), cb_loss_lds(DP, K), stream, image, D, plan.n, ids,
+                           ignore_id, conf, conf_min, codebook, K, assign, plan.tiles, plan.per, w.gcls, w.gclu, w.dpart,
+                           pixel_loss);
+        hipLaunchKernelGGL(k_codebook_finish, dim3((K * D + CB_THREADS - 1) / CB_THREADS + 1), dim3(CB_THREADS), 0, stream, K * D,
+                           plan.G, (const float *)w.gcls, (const float *)w.gclu, (const double *)w.dpart, grad_cls, grad_cluster,
+                           stats);
+    });
+    VP_HIP(attr_rc);
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

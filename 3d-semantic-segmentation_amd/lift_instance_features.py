@@ -25,8 +25,9 @@ byte-identical tensors.
 
 Output (--out): LIFTED.pt's schema -- xyz f32 [N,3], avg_feats f16 [N,dim] (the trained rows), weight f32 [N] (ones),
 views -- which ``render_gaussian_features.py`` and ``query_voxel_features.py gaussians --gauss_feats`` read unchanged.
-Not part of this tool: a codebook of global labels, the linear assignment of view ids to it and a clustering loss.  Runs on
-the GPU only; there is no CPU path.
+The second half of the method -- a code book of global labels, the linear assignment of every view's ids to it and the
+clustering loss -- is ``associate_instances.py``, which trains the code book on the rows this tool wrote and gives one
+instance id per Gaussian and id maps that mean the same thing in every view.  Runs on the GPU only; there is no CPU path.
 """
 import argparse
 

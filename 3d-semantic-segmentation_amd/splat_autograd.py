@@ -18,6 +18,8 @@ between the rasterizer and its backward): no torch pass over an image.
 Each call keeps its own SplatWorkspace until its backward has run (the backward reads the forward's sorted intersections),
 so calls from several threads or views share no state.  The workspace is freed after the backward, or with the graph.
 """
+import math
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -401,3 +403,54 @@ def splat_contrastive(means, quats, scales, opacities, features, viewmat, K, W, 
                  phi_max=float(phi_max))
     return SplatContrastive.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), ids, count, weights,
                                   proto, float(near), float(far), float(eps2d), bool(check))
+
+
+class CodebookLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, codebook, image, ids, conf, assign, weights, conf_min, ignore_id):
+        K = int(codebook.shape[0])
+        stats, g_cls, g_clu, _, _ = _host.codebook_loss(image, ids, conf, codebook.detach(), assign, conf_min=conf_min,
+                                                         ignore_id=ignore_id)
+        n = stats[2].clamp(min=1.0)
+        zero = torch.zeros_like(stats[0])
+        # "never reinforce correct labels": the cross-entropy and its gradient are off when no pixel's argmax misses its
+        # label; log K = 0 at K = 1, where the cross-entropy is identically 0 anyway: it is taken as 0
+        on = (stats[3] > 0) & (stats[2] > 0) if K > 1 else torch.zeros_like(stats[0], dtype=torch.bool)
+        scale_cls = torch.where(on, weights[0] / (n * math.log(max(K, 2))), zero)
+        scale_clu = torch.where(stats[2] > 0, weights[1] / n, zero)
+        loss = scale_cls * stats[0] + scale_clu * stats[1]
+        ctx.save_for_backward(g_cls, g_clu, scale_cls.float(), scale_clu.float())
+        ctx.mark_non_differentiable(stats)
+        return loss.float(), stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        g_cls, g_clu, scale_cls, scale_clu = ctx.saved_tensors
+        grad = None
+        if ctx.needs_input_grad[0]:
+            grad = grad_loss.float() * (scale_cls * g_cls + scale_clu * g_clu)
+        return (grad,) + (None,) * 7
+
+
+def codebook_loss(image, ids, conf, codebook, assign, *, weight_cls=1.0, weight_cluster=1.0, conf_min=0.2, ignore_id=-1):
+    """The loss that ties one view's mask ids to a code book of global instance labels (include/voxproj.h states the
+    contract of vp_codebook_loss), differentiable IN THE CODE BOOK ONLY: the image is a constant, as in the method this
+    follows, where it is detached.
+
+      image f32 [D,H,W] on the GPU    the rendered identity rows (splat_features' logits)
+      ids int32 [H,W]                 the view's mask; conf f32 [H,W] or None: pixels with conf <= conf_min take no part
+      codebook f32 [K,D]              the parameter
+      assign int32 [256] on the GPU   id -> code (voxproj_host.assign_view_ids), -1: the id takes no part
+
+    L = weight_cls cls + weight_cluster stats[1] / n with n = stats[2] the participating pixels and
+    cls = stats[0] / (n log K).  cls and its gradient are 0 when stats[3] = 0 (every pixel's argmax already is its label),
+    L is 0 when n = 0; both switches are torch.where on device scalars, without a synchronisation.  At K = 1, log K = 0 and
+    the cross-entropy of a single code is identically 0: cls is defined as 0 there.
+    Returns (loss f32 0-dim, stats f64 [4], detached).  Forward: vp_codebook_loss, which also leaves the two unscaled
+    gradient sums; backward scales and adds two [K,D] tensors.  No double backward."""
+    _host._require_tensors((codebook, "codebook", (torch.float32,)))
+    if isinstance(image, torch.Tensor) and image.requires_grad:
+        raise ValueError("image requires grad, but codebook_loss is differentiable in the code book only (detach it)")
+    return CodebookLoss.apply(codebook, image, ids, conf, assign, (float(weight_cls), float(weight_cluster)), float(conf_min),
+                              int(ignore_id))

@@ -61,6 +61,7 @@ EXPORTS = [
     "vp_splat_lift_workspace_bytes", "vp_splat_lift", "vp_splat_render",
     "vp_feature_loss_workspace_bytes", "vp_feature_loss", "vp_feature_loss_gradient",
     "vp_proto_contrast_workspace_bytes", "vp_proto_contrast", "vp_proto_contrast_gradient",
+    "vp_codebook_workspace_bytes", "vp_codebook_assoc", "vp_codebook_loss",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -247,6 +248,15 @@ def lib():
                 L.vp_proto_contrast_gradient.restype = ctypes.c_int
                 L.vp_proto_contrast_gradient.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_float,
                                                          ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]
+            if hasattr(L, "vp_codebook_assoc"):  # added after ABI version 4: detected by symbol (codebook_assoc raises without it)
+                L.vp_codebook_workspace_bytes.restype = ctypes.c_size_t
+                L.vp_codebook_workspace_bytes.argtypes = [ctypes.c_int] * 4
+                L.vp_codebook_assoc.restype = ctypes.c_int
+                L.vp_codebook_assoc.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int,
+                                                vp, vp, vp, vp, ctypes.c_size_t, vp]
+                L.vp_codebook_loss.restype = ctypes.c_int
+                L.vp_codebook_loss.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_float,
+                                               vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
             L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
             L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
             L.vp_label_boundary.restype = ctypes.c_int
@@ -1359,6 +1369,101 @@ def proto_contrast_gradient(image, ids, count, workspace, *, weight_contrast=1.0
         _check_rc(L.vp_proto_contrast_gradient(image.data_ptr(), D, W, H, ids.data_ptr(), _ptr(count), float(weight_contrast),
                                                float(weight_norm), _ptr(grad_loss), out.data_ptr(), workspace.ptr(),
                                                workspace.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def _codebook_lib():
+    L = lib()
+    if not hasattr(L, "vp_codebook_assoc"):
+        raise VoxprojError(f"{LIB_PATH} has no vp_codebook_assoc: rebuild it (there is no fallback)")
+    return L
+
+
+VP_CODEBOOK_MAX_CODES = 256
+
+
+def codebook_workspace_bytes(D, K, W, H):
+    """vp_codebook_workspace_bytes: bytes of the workspace of codebook_assoc and codebook_loss for a D-channel W x H image
+    and K codes (0 when out of range).  Needs no GPU."""
+    return int(_codebook_lib().vp_codebook_workspace_bytes(int(D), int(K), int(W), int(H)))
+
+
+def _codebook_args(caller, image, ids, codebook, workspace):
+    """The image f32 [D,H,W], the mask i32 [H,W] and the code book f32 [K,D], contiguous on one GPU, and the workspace."""
+    import torch
+    image, ids, _, D, H, W = _proto_maps(caller, image, ids, None)
+    _require_tensors((codebook, "codebook", (torch.float32,)))
+    _require(codebook.dim() == 2 and int(codebook.shape[1]) == D and codebook.device == image.device,
+             f"{caller}: codebook must be float32 [K, {D}] on the image's device")
+    K = int(codebook.shape[0])
+    _require(1 <= K <= VP_CODEBOOK_MAX_CODES, f"K = {K} outside [1, {VP_CODEBOOK_MAX_CODES}]")
+    ws = workspace if workspace is not None else SplatWorkspace()
+    ptr = ws.ensure(int(_codebook_lib().vp_codebook_workspace_bytes(D, K, W, H)), image.device)
+    return image, ids, codebook.detach().contiguous(), D, H, W, K, ws, ptr
+
+
+def codebook_assoc(image, ids, codebook, *, ignore_id=-1, want_pred=False, workspace=None):
+    """vp_codebook_assoc: how much of every mask id's softmax mass falls on every code.  image f32 [D,H,W], ids int32 [H,W],
+    codebook f32 [K,D] on one GPU.  Returns (score f64 [256,K], id_pixels int32 [256], pred int32 [H,W] or None, workspace);
+    nothing is read back here."""
+    import torch
+    L = _codebook_lib()
+    image, ids, codebook, D, H, W, K, ws, ptr = _codebook_args("codebook_assoc", image, ids, codebook, workspace)
+    dev = image.device
+    score = torch.empty((VP_PROTO_MAX_IDS, K), dtype=torch.float64, device=dev)
+    id_pixels = torch.empty(VP_PROTO_MAX_IDS, dtype=torch.int32, device=dev)
+    pred = torch.empty((H, W), dtype=torch.int32, device=dev) if want_pred else None
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_codebook_assoc(image.data_ptr(), D, W, H, ids.data_ptr(), int(ignore_id), codebook.data_ptr(), K,
+                                      score.data_ptr(), id_pixels.data_ptr(), _ptr(pred), ptr, ws.capacity(),
+                                      torch.cuda.current_stream(dev).cuda_stream))
+    return score, id_pixels, pred, ws
+
+
+def codebook_loss(image, ids, conf, codebook, assign, *, conf_min=0.2, ignore_id=-1, want_pixel_loss=False, workspace=None):
+    """vp_codebook_loss: cross-entropy and clustering loss of the code book against the labels ``assign`` (int32 [256] on
+    the device: id -> code, -1 = takes no part) gives every pixel, over the pixels ``conf`` (f32 [H,W] or None) accepts.
+    Returns (stats f64 [4] = {sum of cross-entropy terms, sum of |s - B_v|, participating pixels, mismatched pixels},
+    grad_cls f32 [K,D], grad_cluster f32 [K,D], pixel_loss f32 [H,W] or None, workspace); nothing is read back here."""
+    import torch
+    L = _codebook_lib()
+    image, ids, codebook, D, H, W, K, ws, ptr = _codebook_args("codebook_loss", image, ids, codebook, workspace)
+    dev = image.device
+    (conf,) = _splat_images(dev, (conf, "conf", (H, W), torch.float32))
+    _require_tensors((assign, "assign", (torch.int32,)))
+    _require(tuple(assign.shape) == (VP_PROTO_MAX_IDS,) and assign.device == dev,
+             f"assign must be int32 [{VP_PROTO_MAX_IDS}] on the image's device")
+    assign = assign.contiguous()
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    grad_cls = torch.empty((K, D), dtype=torch.float32, device=dev)
+    grad_cluster = torch.empty((K, D), dtype=torch.float32, device=dev)
+    pixel_loss = torch.empty((H, W), dtype=torch.float32, device=dev) if want_pixel_loss else None
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_codebook_loss(image.data_ptr(), D, W, H, ids.data_ptr(), int(ignore_id), _ptr(conf), float(conf_min),
+                                     codebook.data_ptr(), K, assign.data_ptr(), stats.data_ptr(), grad_cls.data_ptr(),
+                                     grad_cluster.data_ptr(), _ptr(pixel_loss), ptr, ws.capacity(),
+                                     torch.cuda.current_stream(dev).cuda_stream))
+    return stats, grad_cls, grad_cluster, pixel_loss, ws
+
+
+def assign_view_ids(score, id_pixels, K):
+    """The linear assignment of one view's mask ids to the codes ("virtual labels"), on the host.  score [256,K] and
+    id_pixels [256] are codebook_assoc's outputs (tensors or arrays).  Labels are the ids with id_pixels > 0 in ascending
+    order, the first K of them when there are more; scipy.optimize.linear_sum_assignment maximises the assigned score.
+    Returns a numpy int32 [256]: the code of every label, -1 elsewhere.  With device tensors this is one small
+    device-to-host copy and one host synchronisation per view, as in the method this follows."""
+    import numpy as np
+    from scipy.optimize import linear_sum_assignment
+    score = np.asarray(score.detach().cpu() if hasattr(score, "detach") else score, dtype=np.float64)
+    id_pixels = np.asarray(id_pixels.detach().cpu() if hasattr(id_pixels, "detach") else id_pixels)
+    K = int(K)
+    _require(score.shape == (VP_PROTO_MAX_IDS, K) and id_pixels.shape == (VP_PROTO_MAX_IDS,),
+             f"score must be [{VP_PROTO_MAX_IDS}, {K}] and id_pixels [{VP_PROTO_MAX_IDS}]")
+    labels = np.flatnonzero(id_pixels > 0)[:K]
+    out = np.full(VP_PROTO_MAX_IDS, -1, np.int32)
+    if len(labels):
+        rows, cols = linear_sum_assignment(-score[labels])
+        out[labels[rows]] = cols.astype(np.int32)
     return out
 
 

@@ -883,6 +883,64 @@ int vp_proto_contrast_gradient(const float *image, int D, int W, int H, const in
                                float weight_contrast, float weight_norm, const float *grad_loss, float *grad_image,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * A code book of global instance labels against a rendered identity image and one view's instance mask: the id-by-code
+ * score matrix that a linear assignment turns into "virtual labels", and the cross-entropy / clustering loss against those
+ * labels with its gradient with respect to the code book (the image is a constant).  Added after VP_ABI_VERSION 4 without
+ * changing it or any existing entry point; detect the three functions by symbol.  tests/codebook_reference.py states the
+ * contract in float64.
+ *
+ *   image     f32 planar [D,H,W], contiguous: vp_splat_rasterize's logits.  D in [1, 64], W and H in [1, 32768], 64-bit
+ *             offsets.  Row f_p of pixel p = y W + x below; the raw row enters the logits.
+ *   ids       i32 [H,W]: the mask.       codebook  f32 [K,D], K in [1, VP_CODEBOOK_MAX_CODES].
+ *   conf      f32 [H,W] or NULL: a confidence map (vp_proto_contrast's own_prob).
+ *
+ * Pixel p is valid when 0 <= ids[p] < 256 and ids[p] != ignore_id (-1: none); confident when valid and (conf is NULL or
+ *   conf[p] > conf_min).  All arithmetic fp32:  z_pk = sum_c B_kc f_pc,  P_pk = expf(z_pk - max_k z_pk) / sum_k of the same,
+ *   pred[p] = argmax_k z_pk (lowest k on exact ties; -1 at a pixel that is not valid),  r_p = sqrtf(sum_c f_pc^2),
+ *   s_p = f_p / (r_p + 1e-6).
+ *
+ * vp_codebook_assoc:  score f64 [256,K]: score[l,k] = sum over valid p with ids[p] = l of P_pk;  id_pixels i32 [256]: the
+ *   valid pixels per id;  pred i32 [H,W] or NULL.  Every element of every output is written.
+ * vp_codebook_loss:  assign i32 [256] on the device maps id -> code, a value outside [0, K) meaning "takes no part";
+ *   v_p = assign[ids[p]]; a pixel takes part when it is confident and v_p is a code.
+ *   stats f64 [4] = {sum over participating p of (max_k z_pk + logf(sum_k expf(z_pk - max)) - z_pv): the cross-entropy
+ *                    without an epsilon,
+ *                    sum over participating p of |s_p - B_v|_2,
+ *                    the participating pixels,
+ *                    the valid pixels whose v_p is a code and pred[p] != v_p, confident or not}.
+ *   grad_cls f32 [K,D] = sum over participating p of (P_pk - [k = v_p]) f_p.
+ *   grad_cluster f32 [K,D]: row k = sum over participating p with v_p = k of (B_k - s_p) / |s_p - B_k|_2, a term being 0
+ *     where the distance is 0.  Both are unscaled sums of the gradients of stats[0] and stats[1]; the caller scales them.
+ *   pixel_loss f32 [H,W] or NULL: the cross-entropy term, exactly 0 where a pixel takes no part.
+ *   One deliberate difference from the method this follows: there the pixels of an id that received no code (more ids than
+ *   codes) train towards code 0, an artefact of initialising the label image with zeros.  Here they take no part.
+ * Order: no float atomics.  Tiles are 64 consecutive pixels; with T = ceil(tiles / 256), workgroup b of G = ceil(tiles / T)
+ *   takes tiles b T .. (b + 1) T - 1 in ascending order.  score: per workgroup and code, the probabilities of the valid
+ *   pixels in ascending order, a run of one id summed in fp32 from 0 and added to the workgroup's fp32 sum of that id when
+ *   the id changes; then the workgroups' sums in float64 in ascending b.  The gradients: per workgroup, fp32 accumulation
+ *   over its tiles in ascending order, each tile in 16 steps of four pixels (step (q, i), q = 0 .. 3, i = 0 .. 3, takes
+ *   pixels 16 q + i + {0, 4, 8, 12} of the tile in one matrix instruction); then the workgroups' sums in float64 in
+ *   ascending b, rounded to fp32 once.  stats: fp32 terms added in float64, per lane in tile order, a halving tree over the
+ *   workgroup's 256 threads, the workgroups in ascending b.  Every output is bit-identical from run to run.
+ *
+ * vp_codebook_workspace_bytes: host arithmetic, 0 when D, K, W or H is out of range.  One workspace serves both calls.  At
+ *   most G (1 KiB K + 2 KiB + 8 K D bytes + 256 bytes) with G = min(tiles, 256): 64.5 MiB + 32 MiB at K = 256, D = 64 on an
+ *   image of 16384 pixels or more, 72.5 MiB at D = 16, and proportional to the number of tiles below that.
+ * Both calls are asynchronous on `stream`, allocate nothing and do not synchronise with the host; the workspace may be
+ *   recycled memory (nothing in it is read before it is written).
+ * Refused on the host, no GPU needed, nothing written: VP_EINVAL for a NULL image, ids, codebook, score, id_pixels, stats,
+ *   assign, grad_cls or grad_cluster, for D, K, W or H out of range and for a non-finite conf_min; VP_EWORKSPACE for a
+ *   workspace that is NULL, not 256-byte aligned or smaller than vp_codebook_workspace_bytes.
+ */
+#define VP_CODEBOOK_MAX_CODES 256
+size_t vp_codebook_workspace_bytes(int D, int K, int W, int H);
+int vp_codebook_assoc(const float *image, int D, int W, int H, const int32_t *ids, int ignore_id, const float *codebook, int K,
+                      double *score, int32_t *id_pixels, int32_t *pred, void *workspace, size_t workspace_bytes, void *stream);
+int vp_codebook_loss(const float *image, int D, int W, int H, const int32_t *ids, int ignore_id, const float *conf,
+                     float conf_min, const float *codebook, int K, const int32_t *assign, double *stats, float *grad_cls,
+                     float *grad_cluster, float *pixel_loss, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
