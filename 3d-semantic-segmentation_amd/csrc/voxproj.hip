@@ -44,6 +44,8 @@
 //   vp_feature_loss.h  cosine / L2 loss of a rendered feature image against a 2D feature map, and its binary16 gradient image
 //   vp_proto_loss.h    prototype-contrastive loss of a rendered identity image against an instance mask, and its gradient image
 //   vp_codebook.h      a code book of global instance labels: the id-by-code score matrix, the loss and its gradients on the matrix cores
+//   vp_knn.h           the k nearest other points of every query on the bucketed grid (k_knn_points)
+//   vp_reg3d.h         the 3D neighbourhood regulariser: KL divergence to the nearest neighbours' distributions, and its gradient
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -81,6 +83,8 @@
 #include "vp_feature_loss.h"
 #include "vp_proto_loss.h"
 #include "vp_codebook.h"
+#include "vp_knn.h"
+#include "vp_reg3d.h"
 #include "vp_project.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1355,6 +1359,116 @@ int vp_codebook_loss(const float *image, int D, int W, int H, const int32_t *ids
                            stats);
     });
     VP_HIP(attr_rc);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// k nearest other points (vp_knn.h) and the neighbourhood regulariser (vp_reg3d.h).  Every check is host arithmetic and
+// comes before the first launch.
+// ------------------------------------------------------------------------------------------------
+int vp_knn_points(const float *pts_sorted, const int32_t *perm, const int32_t *cell_start, const double *grid_origin3,
+                  double cell_size, int nx, int ny, int nz, const float *queries, const int32_t *self_index, int64_t M, int k,
+                  int32_t *nbr_idx, double *nbr_d2, void *stream_)
+{
+    if (!pts_sorted || !perm || !cell_start || !grid_origin3 || !queries || !nbr_idx)
+        return fail(VP_EINVAL, "null pointer argument (pts_sorted, perm, cell_start, grid_origin3, queries or nbr_idx)");
+    if (!(cell_size > 0.0) || nx <= 0 || ny <= 0 || nz <= 0 || M < 0) return fail(VP_EINVAL, "bad grid or query count");
+    if ((long long)nx * ny * nz >= (1ll << 31)) return fail(VP_EINVAL, "the grid has >= 2^31 cells");
+    if (k < 1 || k > KNN_MAX_K) return fail(VP_EINVAL, "k = %d outside [1, %d]", k, KNN_MAX_K);
+    if (M * (int64_t)k >= (1ll << 40)) return fail(VP_EINVAL, "M k = %lld is too large", (long long)(M * k));
+    if (M == 0) return VP_OK;
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    hipStream_t stream = (hipStream_t)stream_;
+    auto launch = [&](auto kc) {
+        hipLaunchKernelGGL(k_knn_points<decltype(kc)::value>, grid, block, 0, stream, pts_sorted, (const int *)perm,
+                           (const int *)cell_start, grid_origin3[0], grid_origin3[1], grid_origin3[2], cell_size, nx, ny, nz,
+                           queries, (const int *)self_index, (long long)M, k, (int *)nbr_idx, nbr_d2);
+    };
+    if (k == 1) launch(std::integral_constant<int, 1>{});
+    else if (k <= 4) launch(std::integral_constant<int, 4>{});
+    else if (k <= 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 15>{});
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+size_t vp_neighbor_kl_workspace_bytes(int64_t S)
+{
+    if (S < 0 || S >= (1ll << 31)) return 0;
+    return align256((size_t)std::max<int64_t>(S, 1) * sizeof(float)) + align256(KL_PARTS * sizeof(double));
+}
+
+// the checks both calls share; *G: the lanes per row
+static int kl_check(const float *logits, int64_t N, int P, int64_t row_stride, const int32_t *samples, int64_t S,
+                    const int32_t *nbr, int k, const float *row_lse, int lanes, int *G)
+{
+    if (!logits || !row_lse) return fail(VP_EINVAL, "null pointer argument (logits or row_lse)");
+    if (N < 1 || N >= (1ll << 31)) return fail(VP_EINVAL, "N = %lld outside [1, 2^31)", (long long)N);
+    if (P < 1 || P > KL_MAX_P) return fail(VP_EINVAL, "P = %d outside [1, %d]", P, KL_MAX_P);
+    if (row_stride < P) return fail(VP_EINVAL, "row stride %lld below P = %d", (long long)row_stride, P);
+    if (k < 2 || k > KL_MAX_K) return fail(VP_EINVAL, "k = %d outside [2, %d] (k counts the point itself)", k, KL_MAX_K);
+    if (S < 0 || S * (int64_t)(k - 1) >= (1ll << 31)) return fail(VP_EINVAL, "S = %lld: S (k - 1) outside [0, 2^31)", (long long)S);
+    if (!samples && S != N) return fail(VP_EINVAL, "without a sample list S = %lld must be N = %lld", (long long)S, (long long)N);
+    if (S > 0 && !nbr) return fail(VP_EINVAL, "null pointer argument (the neighbour table)");
+    *G = lanes ? lanes : kl_pick_lanes(P);
+    if (*G < 4 || *G > 64 || (*G & (*G - 1)) || (P + *G - 1) / *G > 4)
+        return fail(VP_EINVAL, "lanes = %d: a power of two in [4, 64] with at most four channels of P = %d per lane (0: chosen here)",
+                    lanes, P);
+    return VP_OK;
+}
+
+int vp_neighbor_kl(const float *logits, int64_t N, int P, int64_t row_stride, const int32_t *samples, int64_t S,
+                   const int32_t *nbr, int k, float *row_lse, float *sample_loss, double *stats, int lanes, void *workspace,
+                   size_t workspace_bytes, void *stream_)
+{
+    int G = 0;
+    if (!stats) return fail(VP_EINVAL, "null pointer argument (stats)");
+    if (int rc = kl_check(logits, N, P, row_stride, samples, S, nbr, k, row_lse, lanes, &G)) return rc;
+    const size_t need = vp_neighbor_kl_workspace_bytes(S);
+    if (!workspace || workspace_bytes < need)
+        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    float *sl = sample_loss ? sample_loss : (float *)workspace;
+    double *part = (double *)((char *)workspace + align256((size_t)std::max<int64_t>(S, 1) * sizeof(float)));
+    const int per = KL_THREADS / G;
+    kl_with_cpl(P, G, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL(k_kl_lse<CPL>, dim3((unsigned)((N + per - 1) / per)), dim3(KL_THREADS), 0, stream, logits,
+                           (long long)row_stride, (long long)N, P, G, row_lse);
+        if (S > 0)
+            hipLaunchKernelGGL(k_kl_forward<CPL>, dim3((unsigned)((S + per - 1) / per)), dim3(KL_THREADS), 0, stream, logits,
+                               (long long)row_stride, (long long)N, P, G, (const int *)samples, (long long)S, (const int *)nbr,
+                               k - 1, (const float *)row_lse, sl);
+    });
+    hipLaunchKernelGGL(k_kl_sum1, dim3(KL_PARTS), dim3(KL_THREADS), 0, stream, (const float *)sl, (long long)S, part);
+    hipLaunchKernelGGL(k_kl_sum2, dim3(1), dim3(64), 0, stream, (const double *)part, (long long)S, stats);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_neighbor_kl_gradient(const float *logits, int64_t N, int P, int64_t row_stride, const int32_t *samples, int64_t S,
+                            const int32_t *nbr, int k, const float *row_lse, const int32_t *rev_start, const int32_t *rev_entry,
+                            const int32_t *smp_start, const int32_t *smp_entry, double scale, const float *grad_loss,
+                            float *grad_logits, int64_t grad_stride, int lanes, void *stream_)
+{
+    int G = 0;
+    if (!grad_logits || !rev_start) return fail(VP_EINVAL, "null pointer argument (grad_logits or rev_start)");
+    if (int rc = kl_check(logits, N, P, row_stride, samples, S, nbr, k, row_lse, lanes, &G)) return rc;
+    if (S > 0 && !rev_entry) return fail(VP_EINVAL, "null pointer argument (rev_entry)");
+    if (samples && (!smp_start || (S > 0 && !smp_entry))) return fail(VP_EINVAL, "a sample list needs smp_start and smp_entry");
+    if (grad_stride < P) return fail(VP_EINVAL, "gradient row stride %lld below P = %d", (long long)grad_stride, P);
+    if (!std::isfinite(scale)) return fail(VP_EINVAL, "scale = %g must be finite", scale);
+    const double coef = S > 0 ? scale / ((double)S * (double)k * (double)P) : 0.0;
+    const int per = KL_THREADS / G;
+    kl_with_cpl(P, G, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL(k_kl_gradient<CPL>, dim3((unsigned)((N + per - 1) / per)), dim3(KL_THREADS), 0, (hipStream_t)stream_,
+                           logits, (long long)row_stride, (long long)N, P, G, (const int *)samples, (long long)S,
+                           (const int *)nbr, k - 1, row_lse, (const int *)rev_start, (const int *)rev_entry,
+                           (const int *)smp_start, (const int *)smp_entry, coef, grad_loss, grad_logits, (long long)grad_stride);
+    });
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

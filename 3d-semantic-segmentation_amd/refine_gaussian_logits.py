@@ -4,6 +4,7 @@ the per-Gaussian logits and the per-view labels) and ``render_semantics_logits.p
   refine_gaussian_logits.py --gaussians_ply point_cloud.ply --logit_path X.npz --cam_params camera_params.json
       --targets_dir DIR [--views NAME ...] [--max_images N] [--downsample_factor F] [--principal_point center|camera]
       [--weight confidence|none] [--steps 200] [--views_per_step 4] [--lr 0.1] [--seed 0] [--report_miou] --out REFINED.npz
+      [--reg3d_weight 0] [--reg3d_k 5] [--reg3d_interval 2] [--reg3d_sample_size 0]
 
 Inputs: the 3DGS point cloud and the .npz of ``query_voxel_features.py gaussians`` ('logits' [N, P], 'prompts'), as
 render_semantics_logits.py reads them, with its cameras and image sizes; the targets ``DIR/<name>_labels.npy`` (int16 [H,W],
@@ -17,6 +18,13 @@ views with a seeded generator and takes the mean of their weighted cross-entropi
 labelled pixels whose rendered label agrees with the target are printed over all views; with --report_miou also the mIoU
 and fwIoU of the rendered labels against the targets (one confusion over all views, voxproj_host.label_scores).  Every kernel on the path is
 deterministic, so two runs with the same arguments write byte-identical logits.
+
+--reg3d_weight W > 0 adds the 3D neighbourhood regulariser (splat_autograd.neighbor_consistency, the reference's loss_cls_3d):
+a Gaussian no training view sees is tied to its --reg3d_k - 1 nearest neighbours in space (k counts the Gaussian itself, as
+the reference's reg3d_k does).  The neighbour table is built once from the ply's means; on every --reg3d_interval-th step W
+times the regulariser (scale 1) is added to the step's loss, over every Gaussian (--reg3d_sample_size 0) or over that many
+drawn from the seeded generator.  The regulariser over all Gaussians joins the before / after lines.  With W = 0 no table is
+built, no random number is drawn and the output is what it was without these flags.
 
 Output: --out, an .npz with the input's schema: 'labels' int16 [N] (argmax of the refined logits), 'logits' f32 [N, P],
 'prompts' (and 'colors' when the input has them), which render_semantics_logits.py --logit_path reads unchanged.
@@ -79,6 +87,10 @@ def build_parser():
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--report_miou", action="store_true", help="add mIoU / fwIoU against the targets to the before / after lines")
+    ap.add_argument("--reg3d_weight", type=float, default=0.0, help="weight of the 3D neighbourhood regulariser (0: off)")
+    ap.add_argument("--reg3d_k", type=int, default=5, help="neighbourhood size, the Gaussian itself included (2..16)")
+    ap.add_argument("--reg3d_interval", type=int, default=2, help="apply the regulariser on every N-th step")
+    ap.add_argument("--reg3d_sample_size", type=int, default=0, help="Gaussians per application (0: every Gaussian)")
     ap.add_argument("--out", required=True, help="the refined .npz")
     return ap
 
@@ -92,6 +104,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 0 or args.views_per_step < 1:
         ap.error("--steps must be >= 0 and --views_per_step >= 1")
+    if args.reg3d_weight < 0 or not 2 <= args.reg3d_k <= 16 or args.reg3d_interval < 1 or args.reg3d_sample_size < 0:
+        ap.error("--reg3d_weight must be >= 0, --reg3d_k in [2, 16], --reg3d_interval >= 1 and --reg3d_sample_size >= 0")
     if not torch.cuda.is_available():
         raise RuntimeError("refine_gaussian_logits runs on the GPU: there is no CPU path")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -157,27 +171,47 @@ def main(argv=None):
         fmt = lambda x: "null" if x is None else f"{x:.4f}"  # noqa: E731
         return f", mIoU {fmt(m['miou'])}, fwIoU {fmt(m['fwiou'])}"
 
+    table = None
+    if args.reg3d_weight > 0:
+        import voxproj_host
+        table = voxproj_host.NeighborTable(g["means"], args.reg3d_k)
+
+    def reg3d(sample=None):
+        return splat_autograd.neighbor_consistency(param, table, scale=1.0, sample=sample)
+
+    def reg_text(r):
+        return "" if r is None else f", reg3d {r:.6f}"
+
     l0, a0, total, m0 = evaluate()
+    r0 = float(reg3d().detach()) if table is not None else None
     print(f"[REFINE] {len(views)} view(s), {total} labelled pixels, {P} classes, {raw.shape[0]} Gaussians")
-    print(f"[REFINE] before: mean loss {l0:.6f}, pixel agreement {a0:.4f}{miou_text(m0)}")
+    print(f"[REFINE] before: mean loss {l0:.6f}, pixel agreement {a0:.4f}{miou_text(m0)}{reg_text(r0)}")
     gen = torch.Generator().manual_seed(args.seed)
     k = min(args.views_per_step, len(views))
-    for _ in range(args.steps):
+    for step in range(args.steps):
         pick = torch.randperm(len(views), generator=gen)[:k].tolist()
         opt.zero_grad(set_to_none=True)
         loss = 0
         for i in pick:
             loss = loss + view_loss(views[i])[0] / k
+        if table is not None and step % args.reg3d_interval == 0:
+            sample = None
+            if 0 < args.reg3d_sample_size < raw.shape[0]:
+                sample = torch.randperm(raw.shape[0], generator=gen)[:args.reg3d_sample_size].to(dev)
+            loss = loss + args.reg3d_weight * reg3d(sample)
         loss.backward()
         opt.step()
     l1, a1, _, m1 = evaluate()
-    print(f"[REFINE] after {args.steps} step(s): mean loss {l1:.6f}, pixel agreement {a1:.4f}{miou_text(m1)}")
+    r1 = float(reg3d().detach()) if table is not None else None
+    print(f"[REFINE] after {args.steps} step(s): mean loss {l1:.6f}, pixel agreement {a1:.4f}{miou_text(m1)}{reg_text(r1)}")
     prompts = d["prompts"] if "prompts" in d else None
     save_refined(args.out, param.detach().cpu().numpy(), prompts, d["colors"] if "colors" in d else None)
     print(f"[REFINE] -> {args.out}")
     res = dict(loss_before=l0, loss_after=l1, agreement_before=a0, agreement_after=a1)
     if scores is not None:
         res.update(miou_before=m0["miou"], miou_after=m1["miou"], fwiou_before=m0["fwiou"], fwiou_after=m1["fwiou"])
+    if table is not None:
+        res.update(reg3d_before=r0, reg3d_after=r1)
     return res
 
 

@@ -454,3 +454,49 @@ def codebook_loss(image, ids, conf, codebook, assign, *, weight_cls=1.0, weight_
         raise ValueError("image requires grad, but codebook_loss is differentiable in the code book only (detach it)")
     return CodebookLoss.apply(codebook, image, ids, conf, assign, (float(weight_cls), float(weight_cluster)), float(conf_min),
                               int(ignore_id))
+
+
+class NeighborConsistency(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, sample, scale, want_sample_loss):
+        stats, row_lse, sample_loss, _ = _host.neighbor_kl(logits, sample, want_sample_loss=want_sample_loss)
+        P = int(logits.shape[1])
+        coef = scale / (sample.S * sample.k * P) if sample.S else 0.0
+        ctx.save_for_backward(logits.detach(), row_lse)
+        ctx.sample, ctx.scale = sample, scale
+        out = sample_loss if sample_loss is not None else stats.new_zeros(0, dtype=torch.float32)
+        ctx.mark_non_differentiable(out)
+        return (coef * stats[0]).float(), out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_sample_loss):
+        logits, row_lse = ctx.saved_tensors
+        grad = None
+        if ctx.needs_input_grad[0]:
+            grad = _host.neighbor_kl_gradient(logits, ctx.sample, row_lse, scale=ctx.scale,
+                                              grad_loss=grad_loss.float().reshape(1).contiguous())
+        return grad, None, None, None
+
+
+def neighbor_consistency(logits, table, *, scale=2.0, sample=None, want_sample_loss=False):
+    """The 3D neighbourhood regulariser (include/voxproj.h states the contract of vp_neighbor_kl; the reference's
+    loss_cls_3d, utils/loss_utils.py:74-115): the mean KL divergence between a Gaussian's class distribution and those of its
+    nearest neighbours in space, differentiable IN THE LOGITS ONLY (the positions are fixed: the table is built once).
+
+      logits f32 [N,P] on the GPU       the parameter, 1 <= P <= 256
+      table                             voxproj_host.NeighborTable(points, k); k counts the point itself (the reference's reg3d_k)
+      scale                             the reference's lambda_val
+      sample                            None: every Gaussian; an integer tensor [S] of rows (repeats allowed), or a
+                                        voxproj_host.NeighborSample from table.select
+
+    loss = scale / (S k P) sum_s sum_j sum_c p_sc (log(p_sc + 1e-10) - log(p_jc + 1e-10)), 0 for an empty sample.
+    Returns the loss (f32 0-dim), or (loss, sample_loss f32 [S], unscaled and detached) with ``want_sample_loss``.  Forward:
+    vp_neighbor_kl; backward: vp_neighbor_kl_gradient, one launch, no float atomics.  No double backward."""
+    _host._require_tensors((logits, "logits", (torch.float32,)))
+    if sample is None:
+        sample = table.all
+    elif isinstance(sample, torch.Tensor):
+        sample = table.select(sample)
+    loss, sample_loss = NeighborConsistency.apply(logits, sample, float(scale), bool(want_sample_loss))
+    return (loss, sample_loss) if want_sample_loss else loss

@@ -62,6 +62,7 @@ EXPORTS = [
     "vp_feature_loss_workspace_bytes", "vp_feature_loss", "vp_feature_loss_gradient",
     "vp_proto_contrast_workspace_bytes", "vp_proto_contrast", "vp_proto_contrast_gradient",
     "vp_codebook_workspace_bytes", "vp_codebook_assoc", "vp_codebook_loss",
+    "vp_knn_points", "vp_neighbor_kl_workspace_bytes", "vp_neighbor_kl", "vp_neighbor_kl_gradient",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -257,6 +258,19 @@ def lib():
                 L.vp_codebook_loss.restype = ctypes.c_int
                 L.vp_codebook_loss.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_float,
                                                vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+            if hasattr(L, "vp_knn_points"):  # added after ABI version 4: detected by symbol (knn_points / neighbor_kl raise without it)
+                i64 = ctypes.c_int64
+                L.vp_knn_points.restype = ctypes.c_int
+                L.vp_knn_points.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, vp, vp, i64, ctypes.c_int, vp, vp, vp]
+                L.vp_neighbor_kl_workspace_bytes.restype = ctypes.c_size_t
+                L.vp_neighbor_kl_workspace_bytes.argtypes = [i64]
+                L.vp_neighbor_kl.restype = ctypes.c_int
+                L.vp_neighbor_kl.argtypes = [vp, i64, ctypes.c_int, i64, vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp,
+                                             ctypes.c_size_t, vp]
+                L.vp_neighbor_kl_gradient.restype = ctypes.c_int
+                L.vp_neighbor_kl_gradient.argtypes = [vp, i64, ctypes.c_int, i64, vp, i64, vp, ctypes.c_int, vp, vp, vp, vp, vp,
+                                                      ctypes.c_double, vp, vp, i64, ctypes.c_int, vp]
             L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
             L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
             L.vp_label_boundary.restype = ctypes.c_int
@@ -1444,6 +1458,180 @@ def codebook_loss(image, ids, conf, codebook, assign, *, conf_min=0.2, ignore_id
                                      grad_cluster.data_ptr(), _ptr(pixel_loss), ptr, ws.capacity(),
                                      torch.cuda.current_stream(dev).cuda_stream))
     return stats, grad_cls, grad_cluster, pixel_loss, ws
+
+
+def _reg3d_lib():
+    L = lib()
+    if not hasattr(L, "vp_knn_points"):
+        raise VoxprojError(f"{LIB_PATH} has no vp_knn_points: rebuild it (there is no fallback)")
+    return L
+
+
+VP_KNN_MAX_K = 15
+VP_NEIGHBOR_KL_MAX_P = 256
+VP_NEIGHBOR_KL_MAX_K = 16
+
+
+def knn_points(points, k, queries=None, *, cell_order=True, want_d2=True):
+    """vp_knn_points: the k nearest OTHER points of every query among ``points`` (f32 [N,3] on a GPU), exact, ordered by
+    (squared distance in float64, index).  ``queries`` None: the points themselves, each one left out of its own result.
+    Returns (idx int32 [M,k], d2 float64 [M,k] or None) on the device; -1 / +inf where fewer than k other points exist.
+    ``cell_order`` (self-queries only): launch the queries in the grid's cell order, so that a wavefront's lanes walk the
+    same cells, and put the rows back in torch; False launches them in the caller's order (the same result)."""
+    import torch
+    import voxel_to_gaussian_map
+    L = _reg3d_lib()
+    _require_tensors((points, "points", (torch.float32,)))
+    _require(points.dim() == 2 and int(points.shape[1]) == 3 and points.is_cuda, "points must be float32 [N, 3] on a GPU")
+    _require(1 <= int(k) <= VP_KNN_MAX_K, f"k = {k} outside [1, {VP_KNN_MAX_K}]")
+    dev = points.device
+    N, k = int(points.shape[0]), int(k)
+    _require(N >= 1, "points is empty")
+    pts, perm, start, origin, h, dims = voxel_to_gaussian_map._bucket(points.detach(), dev)
+    self_index = None
+    if queries is None:
+        q, self_index = (pts, perm) if cell_order else (points.detach().contiguous(), torch.arange(N, dtype=torch.int32, device=dev))
+    else:
+        _require_tensors((queries, "queries", (torch.float32,)))
+        _require(queries.dim() == 2 and int(queries.shape[1]) == 3 and queries.device == dev,
+                 "queries must be float32 [M, 3] on the points' device")
+        q = queries.detach().contiguous()
+    M = int(q.shape[0])
+    idx = torch.empty((M, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((M, k), dtype=torch.float64, device=dev) if want_d2 else None
+    g = (ctypes.c_double * 3)(*origin)
+    with torch.cuda.device(dev):
+        check(L.vp_knn_points(pts.data_ptr(), perm.data_ptr(), start.data_ptr(), g, ctypes.c_double(h), dims[0], dims[1], dims[2],
+                              q.data_ptr(), _ptr(self_index), M, k, idx.data_ptr(), _ptr(d2),
+                              torch.cuda.current_stream(dev).cuda_stream))
+    if queries is None and cell_order:       # row t of the launch is point perm[t]
+        back = perm.long()
+        idx = torch.empty_like(idx).index_copy_(0, back, idx)
+        d2 = torch.empty_like(d2).index_copy_(0, back, d2) if d2 is not None else None
+    return idx, d2
+
+
+def knn_mean_dist2(points):
+    """The counterpart of simple-knn's distCUDA2 (submodules/simple-knn/simple_knn.cu:132-182, read by
+    scene/gaussian_model.py:150): per point the mean of the three smallest squared distances to other points, float32 [N].
+    The three distances are vp_knn_points' float64 ones, their mean (d0 + d1) + d2 over 3 is taken in float64 and rounded once; a point with fewer
+    than three others takes the mean over those it has (0 for a lone point)."""
+    import torch
+    _, d2 = knn_points(points, 3)
+    have = torch.isfinite(d2)
+    z = torch.where(have, d2, torch.zeros_like(d2))
+    return (((z[:, 0] + z[:, 1]) + z[:, 2]) / have.sum(1).clamp_min(1)).to(torch.float32)
+
+
+def reverse_table(nbr, n_rows):
+    """The reversed form of a neighbour table ``nbr`` int [S, k-1] (entries in [0, n_rows), anything else = none), CSR over
+    rows: (rev_start int32 [n_rows+1], rev_entry int32 [S (k-1)]).  rev_entry[rev_start[i] : rev_start[i+1]] are the flat
+    entries s (k-1) + j that name row i, ascending (a stable sort); entries that name no row sit behind rev_start[n_rows]."""
+    import torch
+    flat = nbr.reshape(-1).long()
+    key = torch.where((flat >= 0) & (flat < n_rows), flat, torch.full_like(flat, n_rows))
+    order = torch.argsort(key, stable=True)
+    start = torch.zeros(n_rows + 1, dtype=torch.int32, device=nbr.device)
+    start[1:] = torch.cumsum(torch.bincount(key, minlength=n_rows + 1)[:n_rows], 0).to(torch.int32)
+    return start, order.to(torch.int32).contiguous()
+
+
+class NeighborSample:
+    """What one application of the regulariser reads: the sample list (None: every row in order), its rows of the neighbour
+    table, and both reversed tables; built by NeighborTable.all / .select."""
+
+    def __init__(self, n_rows, k, samples, nbr):
+        import torch
+        self.n_rows, self.k = int(n_rows), int(k)
+        self.samples = None if samples is None else samples.to(torch.int32).contiguous()
+        self.nbr = nbr.contiguous()
+        self.S = int(self.nbr.shape[0])
+        self.rev_start, self.rev_entry = reverse_table(self.nbr, self.n_rows)
+        self.smp_start = self.smp_entry = None
+        if self.samples is not None:
+            self.smp_start, self.smp_entry = reverse_table(self.samples.reshape(-1, 1), self.n_rows)
+            if self.S == 0:              # an empty list is still a list: a non-NULL pointer that is never read
+                self.samples = torch.zeros(1, dtype=torch.int32, device=self.nbr.device)
+
+
+class NeighborTable:
+    """The neighbour table of the regulariser, built once from the points (f32 [N,3] on a GPU): ``nbr`` int32 [N, k-1], the
+    k - 1 nearest other points of every point (k counts the point itself, like the reference's reg3d_k), and its reversed
+    form, both on the device."""
+
+    def __init__(self, points, k):
+        _require(2 <= int(k) <= VP_NEIGHBOR_KL_MAX_K, f"k = {k} outside [2, {VP_NEIGHBOR_KL_MAX_K}] (k counts the point itself)")
+        self.k = int(k)
+        self.n_rows = int(points.shape[0])
+        self.nbr, _ = knn_points(points, self.k - 1, want_d2=False)
+        self.all = NeighborSample(self.n_rows, self.k, None, self.nbr)
+        self.rev_start, self.rev_entry = self.all.rev_start, self.all.rev_entry
+
+    def select(self, samples):
+        """The tables of one sample list (integer tensor [S] of rows in [0, N), repeats allowed) on the table's device."""
+        samples = samples.to(self.nbr.device)
+        return NeighborSample(self.n_rows, self.k, samples, self.nbr[samples.long()])
+
+
+def neighbor_kl_workspace_bytes(S):
+    """vp_neighbor_kl_workspace_bytes: bytes of neighbor_kl's workspace for S sample positions.  Needs no GPU."""
+    return int(_reg3d_lib().vp_neighbor_kl_workspace_bytes(int(S)))
+
+
+def _neighbor_kl_logits(logits):
+    import torch
+    _require_tensors((logits, "logits", (torch.float32,)))
+    _require(logits.dim() == 2 and logits.is_cuda, "logits must be float32 [N, P] on a GPU")
+    N, P = int(logits.shape[0]), int(logits.shape[1])
+    _require(N >= 1 and 1 <= P <= VP_NEIGHBOR_KL_MAX_P, f"logits [{N}, {P}]: N >= 1 and P in [1, {VP_NEIGHBOR_KL_MAX_P}]")
+    logits = logits.detach()
+    if logits.stride(1) != 1 or logits.stride(0) < P:
+        logits = logits.contiguous()
+    return logits, N, P
+
+
+def neighbor_kl(logits, sample, *, want_sample_loss=False, lanes=0, workspace=None):
+    """vp_neighbor_kl: the neighbourhood KL sum of ``logits`` (f32 [N,P], unit channel stride) over a NeighborSample.
+    Returns (stats f64 [2] = {sum, S}, row_lse f32 [N], sample_loss f32 [S] or None, workspace) on the device; the loss is
+    scale / (S k P) stats[0].  Nothing is read back here."""
+    import torch
+    L = _reg3d_lib()
+    logits, N, P = _neighbor_kl_logits(logits)
+    _require(sample.n_rows == N and sample.nbr.device == logits.device, "the neighbour table is of another point set or device")
+    dev = logits.device
+    ws = workspace if workspace is not None else SplatWorkspace()
+    ptr = ws.ensure(int(L.vp_neighbor_kl_workspace_bytes(sample.S)), dev)
+    stats = torch.empty(2, dtype=torch.float64, device=dev)
+    row_lse = torch.empty(N, dtype=torch.float32, device=dev)
+    sample_loss = torch.empty(sample.S, dtype=torch.float32, device=dev) if want_sample_loss else None
+    with torch.cuda.device(dev):
+        check(L.vp_neighbor_kl(logits.data_ptr(), N, P, logits.stride(0), _ptr(sample.samples), sample.S, _ptr(sample.nbr),
+                               sample.k, row_lse.data_ptr(), _ptr(sample_loss), stats.data_ptr(), int(lanes), ptr, ws.capacity(),
+                               torch.cuda.current_stream(dev).cuda_stream))
+    return stats, row_lse, sample_loss, ws
+
+
+def neighbor_kl_gradient(logits, sample, row_lse, *, scale=2.0, grad_loss=None, lanes=0, out=None):
+    """vp_neighbor_kl_gradient: the gradient of scale / (S k P) stats[0] with respect to the logits, times ``grad_loss``
+    (f32 one element on the device, or None): f32 [N,P], every row written.  ``row_lse`` is neighbor_kl's, of the same logits."""
+    import torch
+    L = _reg3d_lib()
+    logits, N, P = _neighbor_kl_logits(logits)
+    _require(sample.n_rows == N and sample.nbr.device == logits.device, "the neighbour table is of another point set or device")
+    dev = logits.device
+    _require_tensors((row_lse, "row_lse", (torch.float32,)))
+    _require(tuple(row_lse.shape) == (N,) and row_lse.device == dev and row_lse.is_contiguous(), f"row_lse must be float32 [{N}]")
+    (grad_loss,) = _splat_images(dev, (grad_loss, "grad_loss", None, torch.float32))
+    if out is None:
+        out = torch.empty((N, P), dtype=torch.float32, device=dev)
+    _require(out.dtype == torch.float32 and tuple(out.shape) == (N, P) and out.device == dev and out.stride(1) == 1 and
+             out.stride(0) >= P, f"out must be float32 [{N}, {P}] with a unit channel stride")
+    with torch.cuda.device(dev):
+        check(L.vp_neighbor_kl_gradient(logits.data_ptr(), N, P, logits.stride(0), _ptr(sample.samples), sample.S, _ptr(sample.nbr),
+                                        sample.k, row_lse.data_ptr(), sample.rev_start.data_ptr(), _ptr(sample.rev_entry),
+                                        _ptr(sample.smp_start), _ptr(sample.smp_entry), float(scale), _ptr(grad_loss),
+                                        out.data_ptr(), out.stride(0), int(lanes), torch.cuda.current_stream(dev).cuda_stream))
+    return out
 
 
 def assign_view_ids(score, id_pixels, K):

@@ -941,6 +941,63 @@ int vp_codebook_loss(const float *image, int D, int W, int H, const int32_t *ids
                      float conf_min, const float *codebook, int K, const int32_t *assign, double *stats, float *grad_cls,
                      float *grad_cluster, float *pixel_loss, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * k nearest OTHER points (csrc/vp_knn.h) and the 3D neighbourhood regulariser built on them (csrc/vp_reg3d.h), the counterpart
+ * of the reference's loss_cls_3d (utils/loss_utils.py:74-115).  Added after ABI version 4: detected by symbol.
+ *
+ * vp_knn_points: the point set bucketed on a uniform grid exactly as vp_nearest_voxel takes it (pts_sorted, perm,
+ *   cell_start, grid_origin3, cell_size, nx ny nz; nx ny nz < 2^31).  queries f32 [M,3];  self_index i32 [M] or NULL: the
+ *   original index of a point that is left out of that query's result (anything outside [0, N) leaves nothing out);
+ *   1 <= k <= VP_KNN_MAX_K.  nbr_idx i32 [M,k], nbr_d2 f64 [M,k] or NULL: the k nearest points by the key (d2, original
+ *   index), ascending; d2 is the float64 sum of squares of the float64-converted fp32 differences (vp_nearest_voxel's).
+ *   Ties, coincident points included, go to the lowest index: the result is a function of the inputs alone and
+ *   bit-identical from run to run.  Where fewer than k other points exist the tail is -1 / +inf.  The search is exact: shells
+ *   of cells are visited until the k-th best d2 is no larger than (r cell_size)^2; queries outside the grid, grids one cell
+ *   thick and far outliers terminate like vp_nearest_voxel.  Needs no workspace.  Asynchronous on `stream`.
+ *   Refused on the host (VP_EINVAL): a NULL pts_sorted, perm, cell_start, grid_origin3, queries or nbr_idx, a bad grid,
+ *   M < 0, k out of range.
+ *
+ * vp_neighbor_kl / vp_neighbor_kl_gradient.  logits z f32 [N,P] with `row_stride` floats between rows (>= P), 1 <= P <=
+ *   VP_NEIGHBOR_KL_MAX_P; samples i32 [S] or NULL (NULL: every row in order, S = N); indices in [0, N), repeats allowed;
+ *   nbr i32 [S,k-1]: the neighbours of every sample position, -1 (or anything outside [0, N)) = no neighbour, skipped.
+ *   k counts the point itself, as the reference's k does (its cdist returns the point first, at distance 0, with a KL term of
+ *   exactly 0): 2 <= k <= VP_NEIGHBOR_KL_MAX_K, the table holds the k - 1 others and the mean divides by k.
+ *   With p_i = softmax(z_i) and eps = 1e-10:
+ *       sum  = sum_s sum_j sum_c p_sc (log(p_sc + eps) - log(p_jc + eps)),      loss = scale / (S k P) sum   (0 when S = 0)
+ *   forward:  row_lse f32 [N] = the log-sum-exp of every row (the gradient call reads it);  sample_loss f32 [S] or NULL: the
+ *     sum's term of every sample position, unscaled;  stats f64 [2] = {sum, S}: the fp32 terms added in float64 in a fixed
+ *     order.  The caller applies scale / (S k P).
+ *   gradient:  grad_logits f32 [N,P] (`grad_stride` floats between rows), every row written, zeros for a row that nobody
+ *     names:  with g the gradient with respect to the probabilities, a sample row receives log(p_s + eps) - log(p_j + eps) +
+ *     p_s / (p_s + eps) per neighbour and a neighbour row - p_s / (p_j + eps) per sample position that lists it; then
+ *     dz = scale / (S k P) grad_loss p (g - <g, p>), grad_loss f32 [1] on the device or NULL (1).  No float atomics: row i
+ *     gathers first what it receives as a sample -- through smp_start i32 [N+1] / smp_entry i32 [S], the CSR form of "the
+ *     sample positions that name row i" (both NULL when samples is NULL) -- then what it receives as a neighbour, through
+ *     rev_start i32 [N+1] / rev_entry i32 [S (k-1)], the CSR form of "the entries s (k-1) + j of nbr that name row i"; within
+ *     a row both lists are walked in the order given, so equal tables give equal bits.
+ *   lanes: lanes per row, a power of two in [4, 64] with ceil(P / lanes) <= 4; 0 = the library's choice (the smallest power
+ *     of two with 4 lanes >= P, eight for P in 9..16).  A test / measurement switch: every value computes the same sums in another association.
+ *   vp_neighbor_kl_workspace_bytes(S): host arithmetic, 0 when S is out of range; the workspace may be recycled memory.
+ *   Both calls are asynchronous on `stream`, allocate nothing and do not synchronise with the host.
+ *   Refused on the host (VP_EINVAL / VP_EWORKSPACE), nothing written: a NULL logits, row_lse, stats, grad_logits, rev_start,
+ *     a NULL table with S > 0, N, P, k, S, a stride or lanes out of range, S != N without samples, samples without
+ *     smp_start / smp_entry, a non-finite scale, a workspace that is NULL, misaligned or too small.
+ */
+#define VP_KNN_MAX_K 15
+#define VP_NEIGHBOR_KL_MAX_P 256
+#define VP_NEIGHBOR_KL_MAX_K 16
+int vp_knn_points(const float *pts_sorted, const int32_t *perm, const int32_t *cell_start, const double *grid_origin3,
+                  double cell_size, int nx, int ny, int nz, const float *queries, const int32_t *self_index, int64_t M, int k,
+                  int32_t *nbr_idx, double *nbr_d2, void *stream);
+size_t vp_neighbor_kl_workspace_bytes(int64_t S);
+int vp_neighbor_kl(const float *logits, int64_t N, int P, int64_t row_stride, const int32_t *samples, int64_t S,
+                   const int32_t *nbr, int k, float *row_lse, float *sample_loss, double *stats, int lanes, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int vp_neighbor_kl_gradient(const float *logits, int64_t N, int P, int64_t row_stride, const int32_t *samples, int64_t S,
+                            const int32_t *nbr, int k, const float *row_lse, const int32_t *rev_start, const int32_t *rev_entry,
+                            const int32_t *smp_start, const int32_t *smp_entry, double scale, const float *grad_loss,
+                            float *grad_logits, int64_t grad_stride, int lanes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
