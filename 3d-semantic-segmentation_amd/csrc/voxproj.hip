@@ -46,6 +46,7 @@
 //   vp_codebook.h      a code book of global instance labels: the id-by-code score matrix, the loss and its gradients on the matrix cores
 //   vp_knn.h           the k nearest other points of every query on the bucketed grid (k_knn_points)
 //   vp_reg3d.h         the 3D neighbourhood regulariser: KL divergence to the nearest neighbours' distributions, and its gradient
+//   vp_photo_loss.h    photometric loss (L1 + D-SSIM) of a rendered image against a photograph, and its gradient image
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -85,6 +86,7 @@
 #include "vp_codebook.h"
 #include "vp_knn.h"
 #include "vp_reg3d.h"
+#include "vp_photo_loss.h"
 #include "vp_project.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1274,6 +1276,67 @@ int vp_proto_contrast_gradient(const float *image, int D, int W, int H, const in
                            count, (const ProtoHeader *)w.hdr, (const int *)w.slot_of_id, (const float *)w.utab,
                            (const float *)w.gn, weight_contrast, weight_norm, grad_loss, grad_image);
     });
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The photometric loss (vp_photo_loss.h).  Every check is host arithmetic and comes before the first launch.
+// ------------------------------------------------------------------------------------------------
+size_t vp_photo_loss_workspace_bytes(int C, int W, int H)
+{
+    if (C < 1 || C > PHOTO_MAX_C || W < 1 || W > PHOTO_MAX_WH || H < 1 || H > PHOTO_MAX_WH) return 0;
+    return photo_bytes(C, W, H);
+}
+
+static int photo_check(const float *image, const float *target, int C, int W, int H, bool need_workspace, const void *workspace,
+                       size_t workspace_bytes)
+{
+    if (!image || !target) return fail(VP_EINVAL, "null pointer argument (image or target)");
+    if (C < 1 || C > PHOTO_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, PHOTO_MAX_C);
+    if (W < 1 || W > PHOTO_MAX_WH || H < 1 || H > PHOTO_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, PHOTO_MAX_WH);
+    if (!workspace && !need_workspace) return VP_OK;
+    const size_t need = photo_bytes(C, W, H);
+    if (!workspace || workspace_bytes < need)
+        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    return VP_OK;
+}
+
+int vp_photo_loss(const float *image, const float *target, int C, int W, int H, double *loss_stats, float *ssim_map,
+                  void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!loss_stats) return fail(VP_EINVAL, "null pointer argument (loss_stats)");
+    if (int rc = photo_check(image, target, C, W, H, false, workspace, workspace_bytes)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!workspace) {
+        hipLaunchKernelGGL(k_photo_loss<true>, dim3(1), dim3(PHOTO_THREADS), 0, stream, image, target, C, W, H, ssim_map,
+                           (float *)nullptr, (double *)nullptr, loss_stats);
+    } else {
+        float *maps = (float *)workspace;
+        double *sums = (double *)((char *)workspace + photo_maps_bytes(C, W, H));
+        hipLaunchKernelGGL(k_photo_loss<false>, dim3((unsigned)photo_tiles_x(W), (unsigned)photo_tiles_x(H), (unsigned)C),
+                           dim3(PHOTO_THREADS), 0, stream, image, target, C, W, H, ssim_map, maps, sums, loss_stats);
+        hipLaunchKernelGGL(k_photo_loss_sum, dim3(1), dim3(PHOTO_THREADS), 0, stream, (const double *)sums, photo_tiles(C, W, H),
+                           loss_stats);
+    }
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_photo_loss_gradient(const float *image, const float *target, int C, int W, int H, float lambda_dssim,
+                           const float *grad_loss, float *grad_image, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!grad_image) return fail(VP_EINVAL, "null pointer argument (grad_image)");
+    if (!std::isfinite(lambda_dssim) || lambda_dssim < 0.0f || lambda_dssim > 1.0f)
+        return fail(VP_EINVAL, "lambda_dssim = %g outside [0, 1]", (double)lambda_dssim);
+    if (int rc = photo_check(image, target, C, W, H, true, workspace, workspace_bytes)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const double n = (double)C * (double)W * (double)H;
+    const float a = (float)((1.0 - (double)lambda_dssim) / n), b = (float)((double)lambda_dssim / n);
+    hipLaunchKernelGGL(k_photo_loss_gradient, dim3((unsigned)photo_tiles_x(W), (unsigned)photo_tiles_x(H), (unsigned)C),
+                       dim3(PHOTO_THREADS), 0, stream, image, target, W, H, (const float *)workspace, a, b, grad_loss, grad_image);
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

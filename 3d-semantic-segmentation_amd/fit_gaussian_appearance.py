@@ -1,0 +1,199 @@
+"""Fit the appearance (and, on request, the opacities and geometry) of a 3DGS point cloud to its photographs with the
+photometric loss of the reference's training loop, (1 - lambda) L1 + lambda (1 - SSIM) (train_unified_lift.py:401-416,
+utils/loss_utils.py:15-71), every view one fused call (splat_autograd.splat_photometric: no torch pass over an image).
+
+  fit_gaussian_appearance.py --gaussians_ply point_cloud.ply --cam_params camera_params.json --images_dir DIR --out REFINED.ply
+      [--views NAME ...] [--max_images N] [--downsample_factor F] [--principal_point center|camera]
+      [--train colors,opacities,scales,quats,means] [--steps 200] [--views_per_step 4] [--lambda_dssim 0.2]
+      [--lr_colors 0.01] [--lr_opacities 0.05] [--lr_scales 0.005] [--lr_quats 0.001] [--lr_means 0.00016] [--seed 0]
+      [--report REPORT.json]
+
+Appearance is one view-independent colour row per Gaussian: it starts at max(0, 0.5 + 0.28209479 f_dc), the reference's
+degree-0 colour, is trained as a row, and is written back as f_dc = (c - 0.5) / 0.28209479.  Higher-order f_rest_* fields are
+neither read nor written; there is no background colour.  --train picks the parameters (default: colors).  Opacities and
+scales are trained through the ply's raw parametrisation (sigmoid, exp) in torch, quaternions raw (the splatter normalises
+them), means as they are.  A field that is not trained is written back bit for bit.  No densification, pruning or opacity
+reset.
+
+Images are paired with the cameras by name, the camera's file extension dropped: DIR/<name>.png / .jpg / .jpeg through PIL
+(8-bit RGB, / 255; resized to the render size when it differs), or DIR/<name>.npy, f32 [3,H,W] at the render size.
+
+Optimisation: torch Adam with one learning rate per parameter; each step draws --views_per_step views with a seeded
+generator and takes the mean of their losses.  Before and after, the mean loss, PSNR, SSIM and L1 over all views are
+printed, computed with voxproj_host.photo_loss(evaluate_only=True); --report writes them per view as JSON.  Every kernel on
+the path is deterministic, so two runs with the same arguments write byte-identical files.
+Runs on the GPU only; there is no CPU path.
+"""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+import render_semantics_logits as rsl
+
+SH_C0 = 0.28209479177387814
+PARAMS = ("colors", "opacities", "scales", "quats", "means")
+IMAGE_EXTS = (".png", ".jpg", ".jpeg", ".PNG", ".JPG", ".JPEG")
+
+
+def colors_from_dc(f_dc):
+    """max(0, 0.5 + C0 f_dc): the reference's colour of a degree-0 Gaussian."""
+    return np.maximum(0.5 + SH_C0 * np.asarray(f_dc, np.float64), 0.0).astype(np.float32)
+
+
+def dc_from_colors(colors):
+    return ((np.asarray(colors, np.float64) - 0.5) / SH_C0).astype(np.float32)
+
+
+def load_image(images_dir, name, W, H):
+    """f32 [3,H,W] in [0, 1] of the view ``name`` (a camera name; its extension is dropped)."""
+    stem = os.path.splitext(name)[0]
+    npy = os.path.join(images_dir, stem + ".npy")
+    if os.path.exists(npy):
+        a = np.load(npy)
+        if a.shape != (3, H, W):
+            raise ValueError(f"{npy}: shape {a.shape}, but the view renders at [3, {H}, {W}]")
+        return np.ascontiguousarray(a, dtype=np.float32)
+    for ext in IMAGE_EXTS:
+        p = os.path.join(images_dir, stem + ext)
+        if os.path.exists(p):
+            from PIL import Image
+            with Image.open(p) as im:
+                im = im.convert("RGB")
+                if im.size != (W, H):
+                    im = im.resize((W, H), Image.BICUBIC)
+                a = np.asarray(im, dtype=np.uint8)
+            return np.ascontiguousarray(a.transpose(2, 0, 1).astype(np.float32) / 255.0)
+    raise FileNotFoundError(f"no image for view {name} in {images_dir} ({stem}.npy or {stem}{{.png,.jpg,.jpeg}})")
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Fit Gaussian colours / opacities / geometry to photographs (fused L1 + D-SSIM)")
+    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian) with f_dc_0..2")
+    ap.add_argument("--cam_params", required=True, help="camera_params.json")
+    ap.add_argument("--images_dir", required=True, help="<name>.png / .jpg / .npy per view")
+    ap.add_argument("--out", required=True, help="the refined .ply")
+    ap.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
+    ap.add_argument("--max_images", type=int, default=None)
+    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
+    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
+    ap.add_argument("--train", default="colors", help="comma-separated subset of " + ",".join(PARAMS))
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--views_per_step", type=int, default=4)
+    ap.add_argument("--lambda_dssim", type=float, default=0.2)
+    ap.add_argument("--lr_colors", type=float, default=0.01)
+    ap.add_argument("--lr_opacities", type=float, default=0.05)
+    ap.add_argument("--lr_scales", type=float, default=0.005)
+    ap.add_argument("--lr_quats", type=float, default=0.001)
+    ap.add_argument("--lr_means", type=float, default=0.00016)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--report", default="", help="write the per-view numbers before and after as JSON")
+    return ap
+
+
+def main(argv=None):
+    import aggregate_voxel_features_onthefly as agg
+    import gaussian_ply
+    import prepare_tensor_data as ptd
+    import splat_autograd
+    import voxproj_host
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    train = tuple(t for t in (s.strip() for s in args.train.split(",")) if t)
+    if not train or any(t not in PARAMS for t in train):
+        ap.error(f"--train takes a comma-separated subset of {','.join(PARAMS)}")
+    if args.steps < 0 or args.views_per_step < 1 or not 0.0 <= args.lambda_dssim <= 1.0:
+        ap.error("--steps must be >= 0, --views_per_step >= 1 and --lambda_dssim in [0, 1]")
+    if not torch.cuda.is_available():
+        raise RuntimeError("fit_gaussian_appearance runs on the GPU: there is no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ply = gaussian_ply.read_gaussian_ply(args.gaussians_ply, want_dc=True, want_raw=True)
+    N = int(ply["means"].shape[0])
+    by_name, cams = ptd.load_camera_params(args.cam_params)
+    names = args.views if args.views else sorted(by_name)
+    if args.max_images is not None:
+        names = names[:args.max_images]
+    if not names:
+        raise ValueError("no views to train on")
+    views = []
+    for name in names:
+        entry = by_name.get(name)
+        if entry is None:
+            raise KeyError(f"no camera entry for {name}")
+        H0, W0 = agg._image_size(entry, cams, "", name)
+        W, H = rsl.render_size(W0, H0, args.downsample_factor)
+        vm, K = rsl.camera(entry, cams, W0, H0, W, H, args.principal_point)
+        views.append((vm, K, W, H, torch.from_numpy(load_image(args.images_dir, name, W, H)).to(dev)))
+
+    # the parameters in the ply's own parametrisation; what is not trained stays a constant
+    raw = dict(colors=colors_from_dc(ply["f_dc"]), opacities=ply["opacity_logits"], scales=ply["log_scales"], quats=ply["rots"],
+               means=ply["means"])
+    p = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in raw.items()}
+    for k in train:
+        p[k] = torch.nn.Parameter(p[k])
+    fixed = {k: torch.from_numpy(ply[k]).to(dev) for k in ("opacities", "scales", "quats")}
+
+    def activated():
+        op = torch.sigmoid(p["opacities"]) if "opacities" in train else fixed["opacities"]
+        sc = torch.exp(p["scales"]) if "scales" in train else fixed["scales"]
+        qt = p["quats"] if "quats" in train else fixed["quats"]
+        return p["means"], qt, sc, op, p["colors"]
+
+    def view_loss(v, tensors):
+        vm, K, W, H, target = v
+        return splat_autograd.splat_photometric(*tensors, vm, K, W, H, target, lambda_dssim=args.lambda_dssim, check=False)
+
+    def evaluate():
+        rows = []
+        with torch.no_grad():
+            m, q, s, o, c = activated()
+            for name, (vm, K, W, H, target) in zip(names, views):
+                r = voxproj_host.splat_features(m, q, s, o, c, vm, K, W, H, want_logits=True, want_alpha=False,
+                                                want_confidence=False, check=False)
+                stats, _, _ = voxproj_host.photo_loss(r.logits, target, evaluate_only=True)
+                n = 3 * W * H
+                row = voxproj_host.image_metrics(stats, n)
+                row["loss"] = (1.0 - args.lambda_dssim) * row["l1"] + args.lambda_dssim * (1.0 - row["ssim"])
+                row["view"] = name
+                rows.append(row)
+        mean = {k: float(np.mean([r[k] for r in rows])) for k in ("loss", "psnr", "ssim", "l1")}
+        return mean, rows
+
+    def line(tag, m):
+        print(f"[FIT] {tag}: mean loss {m['loss']:.6f}, PSNR {m['psnr']:.3f} dB, SSIM {m['ssim']:.5f}, L1 {m['l1']:.6f}")
+
+    before, rows_before = evaluate()
+    print(f"[FIT] {len(views)} view(s), {N} Gaussians, training {','.join(train)}, lambda_dssim {args.lambda_dssim}")
+    line("before", before)
+    opt = torch.optim.Adam([dict(params=[p[k]], lr=getattr(args, "lr_" + k)) for k in train])
+    gen = torch.Generator().manual_seed(args.seed)
+    k = min(args.views_per_step, len(views))
+    for _ in range(args.steps):
+        pick = torch.randperm(len(views), generator=gen)[:k].tolist()
+        opt.zero_grad(set_to_none=True)
+        tensors = activated()
+        loss = 0
+        for i in pick:
+            loss = loss + view_loss(views[i], tensors)[0] / k
+        loss.backward()
+        opt.step()
+    after, rows_after = evaluate()
+    line(f"after {args.steps} step(s)", after)
+    out = {k: p[k].detach().cpu().numpy() for k in raw}
+    f_dc = dc_from_colors(out["colors"]) if "colors" in train else ply["f_dc"]
+    gaussian_ply.write_gaussian_ply(args.out, out["means"], out["opacities"], out["scales"], out["quats"], f_dc=f_dc)
+    print(f"[FIT] -> {args.out}")
+    res = dict(loss_before=before["loss"], loss_after=after["loss"])
+    for key in ("psnr", "ssim", "l1"):
+        res[key + "_before"], res[key + "_after"] = before[key], after[key]
+    if args.report:
+        with open(args.report, "w") as f:
+            json.dump(dict(summary=res, train=list(train), steps=args.steps, lambda_dssim=args.lambda_dssim,
+                           before=rows_before, after=rows_after), f, indent=1)
+    return res
+
+
+if __name__ == "__main__":
+    main()

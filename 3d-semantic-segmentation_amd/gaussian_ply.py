@@ -3,7 +3,8 @@ scenes.  No plyfile dependency: the header is parsed by hand and the vertex reco
 
 The reader follows the reference's GaussianModel.load_ply and its activations (scene/gaussian_model.py): x y z as they are,
 opacity = sigmoid(opacity), scale = exp(scale_*), rotation = normalize(rot_*) (w, x, y, z), the scale_* and rot_* fields in
-the order of their numeric suffix.  The f_dc_* / f_rest_* colour fields (and any others, normals included) are skipped.
+the order of their numeric suffix.  The f_dc_* / f_rest_* colour fields (and any others, normals included) are skipped,
+unless ``want_dc`` asks for the three f_dc_* columns (the degree-0 colour, raw: colour = 0.5 + 0.28209479 f_dc).
 Binary little-endian files only, the format 3DGS writes.
 """
 import numpy as np
@@ -51,9 +52,11 @@ def _sorted_fields(names, prefix):
     return sorted((p for p in names if p.startswith(prefix)), key=lambda p: int(p.rsplit("_", 1)[-1]))
 
 
-def read_gaussian_ply(path):
+def read_gaussian_ply(path, want_dc=False, want_raw=False):
     """dict(means f32 [N,3], quats f32 [N,4] (w,x,y,z, unit norm; a zero quaternion stays zero), scales f32 [N,3],
-    opacities f32 [N]) with the model's activations applied."""
+    opacities f32 [N]) with the model's activations applied.  ``want_dc`` adds f_dc f32 [N,3], the f_dc_0..2 columns as
+    stored; ``want_raw`` adds opacity_logits f32 [N], log_scales f32 [N,3] and rots f32 [N,4], the columns as stored (what
+    write_gaussian_ply takes, so that a field nobody changed is written back bit for bit)."""
     with open(path, "rb") as f:
         n, dt = _header(f, path)
         v = np.fromfile(f, dtype=dt, count=n)
@@ -73,8 +76,17 @@ def read_gaussian_ply(path):
     quats = rot / np.maximum(norm, 1e-12)                       # torch.nn.functional.normalize
     scales = np.exp(col(scale_f))
     op = 1.0 / (1.0 + np.exp(-v["opacity"].astype(np.float64)))
-    return dict(means=means.astype(np.float32), quats=quats.astype(np.float32), scales=scales.astype(np.float32),
-                opacities=op.astype(np.float32))
+    out = dict(means=means.astype(np.float32), quats=quats.astype(np.float32), scales=scales.astype(np.float32),
+               opacities=op.astype(np.float32))
+    if want_dc:
+        dc_f = _sorted_fields(names, "f_dc_")
+        if len(dc_f) != 3:
+            raise ValueError(f"{path}: needs f_dc_0..2 (found {dc_f})")
+        out["f_dc"] = col(dc_f).astype(np.float32)
+    if want_raw:
+        out.update(opacity_logits=v["opacity"].astype(np.float32), log_scales=col(scale_f).astype(np.float32),
+                   rots=rot.astype(np.float32))
+    return out
 
 
 def write_gaussian_ply(path, means, opacity_logits, log_scales, rots, f_dc=None):

@@ -13,7 +13,8 @@ only, with the lift (vp_splat_lift) as its backward.  ``splat_feature_loss`` is 
 against a 2D feature map (vp_feature_loss / vp_feature_loss_gradient): the gradient image is written in binary16 once, and no
 fp32 gradient image or torch reduction over an image appears on the path.  ``splat_contrastive`` is the prototype-contrastive
 loss of the splatted identity features against one view's instance mask (vp_proto_contrast / vp_proto_contrast_gradient
-between the rasterizer and its backward): no torch pass over an image.
+between the rasterizer and its backward): no torch pass over an image.  ``splat_photometric`` is the photometric loss, L1 +
+D-SSIM, of the splatted colour rows against a photograph (vp_photo_loss / vp_photo_loss_gradient in the same place).
 
 Each call keeps its own SplatWorkspace until its backward has run (the backward reads the forward's sorted intersections),
 so calls from several threads or views share no state.  The workspace is freed after the backward, or with the graph.
@@ -27,7 +28,7 @@ import voxproj_host as _host
 
 __all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians", "splat_cross_entropy", "SplatCrossEntropy",
            "splat_wide_features", "SplatWideFeatures", "quantize_gradient_map", "splat_feature_loss", "SplatFeatureLoss",
-           "splat_contrastive", "SplatContrastive"]
+           "splat_contrastive", "SplatContrastive", "splat_photometric", "SplatPhotometric"]
 
 
 class SplatFeatures(torch.autograd.Function):
@@ -403,6 +404,76 @@ def splat_contrastive(means, quats, scales, opacities, features, viewmat, K, W, 
                  phi_max=float(phi_max))
     return SplatContrastive.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), ids, count, weights,
                                   proto, float(near), float(far), float(eps2d), bool(check))
+
+
+class SplatPhotometric(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, quats, scales, opacities, colors, viewmat, K, W, H, target, lambda_dssim, near, far, eps2d, check):
+        ws = _host.SplatWorkspace()
+        m, q, s, f = means.detach(), quats.detach(), scales.detach(), colors.detach()
+        r = _host.splat_features(m, q, s, opacities.detach(), f, viewmat, K, W, H, want_logits=True, want_alpha=False,
+                                 want_confidence=False, near=near, far=far, eps2d=eps2d, workspace=ws, check=check)
+        stats, _, lws = _host.photo_loss(r.logits, target)
+        # three numbers, on the device: (1 - lambda) sum |x - y| / n + lambda (1 - sum m / n)
+        n = float(r.logits.numel())
+        loss = (1.0 - lambda_dssim) * stats[0] / n + lambda_dssim * (1.0 - stats[2] / n)
+        ctx.ws, ctx.lws = ws, lws
+        ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect), lambda_dssim)
+        ctx.maps = (r.logits, target)
+        ctx.save_for_backward(m, q, s, f)
+        ctx.mark_non_differentiable(stats)
+        return loss.float(), stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        m, q, s, f = ctx.saved_tensors
+        ws, ctx.ws = ctx.ws, None
+        lws, ctx.lws = ctx.lws, None
+        (image, target), ctx.maps = ctx.maps, None
+        viewmat, K, W, H, eps2d, cap, lambda_dssim = ctx.view
+        want_m, want_q, want_s, want_o, want_f = ctx.needs_input_grad[:5]
+        g = dict(means=None, quats=None, scales=None, opacities=None, features=None)
+        if want_m or want_q or want_s or want_o or want_f:
+            # the scale stays on the device: the kernel reads it
+            G = _host.photo_loss_gradient(image, target, lws, lambda_dssim=lambda_dssim,
+                                          grad_loss=grad_loss.float().reshape(1).contiguous())
+            if want_m or want_q or want_s:
+                g = _host.splat_rasterize_backward_geometry(m, q, s, f, viewmat, K, W, H, cap, ws, G, None, eps2d=eps2d,
+                                                            want_means=want_m, want_quats=want_q, want_scales=want_s,
+                                                            want_features=want_f, want_opacities=want_o)
+            else:
+                g["features"], g["opacities"] = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws, grad_logits=G,
+                                                                               grad_alpha=None, want_features=want_f,
+                                                                               want_opacities=want_o)
+        return (g["means"], g["quats"], g["scales"], g["opacities"], g["features"]) + (None,) * 10
+
+
+def splat_photometric(means, quats, scales, opacities, colors, viewmat, K, W, H, target, *, lambda_dssim=0.2, near=0.01,
+                      far=1e10, eps2d=0.3, check=True):
+    """The photometric loss of the splatted colour rows of one W x H view against the view's photograph: L1 + D-SSIM with
+    the 11 x 11 Gaussian window (include/voxproj.h states the contract of vp_photo_loss).
+
+      means, quats, scales, opacities, viewmat, K   as ``splat_gaussians``
+      colors f32 [N,C]                the view-independent colour rows (C = 3 for RGB; up to 64); any of the five tensors may
+                                      require grad
+      target f32 [C,H,W] on the GPU   the photograph, planar; no gradient flows to it
+
+    Returns (loss f32 0-dim = (1 - lambda_dssim) mean |x - y| + lambda_dssim (1 - mean SSIM), stats f64 [3] = {sum |x - y|,
+    sum (x - y)^2, sum SSIM}, detached; voxproj_host.image_metrics turns them into l1 / psnr / ssim).  Forward:
+    vp_splat_project, vp_splat_rasterize (the image is kept), vp_photo_loss.  Backward: vp_photo_loss_gradient writes the
+    gradient image (the upstream scalar is read on the device), then vp_splat_rasterize_backward_geometry, or
+    vp_splat_rasterize_backward when no geometry gradient is asked for.  No torch pass over an image, no double backward, no
+    gradient for the camera."""
+    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
+                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
+                              (colors, "colors"), (target, "target"))))
+    lam = float(lambda_dssim)
+    _host._require(0.0 <= lam <= 1.0, f"lambda_dssim = {lambda_dssim} outside [0, 1]")
+    if target.requires_grad:
+        raise ValueError("target requires grad, but no gradient flows to the photograph (detach it)")
+    return SplatPhotometric.apply(means, quats, scales, opacities, colors, viewmat, K, int(W), int(H), target, lam, float(near),
+                                  float(far), float(eps2d), bool(check))
 
 
 class CodebookLoss(torch.autograd.Function):

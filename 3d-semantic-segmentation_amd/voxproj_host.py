@@ -63,6 +63,7 @@ EXPORTS = [
     "vp_proto_contrast_workspace_bytes", "vp_proto_contrast", "vp_proto_contrast_gradient",
     "vp_codebook_workspace_bytes", "vp_codebook_assoc", "vp_codebook_loss",
     "vp_knn_points", "vp_neighbor_kl_workspace_bytes", "vp_neighbor_kl", "vp_neighbor_kl_gradient",
+    "vp_photo_loss_workspace_bytes", "vp_photo_loss", "vp_photo_loss_gradient",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -271,6 +272,14 @@ def lib():
                 L.vp_neighbor_kl_gradient.restype = ctypes.c_int
                 L.vp_neighbor_kl_gradient.argtypes = [vp, i64, ctypes.c_int, i64, vp, i64, vp, ctypes.c_int, vp, vp, vp, vp, vp,
                                                       ctypes.c_double, vp, vp, i64, ctypes.c_int, vp]
+            if hasattr(L, "vp_photo_loss"):  # added after ABI version 4: detected by symbol (photo_loss raises without it)
+                L.vp_photo_loss_workspace_bytes.restype = ctypes.c_size_t
+                L.vp_photo_loss_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+                L.vp_photo_loss.restype = ctypes.c_int
+                L.vp_photo_loss.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]
+                L.vp_photo_loss_gradient.restype = ctypes.c_int
+                L.vp_photo_loss_gradient.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, vp,
+                                                     ctypes.c_size_t, vp]
             L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
             L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
             L.vp_label_boundary.restype = ctypes.c_int
@@ -1384,6 +1393,90 @@ def proto_contrast_gradient(image, ids, count, workspace, *, weight_contrast=1.0
                                                float(weight_norm), _ptr(grad_loss), out.data_ptr(), workspace.ptr(),
                                                workspace.capacity(), torch.cuda.current_stream(dev).cuda_stream))
     return out
+
+
+def _photo_lib():
+    L = lib()
+    if not hasattr(L, "vp_photo_loss"):
+        raise VoxprojError(f"{LIB_PATH} has no vp_photo_loss: rebuild it (there is no fallback)")
+    return L
+
+
+def photo_loss_workspace_bytes(C, W, H):
+    """vp_photo_loss_workspace_bytes: bytes of the photometric loss's workspace for a C-channel W x H image (0 when out of
+    range).  Needs no GPU."""
+    return int(_photo_lib().vp_photo_loss_workspace_bytes(int(C), int(W), int(H)))
+
+
+def _photo_maps(caller, image, target):
+    """The rendered image and the photograph, f32 [C,H,W], contiguous on one GPU."""
+    import torch
+    _require_tensors((image, "image", (torch.float32,)), (target, "target", (torch.float32,)))
+    _require(image.dim() == 3 and image.numel() > 0, "image must be [C, H, W]")
+    C, H, W = (int(v) for v in image.shape)
+    _require(1 <= C <= 64, f"C = {C} outside [1, 64]")
+    _require(1 <= W <= 32768 and 1 <= H <= 32768, f"image size {W} x {H} outside [1, 32768]")
+    _require(tuple(target.shape) == (C, H, W) and target.device == image.device,
+             f"{caller}: target must be float32 [{C}, {H}, {W}] on the image's device")
+    return image.contiguous(), target.contiguous(), C, H, W
+
+
+def photo_loss(image, target, *, want_ssim_map=False, workspace=None, evaluate_only=False):
+    """vp_photo_loss: the L1 / squared-error / SSIM sums of a rendered image against a photograph, both f32 [C,H,W] on one
+    GPU (image: splat_features' logits).  ``workspace``: a SplatWorkspace the call fills for photo_loss_gradient (a fresh one
+    when None).  ``evaluate_only``: no workspace at all -- the same stats bits, nothing kept for a gradient, and the image is
+    walked by one workgroup.
+    Returns (stats f64 [3] = {sum |x - y|, sum (x - y)^2, sum m}, ssim_map f32 [C,H,W] or None, workspace or None); nothing
+    is read back here."""
+    import torch
+    L = _photo_lib()
+    image, target, C, H, W = _photo_maps("photo_loss", image, target)
+    dev = image.device
+    _require(not (evaluate_only and workspace is not None), "photo_loss: evaluate_only takes no workspace")
+    ws, ptr, cap = None, None, 0
+    if not evaluate_only:
+        ws = workspace if workspace is not None else SplatWorkspace()
+        ptr = ws.ensure(int(L.vp_photo_loss_workspace_bytes(C, W, H)), dev)
+        cap = ws.capacity()
+    stats = torch.empty(3, dtype=torch.float64, device=dev)
+    ssim_map = torch.empty((C, H, W), dtype=torch.float32, device=dev) if want_ssim_map else None
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_photo_loss(image.data_ptr(), target.data_ptr(), C, W, H, stats.data_ptr(), _ptr(ssim_map), ptr, cap,
+                                  torch.cuda.current_stream(dev).cuda_stream))
+    return stats, ssim_map, ws
+
+
+def photo_loss_gradient(image, target, workspace, *, lambda_dssim, grad_loss=None, out=None):
+    """vp_photo_loss_gradient after photo_loss on ``workspace`` with the same image and target: the gradient image f32
+    [C,H,W] of  (1 - lambda_dssim) mean |x - y| + lambda_dssim (1 - mean m), times ``grad_loss`` (a device f32 [1]; None: 1).
+    ``out``: a contiguous f32 [C,H,W] tensor, or None for a fresh one.  Nothing is read back here."""
+    import torch
+    L = _photo_lib()
+    image, target, C, H, W = _photo_maps("photo_loss_gradient", image, target)
+    dev = image.device
+    (grad_loss,) = _splat_images(dev, (grad_loss, "grad_loss", None, torch.float32))
+    need = int(L.vp_photo_loss_workspace_bytes(C, W, H))
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= need, "photo_loss_gradient needs the workspace of a photo_loss call")
+    if out is None:
+        out = torch.empty((C, H, W), dtype=torch.float32, device=dev)
+    _require_tensors((out, "out", (torch.float32,)))
+    _require(out.device == dev and tuple(out.shape) == (C, H, W) and out.is_contiguous(),
+             f"out must be a contiguous float32 [{C}, {H}, {W}] tensor on the image's device")
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_photo_loss_gradient(image.data_ptr(), target.data_ptr(), C, W, H, float(lambda_dssim), _ptr(grad_loss),
+                                           out.data_ptr(), workspace.ptr(), workspace.capacity(),
+                                           torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def image_metrics(stats, n):
+    """{l1, psnr, ssim} as Python floats from photo_loss's stats (a tensor or three numbers; a tensor is read back here) and
+    n = C W H.  psnr is inf for identical images."""
+    import math
+    s = [float(v) for v in (stats.tolist() if hasattr(stats, "tolist") else stats)]
+    mse = s[1] / n
+    return {"l1": s[0] / n, "psnr": -10.0 * math.log10(mse) if mse > 0.0 else math.inf, "ssim": s[2] / n}
 
 
 def _codebook_lib():

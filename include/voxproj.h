@@ -998,6 +998,63 @@ int vp_neighbor_kl_gradient(const float *logits, int64_t N, int P, int64_t row_s
                             const int32_t *smp_start, const int32_t *smp_entry, double scale, const float *grad_loss,
                             float *grad_logits, int64_t grad_stride, int lanes, void *stream);
 
+/*
+ * The photometric loss between a rendered image and a photograph, L1 + D-SSIM, and its gradient image: the two calls between
+ * vp_splat_rasterize and vp_splat_rasterize_backward(_geometry) that fit colours, opacities and geometry to photographs, the
+ * counterpart of the reference's l1_loss and ssim (utils/loss_utils.py:15-71).  Added after VP_ABI_VERSION 4 without changing
+ * it or any existing entry point; detect the three functions by symbol.  tests/photo_loss_reference.py states the contract
+ * in float64.
+ *
+ *   image, target, ssim_map, grad_image  f32 planar [C,H,W], contiguous: vp_splat_rasterize's logits and the backward's
+ *               grad_logits as they stand.  C in [1, 64], W and H in [1, 32768], 64-bit offsets, n = C W H.  Inputs must be finite.
+ *
+ * The window, per channel: w(i, j) = g[i] g[j], i, j = 0 .. 10, centred on (5, 5), with g[i] = fp32(exp(-(i - 5)^2 / 4.5))
+ *   divided by the fp32 sum of the eleven, rounded to fp32 (the reference's gaussian(11, 1.5)):
+ *     g[0] = g[10] = 0x1.0d956cp-10   g[1] = g[9] = 0x1.f1fe02p-8   g[2] = g[8] = 0x1.26eb18p-5   g[3] = g[7] = 0x1.bff0fep-4
+ *     g[4] = g[6]  = 0x1.b43c3ep-3    g[5] = 0x1.10656p-2
+ *   (The reference multiplies the two rows in fp32, so its 121 weights are these products rounded once more: a relative
+ *   difference of at most 2^-24 per weight, far inside the error bounds of an fp32 evaluation.)
+ *   Zero padding: a tap outside the image contributes nothing and the weights are not renormalised.
+ * At centre q, with x = image, y = target, C1 = 0.01^2, C2 = 0.03^2 and every sum over the window:
+ *     mu1 = sum w x,  mu2 = sum w y,  e11 = sum w x^2,  e22 = sum w y^2,  e12 = sum w x y,
+ *     s1 = e11 - mu1^2,  s2 = e22 - mu2^2,  s12 = e12 - mu1 mu2,
+ *     A1 = 2 mu1 mu2 + C1,  A2 = 2 s12 + C2,  B1 = mu1^2 + mu2^2 + C1,  B2 = s1 + s2 + C2,     m = A1 A2 / (B1 B2).
+ *   All of it fp32: the eleven taps along a row in ascending order, then the eleven row sums down a column in ascending order.
+ *
+ * vp_photo_loss:  loss_stats (device f64 [3]) = {sum |x - y|, sum (x - y)^2, sum m} over all n elements;  ssim_map f32
+ *   [C,H,W] or NULL receives m.  The caller's arithmetic on three numbers:
+ *     loss = (1 - lambda) stats[0] / n + lambda (1 - stats[2] / n),     PSNR = -10 log10(stats[1] / n).
+ *   Order: no float atomics.  The image is cut into tiles of 32 x 32 pixels per channel, tile index (c, tile row, tile column)
+ *   ascending; the fp32 terms of a tile are added in float64 by a halving tree over its 1024 pixels (pixel (tx, ty) of the
+ *   tile in slot 32 ty + tx, a pixel outside the image adding 0), then the tiles in ascending index (k_feature_loss_sum's
+ *   rule).  Bit-identical from run to run, with or without ssim_map and workspace.
+ *   workspace may be NULL: evaluation only.  The same stats bits, but the tiles are then walked by ONE workgroup, because there
+ *   is nowhere to keep a sum per tile: slow on a large image, and nothing is left for a gradient call.  Otherwise the
+ *   workspace holds vp_photo_loss_workspace_bytes and the forward leaves three f32 maps [3,C,H,W] at its start, followed
+ *   by the tiles' sums:
+ *     Q = dm/ds1 = -A1 A2 / (B1 B2^2),     R = dm/ds12 = 2 A1 / (B1 B2),
+ *     P = 2 mu2 A2 / (B1 B2) - 2 mu1 A1 A2 / (B1^2 B2) - 2 mu1 Q - mu2 R      (dm/dmu1 with e11, e12 held).
+ * vp_photo_loss_gradient: after vp_photo_loss on this workspace with the same image, target, C, W, H and stream; it only
+ *   reads the workspace.  The window is symmetric, so with * the same zero-padded convolution
+ *     d(sum m)/dx(p) = (w * P)(p) + 2 x(p) (w * Q)(p) + y(p) (w * R)(p),
+ *     grad_image[c,p] = s (a sgn(x - y) - b d(sum m)/dx(p)),   a = fp32((1 - lambda) / n),  b = fp32(lambda / n) from float64,
+ *   sgn(0) = 0, s = *grad_loss (device f32 [1], read on the device; NULL = 1).  Every element of grad_image is written.  No
+ *   gradient flows to target.
+ * vp_photo_loss_workspace_bytes: host arithmetic, 0 when C, W or H is out of range:
+ *     align256(12 n) + align256(24 C ceil(W / 32) ceil(H / 32)).  The workspace may be recycled memory.
+ * Both calls are asynchronous on `stream`, allocate nothing and do not synchronise with the host.  Traffic with a workspace:
+ *   2 n reads + 3 n writes forward (+ n with ssim_map), 5 n reads + n writes backward, of 4 bytes.
+ * Refused on the host, no GPU needed, nothing written: VP_EINVAL for a NULL image, target, loss_stats or grad_image, C, W or
+ *   H out of range, a lambda_dssim that is not finite or outside [0, 1]; VP_EWORKSPACE for a non-NULL workspace that is not
+ *   256-byte aligned or smaller than vp_photo_loss_workspace_bytes, and for a NULL workspace in the gradient call.
+ */
+size_t vp_photo_loss_workspace_bytes(int C, int W, int H);
+int vp_photo_loss(const float *image, const float *target, int C, int W, int H, double *loss_stats, float *ssim_map,
+                  void *workspace, size_t workspace_bytes, void *stream);
+int vp_photo_loss_gradient(const float *image, const float *target, int C, int W, int H, float lambda_dssim,
+                           const float *grad_loss, float *grad_image, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif
