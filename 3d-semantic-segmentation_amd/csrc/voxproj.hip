@@ -47,6 +47,7 @@
 //   vp_knn.h           the k nearest other points of every query on the bucketed grid (k_knn_points)
 //   vp_reg3d.h         the 3D neighbourhood regulariser: KL divergence to the nearest neighbours' distributions, and its gradient
 //   vp_photo_loss.h    photometric loss (L1 + D-SSIM) of a rendered image against a photograph, and its gradient image
+//   vp_densify.h       adaptive density control: per-view statistics, the clone / split / prune plan, the row gather, the split
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -87,6 +88,7 @@
 #include "vp_knn.h"
 #include "vp_reg3d.h"
 #include "vp_photo_loss.h"
+#include "vp_densify.h"
 #include "vp_project.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1337,6 +1339,150 @@ int vp_photo_loss_gradient(const float *image, const float *target, int C, int W
     const float a = (float)((1.0 - (double)lambda_dssim) / n), b = (float)((double)lambda_dssim / n);
     hipLaunchKernelGGL(k_photo_loss_gradient, dim3((unsigned)photo_tiles_x(W), (unsigned)photo_tiles_x(H), (unsigned)C),
                        dim3(PHOTO_THREADS), 0, stream, image, target, W, H, (const float *)workspace, a, b, grad_loss, grad_image);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Adaptive density control (vp_densify.h).  Every check is host arithmetic and comes before the first launch.
+// ------------------------------------------------------------------------------------------------
+int vp_densify_accumulate(const float *grad_screen, int64_t n_gaussians, int W, int H, float scale, const float *means,
+                          const float *quats, const float *scales, const float *viewmat, float fx, float fy, float cx, float cy,
+                          float eps2d, float *grad_accum, int32_t *denom, float *max_radius, const void *workspace,
+                          size_t workspace_bytes, void *stream_)
+{
+    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (int rc = splat_check_image(W, H)) return rc;
+    if (n_gaussians > 0 && (!grad_screen || !grad_accum || !denom))
+        return fail(VP_EINVAL, "null pointer argument (grad_screen, grad_accum or denom)");
+    if (!std::isfinite(scale)) return fail(VP_EINVAL, "scale = %g is not finite", (double)scale);
+    SplatCam cam = {};
+    if (max_radius) {
+        if (n_gaussians > 0 && (!means || !quats || !scales))
+            return fail(VP_EINVAL, "null pointer argument (means, quats or scales, needed by max_radius)");
+        if (int rc = splat_check_camera(viewmat, fx, fy, cx, cy, cam)) return rc;
+        if (!(eps2d >= 0.0f) || !std::isfinite(eps2d)) return fail(VP_EINVAL, "need a finite eps2d >= 0 (got %g)", (double)eps2d);
+        cam.eps2d = eps2d;
+        cam.W = W; cam.H = H;
+    }
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    SplatLayout l;
+    if (!splat_layout(n_gaussians, W, H, 0, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (n_gaussians == 0) return VP_OK;
+    const double hw = 0.5 * (double)W, hh = 0.5 * (double)H;
+    hipLaunchKernelGGL(k_densify_accumulate, dim3((unsigned)((n_gaussians + DENSIFY_THREADS - 1) / DENSIFY_THREADS)),
+                       dim3(DENSIFY_THREADS), 0, (hipStream_t)stream_, grad_screen, (long long)n_gaussians, hw * hw, hh * hh,
+                       (double)scale, means, quats, scales, cam, (const int *)((const char *)workspace + l.count), grad_accum,
+                       (int *)denom, max_radius);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+size_t vp_densify_plan_workspace_bytes(int64_t n_gaussians)
+{
+    if (n_gaussians < 0 || n_gaussians > DENSIFY_MAX_N) return 0;
+    DensifyLayout l;
+    return densify_layout(n_gaussians, l) ? l.bytes : 0;
+}
+
+int vp_densify_plan(const float *grad_accum, const int32_t *denom, const float *max_radius, const float *scales,
+                    const float *opacities, int64_t n_gaussians, float grad_threshold, float size_threshold, float min_opacity,
+                    float max_screen_size, float max_world_size, int32_t *src, uint8_t *kind, int64_t *counts, void *workspace,
+                    size_t workspace_bytes, void *stream_)
+{
+    if (n_gaussians < 0 || n_gaussians > DENSIFY_MAX_N)
+        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^30]", (long long)n_gaussians);
+    if (!counts) return fail(VP_EINVAL, "null pointer argument (counts)");
+    if (n_gaussians > 0 && (!grad_accum || !denom || !scales || !opacities || !src || !kind))
+        return fail(VP_EINVAL, "null pointer argument (grad_accum, denom, scales, opacities, src or kind)");
+    if (!(grad_threshold > 0.0f)) return fail(VP_EINVAL, "grad_threshold must be > 0 (got %g)", (double)grad_threshold);
+    if (std::isnan(size_threshold) || std::isnan(min_opacity) || std::isnan(max_screen_size) || std::isnan(max_world_size))
+        return fail(VP_EINVAL, "size_threshold, min_opacity, max_screen_size and max_world_size must not be NaN");
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    DensifyLayout l;
+    if (!densify_layout(n_gaussians, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    unsigned char *flags = (unsigned char *)(ws + l.flags);
+    DensifyCnt *sums = (DensifyCnt *)(ws + l.sums);
+    const unsigned grid = (unsigned)((std::max<long long>(n_gaussians, 1) + DENSIFY_THREADS - 1) / DENSIFY_THREADS);
+    if (n_gaussians > 0) {
+        const DensifyRule rule = {grad_threshold, size_threshold, min_opacity, max_screen_size, max_world_size};
+        hipLaunchKernelGGL(k_densify_decide, dim3(grid), dim3(DENSIFY_THREADS), 0, stream, grad_accum, (const int *)denom,
+                           max_radius, scales, opacities, (long long)n_gaussians, rule, flags);
+        VP_HIP(hipGetLastError());
+        size_t tmp = l.scan_bytes;
+        VP_HIP(rocprim::inclusive_scan(ws + l.scan_tmp, tmp, DensifyFlagIter(flags, DensifyWiden()), sums, (size_t)n_gaussians,
+                                       DensifyPlus(), stream));
+    }
+    hipLaunchKernelGGL(k_densify_emit, dim3(grid), dim3(DENSIFY_THREADS), 0, stream, (const unsigned char *)flags,
+                       (const DensifyCnt *)sums, (long long)n_gaussians, (int *)src, (unsigned char *)kind, (long long *)counts);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+static int densify_check_rows(const int32_t *src, const uint8_t *kind, const int64_t *counts, int64_t n_src, int64_t n_out)
+{
+    if (!counts) return fail(VP_EINVAL, "null pointer argument (counts)");
+    if (n_src < 0 || n_src > DENSIFY_MAX_N) return fail(VP_EINVAL, "n_src = %lld outside [0, 2^30]", (long long)n_src);
+    if (n_out < 0 || n_out > 2 * n_src) return fail(VP_EINVAL, "n_out = %lld outside [0, 2 n_src]", (long long)n_out);
+    if (n_out > 0 && (!src || !kind)) return fail(VP_EINVAL, "null pointer argument (src or kind)");
+    return VP_OK;
+}
+
+int vp_densify_rows(const vp_densify_array *arrays, int n_arrays, const int32_t *src, const uint8_t *kind,
+                    const int64_t *counts, int64_t n_src, int64_t n_out, int32_t *status, void *stream_)
+{
+    if (!arrays) return fail(VP_EINVAL, "null pointer argument (arrays)");
+    if (n_arrays < 1 || n_arrays > VP_DENSIFY_MAX_ARRAYS)
+        return fail(VP_EINVAL, "n_arrays = %d outside [1, %d]", n_arrays, VP_DENSIFY_MAX_ARRAYS);
+    if (int rc = densify_check_rows(src, kind, counts, n_src, n_out)) return rc;
+    DensifyRowsArgs A = {};
+    A.n = n_arrays;
+    int blocks = 0;
+    for (int a = 0; a < n_arrays; ++a) {
+        const vp_densify_array &d = arrays[a];
+        if (d.width < 1 || d.width > VP_DENSIFY_MAX_WIDTH)
+            return fail(VP_EINVAL, "array %d: width = %d outside [1, %d]", a, d.width, VP_DENSIFY_MAX_WIDTH);
+        if (d.src_stride < d.width || d.dst_stride < d.width)
+            return fail(VP_EINVAL, "array %d: a stride (%lld, %lld) is below the width %d", a, (long long)d.src_stride,
+                        (long long)d.dst_stride, d.width);
+        if (d.fill != VP_DENSIFY_COPY && d.fill != VP_DENSIFY_ZERO)
+            return fail(VP_EINVAL, "array %d: fill = %d is neither VP_DENSIFY_COPY nor VP_DENSIFY_ZERO", a, d.fill);
+        if ((n_src > 0 && !d.src) || (n_out > 0 && !d.dst)) return fail(VP_EINVAL, "array %d: null pointer (src or dst)", a);
+        if (((uintptr_t)d.src | (uintptr_t)d.dst) & 3) return fail(VP_EINVAL, "array %d: src and dst must be 4-byte aligned", a);
+        const bool vec = d.width % 4 == 0 && d.src_stride % 4 == 0 && d.dst_stride % 4 == 0 &&
+                         (((uintptr_t)d.src | (uintptr_t)d.dst) & 15) == 0;
+        A.a[a] = d;
+        A.vec[a] = vec;
+        A.lg[a] = (unsigned char)densify_pick_lanes(vec ? d.width / 4 : d.width);
+        const long long rpb = (long long)(DENSIFY_THREADS >> A.lg[a]) * DENSIFY_ROWS_IN_FLIGHT;   // rows per workgroup and round
+        A.blk_start[a] = blocks;
+        blocks += (int)std::min<long long>(std::max<long long>((n_out + rpb - 1) / rpb, 1), DENSIFY_MAX_BLOCKS);
+    }
+    A.blk_start[n_arrays] = blocks;
+    hipLaunchKernelGGL(k_densify_rows, dim3((unsigned)blocks), dim3(DENSIFY_THREADS), 0, (hipStream_t)stream_, A,
+                       (const int *)src, (const unsigned char *)kind, (const long long *)counts, (long long)n_src,
+                       (long long)n_out, (int *)status);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_densify_split(const float *means, const float *quats, const float *log_scales, int64_t n_src, const int32_t *src,
+                     const uint8_t *kind, const int64_t *counts, int64_t n_out, uint64_t seed, float *out_means,
+                     float *out_log_scales, int32_t *status, void *stream_)
+{
+    if (int rc = densify_check_rows(src, kind, counts, n_src, n_out)) return rc;
+    if (n_src > 0 && (!means || !quats || !log_scales))
+        return fail(VP_EINVAL, "null pointer argument (means, quats or log_scales)");
+    if (n_out > 0 && (!out_means || !out_log_scales)) return fail(VP_EINVAL, "null pointer argument (out_means or out_log_scales)");
+    const unsigned grid = (unsigned)((std::max<long long>(n_out, 1) + DENSIFY_THREADS - 1) / DENSIFY_THREADS);
+    hipLaunchKernelGGL(k_densify_split, dim3(grid), dim3(DENSIFY_THREADS), 0, (hipStream_t)stream_, means, quats, log_scales,
+                       (long long)n_src, (const int *)src, (const unsigned char *)kind, (const long long *)counts,
+                       (long long)n_out, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out_means, out_log_scales,
+                       (int *)status);
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

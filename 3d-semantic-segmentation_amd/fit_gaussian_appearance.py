@@ -6,14 +6,26 @@ utils/loss_utils.py:15-71), every view one fused call (splat_autograd.splat_phot
       [--views NAME ...] [--max_images N] [--downsample_factor F] [--principal_point center|camera]
       [--train colors,opacities,scales,quats,means] [--steps 200] [--views_per_step 4] [--lambda_dssim 0.2]
       [--lr_colors 0.01] [--lr_opacities 0.05] [--lr_scales 0.005] [--lr_quats 0.001] [--lr_means 0.00016] [--seed 0]
+      [--densify_interval 0] [--densify_from 500] [--densify_until 15000] [--densify_grad_threshold 0.0002]
+      [--percent_dense 0.01] [--min_opacity 0.005] [--opacity_reset_interval 0] [--max_screen_size 0] [--scene_extent E]
       [--report REPORT.json]
 
 Appearance is one view-independent colour row per Gaussian: it starts at max(0, 0.5 + 0.28209479 f_dc), the reference's
 degree-0 colour, is trained as a row, and is written back as f_dc = (c - 0.5) / 0.28209479.  Higher-order f_rest_* fields are
 neither read nor written; there is no background colour.  --train picks the parameters (default: colors).  Opacities and
 scales are trained through the ply's raw parametrisation (sigmoid, exp) in torch, quaternions raw (the splatter normalises
-them), means as they are.  A field that is not trained is written back bit for bit.  No densification, pruning or opacity
-reset.
+them), means as they are.  Without densification a field that is not trained is written back bit for bit.
+
+Adaptive density control (the reference's train_unified_lift.py:463-473, scene/gaussian_model.py:399-608) is off by default.
+--densify_interval K turns it on: every view's backward adds its screen-space gradient norms to the statistics
+(vp_densify_accumulate behind splat_photometric), and every K steps after --densify_from and up to --densify_until one plan
+(vp_densify_plan) clones the small Gaussians whose mean gradient reaches --densify_grad_threshold, splits the large ones
+(larger than --percent_dense x extent) into two children and prunes those below --min_opacity; with --max_screen_size S > 0
+and once the step is past --opacity_reset_interval it also prunes Gaussians wider than S pixels in some view or larger than
+0.1 x extent.  The extent is --scene_extent, by default 1.1 x the largest distance of a training camera from their mean.
+All five arrays are then resampled in their raw parametrisation (vp_densify_rows, vp_densify_split with the seed
+(--seed, step)), trained or not; Adam's moments follow (kept rows bit for bit, new rows zero) and the statistics start over.
+--opacity_reset_interval R sets raw opacity = min(raw, logit(0.01)) every R steps and zeroes that parameter's moments.
 
 Images are paired with the cameras by name, the camera's file extension dropped: DIR/<name>.png / .jpg / .jpeg through PIL
 (8-bit RGB, / 255; resized to the render size when it differs), or DIR/<name>.npy, f32 [3,H,W] at the render size.
@@ -89,8 +101,29 @@ def build_parser():
     ap.add_argument("--lr_quats", type=float, default=0.001)
     ap.add_argument("--lr_means", type=float, default=0.00016)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--densify_interval", type=int, default=0, help="densify every K steps (0: off)")
+    ap.add_argument("--densify_from", type=int, default=500, help="first densification after this step")
+    ap.add_argument("--densify_until", type=int, default=15000, help="no statistics or densification from this step on")
+    ap.add_argument("--densify_grad_threshold", type=float, default=0.0002)
+    ap.add_argument("--percent_dense", type=float, default=0.01)
+    ap.add_argument("--min_opacity", type=float, default=0.005)
+    ap.add_argument("--opacity_reset_interval", type=int, default=0, help="reset opacities every R steps (0: never)")
+    ap.add_argument("--max_screen_size", type=float, default=0.0, help="prune Gaussians wider than this in pixels (0: off)")
+    ap.add_argument("--scene_extent", type=float, default=None, help="default: the extent of the training cameras")
     ap.add_argument("--report", default="", help="write the per-view numbers before and after as JSON")
     return ap
+
+
+def check_densify_args(ap, args):
+    """Refuse bad values of the densification options (ap.error: exit status 2)."""
+    if args.densify_interval < 0 or args.opacity_reset_interval < 0:
+        ap.error("--densify_interval and --opacity_reset_interval must be >= 0")
+    if args.densify_from < 0 or args.densify_from >= args.densify_until:
+        ap.error("need 0 <= --densify_from < --densify_until")
+    if not args.densify_grad_threshold > 0.0 or not args.percent_dense > 0.0 or not args.min_opacity > 0.0:
+        ap.error("--densify_grad_threshold, --percent_dense and --min_opacity must be > 0")
+    if not args.max_screen_size >= 0.0 or (args.scene_extent is not None and not args.scene_extent > 0.0):
+        ap.error("--max_screen_size must be >= 0 and --scene_extent > 0")
 
 
 def main(argv=None):
@@ -106,6 +139,8 @@ def main(argv=None):
         ap.error(f"--train takes a comma-separated subset of {','.join(PARAMS)}")
     if args.steps < 0 or args.views_per_step < 1 or not 0.0 <= args.lambda_dssim <= 1.0:
         ap.error("--steps must be >= 0, --views_per_step >= 1 and --lambda_dssim in [0, 1]")
+    check_densify_args(ap, args)
+    densify_on = args.densify_interval > 0
     if not torch.cuda.is_available():
         raise RuntimeError("fit_gaussian_appearance runs on the GPU: there is no CPU path")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -141,9 +176,44 @@ def main(argv=None):
         qt = p["quats"] if "quats" in train else fixed["quats"]
         return p["means"], qt, sc, op, p["colors"]
 
-    def view_loss(v, tensors):
+    def view_loss(v, tensors, stats=None, stats_scale=1.0):
         vm, K, W, H, target = v
-        return splat_autograd.splat_photometric(*tensors, vm, K, W, H, target, lambda_dssim=args.lambda_dssim, check=False)
+        return splat_autograd.splat_photometric(*tensors, vm, K, W, H, target, lambda_dssim=args.lambda_dssim, check=False,
+                                                densify_stats=stats, stats_scale=stats_scale)
+
+    def densify(step, opt, stats):
+        """One plan, every array and Adam moment resampled by it: the [FIT] record of the densification."""
+        with torch.no_grad():
+            screen = args.max_screen_size if step > args.opacity_reset_interval else 0.0
+            plan = voxproj_host.densify_plan(stats, torch.exp(p["scales"]), torch.sigmoid(p["opacities"]),
+                                             grad_threshold=args.densify_grad_threshold,
+                                             size_threshold=float(np.float32(args.percent_dense * extent)),
+                                             min_opacity=args.min_opacity, max_screen_size=screen,
+                                             max_world_size=float(np.float32(0.1 * extent)))
+            new = plan.resample({k: (p[k], "copy") for k in ("colors", "opacities", "quats")})
+            new["means"], new["scales"] = plan.split_geometry(p["means"], p["quats"], p["scales"], (args.seed, step))
+            old = {k: p[k] for k in train}
+            for k in PARAMS:
+                p[k] = torch.nn.Parameter(new[k]) if k in train else new[k]
+            voxproj_host.resample_adam(opt, old, {k: p[k] for k in train}, plan)
+            fixed.update(opacities=torch.sigmoid(p["opacities"]).detach(), scales=torch.exp(p["scales"]).detach(),
+                         quats=p["quats"].detach())
+            stats.reset(plan.n_out)
+        rec = dict(step=step, n_before=plan.n, n_after=plan.n_out, kept=plan.kept, clones=plan.clones, split=plan.split,
+                   pruned=plan.n - plan.kept - plan.split)
+        print(f"[FIT] densify at step {step}: {rec['n_before']} -> {rec['n_after']} Gaussians (kept {rec['kept']}, clones "
+              f"{rec['clones']}, split sources {rec['split']}, pruned {rec['pruned']})")
+        return rec
+
+    def reset_opacity(opt):
+        """raw opacity = min(raw, logit(0.01)); that parameter's moments start over."""
+        with torch.no_grad():
+            p["opacities"].clamp_(max=float(np.log(0.01 / 0.99)))
+            st = opt.state.get(p["opacities"]) if "opacities" in train else None
+            for key in ("exp_avg", "exp_avg_sq"):
+                if st and key in st:
+                    st[key].zero_()
+            fixed["opacities"] = torch.sigmoid(p["opacities"]).detach()
 
     def evaluate():
         rows = []
@@ -170,28 +240,40 @@ def main(argv=None):
     opt = torch.optim.Adam([dict(params=[p[k]], lr=getattr(args, "lr_" + k)) for k in train])
     gen = torch.Generator().manual_seed(args.seed)
     k = min(args.views_per_step, len(views))
-    for _ in range(args.steps):
+    extent = args.scene_extent if args.scene_extent is not None else voxproj_host.camera_extent([v[0] for v in views])
+    stats = voxproj_host.DensifyStats(N, dev, want_radius=args.max_screen_size > 0.0) if densify_on else None
+    densifications = []
+    for step in range(1, args.steps + 1):
         pick = torch.randperm(len(views), generator=gen)[:k].tolist()
         opt.zero_grad(set_to_none=True)
         tensors = activated()
         loss = 0
+        collect = stats if densify_on and step < args.densify_until else None
         for i in pick:
-            loss = loss + view_loss(views[i], tensors)[0] / k
+            loss = loss + view_loss(views[i], tensors, collect, float(k))[0] / k
         loss.backward()
         opt.step()
+        if collect is not None and step > args.densify_from and step % args.densify_interval == 0:
+            opt.zero_grad(set_to_none=True)
+            densifications.append(densify(step, opt, stats))
+        if args.opacity_reset_interval > 0 and step % args.opacity_reset_interval == 0:
+            reset_opacity(opt)
     after, rows_after = evaluate()
     line(f"after {args.steps} step(s)", after)
+    n_after = int(p["means"].shape[0])
+    if densify_on:
+        print(f"[FIT] {N} -> {n_after} Gaussians in {len(densifications)} densification(s), extent {extent:.6g}")
     out = {k: p[k].detach().cpu().numpy() for k in raw}
-    f_dc = dc_from_colors(out["colors"]) if "colors" in train else ply["f_dc"]
+    f_dc = dc_from_colors(out["colors"]) if "colors" in train or densifications else ply["f_dc"]
     gaussian_ply.write_gaussian_ply(args.out, out["means"], out["opacities"], out["scales"], out["quats"], f_dc=f_dc)
     print(f"[FIT] -> {args.out}")
-    res = dict(loss_before=before["loss"], loss_after=after["loss"])
+    res = dict(loss_before=before["loss"], loss_after=after["loss"], n_before=N, n_after=n_after)
     for key in ("psnr", "ssim", "l1"):
         res[key + "_before"], res[key + "_after"] = before[key], after[key]
     if args.report:
         with open(args.report, "w") as f:
             json.dump(dict(summary=res, train=list(train), steps=args.steps, lambda_dssim=args.lambda_dssim,
-                           before=rows_before, after=rows_after), f, indent=1)
+                           before=rows_before, after=rows_after, densify=densifications), f, indent=1)
     return res
 
 

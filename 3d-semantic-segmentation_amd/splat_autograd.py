@@ -408,11 +408,13 @@ def splat_contrastive(means, quats, scales, opacities, features, viewmat, K, W, 
 
 class SplatPhotometric(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means, quats, scales, opacities, colors, viewmat, K, W, H, target, lambda_dssim, near, far, eps2d, check):
+    def forward(ctx, means, quats, scales, opacities, colors, viewmat, K, W, H, target, lambda_dssim, near, far, eps2d, check,
+                densify_stats, stats_scale):
         ws = _host.SplatWorkspace()
         m, q, s, f = means.detach(), quats.detach(), scales.detach(), colors.detach()
         r = _host.splat_features(m, q, s, opacities.detach(), f, viewmat, K, W, H, want_logits=True, want_alpha=False,
                                  want_confidence=False, near=near, far=far, eps2d=eps2d, workspace=ws, check=check)
+        ctx.densify = (densify_stats, float(stats_scale))
         stats, _, lws = _host.photo_loss(r.logits, target)
         # three numbers, on the device: (1 - lambda) sum |x - y| / n + lambda (1 - sum m / n)
         n = float(r.logits.numel())
@@ -438,19 +440,25 @@ class SplatPhotometric(torch.autograd.Function):
             # the scale stays on the device: the kernel reads it
             G = _host.photo_loss_gradient(image, target, lws, lambda_dssim=lambda_dssim,
                                           grad_loss=grad_loss.float().reshape(1).contiguous())
-            if want_m or want_q or want_s:
+            dstats, dscale = ctx.densify
+            if want_m or want_q or want_s or dstats is not None:
+                # with statistics the same sweep also hands out the screen-space sums (its world-space outputs may all be NULL)
                 g = _host.splat_rasterize_backward_geometry(m, q, s, f, viewmat, K, W, H, cap, ws, G, None, eps2d=eps2d,
                                                             want_means=want_m, want_quats=want_q, want_scales=want_s,
-                                                            want_features=want_f, want_opacities=want_o)
+                                                            want_features=want_f, want_opacities=want_o,
+                                                            want_screen=dstats is not None)
+                if dstats is not None:
+                    _host.densify_accumulate(dstats, g["screen"], ws, W, H, scale=dscale,
+                                             geometry=(m, q, s, viewmat, K, eps2d))
             else:
                 g["features"], g["opacities"] = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws, grad_logits=G,
                                                                                grad_alpha=None, want_features=want_f,
                                                                                want_opacities=want_o)
-        return (g["means"], g["quats"], g["scales"], g["opacities"], g["features"]) + (None,) * 10
+        return (g["means"], g["quats"], g["scales"], g["opacities"], g["features"]) + (None,) * 12
 
 
 def splat_photometric(means, quats, scales, opacities, colors, viewmat, K, W, H, target, *, lambda_dssim=0.2, near=0.01,
-                      far=1e10, eps2d=0.3, check=True):
+                      far=1e10, eps2d=0.3, check=True, densify_stats=None, stats_scale=1.0):
     """The photometric loss of the splatted colour rows of one W x H view against the view's photograph: L1 + D-SSIM with
     the 11 x 11 Gaussian window (include/voxproj.h states the contract of vp_photo_loss).
 
@@ -464,7 +472,12 @@ def splat_photometric(means, quats, scales, opacities, colors, viewmat, K, W, H,
     vp_splat_project, vp_splat_rasterize (the image is kept), vp_photo_loss.  Backward: vp_photo_loss_gradient writes the
     gradient image (the upstream scalar is read on the device), then vp_splat_rasterize_backward_geometry, or
     vp_splat_rasterize_backward when no geometry gradient is asked for.  No torch pass over an image, no double backward, no
-    gradient for the camera."""
+    gradient for the camera.
+
+    ``densify_stats``: a voxproj_host.DensifyStats.  The backward then runs the geometry backward (also when only the colours
+    or opacities require grad), asks it for the screen-space sums as well and adds the view to the statistics
+    (vp_densify_accumulate) with ``stats_scale``, which undoes the 1 / k of a step that averages k views.  The loss and the
+    gradients are bit-identical with and without it; with None the call sequence is unchanged."""
     _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
                              ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
                               (colors, "colors"), (target, "target"))))
@@ -472,8 +485,11 @@ def splat_photometric(means, quats, scales, opacities, colors, viewmat, K, W, H,
     _host._require(0.0 <= lam <= 1.0, f"lambda_dssim = {lambda_dssim} outside [0, 1]")
     if target.requires_grad:
         raise ValueError("target requires grad, but no gradient flows to the photograph (detach it)")
+    _host._require(densify_stats is None or
+                   (isinstance(densify_stats, _host.DensifyStats) and densify_stats.n == int(means.shape[0])),
+                   "densify_stats must be a voxproj_host.DensifyStats of the cloud's size")
     return SplatPhotometric.apply(means, quats, scales, opacities, colors, viewmat, K, int(W), int(H), target, lam, float(near),
-                                  float(far), float(eps2d), bool(check))
+                                  float(far), float(eps2d), bool(check), densify_stats, float(stats_scale))
 
 
 class CodebookLoss(torch.autograd.Function):

@@ -64,6 +64,7 @@ EXPORTS = [
     "vp_codebook_workspace_bytes", "vp_codebook_assoc", "vp_codebook_loss",
     "vp_knn_points", "vp_neighbor_kl_workspace_bytes", "vp_neighbor_kl", "vp_neighbor_kl_gradient",
     "vp_photo_loss_workspace_bytes", "vp_photo_loss", "vp_photo_loss_gradient",
+    "vp_densify_accumulate", "vp_densify_plan_workspace_bytes", "vp_densify_plan", "vp_densify_rows", "vp_densify_split",
 ]
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
@@ -77,6 +78,10 @@ VP_LOSS_SUM = 0
 VP_LOSS_MEAN = 1
 VP_FEATURE_LOSS_COSINE = 0
 VP_FEATURE_LOSS_L2 = 1
+VP_DENSIFY_MAX_ARRAYS = 16
+VP_DENSIFY_MAX_WIDTH = 4096
+VP_DENSIFY_COPY = 0
+VP_DENSIFY_ZERO = 1
 
 
 class VoxprojError(RuntimeError):
@@ -280,6 +285,20 @@ def lib():
                 L.vp_photo_loss_gradient.restype = ctypes.c_int
                 L.vp_photo_loss_gradient.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, vp,
                                                      ctypes.c_size_t, vp]
+            if hasattr(L, "vp_densify_plan"):  # added after ABI version 4: detected by symbol (densify_* raise without it)
+                f32, i64 = ctypes.c_float, ctypes.c_int64
+                L.vp_densify_accumulate.restype = ctypes.c_int
+                L.vp_densify_accumulate.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int, f32, vp, vp, vp, vp, f32, f32, f32, f32,
+                                                    f32, vp, vp, vp, vp, ctypes.c_size_t, vp]
+                L.vp_densify_plan_workspace_bytes.restype = ctypes.c_size_t
+                L.vp_densify_plan_workspace_bytes.argtypes = [i64]
+                L.vp_densify_plan.restype = ctypes.c_int
+                L.vp_densify_plan.argtypes = [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp, vp, vp, ctypes.c_size_t,
+                                              vp]
+                L.vp_densify_rows.restype = ctypes.c_int
+                L.vp_densify_rows.argtypes = [vp, ctypes.c_int, vp, vp, vp, i64, i64, vp, vp]
+                L.vp_densify_split.restype = ctypes.c_int
+                L.vp_densify_split.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, ctypes.c_uint64, vp, vp, vp, vp]
             L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
             L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
             L.vp_label_boundary.restype = ctypes.c_int
@@ -1477,6 +1496,221 @@ def image_metrics(stats, n):
     s = [float(v) for v in (stats.tolist() if hasattr(stats, "tolist") else stats)]
     mse = s[1] / n
     return {"l1": s[0] / n, "psnr": -10.0 * math.log10(mse) if mse > 0.0 else math.inf, "ssim": s[2] / n}
+
+
+class _DensifyArray(ctypes.Structure):
+    """vp_densify_array of include/voxproj.h."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("width", ctypes.c_int32), ("fill", ctypes.c_int32),
+                ("src_stride", ctypes.c_int64), ("dst_stride", ctypes.c_int64)]
+
+
+_DENSIFY_FILLS = {"copy": VP_DENSIFY_COPY, "zero": VP_DENSIFY_ZERO}
+
+
+def _densify_lib():
+    L = lib()
+    if not hasattr(L, "vp_densify_plan"):
+        raise VoxprojError(f"{LIB_PATH} has no vp_densify_plan: rebuild it (there is no fallback)")
+    return L
+
+
+def camera_extent(viewmats):
+    """1.1 max |c_i - mean c| over the camera centres c = -R^T t of world-to-camera matrices [V,4,4] (any device, read on the
+    host, float64): the reference's cameras_extent, the length the densification's size thresholds are stated in."""
+    import numpy as np
+    import torch
+    vm = np.stack([torch.as_tensor(v, dtype=torch.float64).detach().cpu().numpy().reshape(4, 4) for v in viewmats])
+    c = -np.einsum("nji,nj->ni", vm[:, :3, :3], vm[:, :3, 3])
+    return float(1.1 * np.linalg.norm(c - c.mean(0), axis=1).max())
+
+
+class DensifyStats:
+    """The running statistics of adaptive density control for n Gaussians on ``device``: grad_accum f32 [n], denom i32 [n]
+    and, with ``want_radius``, max_radius f32 [n] (None otherwise).  ``reset(n)`` starts over at a new size."""
+
+    def __init__(self, n, device, want_radius=False):
+        self.device = device
+        self.want_radius = bool(want_radius)
+        self.reset(n)
+
+    def reset(self, n):
+        import torch
+        self.n = int(n)
+        self.grad_accum = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        self.denom = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self.max_radius = torch.zeros(self.n, dtype=torch.float32, device=self.device) if self.want_radius else None
+
+
+def densify_accumulate(stats, grad_screen, workspace, W, H, scale=1.0, geometry=None):
+    """vp_densify_accumulate: add one view to ``stats``.  grad_screen f32 [N,5] from the geometry backward of the view
+    (want_screen=True), ``workspace`` the SplatWorkspace of its splat_project / splat_rasterize (only read); ``scale`` undoes a
+    caller's 1 / k.  ``geometry``: (means, quats, scales, viewmat, K) or (..., eps2d) of the project call, needed when the
+    stats keep max_radius and ignored otherwise.  Asynchronous; nothing is read back."""
+    import torch
+    L = _densify_lib()
+    _require_tensors((grad_screen, "grad_screen", (torch.float32,)))
+    N = stats.n
+    dev = grad_screen.device
+    _require(tuple(grad_screen.shape) == (N, 5) and grad_screen.is_contiguous(), f"grad_screen must be a contiguous [{N}, 5]")
+    _require(stats.grad_accum.device == dev, "the statistics and grad_screen must be on one device")
+    _require(1 <= int(W) <= 32768 and 1 <= int(H) <= 32768, f"image size {W} x {H} outside [1, 32768]")
+    need = int(L.vp_splat_workspace_bytes(N, int(W), int(H), 0))
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= need, "densify_accumulate needs the workspace of a splat_project call")
+    m = q = s = vm = None
+    fx = fy = cx = cy = 0.0
+    eps2d = 0.3
+    if stats.max_radius is not None:
+        _require(geometry is not None and len(geometry) in (5, 6),
+                 "densify_accumulate: statistics with max_radius need geometry = (means, quats, scales, viewmat, K[, eps2d])")
+        _, (m, q, s) = _splat_gaussians(geometry[0].detach(), geometry[1].detach(), geometry[2].detach(), dev=dev)
+        _require(int(m.shape[0]) == N, f"the geometry must have {N} Gaussians")
+        vm, (fx, fy, cx, cy) = _splat_camera(geometry[3], geometry[4], W, H)
+        if len(geometry) == 6:
+            eps2d = float(geometry[5])
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_densify_accumulate(_ptr(grad_screen), N, int(W), int(H), float(scale), _ptr(m), _ptr(q), _ptr(s), vm, fx,
+                                          fy, cx, cy, eps2d, _ptr(stats.grad_accum), _ptr(stats.denom), _ptr(stats.max_radius),
+                                          workspace.ptr(), workspace.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+
+
+def densify_rows(arrays, src, kind, counts, n_src, n_out, status=None):
+    """vp_densify_rows, at most 16 arrays per launch (more are sent in several): ``arrays`` is a list of (src tensor, dst
+    tensor, fill) with 32-bit tensors whose rows are the first dimension: contiguous, or 2-D with a unit element stride and a
+    row stride >= the width.  dst row r = src row src[r] (zeros where fill is "zero" and kind[r] != 0).  ``n_out`` is the
+    host's copy of counts[0]; when the device disagrees nothing is written and ``status`` (device int32 [1]) becomes 1."""
+    import torch
+    L = _densify_lib()
+    descs = []
+    for a, d, fill in arrays:
+        _require_tensors((a, "a source array", (torch.float32, torch.int32)), (d, "a destination array", (a.dtype,)))
+        _require(fill in _DENSIFY_FILLS, f"fill must be 'copy' or 'zero', not {fill!r}")
+        _require(a.dim() >= 1 and d.dim() == a.dim() and int(a.shape[0]) == int(n_src) and int(d.shape[0]) == int(n_out) and
+                 tuple(a.shape[1:]) == tuple(d.shape[1:]) and a.device == src.device and d.device == src.device,
+                 "an array must be [n_src, ...] and its destination [n_out, ...] with the same row shape, on the plan's device")
+        width = 1
+        for v in a.shape[1:]:
+            width *= int(v)
+        strides = []
+        for t in (a, d):
+            if t.is_contiguous():
+                strides.append(width)
+            else:
+                _require(t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1],
+                         "a strided array must be 2-D with a unit element stride and a row stride >= its width")
+                strides.append(int(t.stride(0)))
+        _require(1 <= width <= VP_DENSIFY_MAX_WIDTH, f"a row has {width} words: outside [1, {VP_DENSIFY_MAX_WIDTH}]")
+        descs.append(_DensifyArray(_ptr(a), _ptr(d), width, _DENSIFY_FILLS[fill], strides[0], strides[1]))
+    dev = src.device
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for i in range(0, len(descs), VP_DENSIFY_MAX_ARRAYS):
+            part = descs[i:i + VP_DENSIFY_MAX_ARRAYS]
+            _check_rc(L.vp_densify_rows((_DensifyArray * len(part))(*part), len(part), _ptr(src), _ptr(kind), counts.data_ptr(),
+                                        int(n_src), int(n_out), _ptr(status), stream))
+
+
+class DensifyPlan:
+    """What vp_densify_plan decided: src i32 [2N] and kind u8 [2N] (rows [0, n_out) are meaningful) and counts i64 [4] on the
+    device; n_out, kept, clones, split (splitting sources) as Python ints; status, a device int32 [1] that a resample or split
+    call raises when its n_out is not the device's."""
+
+    def __init__(self, n, src, kind, counts, status):
+        self.n, self.src, self.kind, self.counts, self.status = int(n), src, kind, counts, status
+        self.n_out, self.kept, self.clones, self.split = (int(v) for v in counts.tolist())
+
+    def resample(self, arrays):
+        """{name: (tensor [N, ...] f32 or i32, "copy" | "zero")} -> {name: the new tensor [n_out, ...]}, one launch per 16
+        arrays.  "zero" fills the rows that are not kept originals with zeros (optimiser moments)."""
+        import torch
+        out, todo = {}, []
+        for name, (t, fill) in arrays.items():
+            _require(isinstance(t, torch.Tensor) and t.dim() >= 1 and int(t.shape[0]) == self.n,
+                     f"{name} must be a tensor with {self.n} rows")
+            t = t.detach()
+            if not t.is_contiguous():
+                t = t.contiguous()
+            out[name] = torch.empty((self.n_out,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+            if self.n_out and out[name].numel():
+                todo.append((t, out[name], fill))
+        if todo:
+            densify_rows(todo, self.src, self.kind, self.counts, self.n, self.n_out, self.status)
+        return out
+
+    def split_geometry(self, means, quats, log_scales, seed):
+        """vp_densify_split: (means f32 [n_out,3], log_scales f32 [n_out,3]) of the new cloud: copies for kept rows and
+        clones, sampled positions and shrunk scales for the split children.  ``seed``: an int below 2^64 or (low, high)
+        32-bit words; the same seed and inputs give the same bits."""
+        import torch
+        L = _densify_lib()
+        _, (m, q, s) = _splat_gaussians(means.detach(), quats.detach(), log_scales.detach())
+        _require(int(m.shape[0]) == self.n and m.device == self.src.device, f"the geometry must have {self.n} Gaussians")
+        if isinstance(seed, (tuple, list)):
+            seed = (int(seed[0]) & 0xFFFFFFFF) | ((int(seed[1]) & 0xFFFFFFFF) << 32)
+        _require(0 <= int(seed) < 2 ** 64, "seed must be in [0, 2^64)")
+        dev = m.device
+        om = torch.empty((self.n_out, 3), dtype=torch.float32, device=dev)
+        ol = torch.empty((self.n_out, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _check_rc(L.vp_densify_split(_ptr(m), _ptr(q), _ptr(s), self.n, _ptr(self.src), _ptr(self.kind),
+                                         self.counts.data_ptr(), self.n_out, int(seed), _ptr(om), _ptr(ol), _ptr(self.status),
+                                         torch.cuda.current_stream(dev).cuda_stream))
+        return om, ol
+
+
+def densify_plan(stats, scales, opacities, *, grad_threshold, size_threshold, min_opacity, max_screen_size=0.0, max_world_size,
+                 workspace=None):
+    """vp_densify_plan: the clone / split / prune decision of every Gaussian from ``stats`` and the activated scales f32 [N,3]
+    and opacities f32 [N], and the source row of every output row.  size_threshold = percent_dense x extent, max_world_size =
+    0.1 x extent; max_screen_size 0 turns the size rules off.  Reads the four counters back: the one synchronisation of a
+    densification.  ``workspace``: a SplatWorkspace for the scan's scratch (a fresh one when None)."""
+    import torch
+    L = _densify_lib()
+    _require_tensors((scales, "scales", (torch.float32,)), (opacities, "opacities", (torch.float32,)))
+    N, dev = stats.n, scales.device
+    _require(tuple(scales.shape) == (N, 3) and tuple(opacities.shape) == (N,), f"scales must be [{N}, 3] and opacities [{N}]")
+    _require(opacities.device == dev and stats.grad_accum.device == dev, "the statistics, scales and opacities must be on one device")
+    _require(float(grad_threshold) > 0.0, f"grad_threshold = {grad_threshold} must be > 0")
+    scales, opacities = scales.detach().contiguous(), opacities.detach().contiguous()
+    need = int(L.vp_densify_plan_workspace_bytes(N))
+    _require(need > 0, f"no plan workspace size for N = {N}")
+    ws = workspace if workspace is not None else SplatWorkspace()
+    ptr = ws.ensure(need, dev)
+    src = torch.empty(2 * N, dtype=torch.int32, device=dev)
+    kind = torch.empty(2 * N, dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check_rc(L.vp_densify_plan(_ptr(stats.grad_accum), _ptr(stats.denom), _ptr(stats.max_radius), _ptr(scales),
+                                    _ptr(opacities), N, float(grad_threshold), float(size_threshold), float(min_opacity),
+                                    float(max_screen_size), float(max_world_size), _ptr(src), _ptr(kind), counts.data_ptr(), ptr,
+                                    ws.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+    return DensifyPlan(N, src, kind, counts, status)
+
+
+def resample_adam(optimizer, old_params, new_params, plan):
+    """Replace the parameters {name: old_param} of a torch.optim.Adam by {name: new_param} (resampled by ``plan``) in their
+    groups, and carry exp_avg / exp_avg_sq over in one resample call: the surviving rows keep their moments bit for bit, new
+    rows start at zero, ``step`` is kept (the reference's _prune_optimizer and cat_tensors_to_optimizer together)."""
+    moments, states = {}, {}
+    for name, old in old_params.items():
+        new = new_params[name]
+        for group in optimizer.param_groups:
+            for i, q in enumerate(group["params"]):
+                if q is old:
+                    group["params"][i] = new
+        st = optimizer.state.pop(old, None)
+        if st:
+            states[name] = st
+            for key in ("exp_avg", "exp_avg_sq"):
+                if key in st:
+                    moments[(name, key)] = (st[key], "zero")
+    moved = plan.resample(moments) if moments else {}
+    for name, st in states.items():
+        for key in ("exp_avg", "exp_avg_sq"):
+            if (name, key) in moved:
+                st[key] = moved[(name, key)]
+        optimizer.state[new_params[name]] = st
 
 
 def _codebook_lib():

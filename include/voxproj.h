@@ -1055,6 +1055,93 @@ int vp_photo_loss_gradient(const float *image, const float *target, int C, int W
                            const float *grad_loss, float *grad_image, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/*
+ * Adaptive density control: the step of the reference's training loop that changes the size of the point cloud
+ * (train_unified_lift.py:463-473, scene/gaussian_model.py:399-608).  Per training view vp_densify_accumulate adds the
+ * screen-space gradient of the visible Gaussians to a running statistic; every few hundred steps vp_densify_plan turns the
+ * statistic into one decision per Gaussian and one source row per output row, vp_densify_rows moves every per-Gaussian array
+ * (parameters and optimiser moments) in one launch and vp_densify_split writes the means and log-scales of the new cloud.
+ * Added after VP_ABI_VERSION 4 without changing it or any existing entry point; detect the five functions by symbol.
+ * tests/densify_reference.py states the contract in NumPy.  No float atomics: every result is bit-identical from run to run.
+ * All calls are asynchronous on `stream`, allocate nothing and do not synchronise with the host.
+ *
+ * vp_densify_accumulate: after vp_splat_project (and the geometry backward that wrote grad_screen) of one view, on the same
+ *   splat workspace, which is only read.  A Gaussian is VISIBLE when the projection gave it at least one tile: the rule by
+ *   which the backward writes non-zero rows.  grad_screen f32 [N,5] (columns 0, 1 = dL/d mean2d in pixels).  Per visible g:
+ *     grad_accum[g] += (float)(sqrt((double)gx gx (W/2)^2 + (double)gy gy (H/2)^2) * (double)scale)      (one fp32 addition)
+ *     denom[g] += 1                                                                                       (i32)
+ *     max_radius[g] = max(max_radius[g], (float)(3 sqrt(mid + sqrt(max(0.1, ((s00 - s11) / 2)^2 + s01^2)))))  when not NULL,
+ *   mid = (s00 + s11) / 2, with s00, s01, s11 the float64 screen covariance of vp_splat_project's own chain for the means,
+ *   quats, scales, viewmat, intrinsics and eps2d given (those of the project call; read only when max_radius is not NULL).
+ *   W/2 and H/2 turn the pixel gradient into the NDC gradient the reference's threshold 0.0002 is stated in; scale undoes a
+ *   caller's 1/k when a step averages k views.  The radius is the reference rasterizer's without its ceil: compared with >
+ *   against an integer threshold it decides the same.  Invisible Gaussians are untouched.
+ *   VP_EINVAL: NULL grad_screen / grad_accum / denom (N > 0), N outside [0, 2^31 - 1], W or H outside [1, 32768], a scale that
+ *   is not finite, with max_radius a NULL geometry array or a bad camera / eps2d; VP_EWORKSPACE: a NULL, misaligned or too
+ *   small workspace (vp_splat_workspace_bytes(N, W, H, 0)).
+ *
+ * vp_densify_plan: grad_accum f32 [N], denom i32 [N], max_radius f32 [N] or NULL, activated scales f32 [N,3] and opacities
+ *   f32 [N] on the device; host floats grad_threshold (> 0), size_threshold (percent_dense x extent, rounded to fp32 by the
+ *   caller), min_opacity, max_screen_size (0: the size rules are off), max_world_size (0.1 x extent).  N in [0, 2^30].
+ *   The rule per Gaussian g, every comparison in fp32:
+ *     gm    = denom ? grad_accum / (float)denom : 0        (a NaN counts as 0)
+ *     smax  = fmaxf of the three scales
+ *     sel   = gm >= grad_threshold;  clone = sel && smax <= size_threshold;  split = sel && smax > size_threshold
+ *     low   = opacity < min_opacity;  on = max_screen_size > 0
+ *     bigw(s) = on && s > max_world_size;  bigv = on && max_radius != NULL && max_radius[g] > max_screen_size
+ *     the original survives    iff !split && !low && !bigv && !bigw(smax)
+ *     one clone is emitted     iff clone && !low && !bigw(smax)
+ *     two children are emitted iff split && !low && !bigw(smax * 0.625f)              (0.625f = 1 / (0.8 x 2), exact)
+ *   Output order: the surviving originals in ascending index; the clones in ascending source index; child 0 of every
+ *   emitting source in ascending index; child 1 likewise.  This is the reference's order (clone-append, split-append, remove
+ *   the split sources, prune) with its prune folded in.  The one deliberate difference: the reference zeroes max_radii2D in
+ *   densification_postfix before its prune reads it, so its screen-size rule never fires; here the rule is live for the rows
+ *   that existed while the statistics were taken (new rows have no radius yet, as in the reference).
+ *   src i32 [2N] and kind u8 [2N] (0 kept, 1 clone, 2 / 3 split child 0 / 1): rows [0, total) are written, the rest is left
+ *   alone; total <= 2N always.  counts i64 [4] = {total, kept, clones, splitting sources}, on the device.
+ *   The offsets come from one rocprim inclusive scan; vp_densify_plan_workspace_bytes(N) measures its scratch (0 when N is out
+ *   of range).  VP_EINVAL / VP_EWORKSPACE as above; grad_threshold must be > 0 and the five floats not NaN.
+ *
+ * vp_densify_rows: resamples n_arrays (1 .. VP_DENSIFY_MAX_ARRAYS) arrays of 32-bit words (f32 or i32) in one launch.  For
+ *   every array a and output row r < n_out:  dst_a[r] = src_a[src[r]] bit for bit when kind[r] == 0 or fill is
+ *   VP_DENSIFY_COPY;  zeros when fill is VP_DENSIFY_ZERO and kind[r] != 0 (the Adam moments of new rows).  Widths 1 .. 4096
+ *   words, strides >= width in words; only the `width` words of a row are written.  src and dst must not overlap.
+ *   n_out is the host's copy of counts[0]: when the device's total differs, nothing is written and *status (device i32,
+ *   may be NULL) becomes 1.  A source index outside [0, n_src) writes nothing for that row and raises the status too.
+ *
+ * vp_densify_split: out_means f32 [n_out,3] and out_log_scales f32 [n_out,3] for all rows; kinds 0 and 1 copy bit for bit.
+ *   For child c (kind 2 + c) of source g:  out_log_scale = log_scale[g] + fp32(ln 0.625) (one fp32 addition);  r0..r3 =
+ *   Philox4x32-10 with counter (g, c, 0, 0) and key (seed & 0xffffffff, seed >> 32);  u_i = (r_i + 0.5) 2^-32;
+ *   xi0 = sqrt(-2 ln u0) cos(2 pi u1), xi1 the same with sin, xi2 = sqrt(-2 ln u2) cos(2 pi u3);  s = exp((double)log_scale[g]);
+ *   out_mean = (float)(mean[g] + R(q / |q|) (s * xi)), all float64, rounded once.  The same seed and inputs give the same bits.
+ *   n_out / status as vp_densify_rows.
+ */
+#define VP_DENSIFY_MAX_ARRAYS 16
+#define VP_DENSIFY_MAX_WIDTH 4096
+#define VP_DENSIFY_COPY 0
+#define VP_DENSIFY_ZERO 1
+typedef struct {
+    const void *src;         /* [n_src, src_stride] 32-bit words */
+    void *dst;               /* [n_out, dst_stride] */
+    int32_t width;           /* words of a row that are moved */
+    int32_t fill;            /* VP_DENSIFY_COPY or VP_DENSIFY_ZERO */
+    int64_t src_stride, dst_stride;   /* in words, >= width */
+} vp_densify_array;
+int vp_densify_accumulate(const float *grad_screen, int64_t n_gaussians, int W, int H, float scale, const float *means,
+                          const float *quats, const float *scales, const float *viewmat, float fx, float fy, float cx,
+                          float cy, float eps2d, float *grad_accum, int32_t *denom, float *max_radius, const void *workspace,
+                          size_t workspace_bytes, void *stream);
+size_t vp_densify_plan_workspace_bytes(int64_t n_gaussians);
+int vp_densify_plan(const float *grad_accum, const int32_t *denom, const float *max_radius, const float *scales,
+                    const float *opacities, int64_t n_gaussians, float grad_threshold, float size_threshold, float min_opacity,
+                    float max_screen_size, float max_world_size, int32_t *src, uint8_t *kind, int64_t *counts, void *workspace,
+                    size_t workspace_bytes, void *stream);
+int vp_densify_rows(const vp_densify_array *arrays, int n_arrays, const int32_t *src, const uint8_t *kind,
+                    const int64_t *counts, int64_t n_src, int64_t n_out, int32_t *status, void *stream);
+int vp_densify_split(const float *means, const float *quats, const float *log_scales, int64_t n_src, const int32_t *src,
+                     const uint8_t *kind, const int64_t *counts, int64_t n_out, uint64_t seed, float *out_means,
+                     float *out_log_scales, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
