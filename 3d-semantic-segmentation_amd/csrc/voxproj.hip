@@ -91,6 +91,15 @@
 #include "vp_densify.h"
 #include "vp_project.h"
 
+// The refusal of a caller-provided workspace that is missing, smaller than ``need`` or not 256-byte aligned.
+static int check_workspace(const void *workspace, size_t workspace_bytes, size_t need)
+{
+    if (!workspace || workspace_bytes < need)
+        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
+    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    return VP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // C-ABI
 // ------------------------------------------------------------------------------------------------
@@ -226,9 +235,7 @@ int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, 
     if (P < 1 || P > QUERY_MAX_P) return fail(VP_EINVAL, "P = %d outside [1, %d]", P, QUERY_MAX_P);
     if (row_stride < C) return fail(VP_EINVAL, "row_stride %lld < C = %d", (long long)row_stride, C);
     if (!(scale > 0.0f) || !std::isfinite(scale)) return fail(VP_EINVAL, "scale must be finite and > 0 (got %g)", (double)scale);
-    const size_t need = vp_query_workspace_bytes(P, C);
-    if (!workspace || workspace_bytes < need) return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    if (int rc = check_workspace(workspace, workspace_bytes, vp_query_workspace_bytes(P, C))) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t esz = rows_is_f16 ? 2 : 4;
     const bool vec = C % (16 / esz) == 0 && ((uintptr_t)rows & 15) == 0 && ((size_t)row_stride * esz) % 16 == 0;
@@ -1032,22 +1039,13 @@ static int eval_check_image(int W, int H)
     return VP_OK;
 }
 
-static int eval_check_workspace(const void *workspace, size_t workspace_bytes, int W, int H)
-{
-    const size_t need = vp_label_scores_workspace_bytes(W, H);
-    if (!workspace || workspace_bytes < need)
-        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    return VP_OK;
-}
-
 int vp_label_boundary(const int32_t *labels, int W, int H, int radius, uint8_t *band, void *workspace, size_t workspace_bytes,
                       void *stream_)
 {
     if (!labels || !band) return fail(VP_EINVAL, "null pointer argument (labels or band)");
     if (int rc = eval_check_image(W, H)) return rc;
     if (radius < 1 || radius > EVAL_MAX_RADIUS) return fail(VP_EINVAL, "radius = %d outside [1, %d]", radius, EVAL_MAX_RADIUS);
-    if (int rc = eval_check_workspace(workspace, workspace_bytes, W, H)) return rc;
+    if (int rc = check_workspace(workspace, workspace_bytes, vp_label_scores_workspace_bytes(W, H))) return rc;
     unsigned char *ok = (unsigned char *)workspace + 2 * align256((size_t)W * H);
     eval_launch_band((const int *)labels, W, H, radius, (unsigned char *)band, ok, (hipStream_t)stream_);
     VP_HIP(hipGetLastError());
@@ -1064,7 +1062,7 @@ int vp_label_scores(const int32_t *pred, const int32_t *target, int W, int H, in
     if (radius < 0 || radius > EVAL_MAX_RADIUS) return fail(VP_EINVAL, "radius = %d outside [0, %d]", radius, EVAL_MAX_RADIUS);
     if (radius > 0 && (!bnd_inter || !bnd_union)) return fail(VP_EINVAL, "radius > 0 needs bnd_inter and bnd_union");
     if (radius > 0)
-        if (int rc = eval_check_workspace(workspace, workspace_bytes, W, H)) return rc;
+        if (int rc = check_workspace(workspace, workspace_bytes, vp_label_scores_workspace_bytes(W, H))) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const long long n = (long long)W * H;
     unsigned char *pband = nullptr, *tband = nullptr;
@@ -1106,11 +1104,7 @@ static int floss_check_maps(const void *image, int image_is_f16, int64_t pix_str
         return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, FLOSS_MAX_WH);
     if (pix_stride < C) return fail(VP_EINVAL, "pix_stride %lld < C = %d", (long long)pix_stride, C);
     if (tgt_stride < C) return fail(VP_EINVAL, "tgt_stride %lld < C = %d", (long long)tgt_stride, C);
-    const size_t need = floss_bytes((long long)W * H);
-    if (!workspace || workspace_bytes < need)
-        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    return VP_OK;
+    return check_workspace(workspace, workspace_bytes, floss_bytes((long long)W * H));
 }
 
 // 16-byte loads: whole chunks of 8 channels, every pixel's row 16-byte aligned in both maps
@@ -1202,11 +1196,7 @@ static int proto_check(const float *image, int D, int W, int H, const int32_t *i
     if (D < 1 || D > PROTO_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, PROTO_MAX_D);
     if (W < 1 || W > PROTO_MAX_WH || H < 1 || H > PROTO_MAX_WH)
         return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, PROTO_MAX_WH);
-    const size_t need = vp_proto_contrast_workspace_bytes(D, W, H);
-    if (!workspace || workspace_bytes < need)
-        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    return VP_OK;
+    return check_workspace(workspace, workspace_bytes, vp_proto_contrast_workspace_bytes(D, W, H));
 }
 
 int vp_proto_contrast(const float *image, int D, int W, int H, const int32_t *ids, const int32_t *count, int ignore_id,
@@ -1299,11 +1289,7 @@ static int photo_check(const float *image, const float *target, int C, int W, in
     if (W < 1 || W > PHOTO_MAX_WH || H < 1 || H > PHOTO_MAX_WH)
         return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, PHOTO_MAX_WH);
     if (!workspace && !need_workspace) return VP_OK;
-    const size_t need = photo_bytes(C, W, H);
-    if (!workspace || workspace_bytes < need)
-        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    return VP_OK;
+    return check_workspace(workspace, workspace_bytes, photo_bytes(C, W, H));
 }
 
 int vp_photo_loss(const float *image, const float *target, int C, int W, int H, double *loss_stats, float *ssim_map,
@@ -1505,11 +1491,7 @@ static int cb_check(const float *image, int D, int W, int H, const int32_t *ids,
     if (K < 1 || K > CB_MAX_K) return fail(VP_EINVAL, "K = %d outside [1, %d]", K, CB_MAX_K);
     if (W < 1 || W > CB_MAX_WH || H < 1 || H > CB_MAX_WH)
         return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, CB_MAX_WH);
-    const size_t need = vp_codebook_workspace_bytes(D, K, W, H);
-    if (!workspace || workspace_bytes < need)
-        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
-    return VP_OK;
+    return check_workspace(workspace, workspace_bytes, vp_codebook_workspace_bytes(D, K, W, H));
 }
 
 int vp_codebook_assoc(const float *image, int D, int W, int H, const int32_t *ids, int ignore_id, const float *codebook, int K,
@@ -1634,10 +1616,7 @@ int vp_neighbor_kl(const float *logits, int64_t N, int P, int64_t row_stride, co
     int G = 0;
     if (!stats) return fail(VP_EINVAL, "null pointer argument (stats)");
     if (int rc = kl_check(logits, N, P, row_stride, samples, S, nbr, k, row_lse, lanes, &G)) return rc;
-    const size_t need = vp_neighbor_kl_workspace_bytes(S);
-    if (!workspace || workspace_bytes < need)
-        return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
-    if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    if (int rc = check_workspace(workspace, workspace_bytes, vp_neighbor_kl_workspace_bytes(S))) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     float *sl = sample_loss ? sample_loss : (float *)workspace;
     double *part = (double *)((char *)workspace + align256((size_t)std::max<int64_t>(S, 1) * sizeof(float)));

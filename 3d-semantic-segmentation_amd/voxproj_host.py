@@ -44,28 +44,83 @@ def set_default_option(option, value):
         _default_options[int(option)] = int(value)
     _options_version += 1
 
-EXPORTS = [
-    "vp_abi_version", "vp_last_error", "vp_workspace_bytes", "vp_project_features",
-    "vp_workspace_status", "vp_workspace_counters", "vp_copy_hit_image",
-    "vp_profile_enable", "vp_profile_read", "vp_workspace_release", "vp_project_colors",
-    "vp_project_features_f16", "vp_nearest_voxel",
-    "vp_stream_read", "vp_workspace_table_builds", "vp_colors_workspace_bytes",
-    "vp_upsample_workspace_bytes", "vp_upsample_features", "vp_voxel_coords", "vp_scatter_occupancy",
-    "vp_aggregate_view_f16", "vp_workspace_create", "vp_workspace_set_option",
-    "vp_first_hit_ids", "vp_render_features", "vp_query_workspace_bytes", "vp_query_features",
-    "vp_splat_workspace_bytes", "vp_splat_project", "vp_splat_rasterize",
-    "vp_splat_backward_workspace_bytes", "vp_splat_rasterize_backward",
-    "vp_splat_geometry_backward_workspace_bytes", "vp_splat_rasterize_backward_geometry",
-    "vp_splat_loss_workspace_bytes", "vp_splat_rasterize_loss", "vp_splat_loss_backward",
-    "vp_label_scores_workspace_bytes", "vp_label_boundary", "vp_label_scores",
-    "vp_splat_lift_workspace_bytes", "vp_splat_lift", "vp_splat_render",
-    "vp_feature_loss_workspace_bytes", "vp_feature_loss", "vp_feature_loss_gradient",
-    "vp_proto_contrast_workspace_bytes", "vp_proto_contrast", "vp_proto_contrast_gradient",
-    "vp_codebook_workspace_bytes", "vp_codebook_assoc", "vp_codebook_loss",
-    "vp_knn_points", "vp_neighbor_kl_workspace_bytes", "vp_neighbor_kl", "vp_neighbor_kl_gradient",
-    "vp_photo_loss_workspace_bytes", "vp_photo_loss", "vp_photo_loss_gradient",
-    "vp_densify_accumulate", "vp_densify_plan_workspace_bytes", "vp_densify_plan", "vp_densify_rows", "vp_densify_split",
-]
+
+# The C ABI of include/voxproj.h, one entry per function: "<return type>: <argument types>", one letter per type (the blanks
+# only group runs).  Pointers to device memory, workspaces and streams are ``p``; the capital letters are the host arrays a
+# caller passes as ctypes arrays.  tests/test_abi_cpu.py compares every entry with the header's prototype.
+_C_TYPES = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "q": ctypes.c_longlong, "u": ctypes.c_uint64,
+            "z": ctypes.c_size_t, "f": ctypes.c_float, "d": ctypes.c_double, "s": ctypes.c_char_p,
+            "F": ctypes.POINTER(ctypes.c_float), "D": ctypes.POINTER(ctypes.c_double),
+            "I": ctypes.POINTER(ctypes.c_int32), "L": ctypes.POINTER(ctypes.c_int64)}
+_SIGNATURES = {
+    # ABI version 4
+    "vp_abi_version": "i:",
+    "vp_last_error": "s:",
+    "vp_workspace_bytes": "z: iiiiiiii l",
+    "vp_project_features": "i: pppp F ppp F f iiiiiiii l p z p i",
+    "vp_project_features_f16": "i: pppp F ppp F f iiiiiiii l p z p i",
+    "vp_workspace_status": "i: pp",
+    "vp_workspace_counters": "i: p I i p",
+    "vp_copy_hit_image": "i: pp iiiiiiii l p",
+    "vp_profile_enable": "i: i",
+    "vp_profile_read": "i: D L",
+    "vp_workspace_release": "i: p",
+    "vp_workspace_create": "i: p z",
+    "vp_workspace_set_option": "i: p i q",
+    "vp_workspace_table_builds": "q: p",
+    "vp_project_colors": "i: p iii pp i F d p ii pppp l i p z p",
+    "vp_colors_workspace_bytes": "z: l",
+    "vp_nearest_voxel": "i: ppp D d iii p l pp",
+    "vp_stream_read": "i: p l pp",
+    "vp_upsample_workspace_bytes": "z: iiii",
+    "vp_upsample_features": "i: p iiii p iii p z p",
+    "vp_voxel_coords": "i: p l F f pp I p",
+    "vp_scatter_occupancy": "i: p l I iii ppp",
+    "vp_aggregate_view_f16": "i: ppppp i p l i p",
+    "vp_first_hit_ids": "i: ppp FF f iiiiiii l pp z p i",
+    "vp_render_features": "i: p l p l i p i pp",
+    "vp_query_workspace_bytes": "z: ii",
+    "vp_query_features": "i: p i l i l p i f ppppp z p",
+    "vp_splat_workspace_bytes": "z: l ii l",
+    "vp_splat_project": "i: pppp l F ffff ii fff ppp z p",
+    "vp_splat_rasterize": "i: p i ll ii l pppppp z p",
+    "vp_splat_backward_workspace_bytes": "z: l i",
+    "vp_splat_rasterize_backward": "i: p i ll ii l pppppp z p z p",
+    "vp_splat_geometry_backward_workspace_bytes": "z: l i",
+    "vp_splat_rasterize_backward_geometry": "i: pppp i ll F ffff ii f l pppppppppp z p z p",
+    "vp_splat_loss_workspace_bytes": "z: ii",
+    "vp_splat_rasterize_loss": "i: p i ll ii l pppppppppp z p z p",
+    "vp_splat_loss_backward": "i: pppp i ll F ffff ii f l pppp i pppppppppp z p z p",
+    "vp_label_scores_workspace_bytes": "z: ii",
+    "vp_label_boundary": "i: p iii pp z p",
+    "vp_label_scores": "i: pp iiii ppppp z p",
+    # added after ABI version 4: a library may lack them (detected by symbol; _entry raises for a missing one)
+    "vp_splat_lift_workspace_bytes": "z: l i",
+    "vp_splat_lift": "i: p i l p l ii l i p l ppp z p z p",
+    "vp_splat_render": "i: p ii ll ii l i p i l ppp z p",
+    "vp_feature_loss_workspace_bytes": "z: ii",
+    "vp_feature_loss": "i: p i l p l iii pp f i ppp z p",
+    "vp_feature_loss_gradient": "i: p i l p l iii p i pp l pp z p",
+    "vp_proto_contrast_workspace_bytes": "z: iii",
+    "vp_proto_contrast": "i: p iii pp ii fff pppp z p",
+    "vp_proto_contrast_gradient": "i: p iii pp ff ppp z p",
+    "vp_codebook_workspace_bytes": "z: iiii",
+    "vp_codebook_assoc": "i: p iii p i p i pppp z p",
+    "vp_codebook_loss": "i: p iii p i p f p i pppppp z p",
+    "vp_knn_points": "i: ppp D d iii pp l i ppp",
+    "vp_neighbor_kl_workspace_bytes": "z: l",
+    "vp_neighbor_kl": "i: p l i l p l p i ppp i p z p",
+    "vp_neighbor_kl_gradient": "i: p l i l p l p i ppppp d pp l i p",
+    "vp_photo_loss_workspace_bytes": "z: iii",
+    "vp_photo_loss": "i: pp iii ppp z p",
+    "vp_photo_loss_gradient": "i: pp iii f ppp z p",
+    "vp_densify_accumulate": "i: p l ii f pppp fffff pppp z p",
+    "vp_densify_plan_workspace_bytes": "z: l",
+    "vp_densify_plan": "i: ppppp l fffff pppp z p",
+    "vp_densify_rows": "i: p i ppp ll pp",
+    "vp_densify_split": "i: ppp l ppp l u pppp",
+}
+EXPORTS = list(_SIGNATURES)
 VP_ABI_VERSION = 4
 VP_OPT_HEAVY_THRESHOLD = 1
 VP_OPT_MARCH_LDS_KB = 2
@@ -132,179 +187,12 @@ def lib():
                     f"{LIB_PATH} is missing: build it with `make -C {os.path.join(_HERE, 'csrc')}` "
                     "(there is no CPU fallback)")
             L = ctypes.CDLL(LIB_PATH)
-            L.vp_abi_version.restype = ctypes.c_int
-            L.vp_last_error.restype = ctypes.c_char_p
-            L.vp_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_workspace_bytes.argtypes = [ctypes.c_int] * 8 + [ctypes.c_int64]
-            vp = ctypes.c_void_p
-            L.vp_project_features.restype = ctypes.c_int
-            L.vp_project_features.argtypes = [
-                vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float), vp, vp, vp, ctypes.POINTER(ctypes.c_float),
-                ctypes.c_float] + [ctypes.c_int] * 8 + [ctypes.c_int64, vp, ctypes.c_size_t, vp, ctypes.c_int]
-            L.vp_project_features_f16.restype = ctypes.c_int
-            L.vp_project_features_f16.argtypes = L.vp_project_features.argtypes
-            L.vp_nearest_voxel.restype = ctypes.c_int
-            L.vp_nearest_voxel.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, vp, ctypes.c_int64, vp, vp]
-            L.vp_workspace_status.restype = ctypes.c_int
-            L.vp_workspace_status.argtypes = [vp, vp]
-            L.vp_workspace_counters.restype = ctypes.c_int
-            L.vp_workspace_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, vp]
-            L.vp_copy_hit_image.restype = ctypes.c_int
-            L.vp_copy_hit_image.argtypes = [vp, vp] + [ctypes.c_int] * 8 + [ctypes.c_int64, vp]
-            L.vp_profile_enable.restype = ctypes.c_int
-            L.vp_profile_enable.argtypes = [ctypes.c_int]
-            L.vp_profile_read.restype = ctypes.c_int
-            L.vp_profile_read.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
-            L.vp_workspace_release.restype = ctypes.c_int
-            L.vp_workspace_release.argtypes = [vp]
-            L.vp_workspace_create.restype = ctypes.c_int
-            L.vp_workspace_create.argtypes = [vp, ctypes.c_size_t]
-            L.vp_workspace_set_option.restype = ctypes.c_int
-            L.vp_workspace_set_option.argtypes = [vp, ctypes.c_int, ctypes.c_longlong]
-            L.vp_workspace_table_builds.restype = ctypes.c_longlong
-            L.vp_workspace_table_builds.argtypes = [vp]
-            L.vp_project_colors.restype = ctypes.c_int
-            L.vp_project_colors.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int,
-                                            ctypes.POINTER(ctypes.c_float), ctypes.c_double, vp, ctypes.c_int,
-                                            ctypes.c_int, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp,
-                                            ctypes.c_size_t, vp]
-            L.vp_colors_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_colors_workspace_bytes.argtypes = [ctypes.c_int64]
-            L.vp_upsample_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_upsample_workspace_bytes.argtypes = [ctypes.c_int] * 4
-            L.vp_upsample_features.restype = ctypes.c_int
-            L.vp_upsample_features.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int,
-                                               ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-            L.vp_voxel_coords.restype = ctypes.c_int
-            L.vp_voxel_coords.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.c_float, vp, vp,
-                                          ctypes.POINTER(ctypes.c_int32), vp]
-            L.vp_scatter_occupancy.restype = ctypes.c_int
-            L.vp_scatter_occupancy.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_int, vp, vp, vp]
-            L.vp_aggregate_view_f16.restype = ctypes.c_int
-            L.vp_aggregate_view_f16.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, vp]
-            L.vp_first_hit_ids.restype = ctypes.c_int
-            L.vp_first_hit_ids.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float] + \
-                [ctypes.c_int] * 7 + [ctypes.c_int64, vp, vp, ctypes.c_size_t, vp, ctypes.c_int]
-            L.vp_render_features.restype = ctypes.c_int
-            L.vp_render_features.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int, vp, vp]
-            L.vp_query_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_query_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-            L.vp_query_features.restype = ctypes.c_int
-            L.vp_query_features.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int,
-                                            ctypes.c_float, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-            L.vp_splat_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_splat_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64]
-            L.vp_splat_project.restype = ctypes.c_int
-            L.vp_splat_project.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
-                [ctypes.c_int] * 2 + [ctypes.c_float] * 3 + [vp, vp, vp, ctypes.c_size_t, vp]
-            L.vp_splat_rasterize.restype = ctypes.c_int
-            L.vp_splat_rasterize.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-            L.vp_splat_backward_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_splat_backward_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
-            L.vp_splat_rasterize_backward.restype = ctypes.c_int
-            L.vp_splat_rasterize_backward.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                                      ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp,
-                                                      ctypes.c_size_t, vp]
-            L.vp_splat_geometry_backward_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_splat_geometry_backward_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
-            L.vp_splat_rasterize_backward_geometry.restype = ctypes.c_int
-            L.vp_splat_rasterize_backward_geometry.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                                               ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
-                [ctypes.c_int] * 2 + [ctypes.c_float, ctypes.c_int64] + [vp] * 10 + [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
-            L.vp_splat_loss_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_splat_loss_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-            L.vp_splat_rasterize_loss.restype = ctypes.c_int
-            L.vp_splat_rasterize_loss.argtypes = [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                                  ctypes.c_int64] + [vp] * 10 + [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
-            L.vp_splat_loss_backward.restype = ctypes.c_int
-            L.vp_splat_loss_backward.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                                 ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 4 + \
-                [ctypes.c_int] * 2 + [ctypes.c_float, ctypes.c_int64] + [vp] * 4 + [ctypes.c_int] + [vp] * 10 + \
-                [ctypes.c_size_t, vp, ctypes.c_size_t, vp]
-            if hasattr(L, "vp_splat_lift"):      # added after ABI version 4: detected by symbol (splat_lift raises without it)
-                L.vp_splat_lift_workspace_bytes.restype = ctypes.c_size_t
-                L.vp_splat_lift_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
-                L.vp_splat_lift.restype = ctypes.c_int
-                L.vp_splat_lift.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_size_t, vp,
-                                            ctypes.c_size_t, vp]
-            if hasattr(L, "vp_splat_render"):    # added after ABI version 4: detected by symbol (splat_render raises without it)
-                L.vp_splat_render.restype = ctypes.c_int
-                L.vp_splat_render.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
-                                              ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int64, vp,
-                                              vp, vp, ctypes.c_size_t, vp]
-            if hasattr(L, "vp_feature_loss"):    # added after ABI version 4: detected by symbol (feature_loss raises without it)
-                L.vp_feature_loss_workspace_bytes.restype = ctypes.c_size_t
-                L.vp_feature_loss_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-                L.vp_feature_loss.restype = ctypes.c_int
-                L.vp_feature_loss.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_int, vp, vp, ctypes.c_float, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]
-                L.vp_feature_loss_gradient.restype = ctypes.c_int
-                L.vp_feature_loss_gradient.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int,
-                                                       ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp,
-                                                       vp, ctypes.c_size_t, vp]
-            if hasattr(L, "vp_proto_contrast"):  # added after ABI version 4: detected by symbol (proto_contrast raises without it)
-                L.vp_proto_contrast_workspace_bytes.restype = ctypes.c_size_t
-                L.vp_proto_contrast_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-                L.vp_proto_contrast.restype = ctypes.c_int
-                L.vp_proto_contrast.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, vp]
-                L.vp_proto_contrast_gradient.restype = ctypes.c_int
-                L.vp_proto_contrast_gradient.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_float,
-                                                         ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]
-            if hasattr(L, "vp_codebook_assoc"):  # added after ABI version 4: detected by symbol (codebook_assoc raises without it)
-                L.vp_codebook_workspace_bytes.restype = ctypes.c_size_t
-                L.vp_codebook_workspace_bytes.argtypes = [ctypes.c_int] * 4
-                L.vp_codebook_assoc.restype = ctypes.c_int
-                L.vp_codebook_assoc.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int,
-                                                vp, vp, vp, vp, ctypes.c_size_t, vp]
-                L.vp_codebook_loss.restype = ctypes.c_int
-                L.vp_codebook_loss.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_float,
-                                               vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-            if hasattr(L, "vp_knn_points"):  # added after ABI version 4: detected by symbol (knn_points / neighbor_kl raise without it)
-                i64 = ctypes.c_int64
-                L.vp_knn_points.restype = ctypes.c_int
-                L.vp_knn_points.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_int,
-                                            ctypes.c_int, ctypes.c_int, vp, vp, i64, ctypes.c_int, vp, vp, vp]
-                L.vp_neighbor_kl_workspace_bytes.restype = ctypes.c_size_t
-                L.vp_neighbor_kl_workspace_bytes.argtypes = [i64]
-                L.vp_neighbor_kl.restype = ctypes.c_int
-                L.vp_neighbor_kl.argtypes = [vp, i64, ctypes.c_int, i64, vp, i64, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp,
-                                             ctypes.c_size_t, vp]
-                L.vp_neighbor_kl_gradient.restype = ctypes.c_int
-                L.vp_neighbor_kl_gradient.argtypes = [vp, i64, ctypes.c_int, i64, vp, i64, vp, ctypes.c_int, vp, vp, vp, vp, vp,
-                                                      ctypes.c_double, vp, vp, i64, ctypes.c_int, vp]
-            if hasattr(L, "vp_photo_loss"):  # added after ABI version 4: detected by symbol (photo_loss raises without it)
-                L.vp_photo_loss_workspace_bytes.restype = ctypes.c_size_t
-                L.vp_photo_loss_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-                L.vp_photo_loss.restype = ctypes.c_int
-                L.vp_photo_loss.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]
-                L.vp_photo_loss_gradient.restype = ctypes.c_int
-                L.vp_photo_loss_gradient.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, vp,
-                                                     ctypes.c_size_t, vp]
-            if hasattr(L, "vp_densify_plan"):  # added after ABI version 4: detected by symbol (densify_* raise without it)
-                f32, i64 = ctypes.c_float, ctypes.c_int64
-                L.vp_densify_accumulate.restype = ctypes.c_int
-                L.vp_densify_accumulate.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int, f32, vp, vp, vp, vp, f32, f32, f32, f32,
-                                                    f32, vp, vp, vp, vp, ctypes.c_size_t, vp]
-                L.vp_densify_plan_workspace_bytes.restype = ctypes.c_size_t
-                L.vp_densify_plan_workspace_bytes.argtypes = [i64]
-                L.vp_densify_plan.restype = ctypes.c_int
-                L.vp_densify_plan.argtypes = [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp, vp, vp, ctypes.c_size_t,
-                                              vp]
-                L.vp_densify_rows.restype = ctypes.c_int
-                L.vp_densify_rows.argtypes = [vp, ctypes.c_int, vp, vp, vp, i64, i64, vp, vp]
-                L.vp_densify_split.restype = ctypes.c_int
-                L.vp_densify_split.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, ctypes.c_uint64, vp, vp, vp, vp]
-            L.vp_label_scores_workspace_bytes.restype = ctypes.c_size_t
-            L.vp_label_scores_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-            L.vp_label_boundary.restype = ctypes.c_int
-            L.vp_label_boundary.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]
-            L.vp_label_scores.restype = ctypes.c_int
-            L.vp_label_scores.argtypes = [vp, vp] + [ctypes.c_int] * 4 + [vp] * 5 + [ctypes.c_size_t, vp]
+            for name, signature in _SIGNATURES.items():
+                fn = getattr(L, name, None)
+                if fn is not None:               # a symbol the library lacks is skipped here; _entry raises when it is called
+                    restype, argtypes = signature.split(":")
+                    fn.restype = _C_TYPES[restype]
+                    fn.argtypes = [_C_TYPES[c] for c in argtypes.replace(" ", "")]
             if L.vp_abi_version() != VP_ABI_VERSION:
                 raise VoxprojError(f"{LIB_PATH} has ABI version {L.vp_abi_version()}, this package needs {VP_ABI_VERSION}: rebuild it")
             _lib = L
@@ -318,6 +206,23 @@ def last_error():
 def check(rc):
     if rc != VP_OK:
         raise VoxprojError(f"voxproj error {rc}: {last_error()}")
+
+
+def _entry(name):
+    """The library's function ``name``; a library built before it was added has none, and nothing stands in for it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise VoxprojError(f"{LIB_PATH} has no {name}: rebuild it (there is no fallback)")
+    return fn
+
+
+def _call(dev, name, *args):
+    """Launch entry point ``name`` on ``dev``: the device made current, its current stream appended as the last argument,
+    the return code checked."""
+    import torch
+    fn = _entry(name)
+    with torch.cuda.device(dev):
+        check(fn(*args, torch.cuda.current_stream(dev).cuda_stream))
 
 
 def workspace_bytes(B, V, H, W, C, dimz, dimy, dimx, n_rows):
@@ -602,11 +507,8 @@ def render_features(ids, rows, dtype=None, out=None, check=True):
     _require(isinstance(out, torch.Tensor) and out.is_cuda and out.device == ids.device and out.dtype == dtype
              and tuple(out.shape) == shape and out.is_contiguous(), f"out must be a contiguous {dtype} CUDA tensor of shape {shape}")
     bad = torch.zeros(1, dtype=torch.int32, device=ids.device) if check else None
-    with torch.cuda.device(ids.device):
-        stream = torch.cuda.current_stream(ids.device)
-        _check_rc(lib().vp_render_features(ids.data_ptr(), ids.numel(), rows.data_ptr(), n_rows, C, out.data_ptr(),
-                                           int(dtype == torch.float16), bad.data_ptr() if bad is not None else None,
-                                           stream.cuda_stream))
+    _call(ids.device, "vp_render_features", ids.data_ptr(), ids.numel(), rows.data_ptr(), n_rows, C, out.data_ptr(),
+          int(dtype == torch.float16), _ptr(bad))
     if check:
         n_bad = int(bad.item())
         if n_bad:
@@ -644,16 +546,11 @@ def query_features(rows, text, scale=1.0, want_logits=True, want_margin=True, ch
     if N == 0:
         return labels, logits, margin
     bad = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
-    L = lib()
-    nbytes = int(L.vp_query_workspace_bytes(P, C))
+    nbytes = int(_entry("vp_query_workspace_bytes")(P, C))
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
     ws_ptr = (ws.data_ptr() + 255) & ~255
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_query_features(rows.data_ptr(), int(rows.dtype == torch.float16), N, C, int(rows.stride(0)),
-                                      text.data_ptr(), P, scale, logits.data_ptr() if logits is not None else None,
-                                      labels.data_ptr(), margin.data_ptr() if margin is not None else None,
-                                      bad.data_ptr() if bad is not None else None, ws_ptr, nbytes, stream.cuda_stream))
+    _call(dev, "vp_query_features", rows.data_ptr(), int(rows.dtype == torch.float16), N, C, int(rows.stride(0)),
+          text.data_ptr(), P, scale, _ptr(logits), labels.data_ptr(), _ptr(margin), _ptr(bad), ws_ptr, nbytes)
     if check:
         n_bad = int(bad.item())
         if n_bad:
@@ -742,23 +639,31 @@ def _splat_images(dev, *specs):
     return out
 
 
+def _splat_workspace_bytes(n_gaussians, W, H, capacity):
+    """vp_splat_workspace_bytes for ``capacity`` intersections; a size of 0 (an argument out of range) is refused."""
+    nbytes = int(lib().vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
+    return nbytes
+
+
 def _splat_forward_workspace(workspace, n_gaussians, W, H, capacity, dev):
     """Grow the projection's workspace to ``capacity`` intersections (the projection's bytes kept): its pointer."""
-    L = lib()
-    keep = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), 0))
-    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
-    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
-    return workspace.ensure(nbytes, dev, keep=keep)
+    keep = int(lib().vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), 0))
+    return workspace.ensure(_splat_workspace_bytes(n_gaussians, W, H, capacity), dev, keep=keep)
+
+
+def _filled_workspace(caller, forward, workspace, need, dev):
+    """Check that ``workspace`` can be the one a ``forward`` call filled (on ``dev``, at least ``need`` bytes): its pointer."""
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
+             workspace.capacity() >= need, f"{caller} needs the workspace of a {forward} call")
+    return workspace.ptr()
 
 
 def _splat_backward_workspaces(caller, forward, workspace, bwd_workspace, n_gaussians, W, H, capacity, D, geom, dev):
     """Check that ``workspace`` is the one a ``forward`` call left, and size the backward scratch (rows with the five
     screen sums when ``geom``): (the scratch's SplatWorkspace, its pointer)."""
+    _filled_workspace(caller, forward, workspace, _splat_workspace_bytes(n_gaussians, W, H, capacity), dev)
     L = lib()
-    nbytes = int(L.vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), int(capacity)))
-    _require(nbytes > 0, f"no workspace size for N = {n_gaussians}, {W} x {H}, capacity {capacity}")
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-             workspace.capacity() >= nbytes, f"{caller} needs the workspace of a {forward} call")
     need = int((L.vp_splat_geometry_backward_workspace_bytes if geom else L.vp_splat_backward_workspace_bytes)(int(capacity), D))
     _require(need > 0, f"no backward workspace size for capacity {capacity}, D = {D}")
     bw = bwd_workspace if bwd_workspace is not None else SplatWorkspace()
@@ -788,17 +693,13 @@ def splat_project(means, quats, scales, opacities, viewmat, K, W, H, *, near=0.0
     dev = means.device
     vm, (fx, fy, cx, cy) = _splat_camera(viewmat, K, W, H)
     ws = workspace if workspace is not None else SplatWorkspace()
-    L = lib()
-    nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), 0))
+    nbytes = int(lib().vp_splat_workspace_bytes(N, int(W), int(H), 0))
     _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}")
     ptr = ws.ensure(nbytes, dev)
     n_isect = torch.zeros(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_splat_project(means.data_ptr(), quats.data_ptr(), scales.data_ptr(), opacities.data_ptr(), N, vm,
-                                     fx, fy, cx, cy, int(W), int(H), float(near), float(far), float(eps2d), n_isect.data_ptr(),
-                                     n_nonfinite.data_ptr() if n_nonfinite is not None else None, ptr, ws.capacity(),
-                                     stream.cuda_stream))
+    _call(dev, "vp_splat_project", means.data_ptr(), quats.data_ptr(), scales.data_ptr(), opacities.data_ptr(), N, vm,
+          fx, fy, cx, cy, int(W), int(H), float(near), float(far), float(eps2d), n_isect.data_ptr(),
+          n_nonfinite.data_ptr() if n_nonfinite is not None else None, ptr, ws.capacity())
     return n_isect
 
 
@@ -817,11 +718,8 @@ def splat_rasterize(features, n_gaussians, W, H, capacity, workspace, *, want_lo
     alpha = torch.empty((H, W), dtype=torch.float32, device=dev) if want_alpha else None
     logits = torch.empty((D, H, W), dtype=torch.float32, device=dev) if want_logits else None
     p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(lib().vp_splat_rasterize(features.data_ptr(), D, max(int(features.stride(0)), D), int(n_gaussians), int(W),
-                                           int(H), int(capacity), labels.data_ptr(), p(conf), p(alpha), p(logits), p(status),
-                                           ptr, workspace.capacity(), stream.cuda_stream))
+    _call(dev, "vp_splat_rasterize", features.data_ptr(), D, max(int(features.stride(0)), D), int(n_gaussians), int(W),
+          int(H), int(capacity), labels.data_ptr(), p(conf), p(alpha), p(logits), p(status), ptr, workspace.capacity())
     return labels, conf, alpha, logits
 
 
@@ -841,12 +739,9 @@ def splat_rasterize_backward(features, n_gaussians, W, H, capacity, workspace, g
     bw, bptr = _splat_backward_workspaces("splat_rasterize_backward", "splat_rasterize", workspace, bwd_workspace, N, W, H,
                                           capacity, D, False, dev)
     out = _splat_grads(N, D, dev, features=want_features, opacities=want_opacities)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(lib().vp_splat_rasterize_backward(
-            _ptr(features), D, max(int(features.stride(0)), D), N, int(W), int(H), int(capacity), _ptr(grad_logits),
-            _ptr(grad_alpha), _ptr(out["features"]), _ptr(out["opacities"]), _ptr(status), workspace.ptr(),
-            workspace.capacity(), bptr, bw.capacity(), stream.cuda_stream))
+    _call(dev, "vp_splat_rasterize_backward", _ptr(features), D, max(int(features.stride(0)), D), N, int(W), int(H),
+          int(capacity), _ptr(grad_logits), _ptr(grad_alpha), _ptr(out["features"]), _ptr(out["opacities"]), _ptr(status),
+          workspace.ptr(), workspace.capacity(), bptr, bw.capacity())
     return out["features"], out["opacities"]
 
 
@@ -874,13 +769,11 @@ def splat_rasterize_backward_geometry(means, quats, scales, features, viewmat, K
                                           W, H, capacity, D, True, dev)
     out = _splat_grads(N, D, dev, means=want_means, quats=want_quats, scales=want_scales, features=want_features,
                        opacities=want_opacities, screen=want_screen)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(lib().vp_splat_rasterize_backward_geometry(
-            _ptr(means), _ptr(quats), _ptr(scales), _ptr(features), D, max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy,
-            int(W), int(H), float(eps2d), int(capacity), _ptr(grad_logits), _ptr(grad_alpha), _ptr(out["means"]),
-            _ptr(out["quats"]), _ptr(out["scales"]), _ptr(out["features"]), _ptr(out["opacities"]), _ptr(out["screen"]),
-            _ptr(status), workspace.ptr(), workspace.capacity(), bptr, bw.capacity(), stream.cuda_stream))
+    _call(dev, "vp_splat_rasterize_backward_geometry", _ptr(means), _ptr(quats), _ptr(scales), _ptr(features), D,
+          max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy, int(W), int(H), float(eps2d), int(capacity),
+          _ptr(grad_logits), _ptr(grad_alpha), _ptr(out["means"]), _ptr(out["quats"]), _ptr(out["scales"]),
+          _ptr(out["features"]), _ptr(out["opacities"]), _ptr(out["screen"]), _ptr(status), workspace.ptr(),
+          workspace.capacity(), bptr, bw.capacity())
     return out
 
 
@@ -972,12 +865,9 @@ def splat_rasterize_loss(features, n_gaussians, W, H, capacity, workspace, targe
     labels, conf = img(want_labels, torch.int32), img(want_confidence, torch.float32)
     alpha, logits = img(want_alpha, torch.float32), img(want_logits, torch.float32, D)
     p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(lib().vp_splat_rasterize_loss(_ptr(features), D, max(int(features.stride(0)), D), int(n_gaussians), int(W),
-                                                int(H), int(capacity), p(target), p(pixel_weight), p(stats), p(ploss),
-                                                p(labels), p(conf), p(alpha), p(logits), p(status), ptr, workspace.capacity(),
-                                                lptr, lw.capacity(), stream.cuda_stream))
+    _call(dev, "vp_splat_rasterize_loss", _ptr(features), D, max(int(features.stride(0)), D), int(n_gaussians), int(W),
+          int(H), int(capacity), p(target), p(pixel_weight), p(stats), p(ploss), p(labels), p(conf), p(alpha), p(logits),
+          p(status), ptr, workspace.capacity(), lptr, lw.capacity())
     return stats, ploss, labels, conf, alpha, logits
 
 
@@ -1015,14 +905,11 @@ def splat_loss_backward(means, quats, scales, features, viewmat, K, W, H, capaci
                                           capacity, D, geom, dev)
     out = _splat_grads(N, D, dev, means=want_means, quats=want_quats, scales=want_scales, features=want_features,
                        opacities=want_opacities, screen=want_screen)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(lib().vp_splat_loss_backward(
-            _ptr(means), _ptr(quats), _ptr(scales), _ptr(features), D, max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy,
-            int(W), int(H), float(eps2d), int(capacity), _ptr(target), _ptr(pixel_weight), _ptr(logits), _ptr(loss_stats),
-            _REDUCTIONS[reduction], _ptr(grad_loss), _ptr(grad_alpha), _ptr(out["means"]), _ptr(out["quats"]),
-            _ptr(out["scales"]), _ptr(out["features"]), _ptr(out["opacities"]), _ptr(out["screen"]), _ptr(status),
-            workspace.ptr(), workspace.capacity(), bptr, bw.capacity(), stream.cuda_stream))
+    _call(dev, "vp_splat_loss_backward", _ptr(means), _ptr(quats), _ptr(scales), _ptr(features), D,
+          max(int(features.stride(0)), D), N, vm, fx, fy, cx, cy, int(W), int(H), float(eps2d), int(capacity), _ptr(target),
+          _ptr(pixel_weight), _ptr(logits), _ptr(loss_stats), _REDUCTIONS[reduction], _ptr(grad_loss), _ptr(grad_alpha),
+          _ptr(out["means"]), _ptr(out["quats"]), _ptr(out["scales"]), _ptr(out["features"]), _ptr(out["opacities"]),
+          _ptr(out["screen"]), _ptr(status), workspace.ptr(), workspace.capacity(), bptr, bw.capacity())
     return out
 
 
@@ -1047,17 +934,10 @@ def splat_loss(means, quats, scales, opacities, features, viewmat, K, W, H, targ
     return SplatLossResult(*out, cap, bad)
 
 
-def _lift_lib():
-    L = lib()
-    if not hasattr(L, "vp_splat_lift"):
-        raise VoxprojError(f"{LIB_PATH} has no vp_splat_lift: rebuild it (there is no fallback)")
-    return L
-
-
 def splat_lift_workspace_bytes(capacity, C):
     """vp_splat_lift_workspace_bytes: bytes of the lift's scratch for ``capacity`` intersections and C channels (0 when
     either is out of range).  Needs no GPU."""
-    return int(_lift_lib().vp_splat_lift_workspace_bytes(int(capacity), int(C)))
+    return int(_entry("vp_splat_lift_workspace_bytes")(int(capacity), int(C)))
 
 
 def splat_lift(feats, n_gaussians, W, H, capacity, workspace, sum, wsum, pixel_weight=None, sorted=False, status=None,
@@ -1070,7 +950,6 @@ def splat_lift(feats, n_gaussians, W, H, capacity, workspace, sum, wsum, pixel_w
     call with the same capacity left.  ``lift_workspace``: a SplatWorkspace for the partial rows (a fresh one when None).
     ``status``: optional device int32 [1], set to 1 when the device count exceeds ``capacity`` (then nothing is added)."""
     import torch
-    L = _lift_lib()
     _require(isinstance(sorted, (bool, int)) and int(sorted) in (0, 1), "sorted must be False or True")
     _require_tensors((feats, "feats", (torch.float16,)), (sum, "sum", (torch.float32,)))
     dev, N = feats.device, int(n_gaussians)
@@ -1087,22 +966,17 @@ def splat_lift(feats, n_gaussians, W, H, capacity, workspace, sum, wsum, pixel_w
                  f"wsum must be contiguous float32 [{N}] on the map's device")
     (pixel_weight,) = _splat_images(dev, (pixel_weight, "pixel_weight", (H, W), torch.float32))
     if sorted:
-        nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), int(capacity)))
-        _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}, capacity {capacity}")
-        _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-                 workspace.capacity() >= nbytes, "splat_lift(sorted=True) needs the workspace of a splat_rasterize call")
-        ptr = workspace.ptr()
+        ptr = _filled_workspace("splat_lift(sorted=True)", "splat_rasterize", workspace,
+                                _splat_workspace_bytes(N, W, H, capacity), dev)
     else:
         ptr = _splat_forward_workspace(workspace, N, W, H, capacity, dev)
-    need = int(L.vp_splat_lift_workspace_bytes(int(capacity), C))
+    need = splat_lift_workspace_bytes(capacity, C)
     _require(need > 0, f"no lift workspace size for capacity {capacity}, C = {C}")
     lw = lift_workspace if lift_workspace is not None else SplatWorkspace()
     lptr = lw.ensure(need, dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_splat_lift(feats.data_ptr(), C, int(feats.stride(1)), _ptr(pixel_weight), N, int(W), int(H),
-                                  int(capacity), int(sorted), sum.data_ptr() if N else lptr, max(int(sum.stride(0)), C) if N else C,
-                                  _ptr(wsum), _ptr(status), ptr, workspace.capacity(), lptr, lw.capacity(), stream.cuda_stream))
+    _call(dev, "vp_splat_lift", feats.data_ptr(), C, int(feats.stride(1)), _ptr(pixel_weight), N, int(W), int(H),
+          int(capacity), int(sorted), sum.data_ptr() if N else lptr, max(int(sum.stride(0)), C) if N else C, _ptr(wsum),
+          _ptr(status), ptr, workspace.capacity(), lptr, lw.capacity())
 
 
 def splat_lift_view(means, quats, scales, opacities, feats, viewmat, K, W, H, sum, wsum, pixel_weight=None, *, near=0.01,
@@ -1157,13 +1031,6 @@ class GaussianFeatureLifter:
         return avg.to(torch.float16), self.wsum.clone(), valid
 
 
-def _render_lib():
-    L = lib()
-    if not hasattr(L, "vp_splat_render"):
-        raise VoxprojError(f"{LIB_PATH} has no vp_splat_render: rebuild it (there is no fallback)")
-    return L
-
-
 def splat_render(rows, n_gaussians, W, H, capacity, workspace, *, out=None, dtype=None, want_alpha=False, sorted=False,
                  status=None, check=True):
     """vp_splat_render after splat_project on ``workspace``: blend the Gaussians' wide rows into one view,
@@ -1179,7 +1046,6 @@ def splat_render(rows, n_gaussians, W, H, capacity, workspace, *, out=None, dtyp
     With ``check`` the call reads the status word (one synchronisation) and raises VoxprojError when it is set.
     Returns (out, alpha f32 [H,W] or None); alpha is bit-identical to splat_rasterize's."""
     import torch
-    L = _render_lib()
     _require(isinstance(sorted, (bool, int)) and int(sorted) in (0, 1), "sorted must be False or True")
     _require_tensors((rows, "rows", (torch.float16, torch.float32)))
     dev, N = rows.device, int(n_gaussians)
@@ -1202,20 +1068,14 @@ def splat_render(rows, n_gaussians, W, H, capacity, workspace, *, out=None, dtyp
         _require_tensors((status, "status", (torch.int32,)))
         _require(status.numel() == 1 and status.device == dev, "status must be one int32 on the rows' device")
     if sorted:
-        nbytes = int(L.vp_splat_workspace_bytes(N, int(W), int(H), int(capacity)))
-        _require(nbytes > 0, f"no workspace size for N = {N}, {W} x {H}, capacity {capacity}")
-        _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-                 workspace.capacity() >= nbytes, "splat_render(sorted=True) needs the workspace of a splat_rasterize call")
-        ptr = workspace.ptr()
+        ptr = _filled_workspace("splat_render(sorted=True)", "splat_rasterize", workspace,
+                                _splat_workspace_bytes(N, W, H, capacity), dev)
     else:
         ptr = _splat_forward_workspace(workspace, N, W, H, capacity, dev)
     alpha = torch.empty((int(H), int(W)), dtype=torch.float32, device=dev) if want_alpha else None
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        _check_rc(L.vp_splat_render(rows.data_ptr() if N else ptr, int(rows.dtype == torch.float16), C,
-                                    max(int(rows.stride(0)), C) if N > 1 else C, N, int(W), int(H), int(capacity), int(sorted),
-                                    out.data_ptr(), int(out.dtype == torch.float16), int(out.stride(1)), _ptr(alpha),
-                                    _ptr(status), ptr, workspace.capacity(), stream.cuda_stream))
+    _call(dev, "vp_splat_render", rows.data_ptr() if N else ptr, int(rows.dtype == torch.float16), C,
+          max(int(rows.stride(0)), C) if N > 1 else C, N, int(W), int(H), int(capacity), int(sorted), out.data_ptr(),
+          int(out.dtype == torch.float16), int(out.stride(1)), _ptr(alpha), _ptr(status), ptr, workspace.capacity())
     if check and int(status.item()):
         raise VoxprojError("splat_render: the intersection count outgrew the workspace (nothing written)")
     return out, alpha
@@ -1228,7 +1088,6 @@ def splat_render_view(means, quats, scales, opacities, rows, viewmat, K, W, H, *
     n_nonfinite device int32 [1]); ``out`` / ``dtype`` as in splat_render.  With ``check`` the call synchronises once more
     and raises VoxprojError when a Gaussian had a non-finite parameter (it is culled)."""
     import torch
-    _render_lib()
     _require_tensors(*((t, name, (torch.float32,)) for t, name in
                        ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
     _require(isinstance(rows, torch.Tensor) and rows.device == means.device, "rows and the Gaussians must be on one device")
@@ -1240,21 +1099,13 @@ def splat_render_view(means, quats, scales, opacities, rows, viewmat, K, W, H, *
     return out, alpha, cap, bad
 
 
-def _feature_loss_lib():
-    L = lib()
-    if not hasattr(L, "vp_feature_loss"):
-        raise VoxprojError(f"{LIB_PATH} has no vp_feature_loss: rebuild it (there is no fallback)")
-    return L
-
-
 FEATURE_LOSS_KINDS = {"cosine": VP_FEATURE_LOSS_COSINE, "l2": VP_FEATURE_LOSS_L2}
-_LOSS_REDUCTIONS = {"sum": VP_LOSS_SUM, "mean": VP_LOSS_MEAN}
 
 
 def feature_loss_workspace_bytes(W, H):
     """vp_feature_loss_workspace_bytes: bytes of the feature loss's workspace for a W x H view (0 when out of range).  Needs
     no GPU."""
-    return int(_feature_loss_lib().vp_feature_loss_workspace_bytes(int(W), int(H)))
+    return int(_entry("vp_feature_loss_workspace_bytes")(int(W), int(H)))
 
 
 def _feature_maps(caller, image, target):
@@ -1284,21 +1135,18 @@ def feature_loss(image, target, pixel_weight=None, alpha=None, *, kind="cosine",
     the call fills for feature_loss_gradient (a fresh one when None).
     Returns (loss_stats f64 [2] = {sum m l, sum m}, pixel_loss f32 [H,W] or None, workspace); nothing is read back here."""
     import torch
-    L = _feature_loss_lib()
     _require(kind in FEATURE_LOSS_KINDS, f"kind must be 'cosine' or 'l2', not {kind!r}")
     image, target, H, W, C = _feature_maps("feature_loss", image, target)
     dev = image.device
     pixel_weight, alpha = _splat_images(dev, (pixel_weight, "pixel_weight", (H, W), torch.float32),
                                         (alpha, "alpha", (H, W), torch.float32))
     ws = workspace if workspace is not None else SplatWorkspace()
-    ptr = ws.ensure(int(L.vp_feature_loss_workspace_bytes(W, H)), dev)
+    ptr = ws.ensure(feature_loss_workspace_bytes(W, H), dev)
     stats = torch.empty(2, dtype=torch.float64, device=dev)
     pixel_loss = torch.empty((H, W), dtype=torch.float32, device=dev) if want_pixel_loss else None
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_feature_loss(image.data_ptr(), int(image.dtype == torch.float16), int(image.stride(1)), target.data_ptr(),
-                                    int(target.stride(1)), C, W, H, _ptr(pixel_weight), _ptr(alpha), float(min_alpha),
-                                    FEATURE_LOSS_KINDS[kind], stats.data_ptr(), _ptr(pixel_loss), ptr, ws.capacity(),
-                                    torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_feature_loss", image.data_ptr(), int(image.dtype == torch.float16), int(image.stride(1)), target.data_ptr(),
+          int(target.stride(1)), C, W, H, _ptr(pixel_weight), _ptr(alpha), float(min_alpha), FEATURE_LOSS_KINDS[kind],
+          stats.data_ptr(), _ptr(pixel_loss), ptr, ws.capacity())
     return stats, pixel_loss, ws
 
 
@@ -1310,37 +1158,24 @@ def feature_loss_gradient(image, target, loss_stats, workspace, *, reduction="me
     pixel are not touched), or None for a fresh contiguous one.
     Returns (Gq f16 [H,W,C], k int32 [1] on the device): the gradient is Gq / 2^k; nothing is read back here."""
     import torch
-    L = _feature_loss_lib()
-    _require(reduction in _LOSS_REDUCTIONS, f"reduction must be 'mean' or 'sum', not {reduction!r}")
+    _require(reduction in _REDUCTIONS, f"reduction must be 'mean' or 'sum', not {reduction!r}")
     image, target, H, W, C = _feature_maps("feature_loss_gradient", image, target)
     dev = image.device
     _require_tensors((loss_stats, "loss_stats", (torch.float64,)))
     _require(loss_stats.numel() == 2 and loss_stats.device == dev and loss_stats.is_contiguous(),
              "loss_stats must be the float64 [2] tensor feature_loss returned")
     (grad_loss,) = _splat_images(dev, (grad_loss, "grad_loss", None, torch.float32))
-    need = int(L.vp_feature_loss_workspace_bytes(W, H))
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-             workspace.capacity() >= need, "feature_loss_gradient needs the workspace of a feature_loss call")
+    ptr = _filled_workspace("feature_loss_gradient", "feature_loss", workspace, feature_loss_workspace_bytes(W, H), dev)
     if out is None:
         out = torch.empty((H, W, C), dtype=torch.float16, device=dev)
     _require_tensors((out, "out", (torch.float16,)))
     _require(out.device == dev and tuple(out.shape) == (H, W, C) and out.stride(2) == 1 and out.stride(1) >= C and
              out.stride(0) == W * out.stride(1), f"out must be float16 [{H}, {W}, {C}], channels-last with one pixel stride >= C")
     k = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_feature_loss_gradient(image.data_ptr(), int(image.dtype == torch.float16), int(image.stride(1)),
-                                             target.data_ptr(), int(target.stride(1)), C, W, H, loss_stats.data_ptr(),
-                                             _LOSS_REDUCTIONS[reduction], _ptr(grad_loss), out.data_ptr(), int(out.stride(1)),
-                                             k.data_ptr(), workspace.ptr(), workspace.capacity(),
-                                             torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_feature_loss_gradient", image.data_ptr(), int(image.dtype == torch.float16), int(image.stride(1)),
+          target.data_ptr(), int(target.stride(1)), C, W, H, loss_stats.data_ptr(), _REDUCTIONS[reduction], _ptr(grad_loss),
+          out.data_ptr(), int(out.stride(1)), k.data_ptr(), ptr, workspace.capacity())
     return out, k
-
-
-def _proto_lib():
-    L = lib()
-    if not hasattr(L, "vp_proto_contrast"):
-        raise VoxprojError(f"{LIB_PATH} has no vp_proto_contrast: rebuild it (there is no fallback)")
-    return L
 
 
 VP_PROTO_MAX_IDS = 256
@@ -1349,7 +1184,18 @@ VP_PROTO_MAX_IDS = 256
 def proto_contrast_workspace_bytes(D, W, H):
     """vp_proto_contrast_workspace_bytes: bytes of the prototype-contrastive loss's workspace for a D-channel W x H image
     (0 when out of range).  Needs no GPU."""
-    return int(_proto_lib().vp_proto_contrast_workspace_bytes(int(D), int(W), int(H)))
+    return int(_entry("vp_proto_contrast_workspace_bytes")(int(D), int(W), int(H)))
+
+
+def _gradient_image(out, shape, dev):
+    """The contiguous f32 image of ``shape`` on ``dev`` a gradient call writes: a fresh one, or the caller's ``out`` checked."""
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    _require_tensors((out, "out", (torch.float32,)))
+    _require(out.device == dev and tuple(out.shape) == shape and out.is_contiguous(),
+             f"out must be a contiguous float32 [{shape[0]}, {shape[1]}, {shape[2]}] tensor on the image's device")
+    return out
 
 
 def _proto_maps(caller, image, ids, count):
@@ -1375,18 +1221,16 @@ def proto_contrast(image, ids, count=None, *, ignore_id=-1, min_count=20, phi_sc
     Returns (stats f64 [4] = {sum m l, K, sum (r - 1)^2, sum m}, pixel_loss f32 [H,W] or None, own_prob f32 [H,W] or None,
     workspace); nothing is read back here."""
     import torch
-    L = _proto_lib()
     image, ids, count, D, H, W = _proto_maps("proto_contrast", image, ids, count)
     dev = image.device
     ws = workspace if workspace is not None else SplatWorkspace()
-    ptr = ws.ensure(int(L.vp_proto_contrast_workspace_bytes(D, W, H)), dev)
+    ptr = ws.ensure(proto_contrast_workspace_bytes(D, W, H), dev)
     stats = torch.empty(4, dtype=torch.float64, device=dev)
     pixel_loss = torch.empty((H, W), dtype=torch.float32, device=dev) if want_pixel_loss else None
     own_prob = torch.empty((H, W), dtype=torch.float32, device=dev) if want_own_prob else None
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_proto_contrast(image.data_ptr(), D, W, H, ids.data_ptr(), _ptr(count), int(ignore_id), int(min_count),
-                                      float(phi_scale), float(phi_min), float(phi_max), stats.data_ptr(), _ptr(pixel_loss),
-                                      _ptr(own_prob), ptr, ws.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_proto_contrast", image.data_ptr(), D, W, H, ids.data_ptr(), _ptr(count), int(ignore_id), int(min_count),
+          float(phi_scale), float(phi_min), float(phi_max), stats.data_ptr(), _ptr(pixel_loss), _ptr(own_prob), ptr,
+          ws.capacity())
     return stats, pixel_loss, own_prob, ws
 
 
@@ -1395,36 +1239,20 @@ def proto_contrast_gradient(image, ids, count, workspace, *, weight_contrast=1.0
     image f32 [D,H,W] of  weight_contrast (sum m l) / K + weight_norm (sum (r - 1)^2) / (W H), times ``grad_loss`` (a device
     f32 [1]; None: 1).  ``out``: a contiguous f32 [D,H,W] tensor, or None for a fresh one.  Nothing is read back here."""
     import torch
-    L = _proto_lib()
     image, ids, count, D, H, W = _proto_maps("proto_contrast_gradient", image, ids, count)
     dev = image.device
     (grad_loss,) = _splat_images(dev, (grad_loss, "grad_loss", None, torch.float32))
-    need = int(L.vp_proto_contrast_workspace_bytes(D, W, H))
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-             workspace.capacity() >= need, "proto_contrast_gradient needs the workspace of a proto_contrast call")
-    if out is None:
-        out = torch.empty((D, H, W), dtype=torch.float32, device=dev)
-    _require_tensors((out, "out", (torch.float32,)))
-    _require(out.device == dev and tuple(out.shape) == (D, H, W) and out.is_contiguous(),
-             f"out must be a contiguous float32 [{D}, {H}, {W}] tensor on the image's device")
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_proto_contrast_gradient(image.data_ptr(), D, W, H, ids.data_ptr(), _ptr(count), float(weight_contrast),
-                                               float(weight_norm), _ptr(grad_loss), out.data_ptr(), workspace.ptr(),
-                                               workspace.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+    ptr = _filled_workspace("proto_contrast_gradient", "proto_contrast", workspace, proto_contrast_workspace_bytes(D, W, H), dev)
+    out = _gradient_image(out, (D, H, W), dev)
+    _call(dev, "vp_proto_contrast_gradient", image.data_ptr(), D, W, H, ids.data_ptr(), _ptr(count), float(weight_contrast),
+          float(weight_norm), _ptr(grad_loss), out.data_ptr(), ptr, workspace.capacity())
     return out
-
-
-def _photo_lib():
-    L = lib()
-    if not hasattr(L, "vp_photo_loss"):
-        raise VoxprojError(f"{LIB_PATH} has no vp_photo_loss: rebuild it (there is no fallback)")
-    return L
 
 
 def photo_loss_workspace_bytes(C, W, H):
     """vp_photo_loss_workspace_bytes: bytes of the photometric loss's workspace for a C-channel W x H image (0 when out of
     range).  Needs no GPU."""
-    return int(_photo_lib().vp_photo_loss_workspace_bytes(int(C), int(W), int(H)))
+    return int(_entry("vp_photo_loss_workspace_bytes")(int(C), int(W), int(H)))
 
 
 def _photo_maps(caller, image, target):
@@ -1448,20 +1276,17 @@ def photo_loss(image, target, *, want_ssim_map=False, workspace=None, evaluate_o
     Returns (stats f64 [3] = {sum |x - y|, sum (x - y)^2, sum m}, ssim_map f32 [C,H,W] or None, workspace or None); nothing
     is read back here."""
     import torch
-    L = _photo_lib()
     image, target, C, H, W = _photo_maps("photo_loss", image, target)
     dev = image.device
     _require(not (evaluate_only and workspace is not None), "photo_loss: evaluate_only takes no workspace")
     ws, ptr, cap = None, None, 0
     if not evaluate_only:
         ws = workspace if workspace is not None else SplatWorkspace()
-        ptr = ws.ensure(int(L.vp_photo_loss_workspace_bytes(C, W, H)), dev)
+        ptr = ws.ensure(photo_loss_workspace_bytes(C, W, H), dev)
         cap = ws.capacity()
     stats = torch.empty(3, dtype=torch.float64, device=dev)
     ssim_map = torch.empty((C, H, W), dtype=torch.float32, device=dev) if want_ssim_map else None
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_photo_loss(image.data_ptr(), target.data_ptr(), C, W, H, stats.data_ptr(), _ptr(ssim_map), ptr, cap,
-                                  torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_photo_loss", image.data_ptr(), target.data_ptr(), C, W, H, stats.data_ptr(), _ptr(ssim_map), ptr, cap)
     return stats, ssim_map, ws
 
 
@@ -1470,22 +1295,13 @@ def photo_loss_gradient(image, target, workspace, *, lambda_dssim, grad_loss=Non
     [C,H,W] of  (1 - lambda_dssim) mean |x - y| + lambda_dssim (1 - mean m), times ``grad_loss`` (a device f32 [1]; None: 1).
     ``out``: a contiguous f32 [C,H,W] tensor, or None for a fresh one.  Nothing is read back here."""
     import torch
-    L = _photo_lib()
     image, target, C, H, W = _photo_maps("photo_loss_gradient", image, target)
     dev = image.device
     (grad_loss,) = _splat_images(dev, (grad_loss, "grad_loss", None, torch.float32))
-    need = int(L.vp_photo_loss_workspace_bytes(C, W, H))
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-             workspace.capacity() >= need, "photo_loss_gradient needs the workspace of a photo_loss call")
-    if out is None:
-        out = torch.empty((C, H, W), dtype=torch.float32, device=dev)
-    _require_tensors((out, "out", (torch.float32,)))
-    _require(out.device == dev and tuple(out.shape) == (C, H, W) and out.is_contiguous(),
-             f"out must be a contiguous float32 [{C}, {H}, {W}] tensor on the image's device")
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_photo_loss_gradient(image.data_ptr(), target.data_ptr(), C, W, H, float(lambda_dssim), _ptr(grad_loss),
-                                           out.data_ptr(), workspace.ptr(), workspace.capacity(),
-                                           torch.cuda.current_stream(dev).cuda_stream))
+    ptr = _filled_workspace("photo_loss_gradient", "photo_loss", workspace, photo_loss_workspace_bytes(C, W, H), dev)
+    out = _gradient_image(out, (C, H, W), dev)
+    _call(dev, "vp_photo_loss_gradient", image.data_ptr(), target.data_ptr(), C, W, H, float(lambda_dssim), _ptr(grad_loss),
+          out.data_ptr(), ptr, workspace.capacity())
     return out
 
 
@@ -1508,10 +1324,9 @@ _DENSIFY_FILLS = {"copy": VP_DENSIFY_COPY, "zero": VP_DENSIFY_ZERO}
 
 
 def _densify_lib():
-    L = lib()
-    if not hasattr(L, "vp_densify_plan"):
-        raise VoxprojError(f"{LIB_PATH} has no vp_densify_plan: rebuild it (there is no fallback)")
-    return L
+    """The library, for the GPU tests that drive the densification entry points through the C ABI themselves."""
+    _entry("vp_densify_plan")
+    return lib()
 
 
 def camera_extent(viewmats):
@@ -1547,16 +1362,14 @@ def densify_accumulate(stats, grad_screen, workspace, W, H, scale=1.0, geometry=
     caller's 1 / k.  ``geometry``: (means, quats, scales, viewmat, K) or (..., eps2d) of the project call, needed when the
     stats keep max_radius and ignored otherwise.  Asynchronous; nothing is read back."""
     import torch
-    L = _densify_lib()
     _require_tensors((grad_screen, "grad_screen", (torch.float32,)))
     N = stats.n
     dev = grad_screen.device
     _require(tuple(grad_screen.shape) == (N, 5) and grad_screen.is_contiguous(), f"grad_screen must be a contiguous [{N}, 5]")
     _require(stats.grad_accum.device == dev, "the statistics and grad_screen must be on one device")
     _require(1 <= int(W) <= 32768 and 1 <= int(H) <= 32768, f"image size {W} x {H} outside [1, 32768]")
-    need = int(L.vp_splat_workspace_bytes(N, int(W), int(H), 0))
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and
-             workspace.capacity() >= need, "densify_accumulate needs the workspace of a splat_project call")
+    ptr = _filled_workspace("densify_accumulate", "splat_project", workspace,
+                            int(lib().vp_splat_workspace_bytes(N, int(W), int(H), 0)), dev)
     m = q = s = vm = None
     fx = fy = cx = cy = 0.0
     eps2d = 0.3
@@ -1568,10 +1381,8 @@ def densify_accumulate(stats, grad_screen, workspace, W, H, scale=1.0, geometry=
         vm, (fx, fy, cx, cy) = _splat_camera(geometry[3], geometry[4], W, H)
         if len(geometry) == 6:
             eps2d = float(geometry[5])
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_densify_accumulate(_ptr(grad_screen), N, int(W), int(H), float(scale), _ptr(m), _ptr(q), _ptr(s), vm, fx,
-                                          fy, cx, cy, eps2d, _ptr(stats.grad_accum), _ptr(stats.denom), _ptr(stats.max_radius),
-                                          workspace.ptr(), workspace.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_densify_accumulate", _ptr(grad_screen), N, int(W), int(H), float(scale), _ptr(m), _ptr(q), _ptr(s), vm, fx,
+          fy, cx, cy, eps2d, _ptr(stats.grad_accum), _ptr(stats.denom), _ptr(stats.max_radius), ptr, workspace.capacity())
 
 
 def densify_rows(arrays, src, kind, counts, n_src, n_out, status=None):
@@ -1580,7 +1391,6 @@ def densify_rows(arrays, src, kind, counts, n_src, n_out, status=None):
     row stride >= the width.  dst row r = src row src[r] (zeros where fill is "zero" and kind[r] != 0).  ``n_out`` is the
     host's copy of counts[0]; when the device disagrees nothing is written and ``status`` (device int32 [1]) becomes 1."""
     import torch
-    L = _densify_lib()
     descs = []
     for a, d, fill in arrays:
         _require_tensors((a, "a source array", (torch.float32, torch.int32)), (d, "a destination array", (a.dtype,)))
@@ -1601,13 +1411,10 @@ def densify_rows(arrays, src, kind, counts, n_src, n_out, status=None):
                 strides.append(int(t.stride(0)))
         _require(1 <= width <= VP_DENSIFY_MAX_WIDTH, f"a row has {width} words: outside [1, {VP_DENSIFY_MAX_WIDTH}]")
         descs.append(_DensifyArray(_ptr(a), _ptr(d), width, _DENSIFY_FILLS[fill], strides[0], strides[1]))
-    dev = src.device
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        for i in range(0, len(descs), VP_DENSIFY_MAX_ARRAYS):
-            part = descs[i:i + VP_DENSIFY_MAX_ARRAYS]
-            _check_rc(L.vp_densify_rows((_DensifyArray * len(part))(*part), len(part), _ptr(src), _ptr(kind), counts.data_ptr(),
-                                        int(n_src), int(n_out), _ptr(status), stream))
+    for i in range(0, len(descs), VP_DENSIFY_MAX_ARRAYS):
+        part = descs[i:i + VP_DENSIFY_MAX_ARRAYS]
+        _call(src.device, "vp_densify_rows", (_DensifyArray * len(part))(*part), len(part), _ptr(src), _ptr(kind),
+              counts.data_ptr(), int(n_src), int(n_out), _ptr(status))
 
 
 class DensifyPlan:
@@ -1642,7 +1449,6 @@ class DensifyPlan:
         clones, sampled positions and shrunk scales for the split children.  ``seed``: an int below 2^64 or (low, high)
         32-bit words; the same seed and inputs give the same bits."""
         import torch
-        L = _densify_lib()
         _, (m, q, s) = _splat_gaussians(means.detach(), quats.detach(), log_scales.detach())
         _require(int(m.shape[0]) == self.n and m.device == self.src.device, f"the geometry must have {self.n} Gaussians")
         if isinstance(seed, (tuple, list)):
@@ -1651,10 +1457,8 @@ class DensifyPlan:
         dev = m.device
         om = torch.empty((self.n_out, 3), dtype=torch.float32, device=dev)
         ol = torch.empty((self.n_out, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check_rc(L.vp_densify_split(_ptr(m), _ptr(q), _ptr(s), self.n, _ptr(self.src), _ptr(self.kind),
-                                         self.counts.data_ptr(), self.n_out, int(seed), _ptr(om), _ptr(ol), _ptr(self.status),
-                                         torch.cuda.current_stream(dev).cuda_stream))
+        _call(dev, "vp_densify_split", _ptr(m), _ptr(q), _ptr(s), self.n, _ptr(self.src), _ptr(self.kind),
+              self.counts.data_ptr(), self.n_out, int(seed), _ptr(om), _ptr(ol), _ptr(self.status))
         return om, ol
 
 
@@ -1665,14 +1469,13 @@ def densify_plan(stats, scales, opacities, *, grad_threshold, size_threshold, mi
     0.1 x extent; max_screen_size 0 turns the size rules off.  Reads the four counters back: the one synchronisation of a
     densification.  ``workspace``: a SplatWorkspace for the scan's scratch (a fresh one when None)."""
     import torch
-    L = _densify_lib()
     _require_tensors((scales, "scales", (torch.float32,)), (opacities, "opacities", (torch.float32,)))
     N, dev = stats.n, scales.device
     _require(tuple(scales.shape) == (N, 3) and tuple(opacities.shape) == (N,), f"scales must be [{N}, 3] and opacities [{N}]")
     _require(opacities.device == dev and stats.grad_accum.device == dev, "the statistics, scales and opacities must be on one device")
     _require(float(grad_threshold) > 0.0, f"grad_threshold = {grad_threshold} must be > 0")
     scales, opacities = scales.detach().contiguous(), opacities.detach().contiguous()
-    need = int(L.vp_densify_plan_workspace_bytes(N))
+    need = int(_entry("vp_densify_plan_workspace_bytes")(N))
     _require(need > 0, f"no plan workspace size for N = {N}")
     ws = workspace if workspace is not None else SplatWorkspace()
     ptr = ws.ensure(need, dev)
@@ -1680,11 +1483,9 @@ def densify_plan(stats, scales, opacities, *, grad_threshold, size_threshold, mi
     kind = torch.empty(2 * N, dtype=torch.uint8, device=dev)
     counts = torch.empty(4, dtype=torch.int64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_densify_plan(_ptr(stats.grad_accum), _ptr(stats.denom), _ptr(stats.max_radius), _ptr(scales),
-                                    _ptr(opacities), N, float(grad_threshold), float(size_threshold), float(min_opacity),
-                                    float(max_screen_size), float(max_world_size), _ptr(src), _ptr(kind), counts.data_ptr(), ptr,
-                                    ws.capacity(), torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_densify_plan", _ptr(stats.grad_accum), _ptr(stats.denom), _ptr(stats.max_radius), _ptr(scales),
+          _ptr(opacities), N, float(grad_threshold), float(size_threshold), float(min_opacity), float(max_screen_size),
+          float(max_world_size), _ptr(src), _ptr(kind), counts.data_ptr(), ptr, ws.capacity())
     return DensifyPlan(N, src, kind, counts, status)
 
 
@@ -1713,20 +1514,13 @@ def resample_adam(optimizer, old_params, new_params, plan):
         optimizer.state[new_params[name]] = st
 
 
-def _codebook_lib():
-    L = lib()
-    if not hasattr(L, "vp_codebook_assoc"):
-        raise VoxprojError(f"{LIB_PATH} has no vp_codebook_assoc: rebuild it (there is no fallback)")
-    return L
-
-
 VP_CODEBOOK_MAX_CODES = 256
 
 
 def codebook_workspace_bytes(D, K, W, H):
     """vp_codebook_workspace_bytes: bytes of the workspace of codebook_assoc and codebook_loss for a D-channel W x H image
     and K codes (0 when out of range).  Needs no GPU."""
-    return int(_codebook_lib().vp_codebook_workspace_bytes(int(D), int(K), int(W), int(H)))
+    return int(_entry("vp_codebook_workspace_bytes")(int(D), int(K), int(W), int(H)))
 
 
 def _codebook_args(caller, image, ids, codebook, workspace):
@@ -1739,7 +1533,7 @@ def _codebook_args(caller, image, ids, codebook, workspace):
     K = int(codebook.shape[0])
     _require(1 <= K <= VP_CODEBOOK_MAX_CODES, f"K = {K} outside [1, {VP_CODEBOOK_MAX_CODES}]")
     ws = workspace if workspace is not None else SplatWorkspace()
-    ptr = ws.ensure(int(_codebook_lib().vp_codebook_workspace_bytes(D, K, W, H)), image.device)
+    ptr = ws.ensure(codebook_workspace_bytes(D, K, W, H), image.device)
     return image, ids, codebook.detach().contiguous(), D, H, W, K, ws, ptr
 
 
@@ -1748,16 +1542,13 @@ def codebook_assoc(image, ids, codebook, *, ignore_id=-1, want_pred=False, works
     codebook f32 [K,D] on one GPU.  Returns (score f64 [256,K], id_pixels int32 [256], pred int32 [H,W] or None, workspace);
     nothing is read back here."""
     import torch
-    L = _codebook_lib()
     image, ids, codebook, D, H, W, K, ws, ptr = _codebook_args("codebook_assoc", image, ids, codebook, workspace)
     dev = image.device
     score = torch.empty((VP_PROTO_MAX_IDS, K), dtype=torch.float64, device=dev)
     id_pixels = torch.empty(VP_PROTO_MAX_IDS, dtype=torch.int32, device=dev)
     pred = torch.empty((H, W), dtype=torch.int32, device=dev) if want_pred else None
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_codebook_assoc(image.data_ptr(), D, W, H, ids.data_ptr(), int(ignore_id), codebook.data_ptr(), K,
-                                      score.data_ptr(), id_pixels.data_ptr(), _ptr(pred), ptr, ws.capacity(),
-                                      torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_codebook_assoc", image.data_ptr(), D, W, H, ids.data_ptr(), int(ignore_id), codebook.data_ptr(), K,
+          score.data_ptr(), id_pixels.data_ptr(), _ptr(pred), ptr, ws.capacity())
     return score, id_pixels, pred, ws
 
 
@@ -1767,7 +1558,6 @@ def codebook_loss(image, ids, conf, codebook, assign, *, conf_min=0.2, ignore_id
     Returns (stats f64 [4] = {sum of cross-entropy terms, sum of |s - B_v|, participating pixels, mismatched pixels},
     grad_cls f32 [K,D], grad_cluster f32 [K,D], pixel_loss f32 [H,W] or None, workspace); nothing is read back here."""
     import torch
-    L = _codebook_lib()
     image, ids, codebook, D, H, W, K, ws, ptr = _codebook_args("codebook_loss", image, ids, codebook, workspace)
     dev = image.device
     (conf,) = _splat_images(dev, (conf, "conf", (H, W), torch.float32))
@@ -1779,19 +1569,10 @@ def codebook_loss(image, ids, conf, codebook, assign, *, conf_min=0.2, ignore_id
     grad_cls = torch.empty((K, D), dtype=torch.float32, device=dev)
     grad_cluster = torch.empty((K, D), dtype=torch.float32, device=dev)
     pixel_loss = torch.empty((H, W), dtype=torch.float32, device=dev) if want_pixel_loss else None
-    with torch.cuda.device(dev):
-        _check_rc(L.vp_codebook_loss(image.data_ptr(), D, W, H, ids.data_ptr(), int(ignore_id), _ptr(conf), float(conf_min),
-                                     codebook.data_ptr(), K, assign.data_ptr(), stats.data_ptr(), grad_cls.data_ptr(),
-                                     grad_cluster.data_ptr(), _ptr(pixel_loss), ptr, ws.capacity(),
-                                     torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_codebook_loss", image.data_ptr(), D, W, H, ids.data_ptr(), int(ignore_id), _ptr(conf), float(conf_min),
+          codebook.data_ptr(), K, assign.data_ptr(), stats.data_ptr(), grad_cls.data_ptr(), grad_cluster.data_ptr(),
+          _ptr(pixel_loss), ptr, ws.capacity())
     return stats, grad_cls, grad_cluster, pixel_loss, ws
-
-
-def _reg3d_lib():
-    L = lib()
-    if not hasattr(L, "vp_knn_points"):
-        raise VoxprojError(f"{LIB_PATH} has no vp_knn_points: rebuild it (there is no fallback)")
-    return L
 
 
 VP_KNN_MAX_K = 15
@@ -1807,7 +1588,6 @@ def knn_points(points, k, queries=None, *, cell_order=True, want_d2=True):
     same cells, and put the rows back in torch; False launches them in the caller's order (the same result)."""
     import torch
     import voxel_to_gaussian_map
-    L = _reg3d_lib()
     _require_tensors((points, "points", (torch.float32,)))
     _require(points.dim() == 2 and int(points.shape[1]) == 3 and points.is_cuda, "points must be float32 [N, 3] on a GPU")
     _require(1 <= int(k) <= VP_KNN_MAX_K, f"k = {k} outside [1, {VP_KNN_MAX_K}]")
@@ -1827,10 +1607,8 @@ def knn_points(points, k, queries=None, *, cell_order=True, want_d2=True):
     idx = torch.empty((M, k), dtype=torch.int32, device=dev)
     d2 = torch.empty((M, k), dtype=torch.float64, device=dev) if want_d2 else None
     g = (ctypes.c_double * 3)(*origin)
-    with torch.cuda.device(dev):
-        check(L.vp_knn_points(pts.data_ptr(), perm.data_ptr(), start.data_ptr(), g, ctypes.c_double(h), dims[0], dims[1], dims[2],
-                              q.data_ptr(), _ptr(self_index), M, k, idx.data_ptr(), _ptr(d2),
-                              torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_knn_points", pts.data_ptr(), perm.data_ptr(), start.data_ptr(), g, ctypes.c_double(h), dims[0], dims[1],
+          dims[2], q.data_ptr(), _ptr(self_index), M, k, idx.data_ptr(), _ptr(d2))
     if queries is None and cell_order:       # row t of the launch is point perm[t]
         back = perm.long()
         idx = torch.empty_like(idx).index_copy_(0, back, idx)
@@ -1902,7 +1680,7 @@ class NeighborTable:
 
 def neighbor_kl_workspace_bytes(S):
     """vp_neighbor_kl_workspace_bytes: bytes of neighbor_kl's workspace for S sample positions.  Needs no GPU."""
-    return int(_reg3d_lib().vp_neighbor_kl_workspace_bytes(int(S)))
+    return int(_entry("vp_neighbor_kl_workspace_bytes")(int(S)))
 
 
 def _neighbor_kl_logits(logits):
@@ -1922,19 +1700,16 @@ def neighbor_kl(logits, sample, *, want_sample_loss=False, lanes=0, workspace=No
     Returns (stats f64 [2] = {sum, S}, row_lse f32 [N], sample_loss f32 [S] or None, workspace) on the device; the loss is
     scale / (S k P) stats[0].  Nothing is read back here."""
     import torch
-    L = _reg3d_lib()
     logits, N, P = _neighbor_kl_logits(logits)
     _require(sample.n_rows == N and sample.nbr.device == logits.device, "the neighbour table is of another point set or device")
     dev = logits.device
     ws = workspace if workspace is not None else SplatWorkspace()
-    ptr = ws.ensure(int(L.vp_neighbor_kl_workspace_bytes(sample.S)), dev)
+    ptr = ws.ensure(neighbor_kl_workspace_bytes(sample.S), dev)
     stats = torch.empty(2, dtype=torch.float64, device=dev)
     row_lse = torch.empty(N, dtype=torch.float32, device=dev)
     sample_loss = torch.empty(sample.S, dtype=torch.float32, device=dev) if want_sample_loss else None
-    with torch.cuda.device(dev):
-        check(L.vp_neighbor_kl(logits.data_ptr(), N, P, logits.stride(0), _ptr(sample.samples), sample.S, _ptr(sample.nbr),
-                               sample.k, row_lse.data_ptr(), _ptr(sample_loss), stats.data_ptr(), int(lanes), ptr, ws.capacity(),
-                               torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_neighbor_kl", logits.data_ptr(), N, P, logits.stride(0), _ptr(sample.samples), sample.S, _ptr(sample.nbr),
+          sample.k, row_lse.data_ptr(), _ptr(sample_loss), stats.data_ptr(), int(lanes), ptr, ws.capacity())
     return stats, row_lse, sample_loss, ws
 
 
@@ -1942,7 +1717,6 @@ def neighbor_kl_gradient(logits, sample, row_lse, *, scale=2.0, grad_loss=None, 
     """vp_neighbor_kl_gradient: the gradient of scale / (S k P) stats[0] with respect to the logits, times ``grad_loss``
     (f32 one element on the device, or None): f32 [N,P], every row written.  ``row_lse`` is neighbor_kl's, of the same logits."""
     import torch
-    L = _reg3d_lib()
     logits, N, P = _neighbor_kl_logits(logits)
     _require(sample.n_rows == N and sample.nbr.device == logits.device, "the neighbour table is of another point set or device")
     dev = logits.device
@@ -1953,11 +1727,10 @@ def neighbor_kl_gradient(logits, sample, row_lse, *, scale=2.0, grad_loss=None, 
         out = torch.empty((N, P), dtype=torch.float32, device=dev)
     _require(out.dtype == torch.float32 and tuple(out.shape) == (N, P) and out.device == dev and out.stride(1) == 1 and
              out.stride(0) >= P, f"out must be float32 [{N}, {P}] with a unit channel stride")
-    with torch.cuda.device(dev):
-        check(L.vp_neighbor_kl_gradient(logits.data_ptr(), N, P, logits.stride(0), _ptr(sample.samples), sample.S, _ptr(sample.nbr),
-                                        sample.k, row_lse.data_ptr(), sample.rev_start.data_ptr(), _ptr(sample.rev_entry),
-                                        _ptr(sample.smp_start), _ptr(sample.smp_entry), float(scale), _ptr(grad_loss),
-                                        out.data_ptr(), out.stride(0), int(lanes), torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_neighbor_kl_gradient", logits.data_ptr(), N, P, logits.stride(0), _ptr(sample.samples), sample.S,
+          _ptr(sample.nbr), sample.k, row_lse.data_ptr(), sample.rev_start.data_ptr(), _ptr(sample.rev_entry),
+          _ptr(sample.smp_start), _ptr(sample.smp_entry), float(scale), _ptr(grad_loss), out.data_ptr(), out.stride(0),
+          int(lanes))
     return out
 
 
@@ -1980,9 +1753,6 @@ def assign_view_ids(score, id_pixels, K):
         rows, cols = linear_sum_assignment(-score[labels])
         out[labels[rows]] = cols.astype(np.int32)
     return out
-
-
-_check_rc = check
 
 
 class LabelScores:
@@ -2039,9 +1809,7 @@ def label_boundary(labels, radius, workspace=None):
     dev = labels.device
     ws, ptr = _label_workspace(workspace, W, H, dev)
     band = torch.empty((H, W), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check_rc(lib().vp_label_boundary(labels.data_ptr(), W, H, int(radius), band.data_ptr(), ptr, ws.capacity(),
-                                          torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_label_boundary", labels.data_ptr(), W, H, int(radius), band.data_ptr(), ptr, ws.capacity())
     return band
 
 
@@ -2051,7 +1819,6 @@ def label_scores(pred, target, P, radius=0, out=None, workspace=None):
     radius = 0: confusion and skipped only;
     radius > 0: the boundary counts too, through ``workspace`` (a SplatWorkspace, reused and grown as splat_loss does; a
     fresh one when None).  Nothing is read back here."""
-    import torch
     pred = _label_map(pred, "pred")
     target = _label_map(target, "target", pred.device, pred.shape)
     H, W = (int(v) for v in pred.shape)
@@ -2064,11 +1831,9 @@ def label_scores(pred, target, P, radius=0, out=None, workspace=None):
     ws, ptr = (None, None)
     if radius > 0:
         ws, ptr = _label_workspace(workspace, W, H, dev)
-    with torch.cuda.device(dev):
-        _check_rc(lib().vp_label_scores(pred.data_ptr(), target.data_ptr(), W, H, int(P), radius, out.confusion.data_ptr(),
-                                        out.skipped.data_ptr(), out.bnd_inter.data_ptr() if radius > 0 else None,
-                                        out.bnd_union.data_ptr() if radius > 0 else None, ptr,
-                                        ws.capacity() if ws is not None else 0, torch.cuda.current_stream(dev).cuda_stream))
+    _call(dev, "vp_label_scores", pred.data_ptr(), target.data_ptr(), W, H, int(P), radius, out.confusion.data_ptr(),
+          out.skipped.data_ptr(), out.bnd_inter.data_ptr() if radius > 0 else None,
+          out.bnd_union.data_ptr() if radius > 0 else None, ptr, ws.capacity() if ws is not None else 0)
     return out
 
 
@@ -2134,13 +1899,10 @@ def project_colors_raw(occ_zyx, c2w, intr, grid_origin3, voxel_size, images, col
     ptr = (scratch.data_ptr() + 255) & ~255
     g = (ctypes.c_float * 3)(*[float(v) for v in grid_origin3])
     Z, Y, X = occ_zyx.shape
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        check(lib().vp_project_colors(
-            occ_zyx.data_ptr(), Z, Y, X, c2w.data_ptr(), intr.data_ptr(), V, g, ctypes.c_double(float(voxel_size)),
-            images.data_ptr(), int(images.shape[1]), int(images.shape[2]), color_sum.data_ptr(), hit_count.data_ptr(),
-            first_view.data_ptr() if first_view is not None else None,
-            pixel_uv.data_ptr() if pixel_uv is not None else None, n_rows, int(view_base), ptr, need, stream))
+    _call(dev, "vp_project_colors", occ_zyx.data_ptr(), Z, Y, X, c2w.data_ptr(), intr.data_ptr(), V, g,
+          ctypes.c_double(float(voxel_size)), images.data_ptr(), int(images.shape[1]), int(images.shape[2]), color_sum.data_ptr(),
+          hit_count.data_ptr(), first_view.data_ptr() if first_view is not None else None,
+          pixel_uv.data_ptr() if pixel_uv is not None else None, n_rows, int(view_base), ptr, need)
 
 
 def upsample_features(src_chw, H, W, keep_dtype=False, out=None):
@@ -2159,10 +1921,8 @@ def upsample_features(src_chw, H, W, keep_dtype=False, out=None):
     need = int(lib().vp_upsample_workspace_bytes(C, h, w, int(src16)))
     scratch = torch.empty(need + 256, dtype=torch.uint8, device=src.device)
     ptr = (scratch.data_ptr() + 255) & ~255
-    stream = torch.cuda.current_stream(src.device).cuda_stream
-    with torch.cuda.device(src.device):
-        check(lib().vp_upsample_features(src.data_ptr(), int(src16), C, h, w, out.data_ptr(), int(dst_dtype == torch.float16),
-                                         int(H), int(W), ptr, need, stream))
+    _call(src.device, "vp_upsample_features", src.data_ptr(), int(src16), C, h, w, out.data_ptr(),
+          int(dst_dtype == torch.float16), int(H), int(W), ptr, need)
     return out
 
 
@@ -2179,16 +1939,13 @@ def build_occupancy_device(points_xyz, grid_origin3, voxel_size):
     scratch = torch.zeros(8, dtype=torch.int32, device=dev)
     mm = (ctypes.c_int32 * 6)()
     g = (ctypes.c_float * 3)(*[float(v) for v in grid_origin3])
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        check(lib().vp_voxel_coords(pts.data_ptr(), N, g, ctypes.c_float(float(voxel_size)), coords.data_ptr(),
-                                    scratch.data_ptr(), mm, stream))
-        lo, hi = [int(mm[k]) for k in range(3)], [int(mm[3 + k]) for k in range(3)]
-        shift = lo if min(lo) < 0 else [0, 0, 0]                       # BSO:36-39
-        dx, dy, dz = (hi[k] - shift[k] + 1 for k in range(3))          # BSO:40-41
-        occ = torch.empty((dz, dy, dx), dtype=torch.int32, device=dev)
-        sh = (ctypes.c_int32 * 3)(*shift)
-        check(lib().vp_scatter_occupancy(coords.data_ptr(), N, sh, dz, dy, dx, occ.data_ptr(), scratch.data_ptr(), stream))
+    _call(dev, "vp_voxel_coords", pts.data_ptr(), N, g, ctypes.c_float(float(voxel_size)), coords.data_ptr(), scratch.data_ptr(), mm)
+    lo, hi = [int(mm[k]) for k in range(3)], [int(mm[3 + k]) for k in range(3)]
+    shift = lo if min(lo) < 0 else [0, 0, 0]                       # BSO:36-39
+    dx, dy, dz = (hi[k] - shift[k] + 1 for k in range(3))          # BSO:40-41
+    occ = torch.empty((dz, dy, dx), dtype=torch.int32, device=dev)
+    sh = (ctypes.c_int32 * 3)(*shift)
+    _call(dev, "vp_scatter_occupancy", coords.data_ptr(), N, sh, dz, dy, dx, occ.data_ptr(), scratch.data_ptr())
     return occ, lo
 
 
@@ -2282,8 +2039,6 @@ def stream_read_gbs(buf, repeats=3):
     """Measured streaming-read rate (GB/s) of this GPU over the float32 CUDA tensor ``buf`` (non-temporal loads)."""
     import torch
     L = lib()
-    L.vp_stream_read.restype = ctypes.c_int
-    L.vp_stream_read.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
     sink = torch.zeros(4, dtype=torch.float32, device=buf.device)
     n = (buf.numel() * buf.element_size() // 16) * 4
     stream = torch.cuda.current_stream(buf.device).cuda_stream

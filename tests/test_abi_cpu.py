@@ -30,6 +30,102 @@ def test_library_exports_every_declared_symbol():
     assert lib.vp_abi_version() == 4
 
 
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong}
+
+
+def _declared_prototypes():
+    """{name: (return type, [parameter type, ...])} of every vp_* prototype of include/voxproj.h, as C type strings without
+    ``const`` and parameter names; a pointer type ends in ``*``."""
+    txt = open(os.path.join(ROOT, "include", "voxproj.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+
+    def ctype(decl, named):
+        pointer = "*" in decl
+        words = [w for w in decl.replace("*", " ").split() if w != "const"]
+        if named:
+            words = words[:-1]
+        assert words, decl
+        return " ".join(words) + (" *" if pointer else "")
+
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t]*?[\s\*]+)(vp_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", txt):
+        assert name not in out, name
+        params = params.strip()
+        out[name] = (ctype(ret, False), [] if params == "void" else [ctype(p, True) for p in params.split(",")])
+    return out
+
+
+def _binding_error(prototype, restype, argtypes):
+    """Why the ctypes binding (restype, argtypes) does not match the C prototype, or None when it does."""
+    ret, params = prototype
+    want = ctypes.c_char_p if ret == "char *" else _SCALARS.get(ret)
+    if want is None or restype is not want:
+        return f"returns {ret}, bound as {restype}"
+    if argtypes is None or len(argtypes) != len(params):
+        return f"takes {len(params)} arguments, bound with {None if argtypes is None else len(argtypes)}"
+    for i, (c, bound) in enumerate(zip(params, argtypes)):
+        if c.endswith("*"):
+            ok = [ctypes.c_void_p] + ([ctypes.POINTER(_SCALARS[c[:-2]])] if c[:-2] in _SCALARS else [])
+        else:
+            ok = [_SCALARS[c]]
+        if not any(bound is t for t in ok):
+            return f"argument {i} is {c}, bound as {bound}"
+    return None
+
+
+def test_every_binding_matches_its_prototype():
+    """Every function the header declares is bound by voxproj_host.lib() with exactly its return type, argument count and
+    argument types: a scalar by its own ctypes type, a pointer as c_void_p or POINTER(its pointee)."""
+    import voxproj_host
+    voxproj_host.build()
+    protos = _declared_prototypes()
+    assert sorted(protos) == _declared_functions() == sorted(voxproj_host.EXPORTS)
+    assert len(protos) == len(voxproj_host.EXPORTS) == 64
+    L = voxproj_host.lib()
+    for name, proto in protos.items():
+        fn = getattr(L, name)                       # a function without a binding fails here or just below
+        assert _binding_error(proto, fn.restype, fn.argtypes) is None, (name, _binding_error(proto, fn.restype, fn.argtypes))
+    # the comparison is not vacuous: corruptions of one real entry are each rejected
+    proto = protos["vp_query_features"]
+    good = list(L.vp_query_features.argtypes)
+    assert proto[1][2] == "int64_t" and proto[1][7] == "float" and len(good) == 15
+    assert _binding_error(proto, ctypes.c_int, good) is None
+    assert "argument 2 is int64_t" in _binding_error(proto, ctypes.c_int, good[:2] + [ctypes.c_int] + good[3:])
+    assert "argument 7 is float" in _binding_error(proto, ctypes.c_int, good[:7] + [ctypes.c_double] + good[8:])
+    assert "takes 15 arguments, bound with 14" in _binding_error(proto, ctypes.c_int, good[:-1])
+
+
+def test_a_missing_symbol_is_reported_by_name(monkeypatch):
+    """A library without one of the entry points added after ABI version 4 still loads; calling that entry point raises
+    VoxprojError with its own name.  ctypes.CDLL is a stub here: no GPU and no real library call."""
+    import voxproj_host
+
+    class Function:
+        restype = argtypes = None
+
+        def __call__(self, *args):
+            return 4                                # vp_abi_version(); nothing else is called
+
+    class Library:
+        def __init__(self, path):
+            for name in voxproj_host.EXPORTS:
+                if name != "vp_photo_loss_workspace_bytes":
+                    setattr(self, name, Function())
+
+    monkeypatch.setattr(voxproj_host.ctypes, "CDLL", Library)
+    monkeypatch.setattr(voxproj_host, "LIB_PATH", os.path.abspath(__file__))      # any file that exists
+    monkeypatch.setattr(voxproj_host, "_lib", None)
+    L = voxproj_host.lib()
+    assert isinstance(L, Library) and L.vp_photo_loss.argtypes is not None
+    with pytest.raises(voxproj_host.VoxprojError, match=r"has no vp_photo_loss_workspace_bytes") as e:
+        voxproj_host.photo_loss_workspace_bytes(3, 8, 8)
+    assert re.search(r"rebuild it \(there is no fallback\)", str(e.value))
+    monkeypatch.undo()
+    assert voxproj_host.ctypes.CDLL is not Library and not isinstance(voxproj_host._lib, Library)
+
+
 def test_workspace_record_calls_validate_their_arguments_on_the_host():
     """vp_workspace_create / _set_option / _release keep host-side records only: their argument checks run without a GPU."""
     import voxproj_host
