@@ -34,9 +34,8 @@ import os
 
 import torch
 
-import evaluate_label_maps as elm
+import gaussian_views
 import lift_gaussian_features as lgf
-from render_semantics_logits import camera, render_size
 
 # the confidence map of the method this follows: the prototype softmax at temperature clip(0.1 spread, 0.1, 1), every id
 CONFIDENCE_PARAMS = dict(phi_scale=0.1, phi_min=0.1, phi_max=1.0, min_count=0)
@@ -45,15 +44,9 @@ ROW_IMAGE_WIDTH = 4096
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Associate per-view instance ids across views (fused GPU code book kernels)")
-    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
-    ap.add_argument("--cam_params", required=True, help="camera_params.json")
+    gaussian_views.add_view_arguments(ap, views_help="view names (default: every mask, sorted)")
     ap.add_argument("--masks_dir", required=True, help="per view <name>.png: the 8-bit instance mask")
     ap.add_argument("--gauss_feats", required=True, help="IDENTITY.pt of lift_instance_features.py: one identity row per Gaussian")
-    ap.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
-    ap.add_argument("--views", nargs="*", default=None, help="view names (default: every mask, sorted)")
-    ap.add_argument("--max_images", type=int, default=None)
-    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
-    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
     ap.add_argument("--codes", type=int, default=256, help="rows of the code book (1 .. 256)")
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--lr", type=float, default=5e-4)
@@ -102,15 +95,10 @@ def main(argv=None):
         ap.error("--steps must be >= 0 and --lr > 0")
     if not math.isfinite(args.conf_min) or not math.isfinite(args.weight_cls) or not math.isfinite(args.weight_cluster):
         ap.error("--conf_min, --weight_cls and --weight_cluster must be finite")
-    import aggregate_voxel_features_onthefly as agg
-    import gaussian_ply
-    import prepare_tensor_data as ptd
     import splat_autograd
     import voxproj_host
-    if not torch.cuda.is_available():
-        raise RuntimeError("associate_instances runs on the GPU: there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    g = {k: torch.from_numpy(v).to(dev) for k, v in gaussian_ply.read_gaussian_ply(args.gaussians_ply).items()}
+    dev = gaussian_views.require_gpu("associate_instances")
+    g = gaussian_views.load_gaussians(args.gaussians_ply, dev)
     N = int(g["means"].shape[0])
     _, feats, _ = lgf.load_lifted(args.gauss_feats)
     if int(feats.shape[0]) != N or N == 0:
@@ -119,32 +107,7 @@ def main(argv=None):
     if not 1 <= D <= 64:
         raise ValueError(f"{args.gauss_feats}: {D} channels outside [1, 64]")
     rows = feats.float().to(dev).contiguous()
-    by_name, cams = ptd.load_camera_params(args.cam_params)
-    masks = {k: v for k, v in elm.index_dir(args.masks_dir).items() if v.lower().endswith(".png")}
-    names = list(args.views) if args.views else sorted(masks)
-    if args.max_images is not None:
-        names = names[:args.max_images]
-    if not names:
-        raise ValueError(f"{args.masks_dir}: no .png masks to train on")
-    for name in names:
-        if name not in masks:
-            raise KeyError(f"{args.masks_dir}: no mask for view '{name}'")
-        if name not in by_name:
-            raise KeyError(f"{args.cam_params}: no camera entry for {name}")
-    cache = {}
-
-    def load_view(name):
-        if name not in cache:
-            entry = by_name[name]
-            H0, W0 = agg._image_size(entry, cams, args.images_dir, name)
-            W, H = render_size(W0, H0, args.downsample_factor)
-            vm, K = camera(entry, cams, W0, H0, W, H, args.principal_point)
-            ids = elm.load_label_map(masks[name])
-            if ids.shape != (H, W):
-                ids = elm.resize_nearest(ids, W, H)
-            cache[name] = (vm, K, W, H, torch.from_numpy(ids).to(dev))
-        return cache[name]
-
+    names, load_view = gaussian_views.open_mask_views(args, dev)
     gen = torch.Generator().manual_seed(args.seed)
     param = torch.nn.Parameter(init_codebook(args.codes, D, gen).to(dev))
     opt = torch.optim.Adam([param], lr=args.lr)

@@ -28,20 +28,14 @@ import os
 
 import torch
 
+import gaussian_views
 import lift_gaussian_features as lgf
-from render_semantics_logits import camera, render_size
 
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Distil 2D feature maps into per-Gaussian rows (fused GPU feature loss)")
-    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
-    ap.add_argument("--cam_params", required=True, help="camera_params.json")
+    gaussian_views.add_view_arguments(ap)
     ap.add_argument("--features_dir", required=True, help="per view <name>.npy: the LSeg map fp16 [C, h, w]")
-    ap.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
-    ap.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
-    ap.add_argument("--max_images", type=int, default=None)
-    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
-    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
     ap.add_argument("--weights_dir", default=None, help="optional per view <name>_confidence.npy f32 [H, W]: pixel weights")
     ap.add_argument("--init", default=None, help="LIFTED.pt to start from (default: lift all views first)")
     ap.add_argument("--loss", choices=("cosine", "l2"), default="cosine")
@@ -61,31 +55,18 @@ def main(argv=None):
         ap.error("--steps must be >= 0 and --views_per_step >= 1")
     if not 0.0 <= args.min_alpha <= 1.0:
         ap.error(f"--min_alpha must lie in [0, 1], not {args.min_alpha}")
-    import aggregate_voxel_features_onthefly as agg
-    import gaussian_ply
-    import prepare_tensor_data as ptd
     import splat_autograd
     import voxproj_host
-    if not torch.cuda.is_available():
-        raise RuntimeError("distill_gaussian_features runs on the GPU: there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    g = {k: torch.from_numpy(v).to(dev) for k, v in gaussian_ply.read_gaussian_ply(args.gaussians_ply).items()}
+    dev = gaussian_views.require_gpu("distill_gaussian_features")
+    g = gaussian_views.load_gaussians(args.gaussians_ply, dev)
     N = int(g["means"].shape[0])
-    by_name, cams = ptd.load_camera_params(args.cam_params)
-    names = args.views if args.views else sorted(by_name)
-    if args.max_images is not None:
-        names = names[:args.max_images]
+    names, view = gaussian_views.open_views(args)
     if not names:
         raise ValueError("no views to train on")
 
     def load_view(name):
         """(viewmat, K, W, H, map f16 [H,W,C], pixel weights or None, masked pixels) of one view, as the lift reads it."""
-        entry = by_name.get(name)
-        if entry is None:
-            raise KeyError(f"no camera entry for {name}")
-        H0, W0 = agg._image_size(entry, cams, args.images_dir, name)
-        W, H = render_size(W0, H0, args.downsample_factor)
-        vm, K = camera(entry, cams, W0, H0, W, H, args.principal_point)
+        vm, K, W, H = view(name)
         src = lgf.load_map(os.path.join(args.features_dir, name + ".npy")).to(dev)
         feats = voxproj_host.upsample_features(src, H, W, keep_dtype=True)
         m = None
@@ -135,7 +116,7 @@ def main(argv=None):
     gen = torch.Generator().manual_seed(args.seed)
     k = min(args.views_per_step, len(names))
     for _ in range(args.steps):
-        pick = torch.randperm(len(names), generator=gen)[:k].tolist()
+        pick = gaussian_views.draw_indices(len(names), k, gen)
         opt.zero_grad(set_to_none=True)
         loss = 0
         for i in pick:

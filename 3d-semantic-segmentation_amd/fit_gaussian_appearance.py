@@ -43,7 +43,7 @@ import os
 import numpy as np
 import torch
 
-import render_semantics_logits as rsl
+import gaussian_views
 
 SH_C0 = 0.28209479177387814
 PARAMS = ("colors", "opacities", "scales", "quats", "means")
@@ -83,14 +83,8 @@ def load_image(images_dir, name, W, H):
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Fit Gaussian colours / opacities / geometry to photographs (fused L1 + D-SSIM)")
-    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian) with f_dc_0..2")
-    ap.add_argument("--cam_params", required=True, help="camera_params.json")
-    ap.add_argument("--images_dir", required=True, help="<name>.png / .jpg / .npy per view")
+    gaussian_views.add_view_arguments(ap, images_help="<name>.png / .jpg / .npy per view: the photographs")
     ap.add_argument("--out", required=True, help="the refined .ply")
-    ap.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
-    ap.add_argument("--max_images", type=int, default=None)
-    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
-    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
     ap.add_argument("--train", default="colors", help="comma-separated subset of " + ",".join(PARAMS))
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--views_per_step", type=int, default=4)
@@ -127,9 +121,7 @@ def check_densify_args(ap, args):
 
 
 def main(argv=None):
-    import aggregate_voxel_features_onthefly as agg
     import gaussian_ply
-    import prepare_tensor_data as ptd
     import splat_autograd
     import voxproj_host
     ap = build_parser()
@@ -141,25 +133,15 @@ def main(argv=None):
         ap.error("--steps must be >= 0, --views_per_step >= 1 and --lambda_dssim in [0, 1]")
     check_densify_args(ap, args)
     densify_on = args.densify_interval > 0
-    if not torch.cuda.is_available():
-        raise RuntimeError("fit_gaussian_appearance runs on the GPU: there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = gaussian_views.require_gpu("fit_gaussian_appearance")
     ply = gaussian_ply.read_gaussian_ply(args.gaussians_ply, want_dc=True, want_raw=True)
     N = int(ply["means"].shape[0])
-    by_name, cams = ptd.load_camera_params(args.cam_params)
-    names = args.views if args.views else sorted(by_name)
-    if args.max_images is not None:
-        names = names[:args.max_images]
+    names, view = gaussian_views.open_views(args, images_dir="")      # the size is the camera's, not the photograph's
     if not names:
         raise ValueError("no views to train on")
     views = []
     for name in names:
-        entry = by_name.get(name)
-        if entry is None:
-            raise KeyError(f"no camera entry for {name}")
-        H0, W0 = agg._image_size(entry, cams, "", name)
-        W, H = rsl.render_size(W0, H0, args.downsample_factor)
-        vm, K = rsl.camera(entry, cams, W0, H0, W, H, args.principal_point)
+        vm, K, W, H = view(name)
         views.append((vm, K, W, H, torch.from_numpy(load_image(args.images_dir, name, W, H)).to(dev)))
 
     # the parameters in the ply's own parametrisation; what is not trained stays a constant
@@ -244,7 +226,7 @@ def main(argv=None):
     stats = voxproj_host.DensifyStats(N, dev, want_radius=args.max_screen_size > 0.0) if densify_on else None
     densifications = []
     for step in range(1, args.steps + 1):
-        pick = torch.randperm(len(views), generator=gen)[:k].tolist()
+        pick = gaussian_views.draw_indices(len(views), k, gen)
         opt.zero_grad(set_to_none=True)
         tensors = activated()
         loss = 0

@@ -22,9 +22,8 @@ import os
 import numpy as np
 import torch
 
-import gaussian_ply
+import gaussian_views
 import voxproj_host
-from render_semantics_logits import camera, render_size
 
 
 def load_map(path):
@@ -74,14 +73,8 @@ def load_lifted(path):
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Lift 2D feature maps onto the Gaussians (GPU, splat-weighted means)")
-    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
-    ap.add_argument("--cam_params", required=True, help="camera_params.json")
+    gaussian_views.add_view_arguments(ap)
     ap.add_argument("--features_dir", required=True, help="per view <name>.npy: the LSeg map fp16 [C, h, w]")
-    ap.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
-    ap.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
-    ap.add_argument("--max_images", type=int, default=None)
-    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
-    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
     ap.add_argument("--weights_dir", default=None, help="optional per view <name>_confidence.npy f32 [H, W]: pixel weights")
     ap.add_argument("--min_weight", type=float, default=1e-3, help="Gaussians with less summed weight get a row of zeros")
     ap.add_argument("--out", required=True, help="output LIFTED.pt")
@@ -89,28 +82,16 @@ def build_parser():
 
 
 def main(argv=None):
-    import aggregate_voxel_features_onthefly as agg
-    import prepare_tensor_data as ptd
     ap = build_parser()
     args = ap.parse_args(argv)
     if not (args.min_weight >= 0 and np.isfinite(args.min_weight)):
         ap.error(f"--min_weight must be finite and >= 0, not {args.min_weight}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("lift_gaussian_features runs on the GPU: there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    g = {k: torch.from_numpy(v).to(dev) for k, v in gaussian_ply.read_gaussian_ply(args.gaussians_ply).items()}
-    by_name, cams = ptd.load_camera_params(args.cam_params)
-    names = args.views if args.views else sorted(by_name)
-    if args.max_images is not None:
-        names = names[:args.max_images]
+    dev = gaussian_views.require_gpu("lift_gaussian_features")
+    g = gaussian_views.load_gaussians(args.gaussians_ply, dev)
+    names, view = gaussian_views.open_views(args)
     lifter = None
     for idx, name in enumerate(names):
-        entry = by_name.get(name)
-        if entry is None:
-            raise KeyError(f"no camera entry for {name}")
-        H0, W0 = agg._image_size(entry, cams, args.images_dir, name)
-        W, H = render_size(W0, H0, args.downsample_factor)
-        vm, K = camera(entry, cams, W0, H0, W, H, args.principal_point)
+        vm, K, W, H = view(name)
         src = load_map(os.path.join(args.features_dir, name + ".npy")).to(dev)
         feats = voxproj_host.upsample_features(src, H, W, keep_dtype=True)             # fp16 [H,W,C]
         if lifter is None:

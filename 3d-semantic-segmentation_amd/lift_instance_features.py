@@ -33,21 +33,14 @@ import argparse
 
 import torch
 
-import evaluate_label_maps as elm
+import gaussian_views
 import lift_gaussian_features as lgf
-from render_semantics_logits import camera, render_size
 
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Lift 2D instance masks onto the Gaussians (fused GPU prototype-contrastive loss)")
-    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
-    ap.add_argument("--cam_params", required=True, help="camera_params.json")
+    gaussian_views.add_view_arguments(ap, views_help="view names (default: every mask, sorted)")
     ap.add_argument("--masks_dir", required=True, help="per view <name>.png: the 8-bit instance mask")
-    ap.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
-    ap.add_argument("--views", nargs="*", default=None, help="view names (default: every mask, sorted)")
-    ap.add_argument("--max_images", type=int, default=None)
-    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
-    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
     ap.add_argument("--dim", type=int, default=16, help="channels of the identity rows (1 .. 64)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--views_per_step", type=int, default=1)
@@ -77,43 +70,11 @@ def main(argv=None):
         ap.error(f"--dim must lie in [1, 64], not {args.dim}")
     if args.steps < 0 or args.views_per_step < 1 or args.samples < 1 or args.min_count < 0:
         ap.error("--steps and --min_count must be >= 0, --views_per_step and --samples >= 1")
-    import aggregate_voxel_features_onthefly as agg
-    import gaussian_ply
-    import prepare_tensor_data as ptd
     import splat_autograd
-    if not torch.cuda.is_available():
-        raise RuntimeError("lift_instance_features runs on the GPU: there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    g = {k: torch.from_numpy(v).to(dev) for k, v in gaussian_ply.read_gaussian_ply(args.gaussians_ply).items()}
+    dev = gaussian_views.require_gpu("lift_instance_features")
+    g = gaussian_views.load_gaussians(args.gaussians_ply, dev)
     N = int(g["means"].shape[0])
-    by_name, cams = ptd.load_camera_params(args.cam_params)
-    masks = elm.index_dir(args.masks_dir)
-    masks = {k: v for k, v in masks.items() if v.lower().endswith(".png")}
-    names = list(args.views) if args.views else sorted(masks)
-    if args.max_images is not None:
-        names = names[:args.max_images]
-    if not names:
-        raise ValueError(f"{args.masks_dir}: no .png masks to train on")
-    for name in names:
-        if name not in masks:
-            raise KeyError(f"{args.masks_dir}: no mask for view '{name}'")
-        if name not in by_name:
-            raise KeyError(f"{args.cam_params}: no camera entry for {name}")
-    cache = {}
-
-    def load_view(name):
-        """(viewmat, K, W, H, ids int32 [H,W] on the GPU) of one view; the masks are small, so they stay on the device."""
-        if name not in cache:
-            entry = by_name[name]
-            H0, W0 = agg._image_size(entry, cams, args.images_dir, name)
-            W, H = render_size(W0, H0, args.downsample_factor)
-            vm, K = camera(entry, cams, W0, H0, W, H, args.principal_point)
-            ids = elm.load_label_map(masks[name])
-            if ids.shape != (H, W):
-                ids = elm.resize_nearest(ids, W, H)
-            cache[name] = (vm, K, W, H, torch.from_numpy(ids).to(dev))
-        return cache[name]
-
+    names, load_view = gaussian_views.open_mask_views(args, dev)
     gen = torch.Generator().manual_seed(args.seed)
     param = torch.nn.Parameter(torch.randn((N, args.dim), generator=gen).to(dev))
     opt = torch.optim.Adam([param], lr=args.lr)
@@ -139,7 +100,7 @@ def main(argv=None):
     print(f"[IDENTITY] before: mean loss {l0:.6f}")
     k = min(args.views_per_step, len(names))
     for _ in range(args.steps):
-        pick = torch.randperm(len(names), generator=gen)[:k].tolist()
+        pick = gaussian_views.draw_indices(len(names), k, gen)
         opt.zero_grad(set_to_none=True)
         loss = 0
         for i in pick:

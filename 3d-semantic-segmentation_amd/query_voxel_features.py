@@ -270,6 +270,7 @@ def rendered_labels(img, alpha, labels, margin, logits=None):
 
 
 def _cmd_gaussian_views(args, text, dev):
+    import gaussian_views
     import render_gaussian_features as rgf
     g, rows = rgf.load_scene(args, dev)
     if rows.shape[1] != text.shape[1]:
@@ -278,7 +279,7 @@ def _cmd_gaussian_views(args, text, dev):
     ws = voxproj_host.SplatWorkspace()
     t = text.to(dev)
     all_labels = []
-    for name, vm, K, W, H in rgf.iter_views(args):
+    for name, vm, K, W, H in gaussian_views.iter_views(args):
         # the view channels-last in fp16, then the query on the [H W, C] map in place: cosine normalisation per pixel,
         # after the blend
         img, alpha, _, _ = voxproj_host.splat_render_view(g["means"], g["quats"], g["scales"], g["opacities"], rows, vm, K, W, H,
@@ -301,6 +302,7 @@ def _cmd_gaussian_views(args, text, dev):
 
 def build_parser():
     import aggregate_voxel_features_onthefly as agg
+    import gaussian_views
     ap = argparse.ArgumentParser(description="Score voxel features against text embeddings (GPU)")
     sub = ap.add_subparsers(dest="cmd", required=True)
 
@@ -334,18 +336,12 @@ def build_parser():
     w.add_argument("--out_dir", default="semantic_views")
     w.add_argument("--save_logits", action="store_true", help="also write <name>_logits.npy f16 [P,H,W]")
     w.add_argument("--save_ids", action="store_true", help="also write <name>_ids.npy: the first-hit voxel ID image")
-    # the arguments of render_gaussian_features.add_view_arguments, written out: building this parser imports nothing the
-    # other sub-commands do not need (tests/test_splat_render_cpu.py holds the two lists together)
+    # render_gaussian_features.py's arguments (tests/test_splat_render_cpu.py holds the two lists together); gaussian_views
+    # imports nothing at module level that the other sub-commands do not need
     r = sub.add_parser("gaussian_views", help="semantic segmentation of camera views from the Gaussians' own rendered rows")
     common(r)
-    r.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
+    gaussian_views.add_view_arguments(r)
     r.add_argument("--gauss_feats", required=True, help="LIFTED.pt of lift_gaussian_features.py: one feature row per Gaussian")
-    r.add_argument("--cam_params", required=True, help="camera_params.json")
-    r.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
-    r.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
-    r.add_argument("--max_images", type=int, default=None)
-    r.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
-    r.add_argument("--principal_point", choices=("center", "camera"), default="center")
     r.add_argument("--out_dir", required=True)
     r.add_argument("--save_logits", action="store_true", help="also write <name>_logits.npy f16 [P,H,W]")
     return ap

@@ -36,7 +36,7 @@ import os
 import numpy as np
 import torch
 
-import render_semantics_logits as rsl
+import gaussian_views
 
 
 def load_target(targets_dir, name, W, H, n_classes, weight="confidence"):
@@ -72,15 +72,9 @@ def save_refined(path, logits, prompts=None, colors=None):
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Refine per-Gaussian logits against per-view label maps (fused GPU loss)")
-    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
+    gaussian_views.add_view_arguments(ap)
     ap.add_argument("--logit_path", required=True, help=".npz with 'logits' [N, P] (query_voxel_features.py gaussians)")
-    ap.add_argument("--cam_params", required=True, help="camera_params.json")
     ap.add_argument("--targets_dir", required=True, help="<name>_labels.npy / <name>_confidence.npy per view")
-    ap.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
-    ap.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
-    ap.add_argument("--max_images", type=int, default=None)
-    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
-    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
     ap.add_argument("--weight", choices=("confidence", "none"), default="confidence")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--views_per_step", type=int, default=4)
@@ -96,9 +90,6 @@ def build_parser():
 
 
 def main(argv=None):
-    import aggregate_voxel_features_onthefly as agg
-    import gaussian_ply
-    import prepare_tensor_data as ptd
     import splat_autograd
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -106,10 +97,8 @@ def main(argv=None):
         ap.error("--steps must be >= 0 and --views_per_step >= 1")
     if args.reg3d_weight < 0 or not 2 <= args.reg3d_k <= 16 or args.reg3d_interval < 1 or args.reg3d_sample_size < 0:
         ap.error("--reg3d_weight must be >= 0, --reg3d_k in [2, 16], --reg3d_interval >= 1 and --reg3d_sample_size >= 0")
-    if not torch.cuda.is_available():
-        raise RuntimeError("refine_gaussian_logits runs on the GPU: there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    g = {k: torch.from_numpy(v).to(dev) for k, v in gaussian_ply.read_gaussian_ply(args.gaussians_ply).items()}
+    dev = gaussian_views.require_gpu("refine_gaussian_logits")
+    g = gaussian_views.load_gaussians(args.gaussians_ply, dev)
     d = np.load(args.logit_path)
     if "logits" not in d:
         raise KeyError(f"{args.logit_path}: no 'logits' array")
@@ -119,20 +108,12 @@ def main(argv=None):
     P = int(raw.shape[1])
     if not 1 <= P <= 64:
         raise ValueError(f"{args.logit_path}: {P} classes outside [1, 64]")
-    by_name, cams = ptd.load_camera_params(args.cam_params)
-    names = args.views if args.views else sorted(by_name)
-    if args.max_images is not None:
-        names = names[:args.max_images]
+    names, view = gaussian_views.open_views(args)
     if not names:
         raise ValueError("no views to train on")
     views = []
     for name in names:
-        entry = by_name.get(name)
-        if entry is None:
-            raise KeyError(f"no camera entry for {name}")
-        H0, W0 = agg._image_size(entry, cams, args.images_dir, name)
-        W, H = rsl.render_size(W0, H0, args.downsample_factor)
-        vm, K = rsl.camera(entry, cams, W0, H0, W, H, args.principal_point)
+        vm, K, W, H = view(name)
         target, w = load_target(args.targets_dir, name, W, H, P, args.weight)
         views.append((vm, K, W, H, torch.from_numpy(target).to(dev), torch.from_numpy(w).to(dev) if w is not None else None))
     param = torch.nn.Parameter(torch.from_numpy(raw).to(dev))
@@ -189,7 +170,7 @@ def main(argv=None):
     gen = torch.Generator().manual_seed(args.seed)
     k = min(args.views_per_step, len(views))
     for step in range(args.steps):
-        pick = torch.randperm(len(views), generator=gen)[:k].tolist()
+        pick = gaussian_views.draw_indices(len(views), k, gen)
         opt.zero_grad(set_to_none=True)
         loss = 0
         for i in pick:

@@ -22,28 +22,15 @@ import os
 import numpy as np
 import torch
 
-import gaussian_ply
+import gaussian_ply  # noqa: F401  (tests reach the reader through this module)
+import gaussian_views
 import voxproj_host
-from render_semantics_logits import camera, render_size
-
-
-def add_view_arguments(ap):
-    """The arguments that name the Gaussians, their rows and the cameras (shared with query_voxel_features.py gaussian_views)."""
-    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
-    ap.add_argument("--gauss_feats", required=True, help="LIFTED.pt of lift_gaussian_features.py: one feature row per Gaussian")
-    ap.add_argument("--cam_params", required=True, help="camera_params.json")
-    ap.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
-    ap.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
-    ap.add_argument("--max_images", type=int, default=None)
-    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
-    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
-    ap.add_argument("--out_dir", required=True)
 
 
 def load_scene(args, dev):
     """(the Gaussians' tensors on ``dev``, their rows f16 [N,C] on ``dev``)."""
     import lift_gaussian_features
-    g = {k: torch.from_numpy(v).to(dev) for k, v in gaussian_ply.read_gaussian_ply(args.gaussians_ply).items()}
+    g = gaussian_views.load_gaussians(args.gaussians_ply, dev)
     _, feats, _ = lift_gaussian_features.load_lifted(args.gauss_feats)
     n = int(g["means"].shape[0])
     if int(feats.shape[0]) != n:
@@ -55,42 +42,22 @@ def load_scene(args, dev):
     return g, feats.to(dev).contiguous()
 
 
-def iter_views(args):
-    """(name, viewmat, K, W, H) of every requested view."""
-    import aggregate_voxel_features_onthefly as agg
-    import prepare_tensor_data as ptd
-    by_name, cams = ptd.load_camera_params(args.cam_params)
-    names = args.views if args.views else sorted(by_name)
-    if args.max_images is not None:
-        names = names[:args.max_images]
-    if not names:
-        raise ValueError("no views to render")
-    for name in names:
-        entry = by_name.get(name)
-        if entry is None:
-            raise KeyError(f"no camera entry for {name}")
-        H0, W0 = agg._image_size(entry, cams, args.images_dir, name)
-        W, H = render_size(W0, H0, args.downsample_factor)
-        vm, K = camera(entry, cams, W0, H0, W, H, args.principal_point)
-        yield name, vm, K, W, H
-
-
 def build_parser():
     ap = argparse.ArgumentParser(description="Render the Gaussians' wide feature rows into camera views (GPU)")
-    add_view_arguments(ap)
+    gaussian_views.add_view_arguments(ap)
+    ap.add_argument("--gauss_feats", required=True, help="LIFTED.pt of lift_gaussian_features.py: one feature row per Gaussian")
+    ap.add_argument("--out_dir", required=True)
     ap.add_argument("--save_alpha", action="store_true", help="also write <name>_alpha.npy f32 [H,W]")
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("render_gaussian_features runs on the GPU: there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = gaussian_views.require_gpu("render_gaussian_features")
     g, rows = load_scene(args, dev)
     os.makedirs(args.out_dir, exist_ok=True)
     ws = voxproj_host.SplatWorkspace()
-    for idx, (name, vm, K, W, H) in enumerate(iter_views(args)):
+    for idx, (name, vm, K, W, H) in enumerate(gaussian_views.iter_views(args)):
         out, alpha, n_isect, bad = voxproj_host.splat_render_view(g["means"], g["quats"], g["scales"], g["opacities"], rows, vm, K,
                                                                   W, H, dtype=torch.float16, want_alpha=args.save_alpha,
                                                                   workspace=ws, check=False)

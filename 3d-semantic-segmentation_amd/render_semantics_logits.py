@@ -28,11 +28,12 @@ import numpy as np
 import torch
 
 import gaussian_ply
+import gaussian_views
 import voxproj_host
+from gaussian_views import camera, render_size  # noqa: F401  (tests and tools/*_example.py reach them here)
 from query_voxel_features import palette
 
 NUM_CHANNELS = 32
-MAX_WIDTH = 1600
 
 
 def pad_logits(logits, channels=NUM_CHANNELS):
@@ -43,36 +44,6 @@ def pad_logits(logits, channels=NUM_CHANNELS):
     if lg.shape[1] < channels:
         lg = np.pad(lg, ((0, 0), (0, channels - lg.shape[1])), mode="constant")
     return np.ascontiguousarray(lg[:, :channels])
-
-
-def render_size(W0, H0, downsample_factor=None):
-    """(W, H): 3DGS's -r -1 rule (widths above 1600 down to 1600, int() of the scaled size), or int(W0 * f) x int(H0 * f)."""
-    if downsample_factor is not None:
-        return int(W0 * downsample_factor), int(H0 * downsample_factor)
-    scale = W0 / MAX_WIDTH if W0 > MAX_WIDTH else 1.0
-    return int(W0 / scale), int(H0 / scale)
-
-
-def camera(entry, cams, W0, H0, W, H, principal_point="center"):
-    """(viewmat f64 [4,4] = [R | tvec], K f64 [3,3]) at the render size: focal lengths scaled by W/W0 and H/H0 (the
-    reference's focal = W / (2 tan(FoVx / 2)) with FoVx from the original focal and width); principal point at (W/2, H/2)
-    or, with principal_point='camera', the camera's own scaled to the image."""
-    params = cams[str(entry["camera_id"])]["params"]
-    if len(params) == 4:
-        fx, fy, cx, cy = (float(v) for v in params)
-    else:
-        fx, cx, cy = (float(v) for v in params)
-        fy = fx
-    sx, sy = W / W0, H / H0
-    if principal_point == "camera":
-        ppx, ppy = cx * sx, cy * sy
-    else:
-        ppx, ppy = W / 2.0, H / 2.0
-    K = np.array([[fx * sx, 0.0, ppx], [0.0, fy * sy, ppy], [0.0, 0.0, 1.0]])
-    vm = np.eye(4)
-    vm[:3, :3] = np.asarray(entry["R"], np.float64)
-    vm[:3, 3] = np.asarray(entry["tvec"], np.float64)
-    return vm, K
 
 
 def save_palette_png(path, labels_u8, num_classes):
@@ -109,47 +80,29 @@ def load_inputs(args, dev):
 
 def build_parser():
     ap = argparse.ArgumentParser(description="Render per-Gaussian logits into semantic views (GPU Gaussian splatting)")
-    ap.add_argument("--gaussians_ply", required=True, help="3DGS point_cloud.ply (binary little-endian)")
+    gaussian_views.add_view_arguments(ap)
     ap.add_argument("--logit_path", required=True, help=".npz with 'logits' [N, P] (query_voxel_features.py gaussians)")
-    ap.add_argument("--cam_params", required=True, help="camera_params.json")
-    ap.add_argument("--images_dir", default="", help="the images, for their size (else the camera's width / height)")
-    ap.add_argument("--views", nargs="*", default=None, help="image names (default: all, sorted)")
-    ap.add_argument("--max_images", type=int, default=None)
     ap.add_argument("--out_dir", default="semantic_renders")
     ap.add_argument("--channels", type=int, default=NUM_CHANNELS, help="logit channels rendered (pad / truncate)")
-    ap.add_argument("--principal_point", choices=("center", "camera"), default="center")
-    ap.add_argument("--downsample_factor", type=float, default=None, help="override the 1600-pixel width rule")
     ap.add_argument("--no_logits", action="store_true", help="skip the _logits.npy files (labels and confidence only)")
     return ap
 
 
 def main(argv=None):
-    import aggregate_voxel_features_onthefly as agg
-    import prepare_tensor_data as ptd
     ap = build_parser()
     args = ap.parse_args(argv)
     if not 1 <= args.channels <= 64:
         ap.error(f"--channels must be in [1, 64], not {args.channels}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("render_semantics_logits runs on the GPU: there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = gaussian_views.require_gpu("render_semantics_logits")
     g, feats, num_classes, prompts = load_inputs(args, dev)
-    by_name, cams = ptd.load_camera_params(args.cam_params)
-    names = args.views if args.views else sorted(by_name)
-    if args.max_images is not None:
-        names = names[:args.max_images]
+    names, view = gaussian_views.open_views(args)               # an empty list is accepted: the summary is all it prints
     rdir, ldir = os.path.join(args.out_dir, "renders"), os.path.join(args.out_dir, "labels")
     os.makedirs(rdir, exist_ok=True)
     os.makedirs(ldir, exist_ok=True)
     ws = voxproj_host.SplatWorkspace()
     counts = np.zeros(args.channels, np.int64)
     for idx, name in enumerate(names):
-        entry = by_name.get(name)
-        if entry is None:
-            raise KeyError(f"no camera entry for {name}")
-        H0, W0 = agg._image_size(entry, cams, args.images_dir, name)
-        W, H = render_size(W0, H0, args.downsample_factor)
-        vm, K = camera(entry, cams, W0, H0, W, H, args.principal_point)
+        vm, K, W, H = view(name)
         r = voxproj_host.splat_features(g["means"], g["quats"], g["scales"], g["opacities"], feats, vm, K, W, H,
                                         want_logits=not args.no_logits, want_confidence=True, workspace=ws, check=False)
         n_bad = int(r.n_nonfinite.item())

@@ -31,6 +31,59 @@ __all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians
            "splat_contrastive", "SplatContrastive", "splat_photometric", "SplatPhotometric"]
 
 
+def _require_f32(means, quats, scales, opacities, **more):
+    """The four tensors every call takes, and what else is named, must be torch.float32 tensors on a GPU."""
+    named = dict(means=means, quats=quats, scales=scales, opacities=opacities, **more)
+    _host._require_tensors(*((t, name, (torch.float32,)) for name, t in named.items()))
+
+
+def _refuse_grad(differentiable_in, **tensors):
+    """Raise instead of dropping a gradient: none of ``tensors`` may require grad; the text says what the call is
+    differentiable in, and what to do."""
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError(f"{name} requires grad, but {differentiable_in}")
+
+
+def _reduce(stats, reduction):
+    """stats = (total, weight, ...) on the device: total / weight for "mean" (0 when the weight is 0), the total for "sum"."""
+    total, weight = stats[0], stats[1]
+    return torch.where(weight > 0, total / weight, torch.zeros_like(total)) if reduction == "mean" else total
+
+
+def _take(ctx, *names):
+    """What the forward left on ``ctx`` under ``names`` (workspaces, maps), handed to the backward: ``ctx`` lets go of it, so
+    it is freed when the backward returns, not with the graph."""
+    held = tuple(getattr(ctx, name) for name in names)
+    for name in names:
+        setattr(ctx, name, None)
+    return held
+
+
+def _rasterize_backward(saved, view, ws, grad_logits, grad_alpha, needs, want_screen=False):
+    """The backward of one splatted view, asked only for what is needed.  ``saved`` = (means, quats, scales, features) of
+    the forward, ``view`` = (viewmat, K, W, H, eps2d, capacity), ``ws`` the forward's workspace, ``needs`` =
+    needs_input_grad of (means, quats, scales, opacities, features).  A geometry gradient or the screen-space sums take
+    vp_splat_rasterize_backward_geometry (one fused tile sweep), features and opacities alone vp_splat_rasterize_backward
+    (which reads only the features of ``saved`` and W, H, capacity of ``view``), nothing asked for launches nothing.
+    Returns ((means, quats, scales, opacities, features) gradients, None where not asked for; screen sums [N,5] or None)."""
+    m, q, s, f = saved
+    viewmat, K, W, H, eps2d, cap = view
+    want_m, want_q, want_s, want_o, want_f = needs
+    gl = grad_logits.float() if grad_logits is not None else None
+    ga = grad_alpha.float() if grad_alpha is not None else None
+    g = dict(means=None, quats=None, scales=None, opacities=None, features=None, screen=None)
+    if want_m or want_q or want_s or want_screen:
+        g = _host.splat_rasterize_backward_geometry(m, q, s, f, viewmat, K, W, H, cap, ws, gl, ga, eps2d=eps2d,
+                                                    want_means=want_m, want_quats=want_q, want_scales=want_s,
+                                                    want_features=want_f, want_opacities=want_o, want_screen=want_screen)
+    elif want_f or want_o:
+        g["features"], g["opacities"] = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws, grad_logits=gl,
+                                                                       grad_alpha=ga, want_features=want_f,
+                                                                       want_opacities=want_o)
+    return (g["means"], g["quats"], g["scales"], g["opacities"], g["features"]), g["screen"]
+
+
 class SplatFeatures(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, opacities, means, quats, scales, viewmat, K, W, H, near, far, eps2d, check):
@@ -49,16 +102,12 @@ class SplatFeatures(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_logits, grad_alpha, _grad_labels, _grad_confidence):
         f, = ctx.saved_tensors
-        ws, ctx.ws = ctx.ws, None
+        ws, = _take(ctx, "ws")
         W, H, cap = ctx.shape
-        want_f, want_o = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gf = go = None
-        if want_f or want_o:
-            gf, go = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws,
-                                                    grad_logits=grad_logits.float() if grad_logits is not None else None,
-                                                    grad_alpha=grad_alpha.float() if grad_alpha is not None else None,
-                                                    want_features=want_f, want_opacities=want_o)
-        return gf, go, None, None, None, None, None, None, None, None, None, None, None
+        want_f, want_o = ctx.needs_input_grad[:2]
+        (_, _, _, go, gf), _ = _rasterize_backward((None, None, None, f), (None, None, W, H, None, cap), ws, grad_logits,
+                                                   grad_alpha, (False, False, False, want_o, want_f))
+        return (gf, go) + (None,) * 11
 
 
 def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, *, near=0.01, far=1e10, eps2d=0.3,
@@ -73,13 +122,9 @@ def splat_features(means, quats, scales, opacities, features, viewmat, K, W, H, 
     differentiable.  The images are bit-identical to voxproj_host.splat_features(..., want_logits=True, want_alpha=True).
     ``check``: raise when a Gaussian has a non-finite parameter (it is culled either way).
     For gradients of the means, quats and scales use ``splat_gaussians``."""
-    for t, name in ((means, "means"), (quats, "quats"), (scales, "scales")):
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise ValueError(f"{name} requires grad, but geometry gradients are not implemented: only the features and "
-                             "the opacities are differentiable (detach the geometry)")
-    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
-                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
-                              (features, "features"))))
+    _refuse_grad("geometry gradients are not implemented: only the features and the opacities are differentiable (detach "
+                 "the geometry)", means=means, quats=quats, scales=scales)
+    _require_f32(means, quats, scales, opacities, features=features)
     return SplatFeatures.apply(features, opacities, means, quats, scales, viewmat, K, int(W), int(H), float(near), float(far),
                                float(eps2d), bool(check))
 
@@ -100,22 +145,9 @@ class SplatGaussians(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_logits, grad_alpha, _grad_labels, _grad_confidence):
-        m, q, s, f = ctx.saved_tensors
-        ws, ctx.ws = ctx.ws, None
-        viewmat, K, W, H, eps2d, cap = ctx.view
-        want_m, want_q, want_s, want_o, want_f = ctx.needs_input_grad[:5]
-        gl = grad_logits.float() if grad_logits is not None else None
-        ga = grad_alpha.float() if grad_alpha is not None else None
-        g = dict(means=None, quats=None, scales=None, opacities=None, features=None)
-        if want_m or want_q or want_s:
-            g = _host.splat_rasterize_backward_geometry(m, q, s, f, viewmat, K, W, H, cap, ws, gl, ga, eps2d=eps2d,
-                                                        want_means=want_m, want_quats=want_q, want_scales=want_s,
-                                                        want_features=want_f, want_opacities=want_o)
-        elif want_f or want_o:
-            g["features"], g["opacities"] = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws, grad_logits=gl,
-                                                                           grad_alpha=ga, want_features=want_f,
-                                                                           want_opacities=want_o)
-        return g["means"], g["quats"], g["scales"], g["opacities"], g["features"], None, None, None, None, None, None, None, None
+        ws, = _take(ctx, "ws")
+        grads, _ = _rasterize_backward(ctx.saved_tensors, ctx.view, ws, grad_logits, grad_alpha, ctx.needs_input_grad[:5])
+        return grads + (None,) * 8
 
 
 def splat_gaussians(means, quats, scales, opacities, features, viewmat, K, W, H, *, near=0.01, far=1e10, eps2d=0.3,
@@ -131,9 +163,7 @@ def splat_gaussians(means, quats, scales, opacities, features, viewmat, K, W, H,
     tensor as passed (orthogonal to it), the scales' and the opacities' with respect to the activated values.  The backward
     runs the fused vp_splat_rasterize_backward_geometry once and asks only for what requires grad; without a geometry
     gradient it is ``splat_features``'s backward.  ``check``: raise when a Gaussian has a non-finite parameter."""
-    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
-                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
-                              (features, "features"))))
+    _require_f32(means, quats, scales, opacities, features=features)
     return SplatGaussians.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), float(near), float(far),
                                 float(eps2d), bool(check))
 
@@ -146,11 +176,7 @@ class SplatCrossEntropy(torch.autograd.Function):
         m, q, s, f = means.detach(), quats.detach(), scales.detach(), features.detach()
         r = _host.splat_loss(m, q, s, opacities.detach(), f, viewmat, K, W, H, target, pixel_weight, want_alpha=True,
                              want_logits=keep_logits, near=near, far=far, eps2d=eps2d, workspace=ws, check=check)
-        total, weight = r.loss_stats[0], r.loss_stats[1]
-        if reduction == "mean":
-            loss = torch.where(weight > 0, total / weight, torch.zeros_like(total))
-        else:
-            loss = total
+        loss = _reduce(r.loss_stats, reduction)
         ctx.ws = ws
         ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect), reduction)
         ctx.maps = (target, pixel_weight, r.loss_stats, r.logits)
@@ -162,8 +188,7 @@ class SplatCrossEntropy(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_loss, _grad_labels, _grad_confidence, _grad_alpha):
         m, q, s, f = ctx.saved_tensors
-        ws, ctx.ws = ctx.ws, None
-        (target, weight, stats, logits), ctx.maps = ctx.maps, None
+        ws, (target, weight, stats, logits) = _take(ctx, "ws", "maps")
         viewmat, K, W, H, eps2d, cap, reduction = ctx.view
         want_m, want_q, want_s, want_o, want_f = ctx.needs_input_grad[:5]
         g = dict(means=None, quats=None, scales=None, opacities=None, features=None)
@@ -197,9 +222,7 @@ def splat_cross_entropy(means, quats, scales, opacities, features, viewmat, K, W
     and the backward asks only for what requires grad.  The gradient flowing into the loss is read by the kernel on the
     device.  No double backward, no gradient for the camera."""
     _host._require(reduction in ("mean", "sum"), f"reduction must be 'mean' or 'sum', not {reduction!r}")
-    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
-                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
-                              (features, "features"))))
+    _require_f32(means, quats, scales, opacities, features=features)
     return SplatCrossEntropy.apply(means, quats, scales, opacities, features, viewmat, K, int(W), int(H), target, pixel_weight,
                                    reduction, bool(keep_logits), float(near), float(far), float(eps2d), bool(check))
 
@@ -233,7 +256,7 @@ class SplatWideFeatures(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out, _grad_alpha):
-        ws, ctx.ws = ctx.ws, None
+        ws, = _take(ctx, "ws")
         W, H, cap, N, C, dtype = ctx.shape
         if not ctx.needs_input_grad[0] or grad_out is None:
             return (None,) * 14
@@ -260,11 +283,9 @@ def splat_wide_features(means, quats, scales, opacities, rows, viewmat, K, W, H,
     Gq = f16(G s)) and the lifted sums are divided by s.  The gradient returned is therefore the exact adjoint of the forward
     applied to Gq / s (every element of G rounded to 11 bits relative to the map's largest, not to its own magnitude), within
     the lift's stated accuracy.  An all-zero G gives zero gradients.  No double backward."""
-    for t, name in ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities")):
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise ValueError(f"{name} requires grad, but splat_wide_features is differentiable in the rows only (detach it)")
-    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
-                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
+    _refuse_grad("splat_wide_features is differentiable in the rows only (detach it)", means=means, quats=quats, scales=scales,
+                 opacities=opacities)
+    _require_f32(means, quats, scales, opacities)
     _host._require_tensors((rows, "rows", (torch.float16, torch.float32)))
     return SplatWideFeatures.apply(rows, means, quats, scales, opacities, viewmat, K, int(W), int(H), dtype, float(near),
                                    float(far), float(eps2d), bool(check))
@@ -279,8 +300,7 @@ class SplatFeatureLoss(torch.autograd.Function):
                                                        rows.detach(), viewmat, K, W, H, dtype=dtype, want_alpha=True, near=near,
                                                        far=far, eps2d=eps2d, workspace=ws, check=check)
         stats, _, lws = _host.feature_loss(image, target, pixel_weight, alpha, kind=kind, min_alpha=min_alpha)
-        total, weight = stats[0], stats[1]
-        loss = torch.where(weight > 0, total / weight, torch.zeros_like(total)) if reduction == "mean" else total
+        loss = _reduce(stats, reduction)
         ctx.ws, ctx.lws = ws, lws
         ctx.maps = (image, target, stats)
         ctx.shape = (int(W), int(H), int(cap), int(rows.shape[0]), int(rows.shape[1]), rows.dtype, reduction)
@@ -290,9 +310,7 @@ class SplatFeatureLoss(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_loss, _grad_alpha):
-        ws, ctx.ws = ctx.ws, None
-        lws, ctx.lws = ctx.lws, None
-        (image, target, stats), ctx.maps = ctx.maps, None
+        ws, lws, (image, target, stats) = _take(ctx, "ws", "lws", "maps")
         W, H, cap, N, C, dtype, reduction = ctx.shape
         if not ctx.needs_input_grad[0] or grad_loss is None:
             return (None,) * 19
@@ -325,11 +343,9 @@ def splat_feature_loss(means, quats, scales, opacities, rows, viewmat, K, W, H, 
     _host._require(kind in _host.FEATURE_LOSS_KINDS, f"kind must be 'cosine' or 'l2', not {kind!r}")
     _host._require(reduction in ("mean", "sum"), f"reduction must be 'mean' or 'sum', not {reduction!r}")
     _host._require(dtype in (torch.float16, torch.float32), "dtype must be torch.float16 or torch.float32")
-    for t, name in ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities")):
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise ValueError(f"{name} requires grad, but splat_feature_loss is differentiable in the rows only (detach it)")
-    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
-                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"))))
+    _refuse_grad("splat_feature_loss is differentiable in the rows only (detach it)", means=means, quats=quats, scales=scales,
+                 opacities=opacities)
+    _require_f32(means, quats, scales, opacities)
     _host._require_tensors((rows, "rows", (torch.float16, torch.float32)), (target, "target", (torch.float16,)))
     return SplatFeatureLoss.apply(rows, means, quats, scales, opacities, viewmat, K, int(W), int(H), target, pixel_weight, kind,
                                   reduction, float(min_alpha), dtype, float(near), float(far), float(eps2d), bool(check))
@@ -348,7 +364,8 @@ class SplatContrastive(torch.autograd.Function):
         contrast = torch.where(stats[1] > 0, stats[0] / stats[1].clamp(min=1.0), torch.zeros_like(stats[0]))
         loss = weights[0] * contrast + weights[1] * stats[2] / float(int(W) * int(H))
         ctx.ws, ctx.lws = ws, lws
-        ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect), weights)
+        ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect))
+        ctx.weights = weights
         ctx.maps = (r.logits, ids, count)
         ctx.save_for_backward(m, q, s, f)
         ctx.mark_non_differentiable(stats)
@@ -357,26 +374,15 @@ class SplatContrastive(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_loss, _grad_stats):
-        m, q, s, f = ctx.saved_tensors
-        ws, ctx.ws = ctx.ws, None
-        lws, ctx.lws = ctx.lws, None
-        (image, ids, count), ctx.maps = ctx.maps, None
-        viewmat, K, W, H, eps2d, cap, weights = ctx.view
-        want_m, want_q, want_s, want_o, want_f = ctx.needs_input_grad[:5]
-        g = dict(means=None, quats=None, scales=None, opacities=None, features=None)
-        if want_m or want_q or want_s or want_o or want_f:
-            # the scale stays on the device: the kernel reads it
-            G = _host.proto_contrast_gradient(image, ids, count, lws, weight_contrast=weights[0], weight_norm=weights[1],
-                                              grad_loss=grad_loss.float().reshape(1).contiguous())
-            if want_m or want_q or want_s:
-                g = _host.splat_rasterize_backward_geometry(m, q, s, f, viewmat, K, W, H, cap, ws, G, None, eps2d=eps2d,
-                                                            want_means=want_m, want_quats=want_q, want_scales=want_s,
-                                                            want_features=want_f, want_opacities=want_o)
-            else:
-                g["features"], g["opacities"] = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws, grad_logits=G,
-                                                                               grad_alpha=None, want_features=want_f,
-                                                                               want_opacities=want_o)
-        return (g["means"], g["quats"], g["scales"], g["opacities"], g["features"]) + (None,) * 12
+        ws, lws, (image, ids, count) = _take(ctx, "ws", "lws", "maps")
+        needs = ctx.needs_input_grad[:5]
+        if not any(needs):
+            return (None,) * 17
+        # the scale stays on the device: the kernel reads it
+        G = _host.proto_contrast_gradient(image, ids, count, lws, weight_contrast=ctx.weights[0], weight_norm=ctx.weights[1],
+                                          grad_loss=grad_loss.float().reshape(1).contiguous())
+        grads, _ = _rasterize_backward(ctx.saved_tensors, ctx.view, ws, G, None, needs)
+        return grads + (None,) * 12
 
 
 def splat_contrastive(means, quats, scales, opacities, features, viewmat, K, W, H, ids, count=None, *, weight_contrast=1.0,
@@ -396,9 +402,7 @@ def splat_contrastive(means, quats, scales, opacities, features, viewmat, K, W, 
     Backward: vp_proto_contrast_gradient writes the gradient image (the upstream scalar is read on the device), then
     vp_splat_rasterize_backward_geometry, or vp_splat_rasterize_backward when no geometry gradient is asked for.  No torch
     pass over an image, no double backward, no gradient for the camera."""
-    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
-                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
-                              (features, "features"))))
+    _require_f32(means, quats, scales, opacities, features=features)
     weights = (float(weight_contrast), float(weight_norm))
     proto = dict(ignore_id=int(ignore_id), min_count=int(min_count), phi_scale=float(phi_scale), phi_min=float(phi_min),
                  phi_max=float(phi_max))
@@ -420,7 +424,8 @@ class SplatPhotometric(torch.autograd.Function):
         n = float(r.logits.numel())
         loss = (1.0 - lambda_dssim) * stats[0] / n + lambda_dssim * (1.0 - stats[2] / n)
         ctx.ws, ctx.lws = ws, lws
-        ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect), lambda_dssim)
+        ctx.view = (viewmat, K, int(W), int(H), float(eps2d), int(r.n_isect))
+        ctx.lambda_dssim = lambda_dssim
         ctx.maps = (r.logits, target)
         ctx.save_for_backward(m, q, s, f)
         ctx.mark_non_differentiable(stats)
@@ -429,32 +434,21 @@ class SplatPhotometric(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_loss, _grad_stats):
-        m, q, s, f = ctx.saved_tensors
-        ws, ctx.ws = ctx.ws, None
-        lws, ctx.lws = ctx.lws, None
-        (image, target), ctx.maps = ctx.maps, None
-        viewmat, K, W, H, eps2d, cap, lambda_dssim = ctx.view
-        want_m, want_q, want_s, want_o, want_f = ctx.needs_input_grad[:5]
-        g = dict(means=None, quats=None, scales=None, opacities=None, features=None)
-        if want_m or want_q or want_s or want_o or want_f:
-            # the scale stays on the device: the kernel reads it
-            G = _host.photo_loss_gradient(image, target, lws, lambda_dssim=lambda_dssim,
-                                          grad_loss=grad_loss.float().reshape(1).contiguous())
-            dstats, dscale = ctx.densify
-            if want_m or want_q or want_s or dstats is not None:
-                # with statistics the same sweep also hands out the screen-space sums (its world-space outputs may all be NULL)
-                g = _host.splat_rasterize_backward_geometry(m, q, s, f, viewmat, K, W, H, cap, ws, G, None, eps2d=eps2d,
-                                                            want_means=want_m, want_quats=want_q, want_scales=want_s,
-                                                            want_features=want_f, want_opacities=want_o,
-                                                            want_screen=dstats is not None)
-                if dstats is not None:
-                    _host.densify_accumulate(dstats, g["screen"], ws, W, H, scale=dscale,
-                                             geometry=(m, q, s, viewmat, K, eps2d))
-            else:
-                g["features"], g["opacities"] = _host.splat_rasterize_backward(f, int(f.shape[0]), W, H, cap, ws, grad_logits=G,
-                                                                               grad_alpha=None, want_features=want_f,
-                                                                               want_opacities=want_o)
-        return (g["means"], g["quats"], g["scales"], g["opacities"], g["features"]) + (None,) * 12
+        ws, lws, (image, target) = _take(ctx, "ws", "lws", "maps")
+        needs = ctx.needs_input_grad[:5]
+        if not any(needs):
+            return (None,) * 17
+        # the scale stays on the device: the kernel reads it
+        G = _host.photo_loss_gradient(image, target, lws, lambda_dssim=ctx.lambda_dssim,
+                                      grad_loss=grad_loss.float().reshape(1).contiguous())
+        dstats, dscale = ctx.densify
+        # with statistics the same sweep also hands out the screen-space sums (its world-space outputs may all be NULL)
+        grads, screen = _rasterize_backward(ctx.saved_tensors, ctx.view, ws, G, None, needs, want_screen=dstats is not None)
+        if dstats is not None:
+            m, q, s, _ = ctx.saved_tensors
+            viewmat, K, W, H, eps2d, _ = ctx.view
+            _host.densify_accumulate(dstats, screen, ws, W, H, scale=dscale, geometry=(m, q, s, viewmat, K, eps2d))
+        return grads + (None,) * 12
 
 
 def splat_photometric(means, quats, scales, opacities, colors, viewmat, K, W, H, target, *, lambda_dssim=0.2, near=0.01,
@@ -478,13 +472,10 @@ def splat_photometric(means, quats, scales, opacities, colors, viewmat, K, W, H,
     or opacities require grad), asks it for the screen-space sums as well and adds the view to the statistics
     (vp_densify_accumulate) with ``stats_scale``, which undoes the 1 / k of a step that averages k views.  The loss and the
     gradients are bit-identical with and without it; with None the call sequence is unchanged."""
-    _host._require_tensors(*((t, name, (torch.float32,)) for t, name in
-                             ((means, "means"), (quats, "quats"), (scales, "scales"), (opacities, "opacities"),
-                              (colors, "colors"), (target, "target"))))
+    _require_f32(means, quats, scales, opacities, colors=colors, target=target)
     lam = float(lambda_dssim)
     _host._require(0.0 <= lam <= 1.0, f"lambda_dssim = {lambda_dssim} outside [0, 1]")
-    if target.requires_grad:
-        raise ValueError("target requires grad, but no gradient flows to the photograph (detach it)")
+    _refuse_grad("no gradient flows to the photograph (detach it)", target=target)
     _host._require(densify_stats is None or
                    (isinstance(densify_stats, _host.DensifyStats) and densify_stats.n == int(means.shape[0])),
                    "densify_stats must be a voxproj_host.DensifyStats of the cloud's size")
@@ -537,8 +528,7 @@ def codebook_loss(image, ids, conf, codebook, assign, *, weight_cls=1.0, weight_
     Returns (loss f32 0-dim, stats f64 [4], detached).  Forward: vp_codebook_loss, which also leaves the two unscaled
     gradient sums; backward scales and adds two [K,D] tensors.  No double backward."""
     _host._require_tensors((codebook, "codebook", (torch.float32,)))
-    if isinstance(image, torch.Tensor) and image.requires_grad:
-        raise ValueError("image requires grad, but codebook_loss is differentiable in the code book only (detach it)")
+    _refuse_grad("codebook_loss is differentiable in the code book only (detach it)", image=image)
     return CodebookLoss.apply(codebook, image, ids, conf, assign, (float(weight_cls), float(weight_cluster)), float(conf_min),
                               int(ignore_id))
 
