@@ -48,6 +48,7 @@
 //   vp_reg3d.h         the 3D neighbourhood regulariser: KL divergence to the nearest neighbours' distributions, and its gradient
 //   vp_photo_loss.h    photometric loss (L1 + D-SSIM) of a rendered image against a photograph, and its gradient image
 //   vp_densify.h       adaptive density control: per-view statistics, the clone / split / prune plan, the row gather, the split
+//   vp_sh.h            view-dependent colour: spherical harmonics of degree 0 .. 3 into colour rows, and the adjoint (voxproj_ext.h)
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -61,12 +62,14 @@
 #include <cstring>
 #include <algorithm>
 #include <chrono>
+#include <initializer_list>
 #include <mutex>
 #include <type_traits>
 #include <unordered_map>
 #include <vector>
 
 #include "voxproj.h"
+#include "voxproj_ext.h"
 
 #include "vp_plan.h"
 #include "vp_common.h"
@@ -89,6 +92,7 @@
 #include "vp_reg3d.h"
 #include "vp_photo_loss.h"
 #include "vp_densify.h"
+#include "vp_sh.h"
 #include "vp_project.h"
 
 // The refusal of a caller-provided workspace that is missing, smaller than ``need`` or not 256-byte aligned.
@@ -1469,6 +1473,87 @@ int vp_densify_split(const float *means, const float *quats, const float *log_sc
                        (long long)n_src, (const int *)src, (const unsigned char *)kind, (const long long *)counts,
                        (long long)n_out, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out_means, out_log_scales,
                        (int *)status);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// View-dependent colour (vp_sh.h, declared in voxproj_ext.h).  Every check is host arithmetic and comes before the launch.
+// ------------------------------------------------------------------------------------------------
+static int sh_check(const char *fn, const float *means, const float *campos, int64_t n, int degree, int max_degree)
+{
+    if (n < 0 || n > SH_MAX_N) return fail(VP_EINVAL, "%s: n = %lld outside [0, 2^31 - 1]", fn, (long long)n);
+    if (degree < 0 || degree > max_degree || max_degree > SH_MAX_DEGREE)
+        return fail(VP_EINVAL, "%s: need 0 <= degree <= max_degree <= %d (got %d, %d)", fn, SH_MAX_DEGREE, degree, max_degree);
+    if (!campos) return fail(VP_EINVAL, "%s: null campos", fn);
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(campos[k])) return fail(VP_EINVAL, "%s: campos[%d] is not finite", fn, k);
+    if (n > 0 && !means) return fail(VP_EINVAL, "%s: null pointer argument (means)", fn);
+    return VP_OK;
+}
+
+static bool sh_misaligned(std::initializer_list<const void *> ptrs)
+{
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= (uintptr_t)p;
+    return (bits & 3) != 0;
+}
+
+int vp_sh_colors(const float *f_dc, const float *f_rest, const float *means, const float *campos, int64_t n, int degree,
+                 int max_degree, float *colors, uint8_t *clamped, void *stream_)
+{
+    if (int rc = sh_check("vp_sh_colors", means, campos, n, degree, max_degree)) return rc;
+    if (n > 0 && (!f_dc || !colors || (degree > 0 && !f_rest)))
+        return fail(VP_EINVAL, "vp_sh_colors: null pointer argument (f_dc, colors, or f_rest with degree > 0)");
+    if (sh_misaligned({f_dc, f_rest, means, colors})) return fail(VP_EINVAL, "vp_sh_colors: the float arrays must be 4-byte aligned");
+    if (n == 0) return VP_OK;
+    const dim3 grid((unsigned)((n + SH_THREADS - 1) / SH_THREADS)), block(SH_THREADS);
+    const int row = 3 * (sh_coeffs(max_degree) - 1);
+    hipStream_t stream = (hipStream_t)stream_;
+#define VP_SH_FORWARD(D)                                                                                                 \
+    hipLaunchKernelGGL(k_sh_colors<D>, grid, block, 0, stream, f_dc, f_rest, means, campos[0], campos[1], campos[2],     \
+                       (long long)n, row, colors, (unsigned char *)clamped)
+    switch (degree) {
+    case 0: VP_SH_FORWARD(0); break;
+    case 1: VP_SH_FORWARD(1); break;
+    case 2: VP_SH_FORWARD(2); break;
+    default: VP_SH_FORWARD(3); break;
+    }
+#undef VP_SH_FORWARD
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_sh_colors_backward(const float *f_dc, const float *f_rest, const float *means, const float *campos, int64_t n,
+                          int degree, int max_degree, const float *grad_colors, const uint8_t *clamped, float *grad_dc,
+                          float *grad_rest, float *grad_means, void *stream_)
+{
+    (void)f_dc;                              // Y_0 is a constant: the adjoint never needs f_dc
+    if (int rc = sh_check("vp_sh_colors_backward", means, campos, n, degree, max_degree)) return rc;
+    if (n > 0 && (!grad_colors || !clamped)) return fail(VP_EINVAL, "vp_sh_colors_backward: null pointer argument (grad_colors or clamped)");
+    if (n > 0 && grad_means && degree > 0 && !f_rest)
+        return fail(VP_EINVAL, "vp_sh_colors_backward: grad_means with degree > 0 needs f_rest");
+    if (sh_misaligned({f_rest, means, grad_colors, grad_dc, grad_rest, grad_means}))
+        return fail(VP_EINVAL, "vp_sh_colors_backward: the float arrays must be 4-byte aligned");
+    if (n == 0 || (!grad_dc && !grad_rest && !grad_means)) return VP_OK;
+    const dim3 grid((unsigned)((n + SH_THREADS - 1) / SH_THREADS)), block(SH_THREADS);
+    const int row = 3 * (sh_coeffs(max_degree) - 1);
+    hipStream_t stream = (hipStream_t)stream_;
+    const unsigned char *cl = (const unsigned char *)clamped;
+#define VP_SH_BACKWARD(D, M)                                                                                             \
+    hipLaunchKernelGGL((k_sh_colors_backward<D, M>), grid, block, 0, stream, f_rest, means, campos[0], campos[1],        \
+                       campos[2], (long long)n, row, grad_colors, cl, grad_dc, grad_rest, grad_means)
+    switch (2 * degree + (grad_means ? 1 : 0)) {
+    case 0: VP_SH_BACKWARD(0, false); break;
+    case 1: VP_SH_BACKWARD(0, true); break;
+    case 2: VP_SH_BACKWARD(1, false); break;
+    case 3: VP_SH_BACKWARD(1, true); break;
+    case 4: VP_SH_BACKWARD(2, false); break;
+    case 5: VP_SH_BACKWARD(2, true); break;
+    case 6: VP_SH_BACKWARD(3, false); break;
+    default: VP_SH_BACKWARD(3, true); break;
+    }
+#undef VP_SH_BACKWARD
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

@@ -4,7 +4,10 @@ scenes.  No plyfile dependency: the header is parsed by hand and the vertex reco
 The reader follows the reference's GaussianModel.load_ply and its activations (scene/gaussian_model.py): x y z as they are,
 opacity = sigmoid(opacity), scale = exp(scale_*), rotation = normalize(rot_*) (w, x, y, z), the scale_* and rot_* fields in
 the order of their numeric suffix.  The f_dc_* / f_rest_* colour fields (and any others, normals included) are skipped,
-unless ``want_dc`` asks for the three f_dc_* columns (the degree-0 colour, raw: colour = 0.5 + 0.28209479 f_dc).
+unless ``want_dc`` asks for the three f_dc_* columns (the degree-0 colour, raw: colour = 0.5 + 0.28209479 f_dc) or
+``want_sh`` for the f_rest_* columns, the spherical-harmonics coefficients of degree 1 .. 3.  The file stores those
+channel-major, f_rest_i = channel i // Kr, coefficient i % Kr (scene/gaussian_model.py:385,427-428: the transpose of the
+model's [N,Kr,3] parameter, flattened); reader and writer speak the parameter's layout, [N,Kr,3].
 Binary little-endian files only, the format 3DGS writes.
 """
 import numpy as np
@@ -52,11 +55,21 @@ def _sorted_fields(names, prefix):
     return sorted((p for p in names if p.startswith(prefix)), key=lambda p: int(p.rsplit("_", 1)[-1]))
 
 
-def read_gaussian_ply(path, want_dc=False, want_raw=False):
+SH_MAX_DEGREE = 3
+
+
+def sh_degree_of_width(kr):
+    """The degree D <= 3 with (D + 1)^2 - 1 == kr coefficient rows, or None."""
+    return {(D + 1) ** 2 - 1: D for D in range(SH_MAX_DEGREE + 1)}.get(int(kr))
+
+
+def read_gaussian_ply(path, want_dc=False, want_raw=False, want_sh=False):
     """dict(means f32 [N,3], quats f32 [N,4] (w,x,y,z, unit norm; a zero quaternion stays zero), scales f32 [N,3],
     opacities f32 [N]) with the model's activations applied.  ``want_dc`` adds f_dc f32 [N,3], the f_dc_0..2 columns as
     stored; ``want_raw`` adds opacity_logits f32 [N], log_scales f32 [N,3] and rots f32 [N,4], the columns as stored (what
-    write_gaussian_ply takes, so that a field nobody changed is written back bit for bit)."""
+    write_gaussian_ply takes, so that a field nobody changed is written back bit for bit); ``want_sh`` adds f_rest f32
+    [N,Kr,3] from the f_rest_* columns (Kr = 0, a zero-width array, when the file has none; a column count that is not
+    3 ((D + 1)^2 - 1) for a degree D <= 3 is an error)."""
     with open(path, "rb") as f:
         n, dt = _header(f, path)
         v = np.fromfile(f, dtype=dt, count=n)
@@ -83,19 +96,37 @@ def read_gaussian_ply(path, want_dc=False, want_raw=False):
         if len(dc_f) != 3:
             raise ValueError(f"{path}: needs f_dc_0..2 (found {dc_f})")
         out["f_dc"] = col(dc_f).astype(np.float32)
+    if want_sh:
+        rest_f = _sorted_fields(names, "f_rest_")
+        kr = len(rest_f) // 3
+        if len(rest_f) % 3 or sh_degree_of_width(kr) is None or [int(k.rsplit("_", 1)[-1]) for k in rest_f] != list(range(3 * kr)):
+            raise ValueError(f"{path}: {len(rest_f)} f_rest_* columns are not f_rest_0..{{3 ((D + 1)^2 - 1) - 1}} for a degree D <= {SH_MAX_DEGREE}")
+        rest = np.stack([v[k] for k in rest_f], axis=1).astype(np.float32) if kr else np.zeros((n, 0), np.float32)
+        out["f_rest"] = np.ascontiguousarray(rest.reshape(n, 3, kr).transpose(0, 2, 1))
     if want_raw:
         out.update(opacity_logits=v["opacity"].astype(np.float32), log_scales=col(scale_f).astype(np.float32),
                    rots=rot.astype(np.float32))
     return out
 
 
-def write_gaussian_ply(path, means, opacity_logits, log_scales, rots, f_dc=None):
+def write_gaussian_ply(path, means, opacity_logits, log_scales, rots, f_dc=None, f_rest=None):
     """A binary little-endian 3DGS point cloud: x y z nx ny nz f_dc_0..2 opacity scale_0..2 rot_0..3 (raw, pre-activation
-    values, as 3DGS saves them)."""
+    values, as 3DGS saves them).  With ``f_rest`` [N,Kr,3] the f_rest_0..3Kr-1 columns stand between f_dc_* and opacity,
+    channel-major as the reference writes them; without it the file is the 17-field one."""
     n = len(means)
-    fields = ["x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2",
-              "rot_0", "rot_1", "rot_2", "rot_3"]
+    rest = None
+    if f_rest is not None:
+        rest = np.asarray(f_rest, np.float32)
+        if rest.ndim != 3 or rest.shape[0] != n or rest.shape[2] != 3 or sh_degree_of_width(rest.shape[1]) is None:
+            raise ValueError(f"f_rest must be [{n}, (D + 1)^2 - 1, 3] for a degree D <= {SH_MAX_DEGREE}, not {rest.shape}")
+        rest = rest.transpose(0, 2, 1).reshape(n, -1)
+    fields = (["x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"] +
+              [f"f_rest_{i}" for i in range(rest.shape[1] if rest is not None else 0)] +
+              ["opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3"])
     rec = np.zeros(n, dtype=[(k, "<f4") for k in fields])
+    if rest is not None:
+        for i in range(rest.shape[1]):
+            rec[f"f_rest_{i}"] = rest[:, i]
     for i, k in enumerate("xyz"):
         rec[k] = np.asarray(means)[:, i]
     if f_dc is not None:

@@ -15,6 +15,9 @@ fp32 gradient image or torch reduction over an image appears on the path.  ``spl
 loss of the splatted identity features against one view's instance mask (vp_proto_contrast / vp_proto_contrast_gradient
 between the rasterizer and its backward): no torch pass over an image.  ``splat_photometric`` is the photometric loss, L1 +
 D-SSIM, of the splatted colour rows against a photograph (vp_photo_loss / vp_photo_loss_gradient in the same place).
+``sh_colors`` makes those colour rows view-dependent: spherical harmonics of degree 0 .. 3 evaluated per Gaussian for one
+camera (vp_sh_colors), differentiable in the coefficients and, through the view direction, in the means
+(vp_sh_colors_backward).
 
 Each call keeps its own SplatWorkspace until its backward has run (the backward reads the forward's sorted intersections),
 so calls from several threads or views share no state.  The workspace is freed after the backward, or with the graph.
@@ -28,7 +31,7 @@ import voxproj_host as _host
 
 __all__ = ["splat_features", "SplatFeatures", "splat_gaussians", "SplatGaussians", "splat_cross_entropy", "SplatCrossEntropy",
            "splat_wide_features", "SplatWideFeatures", "quantize_gradient_map", "splat_feature_loss", "SplatFeatureLoss",
-           "splat_contrastive", "SplatContrastive", "splat_photometric", "SplatPhotometric"]
+           "splat_contrastive", "SplatContrastive", "splat_photometric", "SplatPhotometric", "sh_colors", "SHColors"]
 
 
 def _require_f32(means, quats, scales, opacities, **more):
@@ -481,6 +484,45 @@ def splat_photometric(means, quats, scales, opacities, colors, viewmat, K, W, H,
                    "densify_stats must be a voxproj_host.DensifyStats of the cloud's size")
     return SplatPhotometric.apply(means, quats, scales, opacities, colors, viewmat, K, int(W), int(H), target, lam, float(near),
                                   float(far), float(eps2d), bool(check), densify_stats, float(stats_scale))
+
+
+class SHColors(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f_dc, f_rest, means, viewmat, degree):
+        d, r, m = f_dc.detach(), f_rest.detach(), means.detach()
+        colors, clamped = _host.sh_colors(d, r, m, viewmat, degree, want_clamped=True)
+        ctx.view = (viewmat, degree)
+        ctx.save_for_backward(d, r, m, clamped)
+        return colors
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_colors):
+        d, r, m, clamped = ctx.saved_tensors
+        viewmat, degree = ctx.view
+        need_dc, need_rest, need_means = ctx.needs_input_grad[:3]
+        if not (need_dc or need_rest or need_means):
+            return (None,) * 5
+        g_dc, g_rest, g_means = _host.sh_colors_backward(d, r, m, viewmat, degree, grad_colors.float().contiguous(), clamped,
+                                                         want_dc=need_dc, want_rest=need_rest, want_means=need_means)
+        return g_dc, g_rest, g_means, None, None
+
+
+def sh_colors(f_dc, f_rest, means, viewmat, degree):
+    """The view-dependent colour rows f32 [N,3] of Gaussians whose appearance is a spherical-harmonics expansion, for the
+    camera of ``viewmat`` (include/voxproj_ext.h states the contract of vp_sh_colors):
+
+      f_dc f32 [N,3], f_rest f32 [N,Kr,3]   the reference's parameter layout, Kr = (Dmax + 1)^2 - 1 for a Dmax in 0 .. 3
+      means f32 [N,3]                       the direction is (mean - campos) / |mean - campos|, campos = -R^T t of viewmat
+      degree                                the active degree, 0 <= degree <= Dmax; coefficients beyond it are not read
+
+    colour = max(0.5 + sum_k Y_k(dir) sh[k], 0).  The result is what ``splat_photometric(colors=...)`` and ``splat_gaussians``
+    take as their rows.  Differentiable in f_dc, f_rest and means (the gradient passes the clamp where the value before it
+    is >= 0; f_rest receives exact zeros beyond the active degree); a mean that also feeds the rasterizer receives the sum of
+    both gradients through autograd's own accumulation.  No double backward, no gradient for the camera."""
+    _host._require_tensors((f_dc, "f_dc", (torch.float32,)), (f_rest, "f_rest", (torch.float32,)), (means, "means", (torch.float32,)))
+    _refuse_grad("sh_colors has no gradient for the camera (detach viewmat)", viewmat=viewmat)
+    return SHColors.apply(f_dc, f_rest, means, viewmat, int(degree))
 
 
 class CodebookLoss(torch.autograd.Function):

@@ -122,6 +122,14 @@ _SIGNATURES = {
 }
 EXPORTS = list(_SIGNATURES)
 VP_ABI_VERSION = 4
+# The entry points of include/voxproj_ext.h, added after the 64 above (which are frozen with voxproj.h): the same notation, the
+# same tolerant binding and the same _call helper.  tests/test_sh_cpu.py compares every entry with that header's prototype.
+_SIGNATURES_EXT = {
+    "vp_sh_colors": "i: ppp F l ii pp p",
+    "vp_sh_colors_backward": "i: ppp F l ii pp ppp p",
+}
+EXPORTS_EXT = list(_SIGNATURES_EXT)
+VP_SH_MAX_DEGREE = 3
 VP_OPT_HEAVY_THRESHOLD = 1
 VP_OPT_MARCH_LDS_KB = 2
 VP_OPT_ROW_BEGIN = 3
@@ -147,7 +155,7 @@ def build(force=False):
     """Compile libvoxproj.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f == "voxproj.hip" or (f.startswith("vp_") and f.endswith(".h"))]
-    srcs.append(os.path.join(os.path.dirname(_HERE), "include", "voxproj.h"))
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("voxproj.h", "voxproj_ext.h")]
     newest = max(os.path.getmtime(f) for f in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
         subprocess.check_call(["make", "-C", os.path.join(_HERE, "csrc"), "-s"] + (["-B"] if force else []))
@@ -187,7 +195,7 @@ def lib():
                     f"{LIB_PATH} is missing: build it with `make -C {os.path.join(_HERE, 'csrc')}` "
                     "(there is no CPU fallback)")
             L = ctypes.CDLL(LIB_PATH)
-            for name, signature in _SIGNATURES.items():
+            for name, signature in list(_SIGNATURES.items()) + list(_SIGNATURES_EXT.items()):
                 fn = getattr(L, name, None)
                 if fn is not None:               # a symbol the library lacks is skipped here; _entry raises when it is called
                     restype, argtypes = signature.split(":")
@@ -1512,6 +1520,83 @@ def resample_adam(optimizer, old_params, new_params, plan):
             if (name, key) in moved:
                 st[key] = moved[(name, key)]
         optimizer.state[new_params[name]] = st
+
+
+def camera_position(viewmat):
+    """The camera centre -R^T t of a [4,4] world-to-camera matrix (any device, read on the host), in float64: three floats."""
+    import torch
+    vm = torch.as_tensor(viewmat, dtype=torch.float64).detach().cpu().reshape(-1)
+    _require(vm.numel() == 16, "viewmat must be a [4, 4] world-to-camera matrix")
+    vm = vm.reshape(4, 4)
+    return [float(v) for v in -(vm[:3, :3].T @ vm[:3, 3])]
+
+
+def sh_rest_width(max_degree):
+    """Kr = (max_degree + 1)^2 - 1, the coefficient rows of f_rest."""
+    _require(0 <= int(max_degree) <= VP_SH_MAX_DEGREE, f"SH degree {max_degree} outside [0, {VP_SH_MAX_DEGREE}]")
+    return (int(max_degree) + 1) ** 2 - 1
+
+
+def _sh_inputs(caller, f_dc, f_rest, means, degree):
+    """f_dc [N,3], f_rest [N,Kr,3] with Kr = (Dmax + 1)^2 - 1 for a Dmax <= 3, means [N,3], float32 on one GPU, and an active
+    degree <= Dmax: (N, Dmax, contiguous tensors).  Views that are contiguous but start inside a buffer stay views."""
+    import torch
+    _require_tensors((f_dc, "f_dc", (torch.float32,)), (f_rest, "f_rest", (torch.float32,)), (means, "means", (torch.float32,)))
+    N = int(f_dc.shape[0]) if f_dc.dim() == 2 else -1
+    _require(N >= 0 and tuple(f_dc.shape) == (N, 3), f"{caller}: f_dc must be [N, 3]")
+    _require(tuple(means.shape) == (N, 3), f"{caller}: means must be [{N}, 3]")
+    _require(f_rest.dim() == 3 and int(f_rest.shape[0]) == N and int(f_rest.shape[2]) == 3, f"{caller}: f_rest must be [{N}, Kr, 3]")
+    widths = {(D + 1) ** 2 - 1: D for D in range(VP_SH_MAX_DEGREE + 1)}
+    _require(int(f_rest.shape[1]) in widths,
+             f"{caller}: f_rest has {int(f_rest.shape[1])} coefficient rows, not (D + 1)^2 - 1 for a degree D <= {VP_SH_MAX_DEGREE}")
+    max_degree = widths[int(f_rest.shape[1])]
+    _require(isinstance(degree, int) and 0 <= degree <= max_degree, f"{caller}: degree = {degree!r} outside [0, {max_degree}]")
+    _require(f_rest.device == f_dc.device and means.device == f_dc.device, f"{caller}: f_dc, f_rest and means must be on one device")
+    _require(N <= 2 ** 31 - 1, f"{caller}: N = {N} outside [0, 2^31 - 1]")
+    return N, max_degree, f_dc.contiguous(), f_rest.contiguous(), means.contiguous()
+
+
+def sh_colors(f_dc, f_rest, means, viewmat, degree, want_clamped=True):
+    """vp_sh_colors: the colour rows f32 [N,3] of Gaussians with spherical-harmonics coefficients f_dc [N,3] and f_rest
+    [N,Kr,3], seen from the camera of ``viewmat`` (host [4,4] world-to-camera; campos = -R^T t in float64), evaluated up to
+    ``degree``: max(0.5 + sum_k Y_k(dir) sh[k], 0).  Returns (colors, clamped): clamped u8 [N] has bit c set where channel c
+    was clamped (None without ``want_clamped``); sh_colors_backward needs it.  Asynchronous on the current stream."""
+    import torch
+    degree = int(degree)
+    N, max_degree, f_dc, f_rest, means = _sh_inputs("sh_colors", f_dc, f_rest, means, degree)
+    campos = (ctypes.c_float * 3)(*camera_position(viewmat))
+    dev = f_dc.device
+    colors = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    clamped = torch.empty(N, dtype=torch.uint8, device=dev) if want_clamped else None
+    _call(dev, "vp_sh_colors", _ptr(f_dc), _ptr(f_rest), _ptr(means), campos, N, degree, max_degree, _ptr(colors), _ptr(clamped))
+    return colors, clamped
+
+
+def sh_colors_backward(f_dc, f_rest, means, viewmat, degree, grad_colors, clamped, *, want_dc=True, want_rest=True,
+                       want_means=True, out_rest=None):
+    """vp_sh_colors_backward: (grad_dc [N,3], grad_rest [N,Kr,3], grad_means [N,3]) of sh_colors for the upstream gradient
+    grad_colors f32 [N,3] and the ``clamped`` bytes of the forward; None for an output not wanted.  grad_rest is written
+    whole (zeros beyond the active degree), into ``out_rest`` when given.  Without ``want_means`` no coefficient is read."""
+    import torch
+    degree = int(degree)
+    N, max_degree, f_dc, f_rest, means = _sh_inputs("sh_colors_backward", f_dc, f_rest, means, degree)
+    dev = f_dc.device
+    _require_tensors((grad_colors, "grad_colors", (torch.float32,)), (clamped, "clamped", (torch.uint8,)))
+    _require(tuple(grad_colors.shape) == (N, 3) and tuple(clamped.shape) == (N,) and grad_colors.device == dev and
+             clamped.device == dev, f"sh_colors_backward: grad_colors must be [{N}, 3] and clamped [{N}] on the coefficients' device")
+    grad_colors, clamped = grad_colors.contiguous(), clamped.contiguous()
+    campos = (ctypes.c_float * 3)(*camera_position(viewmat))
+    grad_dc = torch.empty((N, 3), dtype=torch.float32, device=dev) if want_dc else None
+    grad_means = torch.empty((N, 3), dtype=torch.float32, device=dev) if want_means else None
+    grad_rest = None
+    if want_rest:
+        grad_rest = out_rest if out_rest is not None else torch.empty(tuple(f_rest.shape), dtype=torch.float32, device=dev)
+        _require(isinstance(grad_rest, torch.Tensor) and grad_rest.is_cuda and grad_rest.device == dev and
+                 grad_rest.dtype == torch.float32 and tuple(grad_rest.shape) == tuple(f_rest.shape) and grad_rest.is_contiguous(),
+                 f"sh_colors_backward: out_rest must be a contiguous float32 CUDA tensor of shape {tuple(f_rest.shape)}")
+    _call(dev, "vp_sh_colors_backward", _ptr(f_dc), _ptr(f_rest), _ptr(means), campos, N, degree, max_degree, _ptr(grad_colors),
+          _ptr(clamped), _ptr(grad_dc), _ptr(grad_rest), _ptr(grad_means))
+    return grad_dc, grad_rest, grad_means
 
 
 VP_CODEBOOK_MAX_CODES = 256
