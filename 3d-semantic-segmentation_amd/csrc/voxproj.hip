@@ -49,6 +49,7 @@
 //   vp_photo_loss.h    photometric loss (L1 + D-SSIM) of a rendered image against a photograph, and its gradient image
 //   vp_densify.h       adaptive density control: per-view statistics, the clone / split / prune plan, the row gather, the split
 //   vp_sh.h            view-dependent colour: spherical harmonics of degree 0 .. 3 into colour rows, and the adjoint (voxproj_ext.h)
+//   vp_mesh.h          triangle-mesh rasterizer: nearest face, depth and label per pixel, integer-decided (voxproj_mesh.h)
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -70,6 +71,7 @@
 
 #include "voxproj.h"
 #include "voxproj_ext.h"
+#include "voxproj_mesh.h"
 
 #include "vp_plan.h"
 #include "vp_common.h"
@@ -93,6 +95,7 @@
 #include "vp_photo_loss.h"
 #include "vp_densify.h"
 #include "vp_sh.h"
+#include "vp_mesh.h"
 #include "vp_project.h"
 
 // The refusal of a caller-provided workspace that is missing, smaller than ``need`` or not 256-byte aligned.
@@ -1554,6 +1557,111 @@ int vp_sh_colors_backward(const float *f_dc, const float *f_rest, const float *m
     default: VP_SH_BACKWARD(3, true); break;
     }
 #undef VP_SH_BACKWARD
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Triangle-mesh rasterizer (vp_mesh.h, declared in voxproj_mesh.h).  Every check is host arithmetic and comes before
+// mesh_layout (rocprim's scratch sizes depend on the device) and before any launch.
+// ------------------------------------------------------------------------------------------------
+static int mesh_check_shape(int64_t n_faces, int W, int H, int64_t capacity)
+{
+    if (n_faces < 0 || n_faces > INT32_MAX) return fail(VP_EINVAL, "n_faces = %lld outside [0, 2^31 - 1]", (long long)n_faces);
+    if (int rc = splat_check_image(W, H)) return rc;
+    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
+    return VP_OK;
+}
+
+size_t vp_mesh_workspace_bytes(int64_t n_faces, int W, int H, int64_t capacity)
+{
+    if (n_faces < 0 || n_faces > INT32_MAX || W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH || capacity < 0 ||
+        capacity > INT32_MAX)
+        return 0;
+    MeshLayout l;
+    return mesh_layout(n_faces, W, H, capacity, l) ? l.bytes : 0;
+}
+
+int vp_mesh_project(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *viewmat,
+                    float fx, float fy, float cx, float cy, int W, int H, float near_plane, float far_plane,
+                    int64_t *n_isect, int32_t *counters, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = mesh_check_shape(n_faces, W, H, 0)) return rc;
+    if (n_verts < 0 || n_verts > INT32_MAX) return fail(VP_EINVAL, "n_verts = %lld outside [0, 2^31 - 1]", (long long)n_verts);
+    if (n_faces > 0 && (!faces || (n_verts > 0 && !verts))) return fail(VP_EINVAL, "null pointer argument (verts or faces)");
+    SplatCam sc;
+    if (int rc = splat_check_camera(viewmat, fx, fy, cx, cy, sc)) return rc;
+    if (!(near_plane > 0.0f) || !(far_plane > near_plane) || !std::isfinite(far_plane))
+        return fail(VP_EINVAL, "need 0 < near < far, both finite (got %g %g)", (double)near_plane, (double)far_plane);
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    MeshLayout l;
+    if (!mesh_layout(n_faces, W, H, 0, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    MeshCam cam;
+    for (int k = 0; k < 12; ++k) cam.r[k] = sc.r[k];
+    cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy; cam.near_z = near_plane; cam.far_z = far_plane;
+    cam.W = W; cam.H = H;
+    long long *total = (long long *)(ws + l.total), *offs = (long long *)(ws + l.offs);
+    hipLaunchKernelGGL(k_mesh_project, dim3((unsigned)l.n_blocks), dim3(256), 0, stream, verts, (long long)n_verts,
+                       (const int *)faces, (long long)n_faces, cam, (MeshCam *)(ws + l.cam), (MeshRec *)(ws + l.rec),
+                       (int4 *)(ws + l.box), (int *)(ws + l.count), (int *)(ws + l.part));
+    VP_HIP(hipGetLastError());
+    if (counters) {
+        hipLaunchKernelGGL(k_mesh_counters, dim3(1), dim3(256), 0, stream, (const int *)(ws + l.part), l.n_blocks,
+                           (int *)counters);
+        VP_HIP(hipGetLastError());
+    }
+    if (n_faces > 0) {
+        size_t tmp = l.scan_bytes;
+        VP_HIP(rocprim::inclusive_scan(ws + l.scan_tmp, tmp, (const int *)(ws + l.count), offs, (size_t)n_faces,
+                                       rocprim::plus<long long>(), stream));
+    }
+    hipLaunchKernelGGL(k_splat_total, dim3(1), dim3(1), 0, stream, (const long long *)offs, (long long)n_faces, total,
+                       (long long *)n_isect);
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int vp_mesh_rasterize(const uint8_t *vertex_labels, const int32_t *faces, int64_t n_faces, int W, int H, int64_t capacity,
+                      int32_t *face_ids, float *depth, uint8_t *labels, int32_t *status, void *workspace,
+                      size_t workspace_bytes, void *stream_)
+{
+    if (int rc = mesh_check_shape(n_faces, W, H, capacity)) return rc;
+    if (labels && n_faces > 0 && (!vertex_labels || !faces))
+        return fail(VP_EINVAL, "null pointer argument (labels needs vertex_labels and faces)");
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    MeshLayout l;
+    if (!mesh_layout(n_faces, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    const long long n_tiles = (long long)l.tiles_x * l.tiles_y;
+    const long long *total = (const long long *)(ws + l.total);
+    unsigned *k0 = (unsigned *)(ws + l.keys0), *k1 = (unsigned *)(ws + l.keys1);
+    int *v0 = (int *)(ws + l.vals0), *v1 = (int *)(ws + l.vals1);
+    longlong2 *ranges = (longlong2 *)(ws + l.ranges);
+    // emit: one thread per face (at least one workgroup, which also pads [total, capacity) and raises the status)
+    hipLaunchKernelGGL(k_mesh_emit, dim3((unsigned)l.n_blocks), dim3(256), 0, stream, (const int4 *)(ws + l.box),
+                       (const long long *)(ws + l.offs), (long long)n_faces, l.tiles_x, (unsigned)n_tiles, total,
+                       (long long)capacity, k0, v0, (int *)status);
+    VP_HIP(hipGetLastError());
+    if (capacity > 0) {
+        size_t tmp = l.sort_bytes;
+        VP_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, tmp, k0, k1, v0, v1, (size_t)capacity, 0u, (unsigned)l.end_bit,
+                                         stream));
+    }
+    VP_HIP(hipMemsetAsync(ranges, 0, (size_t)n_tiles * sizeof(longlong2), stream));
+    if (capacity > 0) {
+        hipLaunchKernelGGL(k_mesh_ranges, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, stream, k1, total,
+                           (long long)capacity, ranges);
+        VP_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_mesh_tiles, dim3((unsigned)l.tiles_x, (unsigned)l.tiles_y), dim3(SPLAT_THREADS), 0, stream,
+                       (const MeshRec *)(ws + l.rec), (const int *)v1, (const longlong2 *)ranges, total, (long long)capacity,
+                       (const MeshCam *)(ws + l.cam), (const int *)faces, (const unsigned char *)vertex_labels,
+                       (int *)face_ids, depth, (unsigned char *)labels);
     VP_HIP(hipGetLastError());
     return VP_OK;
 }

@@ -129,6 +129,14 @@ _SIGNATURES_EXT = {
     "vp_sh_colors_backward": "i: ppp F l ii pp ppp p",
 }
 EXPORTS_EXT = list(_SIGNATURES_EXT)
+# The entry points of include/voxproj_mesh.h (the triangle-mesh rasterizer): the third table, same notation, same tolerant
+# binding.  tests/test_mesh_cpu.py compares every entry with that header's prototype.
+_SIGNATURES_MESH = {
+    "vp_mesh_workspace_bytes": "z: l ii l",
+    "vp_mesh_project": "i: p l p l F ffff ii ff pp p z p",
+    "vp_mesh_rasterize": "i: pp l ii l pppp p z p",
+}
+EXPORTS_MESH = list(_SIGNATURES_MESH)
 VP_SH_MAX_DEGREE = 3
 VP_OPT_HEAVY_THRESHOLD = 1
 VP_OPT_MARCH_LDS_KB = 2
@@ -155,7 +163,7 @@ def build(force=False):
     """Compile libvoxproj.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f == "voxproj.hip" or (f.startswith("vp_") and f.endswith(".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("voxproj.h", "voxproj_ext.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("voxproj.h", "voxproj_ext.h", "voxproj_mesh.h")]
     newest = max(os.path.getmtime(f) for f in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
         subprocess.check_call(["make", "-C", os.path.join(_HERE, "csrc"), "-s"] + (["-B"] if force else []))
@@ -195,7 +203,7 @@ def lib():
                     f"{LIB_PATH} is missing: build it with `make -C {os.path.join(_HERE, 'csrc')}` "
                     "(there is no CPU fallback)")
             L = ctypes.CDLL(LIB_PATH)
-            for name, signature in list(_SIGNATURES.items()) + list(_SIGNATURES_EXT.items()):
+            for name, signature in list(_SIGNATURES.items()) + list(_SIGNATURES_EXT.items()) + list(_SIGNATURES_MESH.items()):
                 fn = getattr(L, name, None)
                 if fn is not None:               # a symbol the library lacks is skipped here; _entry raises when it is called
                     restype, argtypes = signature.split(":")
@@ -1520,6 +1528,104 @@ def resample_adam(optimizer, old_params, new_params, plan):
             if (name, key) in moved:
                 st[key] = moved[(name, key)]
         optimizer.state[new_params[name]] = st
+
+
+def _mesh_arrays(verts, faces, vertex_labels=None):
+    """The float32 [V,3] vertices, int32 [F,3] faces and optional uint8 [V] labels on one GPU, contiguous: (V, F, arrays)."""
+    import torch
+    specs = [(verts, "verts", (torch.float32,)), (faces, "faces", (torch.int32,))]
+    if vertex_labels is not None:
+        specs.append((vertex_labels, "vertex_labels", (torch.uint8,)))
+    _require_tensors(*specs)
+    _require(verts.dim() == 2 and int(verts.shape[1]) == 3, "verts must be [V, 3]")
+    _require(faces.dim() == 2 and int(faces.shape[1]) == 3, "faces must be [F, 3]")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    _require(vertex_labels is None or tuple(vertex_labels.shape) == (V,), f"vertex_labels must be [{V}]")
+    _require(all(t.device == verts.device for t, _, _ in specs), "the mesh tensors must be on one device")
+    return V, F, [t.contiguous() for t, _, _ in specs]
+
+
+def _mesh_workspace_bytes(n_faces, W, H, capacity):
+    nbytes = int(_entry("vp_mesh_workspace_bytes")(int(n_faces), int(W), int(H), int(capacity)))
+    _require(nbytes > 0, f"no workspace size for {n_faces} faces, {W} x {H}, capacity {capacity}")
+    return nbytes
+
+
+def mesh_project(verts, faces, viewmat, K, W, H, *, near=0.01, far=100.0, workspace=None, counters=None):
+    """vp_mesh_project (the contract is in include/voxproj_mesh.h): every face of the mesh set up once into ``workspace`` (a
+    SplatWorkspace; grown to the projection's size).  verts f32 [V,3] and faces i32 [F,3] on one GPU, viewmat [4,4]
+    world-to-camera and K [3,3] (read on the host), as for splat_project.  Returns the device int64 [1] count of (tile, face)
+    pairs (not read here).  ``counters``: optional device int32 [3], += the faces dropped for {an index outside the vertices,
+    a non-finite vertex, a coordinate beyond the guard band}."""
+    import torch
+    V, F, (verts, faces) = _mesh_arrays(verts, faces)
+    dev = verts.device
+    vm, (fx, fy, cx, cy) = _splat_camera(viewmat, K, W, H)
+    _require(0.0 < float(near) < float(far) < float("inf"), f"need 0 < near < far (got {near}, {far})")
+    if counters is not None:
+        _require_tensors((counters, "counters", (torch.int32,)))
+        _require(tuple(counters.shape) == (3,) and counters.device == dev and counters.is_contiguous(),
+                 "counters must be a contiguous int32 [3] on the mesh's device")
+    ws = workspace if workspace is not None else SplatWorkspace()
+    ptr = ws.ensure(_mesh_workspace_bytes(F, W, H, 0), dev)
+    n_isect = torch.zeros(1, dtype=torch.int64, device=dev)
+    _call(dev, "vp_mesh_project", _ptr(verts), V, _ptr(faces), F, vm, fx, fy, cx, cy, int(W), int(H), float(near), float(far),
+          n_isect.data_ptr(), _ptr(counters), ptr, ws.capacity())
+    return n_isect
+
+
+def mesh_rasterize(faces, vertex_labels, W, H, capacity, workspace, *, want_depth=True, want_labels=True, status=None, out=None):
+    """vp_mesh_rasterize after mesh_project on ``workspace`` with the same faces, W and H: sort ``capacity`` (tile, face)
+    pairs and run the tile kernel.  The workspace grows to ``capacity`` (the projection's bytes kept).  Returns (face_ids int32
+    [H,W], depth f32 [H,W] or None, labels uint8 [H,W] or None); ``out``: three tensors (or None) to write instead of new
+    ones.  ``vertex_labels`` uint8 [V] may be None without labels.  ``status``: optional device int32 [1], set to 1 when the
+    device count exceeds ``capacity`` (then no output is written)."""
+    import torch
+    _require_tensors((faces, "faces", (torch.int32,)))
+    _require(faces.dim() == 2 and int(faces.shape[1]) == 3, "faces must be [F, 3]")
+    faces = faces.contiguous()
+    F, dev = int(faces.shape[0]), faces.device
+    want_labels = bool(want_labels and vertex_labels is not None)
+    if want_labels:
+        _require_tensors((vertex_labels, "vertex_labels", (torch.uint8,)))
+        _require(vertex_labels.dim() == 1 and vertex_labels.device == dev, "vertex_labels must be uint8 [V] on the faces' device")
+        vertex_labels = vertex_labels.contiguous()
+    keep = _mesh_workspace_bytes(F, W, H, 0)
+    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and workspace.capacity() >= keep,
+             "mesh_rasterize needs the workspace of a mesh_project call")
+    ptr = workspace.ensure(_mesh_workspace_bytes(F, W, H, capacity), dev, keep=keep)
+    if out is None:
+        out = (torch.empty((H, W), dtype=torch.int32, device=dev),
+               torch.empty((H, W), dtype=torch.float32, device=dev) if want_depth else None,
+               torch.empty((H, W), dtype=torch.uint8, device=dev) if want_labels else None)
+    ids, depth, labels = _splat_images(dev, (out[0], "face_ids", (H, W), torch.int32), (out[1], "depth", (H, W), torch.float32),
+                                       (out[2], "labels", (H, W), torch.uint8))
+    _require(labels is None or want_labels, "labels need vertex_labels")
+    _call(dev, "vp_mesh_rasterize", _ptr(vertex_labels) if want_labels else None, _ptr(faces), F, int(W), int(H), int(capacity),
+          _ptr(ids), _ptr(depth), _ptr(labels), _ptr(status), ptr, workspace.capacity())
+    return ids, depth, labels
+
+
+def mesh_render(verts, faces, vertex_labels, viewmat, K, W, H, near=0.01, far=100.0, workspace=None):
+    """Rasterize an annotated triangle mesh into one W x H view (vp_mesh_project + vp_mesh_rasterize): per pixel the nearest
+    face, its depth and the majority label of its vertices, at the splatter's camera and pixel centres.  Reads the 8-byte pair
+    count once to size the sort, as splat_features does (``workspace``: a SplatWorkspace, kept and regrown across calls).
+    Returns (face_ids int32 [H,W], -1 where nothing is drawn; depth f32 [H,W], 0 there; labels uint8 [H,W], 255 there, None
+    without vertex_labels; counters int32 [3] on the device: the faces dropped for a bad index, a non-finite vertex, the
+    guard band)."""
+    import torch
+    _mesh_arrays(verts, faces, vertex_labels)
+    dev = verts.device
+    ws = workspace if workspace is not None else SplatWorkspace()
+    counters = torch.zeros(3, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_isect = mesh_project(verts, faces, viewmat, K, W, H, near=near, far=far, workspace=ws, counters=counters)
+    cap = int(n_isect.item())
+    _require(cap <= 2 ** 31 - 1, f"{cap} tile intersections: more than 2^31 - 1")
+    ids, depth, labels = mesh_rasterize(faces, vertex_labels, W, H, cap, ws, status=status)
+    if int(status.item()):
+        raise VoxprojError("mesh_render: the pair count outgrew the workspace (no image written)")
+    return ids, depth, labels, counters
 
 
 def camera_position(viewmat):
