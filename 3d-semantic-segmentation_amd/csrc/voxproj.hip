@@ -50,6 +50,7 @@
 //   vp_densify.h       adaptive density control: per-view statistics, the clone / split / prune plan, the row gather, the split
 //   vp_sh.h            view-dependent colour: spherical harmonics of degree 0 .. 3 into colour rows, and the adjoint (voxproj_ext.h)
 //   vp_mesh.h          triangle-mesh rasterizer: nearest face, depth and label per pixel, integer-decided (voxproj_mesh.h)
+//   vp_grid.h          stage 2, the voxel grid of a Gaussian cloud: ball statistics on the bucketed grid, voxelisation (voxproj_grid.h)
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -72,6 +73,7 @@
 #include "voxproj.h"
 #include "voxproj_ext.h"
 #include "voxproj_mesh.h"
+#include "voxproj_grid.h"
 
 #include "vp_plan.h"
 #include "vp_common.h"
@@ -96,6 +98,7 @@
 #include "vp_densify.h"
 #include "vp_sh.h"
 #include "vp_mesh.h"
+#include "vp_grid.h"
 #include "vp_project.h"
 
 // The refusal of a caller-provided workspace that is missing, smaller than ``need`` or not 256-byte aligned.
@@ -1663,6 +1666,107 @@ int vp_mesh_rasterize(const uint8_t *vertex_labels, const int32_t *faces, int64_
                        (const MeshCam *)(ws + l.cam), (const int *)faces, (const unsigned char *)vertex_labels,
                        (int *)face_ids, depth, (unsigned char *)labels);
     VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stage 2, the voxel grid of a Gaussian cloud (vp_grid.h, declared in voxproj_grid.h).  Every check is host arithmetic and
+// comes before grid_layout (rocprim's scratch sizes depend on the device) and before any launch.
+// ------------------------------------------------------------------------------------------------
+int vp_ball_count(const float *pts_sorted, const int32_t *perm, const int32_t *cell_start, const double *grid_origin3,
+                  double cell_size, int nx, int ny, int nz, const float *queries, int64_t M, double radius, const float *radii,
+                  const float *point_normals, const float *query_normals, double min_dot, int32_t *count,
+                  int32_t *consistent, void *stream_)
+{
+    if (!pts_sorted || !perm || !cell_start || !grid_origin3 || !queries || !count)
+        return fail(VP_EINVAL, "null pointer argument (pts_sorted, perm, cell_start, grid_origin3, queries or count)");
+    if (M < 0 || M > INT32_MAX) return fail(VP_EINVAL, "M = %lld outside [0, 2^31 - 1]", (long long)M);
+    if (!(cell_size > 0.0) || !std::isfinite(cell_size) || nx <= 0 || ny <= 0 || nz <= 0)
+        return fail(VP_EINVAL, "bad grid (cell size %g, dims %d %d %d)", cell_size, nx, ny, nz);
+    if ((long long)nx * ny * nz >= (1ll << 31)) return fail(VP_EINVAL, "the grid has >= 2^31 cells");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(grid_origin3[a])) return fail(VP_EINVAL, "grid_origin3[%d] is not finite", a);
+    if (!radii && (!(radius >= 0.0) || !std::isfinite(radius)))
+        return fail(VP_EINVAL, "radius = %g must be finite and >= 0", radius);
+    if ((point_normals != nullptr) != (query_normals != nullptr))
+        return fail(VP_EINVAL, "normals for only one side (point_normals and query_normals go together)");
+    if (point_normals && !consistent) return fail(VP_EINVAL, "null pointer argument (consistent, with normals)");
+    if (point_normals && std::isnan(min_dot)) return fail(VP_EINVAL, "min_dot is NaN");
+    if (M == 0) return VP_OK;
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    hipStream_t stream = (hipStream_t)stream_;
+    auto launch = [&](auto normals) {
+        hipLaunchKernelGGL(k_ball_count<decltype(normals)::value>, grid, block, 0, stream, pts_sorted, (const int *)perm,
+                           (const int *)cell_start, grid_origin3[0], grid_origin3[1], grid_origin3[2], cell_size, nx, ny, nz,
+                           queries, (long long)M, radius, radii, point_normals, query_normals, min_dot, (int *)count,
+                           (int *)consistent);
+    };
+    if (point_normals) launch(std::true_type{});
+    else launch(std::false_type{});
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+size_t vp_voxel_grid_workspace_bytes(int64_t N)
+{
+    if (N < 0 || N > INT32_MAX) return 0;
+    GridLayout l;
+    return grid_layout(N, l) ? l.bytes : 0;
+}
+
+int vp_voxel_grid(const float *points, const uint8_t *colors, const uint8_t *keep, int64_t N, double voxel_size,
+                  float *centers, uint8_t *voxel_colors, int32_t *counts, int32_t *voxel_index, int32_t *point_voxel,
+                  int32_t *n_voxels, float *min_corner, int32_t *status, void *workspace, size_t workspace_bytes,
+                  void *stream_)
+{
+    if (N < 0 || N > INT32_MAX) return fail(VP_EINVAL, "N = %lld outside [0, 2^31 - 1]", (long long)N);
+    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size) || !((float)voxel_size > 0.0f) || !std::isfinite((float)voxel_size))
+        return fail(VP_EINVAL, "voxel_size = %g must be finite and > 0 (in float32 too)", voxel_size);
+    if (!n_voxels || !min_corner) return fail(VP_EINVAL, "null pointer argument (n_voxels or min_corner)");
+    if (N > 0 && (!points || !colors || !centers || !voxel_colors || !counts || !voxel_index || !point_voxel))
+        return fail(VP_EINVAL, "null pointer argument (points, colors, centers, voxel_colors, counts, voxel_index or point_voxel)");
+    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    GridLayout l;
+    if (!grid_layout(N, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
+    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    GridMeta *meta = (GridMeta *)(ws + l.meta);
+    int *over = (int *)(ws + l.over), *total = (int *)(ws + l.total);
+    unsigned long long *k0 = (unsigned long long *)(ws + l.keys0), *k1 = (unsigned long long *)(ws + l.keys1);
+    int *v0 = (int *)(ws + l.vals0), *v1 = (int *)(ws + l.vals1);
+    int *heads = (int *)(ws + l.heads), *rank = (int *)(ws + l.rank), *run_start = (int *)(ws + l.run_start);
+    const dim3 per_point((unsigned)((std::max<int64_t>(N, 1) + 255) / 256)), block(256);
+    VP_HIP(hipMemsetAsync(over, 0, sizeof(int), stream));
+    hipLaunchKernelGGL(k_grid_min_part, dim3((unsigned)l.n_parts), block, 0, stream, points, (const unsigned char *)keep,
+                       (long long)N, (float *)(ws + l.part_min), (int *)(ws + l.part_cnt));
+    hipLaunchKernelGGL(k_grid_min_final, dim3(1), dim3(GRID_PARTS), 0, stream, (const float *)(ws + l.part_min),
+                       (const int *)(ws + l.part_cnt), l.n_parts, meta);
+    VP_HIP(hipGetLastError());
+    if (N > 0) {
+        hipLaunchKernelGGL(k_grid_keys, per_point, block, 0, stream, points, (const unsigned char *)keep, (long long)N,
+                           (float)voxel_size, (const GridMeta *)meta, k0, v0, over);
+        VP_HIP(hipGetLastError());
+        size_t tmp = l.sort_bytes;
+        VP_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, tmp, k0, k1, v0, v1, (size_t)N, 0u, 64u, stream));
+        hipLaunchKernelGGL(k_grid_heads, per_point, block, 0, stream, (const unsigned long long *)k1, (long long)N, heads);
+        VP_HIP(hipGetLastError());
+        tmp = l.scan_bytes;
+        VP_HIP(rocprim::inclusive_scan(ws + l.scan_tmp, tmp, (const int *)heads, rank, (size_t)N, rocprim::plus<int>(), stream));
+    }
+    hipLaunchKernelGGL(k_grid_total, dim3(1), dim3(1), 0, stream, (const int *)rank, (long long)N, (const GridMeta *)meta,
+                       (const int *)over, total, (int *)n_voxels, min_corner, (int *)status);
+    VP_HIP(hipGetLastError());
+    if (N > 0) {
+        hipLaunchKernelGGL(k_grid_points, per_point, block, 0, stream, (const unsigned long long *)k1, (const int *)v1,
+                           (const int *)heads, (const int *)rank, (long long)N, (const int *)total, run_start,
+                           (int *)point_voxel);
+        // one thread per voxel; V <= N is on the device only, so the grid covers N and the surplus threads leave at once
+        hipLaunchKernelGGL(k_grid_voxels, per_point, block, 0, stream, (const unsigned long long *)k1, (const int *)v1,
+                           (const int *)run_start, (const int *)total, (const GridMeta *)meta, (const unsigned char *)colors,
+                           voxel_size, centers, (unsigned char *)voxel_colors, (int *)counts, (int *)voxel_index);
+        VP_HIP(hipGetLastError());
+    }
     return VP_OK;
 }
 

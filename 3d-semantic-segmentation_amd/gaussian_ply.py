@@ -63,6 +63,17 @@ def sh_degree_of_width(kr):
     return {(D + 1) ** 2 - 1: D for D in range(SH_MAX_DEGREE + 1)}.get(int(kr))
 
 
+def read_vertex_records(path):
+    """The vertex records of a binary little-endian point cloud as one NumPy structured array: every column as stored, no
+    field required, no activation (what plyfile's PlyData.read(path)['vertex'].data holds)."""
+    with open(path, "rb") as f:
+        n, dt = _header(f, path)
+        v = np.fromfile(f, dtype=dt, count=n)
+    if len(v) != n:
+        raise ValueError(f"{path}: {len(v)} of {n} vertex records")
+    return v
+
+
 def read_gaussian_ply(path, want_dc=False, want_raw=False, want_sh=False):
     """dict(means f32 [N,3], quats f32 [N,4] (w,x,y,z, unit norm; a zero quaternion stays zero), scales f32 [N,3],
     opacities f32 [N]) with the model's activations applied.  ``want_dc`` adds f_dc f32 [N,3], the f_dc_0..2 columns as

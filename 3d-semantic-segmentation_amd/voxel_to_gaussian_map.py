@@ -15,7 +15,9 @@ import torch
 import voxproj_host
 
 
-def _bucket(voxel_pos, device):
+def _bucket(voxel_pos, device, min_cell=None):
+    """The points sorted by the cell of a uniform grid: (sorted points, perm, cell_start, origin, cell size, dims).
+    ``min_cell``: a lower bound of the cell size (a ball search wants cells no smaller than its largest radius)."""
     pos = voxel_pos.to(device, torch.float32).contiguous()
     N = pos.shape[0]
     p64 = pos.double()
@@ -24,6 +26,8 @@ def _bucket(voxel_pos, device):
     # cell size ~ mean spacing of a volume-filling set, never more than ~8M cells
     h = float((ext.prod() / max(N, 1)) ** (1.0 / 3.0))
     h = max(h, float(ext.max()) / 200.0, 1e-9)
+    if min_cell is not None:
+        h = max(h, float(min_cell))
     dims = [int(v) for v in (torch.floor(ext / h).long() + 1).tolist()]
     cell = torch.floor((p64 - lo) / h).long()
     for a in range(3):

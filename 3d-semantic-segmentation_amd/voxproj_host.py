@@ -137,6 +137,14 @@ _SIGNATURES_MESH = {
     "vp_mesh_rasterize": "i: pp l ii l pppp p z p",
 }
 EXPORTS_MESH = list(_SIGNATURES_MESH)
+# The entry points of include/voxproj_grid.h (stage 2, the voxel grid of a Gaussian cloud): the fourth table, same notation,
+# same tolerant binding.  tests/test_voxel_grid_cpu.py compares every entry with that header's prototype.
+_SIGNATURES_GRID = {
+    "vp_ball_count": "i: ppp D d iii p l d ppp d pp p",
+    "vp_voxel_grid_workspace_bytes": "z: l",
+    "vp_voxel_grid": "i: ppp l d ppppp ppp p z p",
+}
+EXPORTS_GRID = list(_SIGNATURES_GRID)
 VP_SH_MAX_DEGREE = 3
 VP_OPT_HEAVY_THRESHOLD = 1
 VP_OPT_MARCH_LDS_KB = 2
@@ -163,7 +171,7 @@ def build(force=False):
     """Compile libvoxproj.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f == "voxproj.hip" or (f.startswith("vp_") and f.endswith(".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("voxproj.h", "voxproj_ext.h", "voxproj_mesh.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("voxproj.h", "voxproj_ext.h", "voxproj_mesh.h", "voxproj_grid.h")]
     newest = max(os.path.getmtime(f) for f in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
         subprocess.check_call(["make", "-C", os.path.join(_HERE, "csrc"), "-s"] + (["-B"] if force else []))
@@ -203,7 +211,8 @@ def lib():
                     f"{LIB_PATH} is missing: build it with `make -C {os.path.join(_HERE, 'csrc')}` "
                     "(there is no CPU fallback)")
             L = ctypes.CDLL(LIB_PATH)
-            for name, signature in list(_SIGNATURES.items()) + list(_SIGNATURES_EXT.items()) + list(_SIGNATURES_MESH.items()):
+            for name, signature in list(_SIGNATURES.items()) + list(_SIGNATURES_EXT.items()) + list(_SIGNATURES_MESH.items()) + \
+                    list(_SIGNATURES_GRID.items()):
                 fn = getattr(L, name, None)
                 if fn is not None:               # a symbol the library lacks is skipped here; _entry raises when it is called
                     restype, argtypes = signature.split(":")
@@ -1817,6 +1826,126 @@ def knn_mean_dist2(points):
     have = torch.isfinite(d2)
     z = torch.where(have, d2, torch.zeros_like(d2))
     return (((z[:, 0] + z[:, 1]) + z[:, 2]) / have.sum(1).clamp_min(1)).to(torch.float32)
+
+
+def _rows3(t, name, dev=None):
+    """``t`` as a contiguous float32 [M,3] on a GPU (on ``dev`` when given)."""
+    import torch
+    _require_tensors((t, name, (torch.float32,)))
+    _require(t.dim() == 2 and int(t.shape[1]) == 3 and (dev is None or t.device == dev),
+             f"{name} must be float32 [M, 3]" + (" on the points' device" if dev is not None else ""))
+    return t.detach().contiguous()
+
+
+def ball_count(points, radius_or_radii, queries=None, normals=None, query_normals=None, min_dot=None):
+    """vp_ball_count (the contract is in include/voxproj_grid.h): per query the number of ``points`` (f32 [N,3] on a GPU)
+    with float64 squared distance <= r^2, boundary points and the query itself included, as cKDTree.query_ball_point counts
+    them.  ``radius_or_radii``: a Python float, or a float32 [M] tensor with one radius per query.  ``queries`` None: the
+    points themselves.  With ``normals`` (unit, f32 [N,3]; ``query_normals`` f32 [M,3] for queries that are not the points)
+    and ``min_dot`` also the number of points within the ball whose normal has a float64 dot product > min_dot with the
+    query's.  Returns (count int32 [M], consistent int32 [M] or None) on the device, in the caller's row order; nothing is
+    read back here.  The queries are launched in the grid's cell order, so that a wavefront's lanes walk the same cells."""
+    import torch
+    import voxel_to_gaussian_map
+    points = _rows3(points, "points")
+    dev, N = points.device, int(points.shape[0])
+    q = points if queries is None else _rows3(queries, "queries", dev)
+    M = int(q.shape[0])
+    radii = None
+    if isinstance(radius_or_radii, torch.Tensor):
+        _require_tensors((radius_or_radii, "radii", (torch.float32,)))
+        _require(tuple(radius_or_radii.shape) == (M,) and radius_or_radii.device == dev, f"radii must be float32 [{M}] on the points' device")
+        radii, radius = radius_or_radii.detach().contiguous(), 0.0
+    else:
+        radius = float(radius_or_radii)
+        _require(0.0 <= radius < float("inf"), f"radius = {radius} must be finite and >= 0")
+    _require((normals is None) == (min_dot is None), "normals and min_dot go together")
+    qn = None
+    if normals is not None:
+        normals = _rows3(normals, "normals", dev)
+        _require(int(normals.shape[0]) == N, f"normals must be [{N}, 3]")
+        _require(queries is None or query_normals is not None, "queries that are not the points need query_normals")
+        qn = normals if queries is None else _rows3(query_normals, "query_normals", dev)
+        _require(int(qn.shape[0]) == M, f"query_normals must be [{M}, 3]")
+    else:
+        _require(query_normals is None, "query_normals without normals")
+    count = torch.zeros(M, dtype=torch.int32, device=dev)
+    consistent = torch.zeros(M, dtype=torch.int32, device=dev) if normals is not None else None
+    if N == 0 or M == 0:
+        return count, consistent
+    # cells no smaller than the largest finite radius: the box of a query is 3 x 3 x 3 cells
+    if radii is not None:
+        finite = radii[torch.isfinite(radii)].abs()
+        rmax = float(finite.max()) if finite.numel() else 0.0
+    else:
+        rmax = radius
+    pts, perm, start, origin, h, dims = voxel_to_gaussian_map._bucket(points, dev, min_cell=rmax if rmax > 0.0 else None)
+    if queries is None:
+        order = perm.long()
+        qs = pts
+    else:                                        # the queries in the order of the cell nearest to them
+        lo = torch.tensor(origin, dtype=torch.float64, device=dev)
+        cell = torch.floor((q.double() - lo) / h).nan_to_num(nan=0.0).clamp(-1.0, 2.0 ** 31)
+        for a in range(3):
+            cell[:, a].clamp_(0, dims[a] - 1)
+        cell = cell.long()
+        order = torch.argsort((cell[:, 2] * dims[1] + cell[:, 1]) * dims[0] + cell[:, 0], stable=True)
+        qs = q[order].contiguous()
+    rs = radii[order].contiguous() if radii is not None else None
+    qns = qn[order].contiguous() if qn is not None else None
+    cnt = torch.empty(M, dtype=torch.int32, device=dev)
+    con = torch.empty(M, dtype=torch.int32, device=dev) if normals is not None else None
+    g = (ctypes.c_double * 3)(*origin)
+    _call(dev, "vp_ball_count", pts.data_ptr(), perm.data_ptr(), start.data_ptr(), g, ctypes.c_double(h), dims[0], dims[1],
+          dims[2], qs.data_ptr(), M, ctypes.c_double(radius), _ptr(rs), _ptr(normals), _ptr(qns),
+          ctypes.c_double(float(min_dot) if min_dot is not None else 0.0), cnt.data_ptr(), _ptr(con))
+    count.index_copy_(0, order, cnt)                 # row t of the launch is query order[t]
+    if con is not None:
+        consistent.index_copy_(0, order, con)
+    return count, consistent
+
+
+def voxel_grid_workspace_bytes(N):
+    nbytes = int(_entry("vp_voxel_grid_workspace_bytes")(int(N)))
+    _require(nbytes > 0, f"no workspace size for N = {N}")
+    return nbytes
+
+
+def voxel_grid(points, colors, voxel_size, keep=None, workspace=None):
+    """vp_voxel_grid (the contract is in include/voxproj_grid.h): the sparse voxel grid of the kept ``points`` (f32 [N,3] on a
+    GPU) with ``colors`` uint8 [N,3]; ``keep`` uint8 or bool [N] or None (all).  Returns dict(centers f32 [V,3], colors uint8
+    [V,3], counts int32 [V], voxel_index int32 [V,3], point_voxel int32 [N] (-1: not kept), n_voxels int32 [1], min_corner
+    f32 [3], status int32 [1]) on the device, the voxels in lexicographic (x, y, z) order.  The 4-byte voxel count is read
+    once to trim the rows, as mesh_render reads its pair count.  status 1 (a non-finite kept point, or a cell index above
+    2^21 - 1): no voxel, V = 0; the caller decides what that means.  ``workspace``: a SplatWorkspace, kept across calls."""
+    import torch
+    points = _rows3(points, "points")
+    dev, N = points.device, int(points.shape[0])
+    _require_tensors((colors, "colors", (torch.uint8,)))
+    _require(tuple(colors.shape) == (N, 3) and colors.device == dev, f"colors must be uint8 [{N}, 3] on the points' device")
+    colors = colors.contiguous()
+    if keep is not None:
+        _require_tensors((keep, "keep", (torch.uint8, torch.bool)))
+        _require(tuple(keep.shape) == (N,) and keep.device == dev, f"keep must be uint8 or bool [{N}] on the points' device")
+        keep = keep.to(torch.uint8).contiguous()
+    vs = float(voxel_size)
+    _require(0.0 < vs < float("inf"), f"voxel_size = {voxel_size} must be finite and > 0")
+    ws = workspace if workspace is not None else SplatWorkspace()
+    ptr = ws.ensure(voxel_grid_workspace_bytes(N), dev)
+    centers = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    vcolors = torch.empty((N, 3), dtype=torch.uint8, device=dev)
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    vindex = torch.empty((N, 3), dtype=torch.int32, device=dev)
+    point_voxel = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    n_voxels = torch.zeros(1, dtype=torch.int32, device=dev)
+    min_corner = torch.full((3,), float("inf"), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _call(dev, "vp_voxel_grid", _ptr(points), _ptr(colors), _ptr(keep), N, ctypes.c_double(vs), _ptr(centers), _ptr(vcolors),
+          _ptr(counts), _ptr(vindex), _ptr(point_voxel), n_voxels.data_ptr(), min_corner.data_ptr(), status.data_ptr(), ptr,
+          ws.capacity())
+    V = int(n_voxels.item())
+    return dict(centers=centers[:V], colors=vcolors[:V], counts=counts[:V], voxel_index=vindex[:V], point_voxel=point_voxel,
+                n_voxels=n_voxels, min_corner=min_corner, status=status)
 
 
 def reverse_table(nbr, n_rows):
