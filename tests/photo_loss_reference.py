@@ -33,6 +33,8 @@ quantities by other routes than the traced one -- m^2 formed before a division i
 other way, an autograd chain that forms dm/dmu1 from four terms instead of two -- whose rounding counts per quantity differ
 from the trace's by less than a factor of two.  No bound is floored or fitted to any output.
 """
+import hashlib
+
 import numpy as np
 
 U = 2.0 ** -24
@@ -50,17 +52,41 @@ def gamma(k):
     return k * U / (1.0 - k * U)
 
 
+_SUMS = {}                                                 # window_sum's results by the digest of the input (see there)
+_SUMS_LIMIT = 256 << 20                                    # bytes of results kept
+_STRIP = 64                                                # rows summed at a time: one strip and its taps stay in cache
+
+
 def window_sum(a, window2d=None):
-    """sum over the window of w a with zero padding, per plane of a [C,H,W], tap by tap in float64."""
+    """sum over the window of w a with zero padding, per plane of a [C,H,W], tap by tap in float64 (every element adds its
+    121 products in the order i, j whatever the strips are).  With the contract's window the result is remembered under a
+    128-bit digest of the input and handed out read-only: statement64() and bounds() of one pair of images form eight of their
+    27 sums twice, and at a million elements a sum takes a fifth of a second."""
     w = np.outer(ROW, ROW) if window2d is None else np.asarray(window2d, np.float64)
-    a = np.asarray(a, np.float64)
+    a = np.ascontiguousarray(a, np.float64)
+    key = None
+    if window2d is None:
+        key = (a.shape, hashlib.blake2b(a, digest_size=16).digest())
+        if key in _SUMS:
+            return _SUMS[key]
     C, H, W = a.shape
     pad = np.zeros((C, H + 2 * RADIUS, W + 2 * RADIUS), np.float64)
     pad[:, RADIUS:RADIUS + H, RADIUS:RADIUS + W] = a
     out = np.zeros_like(a)
-    for i in range(2 * RADIUS + 1):
-        for j in range(2 * RADIUS + 1):
-            out += w[i, j] * pad[:, i:i + H, j:j + W]
+    tmp = np.empty((min(_STRIP, H), W), np.float64)
+    for c in range(C):
+        for r0 in range(0, H, _STRIP):
+            h = min(_STRIP, H - r0)
+            o, t = out[c, r0:r0 + h], tmp[:h]
+            for i in range(2 * RADIUS + 1):
+                for j in range(2 * RADIUS + 1):
+                    np.multiply(pad[c, r0 + i:r0 + i + h, j:j + W], w[i, j], out=t)
+                    o += t
+    if key is not None:
+        if sum(v.nbytes for v in _SUMS.values()) + out.nbytes > _SUMS_LIMIT:
+            _SUMS.clear()
+        out.flags.writeable = False
+        _SUMS[key] = out
     return out
 
 

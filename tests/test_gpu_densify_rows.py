@@ -103,6 +103,43 @@ def test_many_arrays_in_one_call(plan, count):
     assert int(pl.status.item()) == 0
 
 
+def test_rows_beyond_the_capped_grid():
+    """vp_densify_rows gives an array min(ceil(n_out / rows per round), DENSIFY_MAX_BLOCKS = 65 536) workgroups, and a
+    workgroup moves (256 / lanes per row) * DENSIFY_ROWS_IN_FLIGHT = 4 rows per round.  A row of 45 words is not a multiple of
+    four words, so it moves word by word with 64 lanes: 4 * 4 = 16 rows per round, and a second round iff
+    n_out > 65 536 * 16 = 1 048 576.  n_out = 1 048 576 + 16 + 3: workgroup 0 has a full second round, workgroup 1 three rows
+    of one.  The 3-word array of the same launch (4 lanes, 256 rows per round, 4097 workgroups) stays below its cap.  The rows
+    of the second round name sources that no other row names; everything is built and compared on the device."""
+    import voxproj_host
+    dev = torch.device("cuda:0")
+    lap = 65536 * 16
+    n_src, n_out, wide, narrow = 600000, lap + 16 + 3, 45, 3          # the library takes n_out <= 2 n_src
+    gen = torch.Generator(device=dev).manual_seed(45)
+    src = torch.randint(0, n_src - 19, (n_out,), generator=gen, device=dev, dtype=torch.int32)
+    src[lap:] = torch.arange(n_src - 19, n_src, dtype=torch.int32, device=dev).flip(0)
+    kind = torch.randint(0, 4, (n_out,), generator=gen, device=dev, dtype=torch.int32).to(torch.uint8)
+    kind[lap:] = torch.arange(19, device=dev).to(torch.uint8) % 4
+    counts = torch.tensor([n_out] + [int((kind == v).sum()) for v in (0, 1, 2)], dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    a_copy = torch.randint(-2 ** 31, 2 ** 31 - 1, (n_src, wide), generator=gen, device=dev, dtype=torch.int64).to(torch.int32)
+    a_zero = torch.randn((n_src, wide), generator=gen, device=dev)
+    a_thin = torch.randint(-2 ** 31, 2 ** 31 - 1, (n_src, narrow), generator=gen, device=dev, dtype=torch.int64).to(torch.int32)
+    d_copy = torch.full((n_out, wide), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    d_zero = torch.full((n_out, wide), -7.25, device=dev)
+    d_thin = torch.full((n_out, narrow), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    voxproj_host.densify_rows([(a_copy, d_copy, "copy"), (a_zero, d_zero, "zero"), (a_thin, d_thin, "zero")], src, kind, counts,
+                              n_src, n_out, status)
+    idx, fresh = src.long(), (kind != 0)[:, None]
+    assert int(status.item()) == 0
+    assert torch.equal(d_copy, a_copy.index_select(0, idx))
+    assert torch.equal(d_thin, torch.where(fresh, torch.zeros_like(d_thin), a_thin.index_select(0, idx)))
+    want = torch.where(fresh, torch.zeros_like(d_zero), a_zero.index_select(0, idx))
+    assert torch.equal(d_zero.view(torch.int32), want.view(torch.int32))
+    assert bool(fresh[lap:].any()) and not bool(fresh[lap:].all()) and int(src[:lap].max()) < n_src - 19
+    del d_copy, d_zero, d_thin, a_copy, a_zero, a_thin, want, idx, src, kind
+    torch.cuda.empty_cache()
+
+
 def test_wrong_n_out_raises_the_status_and_writes_nothing(plan):
     import voxproj_host
     pl, src, kind = plan

@@ -9,7 +9,7 @@ sum over workgroups).  C = 4096 is run at 1x1 and 37x19 only: the kernel's path 
 of 130 x 67 x 4096 elements would take the test from seconds to a minute.  Both image dtypes and both kinds are crossed with
 these; SUM / MEAN with and without grad_loss, pixel strides of C and C + 24 and a base offset by one element (which forces
 the element path) are drawn per case with a seeded generator, and test_layout_and_reduction_variants crosses them in full
-at C = 72 and C = 8.
+at C = 72 and C = 8.  257 x 256 at C = 8 has 257 workgroups: one more than k_feature_loss_sum stages at a time.
 
 The one ill-posed comparison: with C = 1 the cosine of two scalars is +-1 and its gradient is identically zero, so the
 float64 maximum is rounding noise (or 0) and fixes no exponent.  There the device's k is checked against the device's own
@@ -169,6 +169,25 @@ def test_against_float64(C, W, H, f16, kind):
     tv, _ = strided(target, pad, int(off))
     out = run(iv, tv, gpad=gpad, goff=int(off), **kw)
     check(out, image, target, **kw)
+
+
+@pytest.mark.parametrize("kind", fref.KINDS)
+@pytest.mark.parametrize("f16", [True, False], ids=["f16", "f32"])
+def test_more_workgroups_than_one_staging_of_the_sum(f16, kind):
+    """k_feature_loss_sum stages FLOSS_THREADS = 256 workgroup pairs at a time and a workgroup of the loss kernel holds 256
+    pixels: a second staging iff W H > 256 * 256 = 65 536.  257 x 256 pixels are 257 workgroups: the second staging holds the
+    pair of workgroup 256 alone, the pixels 65 536.. (the last image row from x = 1 on), which are all valid here and carry
+    the largest weights of the image: without them both statistics leave their bounds by orders of magnitude."""
+    C, W, H = 8, 257, 256
+    assert (W * H + 255) // 256 == 257
+    image, target, weight, alpha = maps(C, W, H, f16, seed=257 + int(f16) * 2 + KIND[kind])
+    weight.reshape(-1)[65536:] = np.float32(6.0)
+    alpha.reshape(-1)[65536:] = np.float32(0.9)
+    kw = dict(weight=weight, alpha=alpha, min_alpha=0.2, kind=kind, reduction="mean", grad_loss=0.37)
+    out = run(strided(image)[0], strided(target)[0], **kw)
+    r = check(out, image, target, **kw)
+    last = r["valid"].reshape(-1)[65536:]
+    assert last.all() and r["m"].reshape(-1)[65536:].sum() > 1e3 * fref.stats_bound(r)
 
 
 @pytest.mark.parametrize("goff", [0, 1])

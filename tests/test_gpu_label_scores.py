@@ -11,6 +11,8 @@ max(256, r + 1 rounded up to 64) pixels and columns into segments of max(64, r +
 The last two are maps with pixels outside the band on both sides of segment edges along both axes (asserted below), so
 their expected band is not all ones.  100 x 70 r = 40, 64 x 48 r = 64 and 130 x 200 r = 70 have a window larger than the
 image: every pixel is band, which checks the border rule, not the sweeps.
+The scores' grid is capped at 2048 workgroups of 256 pixels: 1024 x 513 (section 6b) is the least ragged size whose last
+pixels are a workgroup's second lap, on both sides of the dispatcher's threshold.
 
 Every test here fails on a library without the three vp_label_* symbols."""
 import os
@@ -261,6 +263,52 @@ def test_one_larger_view():
     assert np.array_equal(gpu_band(pred, r), pb) and np.array_equal(gpu_band(target, r), tb)
     conf, skipped = lref.confusion(pred, target, P)
     inter, union = lref.boundary_counts_from_bands(pred, target, P, pb, tb)
+    assert_scores(gpu_scores(pred, target, P, r), conf, skipped, inter, union)
+
+
+# ------------------------------------------------------------------------------------------------ 6b. past the grid cap
+# vp_label_scores launches min(ceil(W H / 256), EVAL_SCORE_BLOCKS = 2048) workgroups of 256 pixels and k_eval_scores strides by
+# gridDim * 256: a workgroup takes a second lap iff W H > 2048 * 256 = 524 288.  1024 x 513 = 524 288 + 1024: the last image row
+# is the second lap of workgroups 0..3 and of nobody else.
+LAP = 2048 * 256
+
+
+def second_lap_maps(P):
+    """(pred, target) at 1024 x 513 over the labels [0, P - 2), without one invalid pixel, and then a last row (pixel indices
+    >= LAP) that holds the only pixels of the classes P - 2 and P - 1, the only invalid targets and the only invalid
+    predictions.  The pair (0, 1) fills pixels 32..63 and LAP..LAP + 31: the second half of wavefront 0's first batch and the
+    first half of its second, so the global path's held key runs across the lap boundary."""
+    W, H = 1024, 513
+    assert W * H > LAP and (H - 1) * W == LAP
+    target = lref.make_map(W, H, P - 2, seed=40 + P, n_rects=14, n_dots=30)
+    pred = lref.perturb(target, P - 2, seed=41 + P, n_rects=8, n_bad=0)
+    a, b = P - 2, P - 1
+    target[0, :64], pred[0, :32], pred[0, 32:64] = 0, 0, 1
+    last_t, last_p = target[H - 1], pred[H - 1]
+    last_t[:32], last_p[:32] = 0, 1
+    last_t[32:100], last_p[32:100] = a, b
+    last_t[100:115], last_t[115:130] = -1, 255 if P < 255 else 1000
+    last_t[130:160], last_p[130:150], last_p[150:160] = a, P, 1 << 20
+    last_t[160:300], last_p[160:300] = b, b
+    last_t[700:800], last_p[700:800] = b, a                  # workgroup 2's second lap
+    return pred, target
+
+
+@pytest.mark.parametrize("P", [13, 65], ids=["lds-P13", "global-P65"])
+def test_scores_past_the_grid_cap(P):
+    """Both kernels' second lap: the LDS histograms and the global path's held key and count are carried into it.  Confusion
+    cells, both skipped counts and the boundary counts of two classes come from the second lap alone."""
+    assert (P <= 64) == (P == 13)                            # EVAL_LDS_P = 64: one case on either side
+    pred, target = second_lap_maps(P)
+    r = 2
+    conf, skipped = lref.confusion(pred, target, P)
+    first = lref.confusion(pred.ravel()[:LAP], target.ravel()[:LAP], P)
+    assert not first[1].any() and skipped.tolist() == [30, 30]
+    assert not first[0][P - 2:].any() and not first[0][:, P - 2:].any()
+    assert conf[P - 2, P - 1] == 68 and conf[P - 1, P - 1] == 140 and conf[P - 1, P - 2] == 100
+    assert conf[0, 1] - first[0][0, 1] == 32 and first[0][0, 1] >= 32
+    inter, union = lref.boundary_counts_from_bands(pred, target, P, lref.band_by_window(pred, r), lref.band_by_window(target, r))
+    assert inter[P - 1] == 140 and union[P - 2] > 0          # the last row is band by the border rule
     assert_scores(gpu_scores(pred, target, P, r), conf, skipped, inter, union)
 
 

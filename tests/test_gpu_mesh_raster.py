@@ -126,6 +126,69 @@ def test_counters_accumulate_and_may_be_absent():
     assert c.tolist() == [14, 22, 31] and int(a.item()) == int(b.item())
 
 
+COUNTER_LAP = 256 * 256         # k_mesh_counters: one workgroup, thread t adds the workgroups t, t + 256, ..; 256 faces each
+
+
+def _padded_room():
+    """room(0) with its faces split round 64 522 faces that lie behind the near plane (the twin and mesh_setup leave them
+    after the depth test of their vertices), so that the mesh has more than 65 536 faces: k_mesh_project runs more than 256
+    workgroups and every thread of k_mesh_counters that serves one of the workgroups 256.. takes a second lap.  Every dropped
+    face (5 bad indices, 3 non-finite, 2 guard band) has an index >= 65 536, in the workgroups 256 and 260."""
+    v, f, l = ms.room(0)
+    vm = ms.room_camera(0)
+    n = len(v)
+    R, t = vm[:3, :3].astype(np.float64), vm[:3, 3].astype(np.float64)
+    world = lambda cam: (np.asarray(cam, np.float64) - t) @ R  # noqa: E731   (camera space -> world)
+    behind = world([[0.3, 0.2, -1.0], [-0.4, 0.1, -1.5], [0.1, -0.3, -2.0]])
+    guard = world([[1e6, 0.5, 0.02], [0.1, 0.1, 0.5], [0.2, 0.1, 0.5]])       # _bad_mesh's face: 10^12 sub-pixel units out
+    verts = np.concatenate([v, behind, [[np.nan, 0, 0], [0, np.inf, 1]], guard]).astype(np.float32)
+    nv = len(verts)
+    even, odd = f[::2], f[1::2]                              # both halves hold faces of every wall
+    half = len(even)
+    pad = np.tile(np.array([[n, n + 1, n + 2]], np.int32), (COUNTER_LAP - half, 1))
+    drop_a = np.array([[nv, 1, 2], [-5, 1, 2], [n + 3, 1, 2], [n + 5, n + 6, n + 7]], np.int32)
+    drop_b = np.array([[1, -2 ** 31, 7], [0, 1, 2 ** 31 - 1], [nv + 9, nv, -1], [3, n + 4, 4], [n + 3, n + 4, 0],
+                       [n + 6, n + 7, n + 5]], np.int32)
+    faces = np.concatenate([even, pad, drop_a, odd, pad[:7], drop_b])
+    assert len(faces) > COUNTER_LAP and half + len(pad) == COUNTER_LAP
+    assert (len(faces) + 255) // 256 == 261 and len(faces) % 256 not in (0, 255)
+    labels = np.concatenate([l, np.arange(1, nv - n + 1, dtype=np.uint8)])
+    return verts, faces, labels, vm
+
+
+def test_more_than_65536_faces_and_counters_from_the_second_lap():
+    s = _padded_room() + (ms.intrinsics(96, 64), 96, 64)
+    want = mr.render(*s)
+    assert want["counters"].tolist() == [5, 3, 2]
+    assert not mr.render(s[0], s[1][:COUNTER_LAP], *s[2:])["counters"].any()          # none of them in the first lap
+    seen = np.unique(want["face_ids"])
+    assert seen.min() >= 0 and (seen < 1014).sum() > 20 and (seen > COUNTER_LAP).sum() > 20      # drawn faces on both sides
+    _same(_gpu(s), want)
+
+
+def test_padding_beyond_two_strides_of_the_emit_kernel():
+    """k_mesh_emit pads the slots [total, capacity) with a stride of gridDim * 256 = 256 * ceil(n_faces / 256) slots: 2048 for
+    the 2028 faces of a room.  A spare capacity of 2 * 2048 + 500 gives some threads a third lap, on a workspace whose every
+    byte is 0xA5: a slot left unpadded holds the key 0xA5A5A5A5, whose low bits sort it among the real ones."""
+    import voxproj_host as vh
+    s, want = _twin("room:3,96,64")
+    W, H = s[5], s[6]
+    stride = 256 * ((len(s[1]) + 255) // 256)
+    assert stride == 2048
+    runs = []
+    for spare in (0, 2 * stride + 500):
+        ws = vh.SplatWorkspace()
+        ws.ensure(64 << 20, DEV)
+        ws.buf.fill_(0xA5)
+        (tv, tf, tl), n = _project(s, ws)
+        ids, depth, labels = vh.mesh_rasterize(tf, tl, W, H, n + spare, ws)
+        runs.append(dict(face_ids=ids.cpu().numpy(), depth=depth.cpu().numpy(), labels=labels.cpu().numpy(),
+                         counters=want["counters"]))
+    for k in ("face_ids", "depth", "labels"):
+        assert runs[0][k].tobytes() == runs[1][k].tobytes(), k
+    _same(runs[1], want)
+
+
 def test_no_faces_draw_nothing():
     s = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros(0, np.uint8), np.eye(4, dtype=np.float32),
          ms.intrinsics(40, 20), 40, 20)

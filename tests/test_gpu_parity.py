@@ -398,6 +398,34 @@ def test_full_resolution_view_properties(oracle_mod):
     assert ((out_t.double().sum(0) - 2 * tot_px).abs() <= 2e-6 * tot_abs).all()
 
 
+def test_grid_with_more_cells_than_one_round_of_the_table_build(oracle_mod):
+    """k_build_cells runs min(ceil(cells / 256), 16 384) workgroups of 256 threads and strides by gridDim * 256: a thread reads
+    a second cell iff the grid has more than 16 384 * 256 = 4 194 304 cells (the 200k-voxel scene above has 3.96 M).  210 000
+    voxels in the default room are 81 x 204 x 255 = 4 213 620 cells; the 19 316 cells past the first round hold voxels of the
+    top layers, and a few hundred pixels of the two small views must hit them.
+    k_occ_compare_copy (the drop-in's check that a new tensor still holds the grid the tables were built from) runs at most
+    8192 workgroups the same way: those cells are its third lap.  A second call with a new tensor that differs in one of them
+    alone, a voxel the first call hit, must rebuild the tables and lose that voxel."""
+    import voxproj_host
+    s = make_scene(210000, 2, 64, 48, seed=3)
+    lap = 16384 * 256
+    assert lap < s.occ.size < lap + lap // 64 and lap == 2 * 8192 * 256
+    feats = make_features_np(2, 48, 64, 8, seed=3)[None]
+    case = (s.c2w, s.intr, s.opts(), s.grid_origin, s.voxel_size, s.n_vox + 1)
+    r, _, _ = _compare(oracle_mod, feats, s.occ[None], *case, expect_boxmiss=None)
+    builds = voxproj_host.table_builds(_last_ws())
+    tail = s.occ.reshape(-1)[lap:]
+    late = np.isin(r["hits"], tail[tail > 0])
+    assert late.sum() > 300
+    gone = int(np.bincount(r["hits"][late]).argmax())        # the voxel of the tail that most pixels hit
+    occ = s.occ.copy()
+    occ[occ == gone] = 0
+    assert (occ != s.occ).sum() == 1 and int(np.flatnonzero(occ.reshape(-1) != s.occ.reshape(-1))[0]) >= lap
+    r2, _, _ = _compare(oracle_mod, feats, occ[None], *case, expect_boxmiss=None)
+    assert voxproj_host.table_builds(_last_ws()) == builds + 1
+    assert not (r2["hits"] == gone).any() and (r["hits"] == gone).sum() >= 1
+
+
 def test_far_from_origin_disables_leaping_but_stays_exact(oracle_mod):
     # world coordinates ~1e6 voxel sizes from zero: fp32 positions are too coarse for the leap bound, the kernel
     # must fall back to evaluating every sample (leap_ok = false) and still match the oracle bit for bit

@@ -4,7 +4,7 @@ inside its derived bound, the three statistics inside the summed bounds.
 
 Shapes (photo_loss_reference.gpu_cases): W x H in {1x1, 5x7 (smaller than the window), 11x11, 32x32 and 33x32 (the kernel's
 tile and one column more), 37x21, 130x67 (5 x 3 tiles per channel: the ordered combine)}, all at C = 3 with the five input
-kinds; C = 1 and 4 at four of the sizes.  Every test here fails on a library without the three vp_photo_loss symbols."""
+kinds; C = 1 and 4 at four of the sizes; 530x490 at C = 4 (1088 tile triples, more than the sum stages at a time).  Every test here fails on a library without the three vp_photo_loss symbols."""
 import os
 import sys
 
@@ -91,8 +91,7 @@ def inside(name, got, want, bound, what):
     assert (err <= bound).all(), f"{what} {name}: {int((err > bound).sum())} elements outside their bound, worst {ratio:.3f}"
 
 
-@pytest.mark.parametrize("case", pref.gpu_cases(), ids=lambda c: "%s-C%d-%dx%d" % c[:4])
-def test_every_element_inside_its_bound(case):
+def every_element(case):
     x, y, ref, bnd = reference(case)
     out = run(x, y)
     what = "%s C=%d %dx%d" % case[:4]
@@ -108,6 +107,27 @@ def test_every_element_inside_its_bound(case):
         assert out["stats"][0] == 0 and out["stats"][1] == 0
         zero = run(x, y, lam=0.0)["grad"]
         assert not zero.any(), "x = y: the L1 part of the gradient is exactly 0 everywhere"
+    return x, y, ref, bnd, out
+
+
+@pytest.mark.parametrize("case", pref.gpu_cases(), ids=lambda c: "%s-C%d-%dx%d" % c[:4])
+def test_every_element_inside_its_bound(case):
+    every_element(case)
+
+
+def test_more_tiles_than_one_staging_of_the_sum():
+    """k_photo_loss_sum stages PHOTO_THREADS = 1024 tile triples at a time; there is one triple per 32 x 32 tile and channel:
+    a second staging iff C ceil(W / 32) ceil(H / 32) > 1024.  C = 4 at 530 x 490 has 4 x 17 x 16 = 1088 triples (both edges
+    ragged: 530 = 16 x 32 + 18, 490 = 15 x 32 + 10); the second staging holds the last 64: channel 3 from tile 4 of tile row
+    12 on.  On noise the tile rows 13..15 of that channel alone carry more than ten times the bound of each of the three sums."""
+    case = ("noise", 4, 530, 490, 1088)
+    assert case[1] * ((case[2] + 31) // 32) * ((case[3] + 31) // 32) == 1088
+    x, y, ref, bnd, out = every_element(case)
+    d = x[3, 13 * 32:].astype(np.float64) - y[3, 13 * 32:]
+    share = np.array([np.abs(d).sum(), np.square(d).sum(), abs(ref["m"][3, 13 * 32:].sum())])
+    assert (share > 10 * np.asarray(bnd["stats"])).all(), (share, bnd["stats"])
+    del _REF[(case, LAMBDA)]                                            # a million float64 elements per map: not kept
+    pref._SUMS.clear()
 
 
 BIG = ("noise", 3, 130, 67, 160)

@@ -73,8 +73,8 @@ def run(logits, samples, nbr, k, *, lanes=0, pad=0, ws=None, spare=0, optional=T
     return host
 
 
-def check(out, logits, samples, nbr, k, *, grad_loss=None, scale=SCALE, optional=True):
-    """Every output against the statement within its bound, element by element.  Returns the statement."""
+def check(out, logits, samples, nbr, k, *, grad_loss=None, scale=SCALE, optional=True, with_bounds=False):
+    """Every output against the statement within its bound, element by element.  Returns the statement (and the bounds)."""
     gl = 1.0 if grad_loss is None else float(np.float32(grad_loss))
     st = r3.statement64(logits, samples, nbr, k, scale=scale, grad_loss=gl)
     b = r3.bounds(logits, samples, nbr, k, scale=scale, grad_loss=gl)
@@ -95,7 +95,7 @@ def check(out, logits, samples, nbr, k, *, grad_loss=None, scale=SCALE, optional
         print(f"{name}: worst error / bound {worst:.4f} (largest error {float(err.max()) if err.size else 0.0:.3e})")
         assert (err <= bound).all(), f"{name} off by {worst:.3f} of its bound at {np.unravel_index(ratio.argmax(), ratio.shape)}"
     print(f"worst so far, of the bounds: {WORST}")
-    return st
+    return (st, b) if with_bounds else st
 
 
 def golden(i):
@@ -201,6 +201,34 @@ def test_sample_lists(kind):
         assert out["stats"].tolist() == [0.0, 0.0] and not out["grad"].any() and st["loss"] == 0.0
     if kind == "repeats":
         assert not out["sample_loss"][3]
+
+
+@pytest.mark.parametrize("S", [257, 65536 + 1 + 300])
+def test_sample_lists_longer_than_one_round_of_the_sum(S):
+    """k_kl_sum1 gives each of its KL_PARTS = 256 workgroups per = ceil(S / 256) consecutive sample losses, which its 256
+    threads walk with a stride of 256.  S <= 256: per = 1, one thread per workgroup has work.  S = 257: per = 2, so the
+    workgroups 0..128 share the list and the others are empty (lo = hi = S), the last one used holds one element.
+    S > 256 * 256 = 65 536: per > 256 and a thread takes a second lap; S = 65 837 gives per = 258, threads 0 and 1 of every
+    used workgroup add two losses.  The samples are drawn with repeats from the 300 points, so the per-row lists of the
+    gradient are long too."""
+    P, k = 16, 5
+    logits, full = cloud_case(P, k, 11)
+    N = len(logits)
+    per = (S + 255) // 256
+    assert (per == 2 and S - 128 * per == 1) if S < 1000 else (per > 256 and S % per not in (0, 1))
+    samples = np.random.default_rng(S).integers(0, N, S)
+    nbr = full[samples].reshape(S, k - 1).copy()
+    # the positions a thread reaches after its first: the second of a pair (S = 257), the second lap (S > 65 536)
+    later = np.concatenate([np.arange(lo + (256 if per > 256 else 1), min(lo + per, S)) for lo in range(0, S, per)])
+    if per > 256:                  # the float64 statement is a Python loop over the table: 15 of 16 first-lap rows name nobody
+        bare = np.ones(S, bool)
+        bare[::16] = False
+        bare[later] = False
+        nbr[bare] = -1
+    out = run(logits, samples, nbr, k, grad_loss=0.625)
+    st, b = check(out, logits, samples, nbr, k, grad_loss=0.625, with_bounds=True)
+    # what those positions add is far above the sum's bound
+    assert len(later) >= 128 and st["sample_loss"][later].sum() > 10 * b["sum"], (st["sample_loss"][later].sum(), b["sum"])
 
 
 def test_row_stride_recycled_workspace_and_two_runs():

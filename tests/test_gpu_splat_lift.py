@@ -300,6 +300,59 @@ def test_culled_nan_and_never_added_rows_keep_their_bits():
     assert changed.sum() >= 100 and (gw[changed] != prew[changed]).all()
 
 
+# k_splat_lift_reduce<CC> gives CC lanes to a Gaussian, 256 / CC Gaussians to a workgroup, and vp_splat_lift caps its grid at
+# 2048 workgroups: C <= 16 -> CC = 16, 16 Gaussians per workgroup, a second lap iff N > 2048 * 16 = 32 768; C > 16 -> CC = 64, 4
+# per workgroup, iff N > 2048 * 4 = 8 192.  N = 8 200 and 32 800 are the least ragged sizes past the caps (8 and 32 Gaussians in
+# the second lap); 8 612 and 33 188 put 420 there, in 105 and 27 workgroups.
+REDUCE_LAPS = [(8200, 24, 8192), (32800, 8, 32768), (8612, 24, 8192), (33188, 8, 32768)]
+
+
+def reduce_lap_scene(N, lap):
+    """N Gaussians of which the first 300 and those from index ``lap`` on are in view, the latter in the middle of the image
+    and not faint; every other one, and every fourth from ``lap`` on, lies behind the camera.  (scene, the indices >= lap)"""
+    s = scene(N, 1, N)
+    rng = np.random.default_rng(N + 1)
+    tail = np.arange(lap, N)
+    z = rng.uniform(1.5, 3.5, len(tail))
+    s["means"][tail] = np.stack([rng.uniform(-0.4, 0.4, len(tail)) * z, rng.uniform(-0.3, 0.3, len(tail)) * z, z], 1)
+    s["opacities"][tail] = rng.uniform(0.3, 0.9, len(tail))
+    gone = np.ones(N, bool)
+    gone[:300] = False
+    gone[tail[tail % 4 != 2]] = False
+    s["means"][gone] = (0.0, 0.0, -2.0)
+    return s, tail
+
+
+@pytest.mark.parametrize("N,C,lap", REDUCE_LAPS, ids=[f"N{n}-C{c}" for n, c, _ in REDUCE_LAPS])
+def test_more_gaussians_than_one_round_of_the_reduce(N, C, lap):
+    """The Gaussians in view are the first 300 and those from the cap on; the rest, and every fourth past the cap, lie behind
+    the camera (the float64 reference drops them at once).  From zero the sums meet the module's bounds; on top of random rows
+    every row that nothing was added to keeps its bits and every other is the fp32 sum of its old value and the same addend."""
+    assert lap == 2048 * (256 // (16 if C <= 16 else 64)) and N > lap
+    W, H = 61, 47
+    s, tail = reduce_lap_scene(N, lap)
+    vm, K = camera(W, H)
+    feats, m = make_map(W, H, C, N), safe_weight(s, vm, K, W, H)
+    got = run_lift(s, vm, K, W, H, feats, m)
+    r = compare(s, vm, K, W, H, feats, m, got[0], got[1])
+    above = (r["added"][lap:] > 0).sum()
+    assert above >= (N - lap) // 2 and (r["added"][:300] > 0).sum() >= 150, (above, N - lap)
+    assert (np.abs(r["sum"][lap:]).sum(axis=1) > 0).sum() == above
+    keep = r["added"] == 0
+    assert keep[tail[tail % 4 == 2]].all() and keep[300:lap].all()
+    rng = np.random.default_rng(C)
+    pre, prew = rng.normal(size=(N, C)).astype(np.float32), rng.normal(size=N).astype(np.float32)
+    pre[:, ::5], prew[::2] = -0.0, -0.0
+    pt, pwt = torch.from_numpy(pre).to(DEV), torch.from_numpy(prew).to(DEV)
+    two = run_lift(s, vm, K, W, H, feats, m, sum_=pt.clone(), wsum=pwt.clone())
+    gs, gw = two[0].cpu().numpy(), two[1].cpu().numpy()
+    assert gs[keep].tobytes() == pre[keep].tobytes() and gw[keep].tobytes() == prew[keep].tobytes()
+    live = torch.from_numpy(~keep).to(DEV)
+    zero_s, zero_w = got[0] == 0, got[1] == 0                 # an addend of exactly 0 is not added: a -0 stays a -0
+    assert torch.equal(torch.where(zero_s, pt, pt + got[0])[live], two[0][live])
+    assert torch.equal(torch.where(zero_w, pwt, pwt + got[1])[live], two[1][live])
+
+
 def test_two_views_accumulate():
     W, H = 61, 47
     s = scene(400, 1, 15)

@@ -74,6 +74,38 @@ def test_five_thousand_points_two_runs_and_a_recycled_workspace():
     assert all(torch.equal(a[k], b[k]) for k in ("centers", "colors", "counts", "voxel_index", "point_voxel"))
 
 
+def test_seventy_thousand_points_take_the_min_reduction_round_twice():
+    """k_grid_min_part runs min(ceil(N / 256), GRID_PARTS = 256) workgroups of 256 lanes and strides by gridDim * 256: a lane
+    takes a second point iff N > 256 * 256 = 65 536.  N = 70 001: the points 65 536.. are second-lap points (the last workgroup
+    to get one is 17, its lanes 113.. get none).  The minimum of every axis is attained by one second-lap point alone, a
+    different one per axis; first-lap points below those minima are not kept; the sort and the scan see 70 001 keys."""
+    import voxproj_host
+    N, LAP = 70001, 256 * 256
+    rng = np.random.default_rng(9)
+    p = np.clip(rng.normal(size=(N, 3)) * 0.5, -2.0, 2.0).astype(np.float32)
+    c = rng.integers(0, 256, (N, 3)).astype(np.uint8)
+    lows = {LAP + 7: (0, -3.25), 68000: (1, -3.5), N - 1: (2, -2.75)}
+    for i, (axis, v) in lows.items():
+        p[i, axis] = v
+    keep = (rng.uniform(size=N) < 0.9).astype(np.uint8)
+    keep[LAP:] = 1
+    dropped = np.flatnonzero(keep[:LAP] == 0)[:50]
+    p[dropped] = rng.uniform(-6.0, -4.0, (50, 3)).astype(np.float32)   # below every kept point: the mask decides the corner
+    assert (keep[:LAP] == 0).sum() > 5000
+    ws = voxproj_host.SplatWorkspace()
+    got = check(p, c, 0.05, keep=keep, workspace=ws)
+    assert got["min_corner"].tolist() == [-3.25, -3.5, -2.75] and 20000 < got["centers"].shape[0] < N
+    assert int(got["counts"].sum()) == int(keep.sum()) and (got["point_voxel"][LAP:] >= 0).all()
+    # the status word: one non-finite kept point in the second lap refuses the call; not kept, it is a point like any dropped one
+    bad = p.copy()
+    bad[66000, 1] = np.nan
+    check(bad, c, 0.05, keep=keep, workspace=ws)
+    off = keep.copy()
+    off[66000] = 0
+    check(bad, c, 0.05, keep=off, workspace=ws)
+    check(p, c, 0.05, workspace=ws)                                     # and without a mask: the dropped points set the corner
+
+
 def test_status_cases_leave_the_next_call_alone():
     import voxproj_host
     ws = voxproj_host.SplatWorkspace()
