@@ -28,7 +28,8 @@
 //
 // One translation unit: this file holds the host side (launch plumbing, C-ABI entry points) and includes
 //   vp_plan.h    the split plan of a projector call and the part slots, as pure host arithmetic (plan_split)
-//   vp_common.h  error text, timing spans, VP_FLAG_PIPELINE stream state, Params, workspace Layout
+//   vp_common.h  error text, timing spans, compile-time dispatch (with_step, with_flags), VP_FLAG_PIPELINE stream state, Params, workspace Layout
+//   vp_reduce.h  the fixed-order float64 sums of the loss families (block_tree_sum, k_ordered_sum) and the lane butterflies
 //   vp_tables.h  arithmetic contract helpers, occupancy-derived tables, view table
 //   vp_march.h   phase 1 (k_first_hit)
 //   vp_gather.h  work list and phase 2 (k_worklist; k_gather, k_gather_one: one wavefront per voxel or per part of a split voxel; k_combine_parts)
@@ -77,6 +78,7 @@
 
 #include "vp_plan.h"
 #include "vp_common.h"
+#include "vp_reduce.h"
 #include "vp_tables.h"
 #include "vp_march.h"
 #include "vp_gather.h"
@@ -424,17 +426,17 @@ static int splat_forward_impl(const float *features, int D, int64_t row_stride, 
     const long long *total = (const long long *)(ws + l.total);
     if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
     const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-    splat_with_dt(D, [&](auto dt) {
-        splat_with_flag(ls != nullptr, [&](auto loss) {
-            hipLaunchKernelGGL((k_splat_blend<decltype(dt)::value, decltype(loss)::value>), grid, block, 0, stream,
+    with_step<8, 16, 32, 64>(D, [&](auto dt) {
+        with_flags([&](auto loss) {
+            hipLaunchKernelGGL((k_splat_blend<dt.value, loss.value>), grid, block, 0, stream,
                                (const SplatRec *)(ws + l.rec), (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges),
                                total, (long long)capacity, features, D, (long long)row_stride, W, H, (int *)labels, confidence,
                                alpha, logits, ls ? *ls : SplatLoss{});
-        });
+        }, ls != nullptr);
     });
     VP_HIP(hipGetLastError());
     if (ls) {
-        hipLaunchKernelGGL(k_splat_loss_sum, dim3(1), block, 0, stream, (const double2 *)ls->tile_sums,
+        hipLaunchKernelGGL((k_ordered_sum<2, SPLAT_THREADS>), dim3(1), block, 0, stream, (const double *)ls->tile_sums,
                            (long long)l.tiles_x * l.tiles_y, total, (long long)capacity, loss_stats);
         VP_HIP(hipGetLastError());
     }
@@ -514,27 +516,24 @@ static int splat_backward_impl(const SplatBackward &a)
     const long long *offs = (const long long *)(ws + l.offs);
     float *part = (float *)a.bwd_workspace;
     const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-    splat_with_dt(D, [&](auto dt) {
-        splat_with_flag(a.geom, [&](auto geom) {
-            splat_with_flag(a.loss, [&](auto loss) {
-                hipLaunchKernelGGL((k_splat_blend_backward<decltype(dt)::value, decltype(geom)::value, decltype(loss)::value>),
-                                   grid, block, 0, stream, (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), count,
-                                   offs, (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges), total,
-                                   (long long)capacity, a.features, D, (long long)a.row_stride, a.W, a.H, a.logits,
-                                   a.grad_alpha, part, a.ls);
-            });
-        });
+    with_step<8, 16, 32, 64>(D, [&](auto dt) {
+        with_flags([&](auto geom, auto loss) {
+            hipLaunchKernelGGL((k_splat_blend_backward<dt.value, geom.value, loss.value>), grid, block, 0, stream,
+                               (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), count, offs,
+                               (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges), total, (long long)capacity,
+                               a.features, D, (long long)a.row_stride, a.W, a.H, a.logits, a.grad_alpha, part, a.ls);
+        }, a.geom, a.loss);
     });
     VP_HIP(hipGetLastError());
     // grid-stride over the Gaussians, at most one resident round (2048 workgroups of 4 wavefronts: 32 per CU on 256 CUs)
     const int gs = splat_reduce_group(a.geom ? D + SPLAT_SCREEN : D);
     const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / gs - 1) / (256 / gs), 2048LL);
-    splat_with_group(gs, [&](auto group) {
-        splat_with_flag(a.geom, [&](auto geom) {
-            hipLaunchKernelGGL((k_splat_grad_reduce<decltype(group)::value, decltype(geom)::value>), dim3(g_red), dim3(256), 0,
-                               stream, count, offs, (long long)n_gaussians, total, (long long)capacity, part, D,
-                               a.grad_features, a.grad_opacities, a.grad_screen, (int *)a.status);
-        });
+    with_step<16, 32, 64>(gs, [&](auto group) {
+        with_flags([&](auto geom) {
+            hipLaunchKernelGGL((k_splat_grad_reduce<group.value, geom.value>), dim3(g_red), dim3(256), 0, stream, count, offs,
+                               (long long)n_gaussians, total, (long long)capacity, part, D, a.grad_features, a.grad_opacities,
+                               a.grad_screen, (int *)a.status);
+        }, a.geom);
     });
     VP_HIP(hipGetLastError());
     if (a.chain) {
@@ -666,24 +665,22 @@ int vp_splat_lift(const void *feats_f16, int C, int64_t pix_stride, const float 
     float *part = (float *)lift_workspace, *wpart = (float *)((char *)lift_workspace + lift_part_bytes(capacity, C));
     const bool vec = C % 8 == 0 && pix_stride % 8 == 0 && ((uintptr_t)feats_f16 & 15) == 0;
     const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-    splat_with_flag(C > 16, [&](auto wide) {
-        constexpr int CC = decltype(wide)::value ? 64 : 16;
-        static_assert(lift_chunk(decltype(wide)::value ? 17 : 16) == CC, "the pass width is lift_chunk's");
+    with_flags([&](auto wide, auto v) {
+        constexpr int CC = wide.value ? 64 : 16;
+        static_assert(lift_chunk(wide.value ? 17 : 16) == CC, "the pass width is lift_chunk's");
         // grid-stride over the Gaussians, at most one resident round (as the backward's reduce)
         const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / CC - 1) / (256 / CC), 2048LL);
         for (int c0 = 0; c0 < C; c0 += CC) {
             float *wp = c0 == 0 && wsum ? wpart : nullptr;
-            splat_with_flag(vec, [&](auto v) {
-                hipLaunchKernelGGL((k_splat_lift<CC, decltype(v)::value>), grid, block, 0, stream,
-                                   (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), count, offs,
-                                   (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges), total, (long long)capacity,
-                                   feats, C, (long long)pix_stride, c0, pixel_weight, W, H, part, wp);
-            });
+            hipLaunchKernelGGL((k_splat_lift<CC, v.value>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec),
+                               (const int4 *)(ws + l.box), count, offs, (const int *)(ws + l.vals1),
+                               (const longlong2 *)(ws + l.ranges), total, (long long)capacity, feats, C, (long long)pix_stride, c0,
+                               pixel_weight, W, H, part, wp);
             hipLaunchKernelGGL((k_splat_lift_reduce<CC>), dim3(g_red), dim3(256), 0, stream, count, offs,
                                (long long)n_gaussians, total, (long long)capacity, (const float *)part, (const float *)wp,
                                std::min(CC, C - c0), c0, sum, (long long)sum_stride, wsum, (int *)status);
         }
-    });
+    }, C > 16, vec);
     VP_HIP(hipGetLastError());
     return VP_OK;
 }
@@ -715,24 +712,18 @@ int vp_splat_render(const void *rows, int rows_is_f16, int C, int64_t row_stride
     const bool vec = C % epl == 0 && row_stride % epl == 0 && ((uintptr_t)rows & 15) == 0;
     const int CC = render_chunk(C);
     const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
-    auto launch = [&](auto nt) {
-        splat_with_flag(!rows_is_f16, [&](auto f32) {
-            splat_with_flag(vec, [&](auto v) {
-                splat_with_flag(out_is_f16 != 0, [&](auto o16) {
-                    for (int c0 = 0; c0 < C; c0 += CC)
-                        hipLaunchKernelGGL(
-                            (k_splat_render<decltype(nt)::value, decltype(f32)::value, decltype(v)::value, decltype(o16)::value>),
-                            grid, block, 0, stream, (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box),
-                            (const int *)(ws + l.count), (const long long *)(ws + l.offs), (const int *)(ws + l.vals1),
-                            (const longlong2 *)(ws + l.ranges), (const long long *)(ws + l.total), (long long)capacity, rows, C,
-                            (long long)row_stride, c0, W, H, out, (long long)pix_stride, c0 == 0 ? alpha : nullptr,
-                            (int *)status);
-                });
-            });
-        });
-    };
-    if (CC == 16) launch(std::integral_constant<int, 1>{});
-    else launch(std::integral_constant<int, 4>{});
+    // 16-channel tiles of a pass: 1 or 4
+    with_step<1, 4>(CC / 16, [&](auto nt) {
+        with_flags([&](auto f32, auto v, auto o16) {
+            for (int c0 = 0; c0 < C; c0 += CC)
+                hipLaunchKernelGGL((k_splat_render<nt.value, f32.value, v.value, o16.value>), grid, block, 0, stream,
+                                   (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), (const int *)(ws + l.count),
+                                   (const long long *)(ws + l.offs), (const int *)(ws + l.vals1),
+                                   (const longlong2 *)(ws + l.ranges), (const long long *)(ws + l.total), (long long)capacity,
+                                   rows, C, (long long)row_stride, c0, W, H, out, (long long)pix_stride,
+                                   c0 == 0 ? alpha : nullptr, (int *)status);
+        }, !rows_is_f16, vec, out_is_f16 != 0);
+    });
     VP_HIP(hipGetLastError());
     return VP_OK;
 }
@@ -1141,20 +1132,15 @@ int vp_feature_loss(const void *image, int image_is_f16, int64_t pix_stride, con
     float4 *coef = (float4 *)(ws + FLOSS_HEADER + floss_sums_bytes(n));
     VP_HIP(hipMemsetAsync(ws, 0, FLOSS_HEADER, stream));
     const bool vec = floss_vec(image, image_is_f16, pix_stride, target_f16, tgt_stride, C);
-    floss_with_nch(C, [&](auto nch) {
-        splat_with_flag(vec, [&](auto v) {
-            splat_with_flag(image_is_f16 != 0, [&](auto f16) {
-                splat_with_flag(kind == VP_FEATURE_LOSS_COSINE, [&](auto cosine) {
-                    hipLaunchKernelGGL(
-                        (k_feature_loss<decltype(nch)::value, decltype(v)::value, decltype(f16)::value, decltype(cosine)::value>),
-                        dim3((unsigned)blocks), dim3(FLOSS_THREADS), 0, stream, image, (long long)pix_stride,
-                        (const _Float16 *)target_f16, (long long)tgt_stride, C, n, pixel_weight, alpha, min_alpha, coef, sums,
-                        max_bits, pixel_loss);
-                });
-            });
-        });
+    with_step<1, 2, 4, 8>(floss_nch(C), [&](auto nch) {
+        with_flags([&](auto v, auto f16, auto cosine) {
+            hipLaunchKernelGGL((k_feature_loss<nch.value, v.value, f16.value, cosine.value>), dim3((unsigned)blocks),
+                               dim3(FLOSS_THREADS), 0, stream, image, (long long)pix_stride, (const _Float16 *)target_f16,
+                               (long long)tgt_stride, C, n, pixel_weight, alpha, min_alpha, coef, sums, max_bits, pixel_loss);
+        }, vec, image_is_f16 != 0, kind == VP_FEATURE_LOSS_COSINE);
     });
-    hipLaunchKernelGGL(k_feature_loss_sum, dim3(1), dim3(FLOSS_THREADS), 0, stream, (const double2 *)sums, blocks, loss_stats);
+    hipLaunchKernelGGL((k_ordered_sum<2, FLOSS_THREADS>), dim3(1), dim3(FLOSS_THREADS), 0, stream, (const double *)sums, blocks,
+                       (const long long *)nullptr, 0LL, loss_stats);
     VP_HIP(hipGetLastError());
     return VP_OK;
 }
@@ -1176,16 +1162,14 @@ int vp_feature_loss_gradient(const void *image, int image_is_f16, int64_t pix_st
     const float4 *coef = (const float4 *)(ws + FLOSS_HEADER + floss_sums_bytes(n));
     const bool vec = floss_vec(image, image_is_f16, pix_stride, target_f16, tgt_stride, C) && grad_stride % 8 == 0 &&
                      ((uintptr_t)grad_f16 & 15) == 0;
-    floss_with_nch(C, [&](auto nch) {
-        splat_with_flag(vec, [&](auto v) {
-            splat_with_flag(image_is_f16 != 0, [&](auto f16) {
-                hipLaunchKernelGGL((k_feature_loss_gradient<decltype(nch)::value, decltype(v)::value, decltype(f16)::value>),
-                                   dim3((unsigned)blocks), dim3(FLOSS_THREADS), 0, stream, image, (long long)pix_stride,
-                                   (const _Float16 *)target_f16, (long long)tgt_stride, C, n, coef, (const unsigned *)ws, loss_stats,
-                                   (int)(reduction == VP_LOSS_MEAN), grad_loss, (_Float16 *)grad_f16, (long long)grad_stride,
-                                   (int *)grad_exponent);
-            });
-        });
+    with_step<1, 2, 4, 8>(floss_nch(C), [&](auto nch) {
+        with_flags([&](auto v, auto f16) {
+            hipLaunchKernelGGL((k_feature_loss_gradient<nch.value, v.value, f16.value>), dim3((unsigned)blocks),
+                               dim3(FLOSS_THREADS), 0, stream, image, (long long)pix_stride, (const _Float16 *)target_f16,
+                               (long long)tgt_stride, C, n, coef, (const unsigned *)ws, loss_stats,
+                               (int)(reduction == VP_LOSS_MEAN), grad_loss, (_Float16 *)grad_f16, (long long)grad_stride,
+                               (int *)grad_exponent);
+        }, vec, image_is_f16 != 0);
     });
     VP_HIP(hipGetLastError());
     return VP_OK;
@@ -1225,7 +1209,7 @@ int vp_proto_contrast(const float *image, int D, int W, int H, const int32_t *id
     const ProtoWs w = proto_carve(workspace, D, n);
     const size_t lds = (size_t)PROTO_IDS * D * sizeof(float);
     hipError_t attr_rc = hipSuccess;
-    proto_with_dp(D, [&](auto dp) {
+    with_step<16, 32, 64>(D, [&](auto dp) {
         constexpr int DP = decltype(dp)::value;
         // with the static tiles the two accumulating kernels pass 64 KiB of the CU's 160 at large D: said once per variant
         static hipError_t lds_attr = [] {
@@ -1272,7 +1256,7 @@ int vp_proto_contrast_gradient(const float *image, int D, int W, int H, const in
     hipStream_t stream = (hipStream_t)stream_;
     const long long n = (long long)W * H;
     const ProtoWs w = proto_carve(workspace, D, n);
-    proto_with_dp(D, [&](auto dp) {
+    with_step<16, 32, 64>(D, [&](auto dp) {
         constexpr int DP = decltype(dp)::value;
         hipLaunchKernelGGL(k_proto_gradient<DP>, dim3((unsigned)proto_tiles(n)), dim3(PROTO_THREADS), 0, stream, image, D, n, ids,
                            count, (const ProtoHeader *)w.hdr, (const int *)w.slot_of_id, (const float *)w.utab,
@@ -1316,8 +1300,8 @@ int vp_photo_loss(const float *image, const float *target, int C, int W, int H, 
         double *sums = (double *)((char *)workspace + photo_maps_bytes(C, W, H));
         hipLaunchKernelGGL(k_photo_loss<false>, dim3((unsigned)photo_tiles_x(W), (unsigned)photo_tiles_x(H), (unsigned)C),
                            dim3(PHOTO_THREADS), 0, stream, image, target, C, W, H, ssim_map, maps, sums, loss_stats);
-        hipLaunchKernelGGL(k_photo_loss_sum, dim3(1), dim3(PHOTO_THREADS), 0, stream, (const double *)sums, photo_tiles(C, W, H),
-                           loss_stats);
+        hipLaunchKernelGGL((k_ordered_sum<3, PHOTO_THREADS>), dim3(1), dim3(PHOTO_THREADS), 0, stream, (const double *)sums,
+                           photo_tiles(C, W, H), (const long long *)nullptr, 0LL, loss_stats);
     }
     VP_HIP(hipGetLastError());
     return VP_OK;
@@ -1800,7 +1784,7 @@ int vp_codebook_assoc(const float *image, int D, int W, int H, const int32_t *id
     const CbPlan plan = cb_plan(W, H);
     const CbWs w = cb_carve(workspace, D, K, plan.G);
     hipError_t attr_rc = hipSuccess;
-    cb_with_dp(D, [&](auto dp) {
+    with_step<16, 32, 64>(D, [&](auto dp) {
         constexpr int DP = decltype(dp)::value;
         // code book and probability tile pass 64 KiB of the CU's 160: said once per variant
         static hipError_t lds_attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_codebook_assoc<DP>),
@@ -1831,7 +1815,7 @@ int vp_codebook_loss(const float *image, int D, int W, int H, const int32_t *ids
     const CbPlan plan = cb_plan(W, H);
     const CbWs w = cb_carve(workspace, D, K, plan.G);
     hipError_t attr_rc = hipSuccess;
-    cb_with_dp(D, [&](auto dp) {
+    with_step<16, 32, 64>(D, [&](auto dp) {
         constexpr int DP = decltype(dp)::value;
         static hipError_t lds_attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_codebook_loss<DP>),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)cb_loss_lds(DP, CB_MAX_K));
@@ -1918,7 +1902,7 @@ int vp_neighbor_kl(const float *logits, int64_t N, int P, int64_t row_stride, co
     float *sl = sample_loss ? sample_loss : (float *)workspace;
     double *part = (double *)((char *)workspace + align256((size_t)std::max<int64_t>(S, 1) * sizeof(float)));
     const int per = KL_THREADS / G;
-    kl_with_cpl(P, G, [&](auto cpl) {
+    with_step<1, 2, 4>(kl_cpl(P, G), [&](auto cpl) {
         constexpr int CPL = decltype(cpl)::value;
         hipLaunchKernelGGL(k_kl_lse<CPL>, dim3((unsigned)((N + per - 1) / per)), dim3(KL_THREADS), 0, stream, logits,
                            (long long)row_stride, (long long)N, P, G, row_lse);
@@ -1947,7 +1931,7 @@ int vp_neighbor_kl_gradient(const float *logits, int64_t N, int P, int64_t row_s
     if (!std::isfinite(scale)) return fail(VP_EINVAL, "scale = %g must be finite", scale);
     const double coef = S > 0 ? scale / ((double)S * (double)k * (double)P) : 0.0;
     const int per = KL_THREADS / G;
-    kl_with_cpl(P, G, [&](auto cpl) {
+    with_step<1, 2, 4>(kl_cpl(P, G), [&](auto cpl) {
         constexpr int CPL = decltype(cpl)::value;
         hipLaunchKernelGGL(k_kl_gradient<CPL>, dim3((unsigned)((N + per - 1) / per)), dim3(KL_THREADS), 0, (hipStream_t)stream_,
                            logits, (long long)row_stride, (long long)N, P, G, (const int *)samples, (long long)S,

@@ -179,8 +179,7 @@ __device__ __forceinline__ void cb_softmax(cb_f4 (&acc)[16], int K, int ntile, i
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) sum[i] += __shfl_xor(sum[i], o);
+        sum[i] = lanes_sum_up<16>(sum[i]);
         const float inv = 1.0f / sum[i];
 #pragma unroll
         for (int t = 0; t < 16; ++t)
@@ -189,20 +188,6 @@ __device__ __forceinline__ void cb_softmax(cb_f4 (&acc)[16], int K, int ntile, i
 }
 
 __device__ __forceinline__ bool cb_valid(int id, int ignore_id) { return id >= 0 && id < CB_IDS && id != ignore_id; }
-
-// the workgroup's float64 sum by a fixed halving tree; every thread returns it
-__device__ __forceinline__ double cb_block_sum(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int h = CB_THREADS / 2; h >= 1; h /= 2) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 template <int DP>
 __global__ __launch_bounds__(CB_THREADS) void k_codebook_assoc(const float *__restrict__ image, int D, long long n,
@@ -465,8 +450,10 @@ __global__ __launch_bounds__(CB_THREADS) void k_codebook_loss(const float *__res
                     gclu_part[(b * K + k) * D + c] = gk[tt][cc][i];
                 }
             }
-    const double s0 = cb_block_sum(ce_sum, s_red), s1 = cb_block_sum(dist_sum, s_red);
-    const double s2 = cb_block_sum((double)n_part, s_red), s3 = cb_block_sum((double)n_mis, s_red);   // integers: exact
+    // four trees of one value on one buffer, not one tree of four: the kernel's LDS stays what it was
+    const double s0 = block_tree_sum<CB_THREADS>(ce_sum, s_red), s1 = block_tree_sum<CB_THREADS>(dist_sum, s_red);
+    const double s2 = block_tree_sum<CB_THREADS>((double)n_part, s_red);                      // integers: exact
+    const double s3 = block_tree_sum<CB_THREADS>((double)n_mis, s_red);
     if (tid == 0) {
         dpart[b * 4 + 0] = s0;
         dpart[b * 4 + 1] = s1;
@@ -501,11 +488,4 @@ __global__ __launch_bounds__(CB_THREADS) void k_codebook_finish(int KD, int G, c
     }
     grad_cls[e] = (float)s;
     grad_cluster[e] = (float)t;
-}
-
-template <typename F> inline void cb_with_dp(int D, F &&f)
-{
-    if (D <= 16) f(std::integral_constant<int, 16>{});
-    else if (D <= 32) f(std::integral_constant<int, 32>{});
-    else f(std::integral_constant<int, 64>{});
 }

@@ -1,6 +1,6 @@
 // vp_common.h -- host-side plumbing shared by every part of libvoxproj: error text, HIP call checking, optional
-// per-kernel timing (HIP events), the per-workspace state record (streams/events of VP_FLAG_PIPELINE, table shape, options), kernel parameters and
-// the workspace layout.  Included by voxproj.hip only (one translation unit), behind vp_plan.h.
+// per-kernel timing (HIP events), the compile-time dispatch helpers (with_step, with_flags), the per-workspace state record
+// (streams/events of VP_FLAG_PIPELINE, table shape, options), kernel parameters and the workspace layout. Included by voxproj.hip only (one translation unit), behind vp_plan.h.
 #pragma once
 
 namespace {
@@ -23,6 +23,26 @@ int fail(int code, const char *fmt, ...)
             return fail(VP_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_),   \
                         __FILE__, __LINE__);                                              \
     } while (0)
+
+// ------------------------------------------------------------------------------------------------
+// Run-time values as template arguments of a kernel: the dispatcher names the choices, f launches.
+// ------------------------------------------------------------------------------------------------
+// with_step<8, 16, 32, 64>(v, f) calls f with the first listed constant >= v as a std::integral_constant, with the last one
+// when there is none
+template <int S0, int... S, class F> inline void with_step(int v, F &&f)
+{
+    if constexpr (sizeof...(S) == 0) f(std::integral_constant<int, S0>{});
+    else if (v <= S0) f(std::integral_constant<int, S0>{});
+    else with_step<S...>(v, f);
+}
+
+// with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...)
+template <class F> inline void with_flags(F &&f) { f(); }
+template <class F, class... B> inline void with_flags(F &&f, bool flag, B... rest)
+{
+    if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 
 // ------------------------------------------------------------------------------------------------
 // optional per-kernel timing (HIP events on the launch stream)

@@ -6,11 +6,11 @@
 //                            binary16), sums a = sum o^2, b = sum t^2, d = sum o t (or sum (o - t)^2) over its channels in
 //                            ascending order, the wavefront adds the 64 lane sums in a butterfly (every lane ends with the same
 //                            bits), and a second pass over the registers takes max_c |A t_c + B o_c|.  Lane i keeps pixel i's
-//                            results, so the per-pixel outputs are written coalesced; {m l, m} go through a float64 halving
-//                            tree over the workgroup's 256 pixels to one pair per workgroup; the largest m max_c |...| of a
-//                            wavefront goes to the map's maximum with one integer atomic max (non-negative floats order like
-//                            their bit patterns; a maximum does not depend on the order of arrival).
-//   k_feature_loss_sum       one workgroup: the pairs in ascending workgroup index (k_splat_loss_sum's rule).
+//                            results, so the per-pixel outputs are written coalesced; {m l, m} go through the tree and the
+//                            ordered sum of vp_reduce.h: slot t of workgroup b is pixel 256 b + t, one pair per workgroup; the
+//                            largest m max_c |...| of a wavefront goes to the map's maximum with one integer atomic max
+//                            (non-negative floats order like their bit patterns; a maximum does not depend on the order of
+//                            arrival).
 //   k_feature_loss_gradient  the same lane layout.  Every thread derives s and the exponent k from loss_stats, grad_loss and
 //                            the map's maximum; a pixel reads its {m, A, B} and writes f16((s m) (A t_c + B o_c) 2^k).
 //
@@ -69,27 +69,13 @@ template <> struct FlossRow8<false> {
     }
 };
 
-__device__ __forceinline__ float floss_wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);           // a + b = b + a: every lane ends with the same bits
-    return v;
-}
-
-__device__ __forceinline__ float floss_wave_max(float v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
-    return v;
-}
-
 template <int NCH, bool VEC, bool F16, bool COS>
 __global__ __launch_bounds__(FLOSS_THREADS) void k_feature_loss(
     const void *__restrict__ image, long long pix_stride, const _Float16 *__restrict__ target, long long tgt_stride, int C,
     long long n, const float *__restrict__ weight, const float *__restrict__ alpha, float min_alpha, float4 *__restrict__ coef,
     double2 *__restrict__ block_sums, unsigned *max_bits, float *__restrict__ pixel_loss)
 {
-    __shared__ double2 s_sum[FLOSS_THREADS];
+    __shared__ double s_red[2 * FLOSS_THREADS];
     const int tid = threadIdx.x, lane = tid & 63;
     const long long p_mine = (long long)blockIdx.x * FLOSS_THREADS + tid;
     // lane i of a wavefront owns pixel i of the wavefront's 64: its weight here, its results below
@@ -132,12 +118,12 @@ __global__ __launch_bounds__(FLOSS_THREADS) void k_feature_loss(
                     a += df * df;
                 }
             }
-        a = floss_wave_sum(a);
+        a = lanes_sum_up<64>(a);
         float l, A, B;
         bool valid = true;
         if constexpr (COS) {
-            b = floss_wave_sum(b);
-            d = floss_wave_sum(d);
+            b = lanes_sum_up<64>(b);
+            d = lanes_sum_up<64>(d);
             valid = a > 0.0f && b > 0.0f;                             // false for a NaN sum as well
             const float nn = sqrtf(a) * sqrtf(b);
             const float cs = d / nn;
@@ -155,7 +141,7 @@ __global__ __launch_bounds__(FLOSS_THREADS) void k_feature_loss(
             for (int j = 0; j < NCH; ++j)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(A * t[j].get(e) + B * o[j].get(e)));
-            mx = floss_wave_max(mx) * m;
+            mx = lanes_max<64>(mx) * m;
         }
         if (lane == i) {
             if (valid) { l_mine = l; A_mine = A; B_mine = B; mx_mine = mx; }
@@ -167,45 +153,11 @@ __global__ __launch_bounds__(FLOSS_THREADS) void k_feature_loss(
         coef[p_mine] = make_float4(m_mine, A_mine, B_mine, mx_mine);
         if (pixel_loss) pixel_loss[p_mine] = wl;
     }
-    const float wmax = floss_wave_max(mx_mine);
+    const float wmax = lanes_max<64>(mx_mine);
     if (lane == 0 && wmax > 0.0f) atomicMax(max_bits, __float_as_uint(wmax));
-    // the workgroup's pair in float64: a fixed halving tree over its 256 pixels
-    s_sum[tid] = make_double2((double)wl, (double)m_mine);
-    __syncthreads();
-    for (int h = FLOSS_THREADS / 2; h >= 1; h /= 2) {
-        if (tid < h) {
-            const double2 x = s_sum[tid], y = s_sum[tid + h];
-            s_sum[tid] = make_double2(x.x + y.x, x.y + y.y);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) block_sums[blockIdx.x] = s_sum[0];
-}
-
-// loss_stats = the workgroup pairs summed in float64 in ascending workgroup index.  One workgroup: its threads stage 256
-// pairs at a time in LDS, thread 0 adds them in order.
-__global__ __launch_bounds__(FLOSS_THREADS) void k_feature_loss_sum(const double2 *__restrict__ block_sums, long long n_blocks,
-                                                                     double *__restrict__ loss_stats)
-{
-    __shared__ double2 s_sum[FLOSS_THREADS];
-    const int tid = threadIdx.x;
-    double2 a = make_double2(0.0, 0.0);
-    for (long long b0 = 0; b0 < n_blocks; b0 += FLOSS_THREADS) {
-        const int nb = (int)(n_blocks - b0 < FLOSS_THREADS ? n_blocks - b0 : FLOSS_THREADS);
-        __syncthreads();
-        if (tid < nb) s_sum[tid] = block_sums[b0 + tid];
-        __syncthreads();
-        if (tid == 0)
-#pragma unroll 8
-            for (int k = 0; k < nb; ++k) {
-                a.x += s_sum[k].x;
-                a.y += s_sum[k].y;
-            }
-    }
-    if (tid == 0) {
-        loss_stats[0] = a.x;
-        loss_stats[1] = a.y;
-    }
+    double sums[2] = {(double)wl, (double)m_mine};
+    block_tree_sum<FLOSS_THREADS>(sums, s_red);
+    if (tid == 0) block_sums[blockIdx.x] = make_double2(sums[0], sums[1]);
 }
 
 template <int NCH, bool VEC, bool F16>
@@ -285,14 +237,3 @@ __global__ __launch_bounds__(FLOSS_THREADS) void k_feature_loss_gradient(
 
 // chunks of 512 channels a wavefront holds per row: 1, 2, 4 or 8
 static inline int floss_nch(int C) { return C <= 512 ? 1 : C <= 1024 ? 2 : C <= 2048 ? 4 : 8; }
-
-// the call with NCH as a compile-time constant
-template <typename F> inline void floss_with_nch(int C, F &&f)
-{
-    switch (floss_nch(C)) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    default: f(std::integral_constant<int, 8>{}); break;
-    }
-}

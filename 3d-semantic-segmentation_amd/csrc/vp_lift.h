@@ -96,9 +96,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_lift(
     // 1. the pixel's weight, and the tile's power-of-two scale
     float m = inside ? (pixel_weight ? pixel_weight[(long long)py * W + px] : 1.0f) : 0.0f;
     if (!(m > 0.0f)) m = 0.0f;
-    float mmax = m;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mmax = fmaxf(mmax, __shfl_xor(mmax, o));
+    float mmax = lanes_max<64>(m);
     if (lane == 0) s_max[wave] = mmax;
     __syncthreads();
     mmax = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
@@ -185,8 +183,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_lift(
                 const int p = qs * NB + i;
                 q += (float)s_Wh[qk * LIFT_ROW + p] + (float)s_Wl[qk * LIFT_ROW + p];
             }
-#pragma unroll
-            for (int o = QSEG / 2; o >= 1; o /= 2) q += __shfl_xor(q, o);
+            q = lanes_sum_down<QSEG>(q);
             if (qs == 0 && qk < nb) wpart[s_slot[qk]] = q * back;
         }
     }

@@ -8,8 +8,9 @@
 //                          row by row; pass 1 takes the 11 taps along a row for the five quantities x, y, x^2, y^2, x y at
 //                          42 rows x 32 columns into LDS; pass 2 takes the 11 taps down a column into registers, one pixel
 //                          per thread; the epilogue computes m and the three maps P, Q, R the gradient needs, and the
-//                          workgroup's three sums go through a float64 halving tree over its 1024 pixels.
-//   k_photo_loss_sum       one workgroup: the tiles' triples in ascending tile index (k_feature_loss_sum's rule).
+//                          three sums go through the tree (written out here, in planes) and the ordered sum of
+//                          vp_reduce.h: slot 32 ty + tx is the tile's pixel (tx, ty), zeros outside the image; one triple
+//                          per tile, tile index (c, tile row, tile).
 //   k_photo_loss_gradient  the same two passes over P, Q, R; the epilogue combines them with x(p), y(p).
 //
 // Without a workspace there is nowhere to keep one triple per tile, so k_photo_loss<true> walks the tiles in ascending index
@@ -74,7 +75,7 @@ __device__ __forceinline__ float photo_down(const float *h, int tx, int ty)
     return a;
 }
 
-// One tile of one plane.  Thread 0 returns the tile's {sum |x - y|, sum (x - y)^2, sum m} in t3.
+// One tile of one plane.  Every thread returns the tile's {sum |x - y|, sum (x - y)^2, sum m} in t3.
 __device__ __forceinline__ void photo_tile(const float *__restrict__ xp, const float *__restrict__ yp, int W, int H, int x0,
                                            int y0, float *__restrict__ mp, float *__restrict__ Pp, float *__restrict__ Qp,
                                            float *__restrict__ Rp, float *s_x, float *s_y, float *s_h, double (&t3)[3])
@@ -131,6 +132,8 @@ __device__ __forceinline__ void photo_tile(const float *__restrict__ xp, const f
             Rp[at] = R;
         }
     }
+    // The tree of vp_reduce.h, written out with its three values in planes: the one-workgroup evaluation path runs it once per
+    // tile, and block_tree_sum's interleaved slots (24 bytes apart) measured 1.7 % slower there.
     __syncthreads();                                                   // pass 2 is over: its rows become the tree's
     double *red = (double *)s_h;
     red[tid] = (double)l1;
@@ -193,34 +196,6 @@ __global__ __launch_bounds__(PHOTO_THREADS) void k_photo_loss(const float *__res
             loss_stats[1] = a1;
             loss_stats[2] = a2;
         }
-    }
-}
-
-// loss_stats = the tiles' triples summed in float64 in ascending tile index.  One workgroup: its threads stage 1024 triples at
-// a time in LDS, thread 0 adds them in order.
-__global__ __launch_bounds__(PHOTO_THREADS) void k_photo_loss_sum(const double *__restrict__ block_sums, long long n_blocks,
-                                                                  double *__restrict__ loss_stats)
-{
-    __shared__ double s_sum[3 * PHOTO_THREADS];
-    const int tid = threadIdx.x;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    for (long long b0 = 0; b0 < n_blocks; b0 += PHOTO_THREADS) {
-        const int nb = (int)(n_blocks - b0 < PHOTO_THREADS ? n_blocks - b0 : PHOTO_THREADS);
-        __syncthreads();
-        for (int i = tid; i < 3 * nb; i += PHOTO_THREADS) s_sum[i] = block_sums[3 * b0 + i];
-        __syncthreads();
-        if (tid == 0)
-#pragma unroll 8
-            for (int k = 0; k < nb; ++k) {
-                a0 += s_sum[3 * k];
-                a1 += s_sum[3 * k + 1];
-                a2 += s_sum[3 * k + 2];
-            }
-    }
-    if (tid == 0) {
-        loss_stats[0] = a0;
-        loss_stats[1] = a1;
-        loss_stats[2] = a2;
     }
 }
 

@@ -137,19 +137,6 @@ template <int WAVES = PROTO_THREADS / 64> __device__ __forceinline__ int proto_c
     return off + __popcll(b & ((1ull << lane) - 1ull));
 }
 
-// the workgroup's float64 sum by a fixed halving tree; thread 0 has it
-__device__ __forceinline__ double proto_block_sum(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    if (tid < PROTO_THREADS) red[tid] = v;
-    __syncthreads();
-    for (int h = PROTO_THREADS / 2; h >= 1; h /= 2) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 template <int DP>
 __global__ __launch_bounds__(PROTO_THREADS) void k_proto_sums(const float *__restrict__ image, int D, long long n,
                                                               const int *__restrict__ ids, const int *__restrict__ count,
@@ -211,7 +198,7 @@ __global__ __launch_bounds__(PROTO_THREADS) void k_proto_sums(const float *__res
     cnt_part[b * PROTO_IDS + tid] = s_cnt[tid];
     for (int i = tid; i < PROTO_IDS * D; i += PROTO_THREADS)
         s_part[b * PROTO_IDS * D + i] = proto_acc[i];
-    const double tot = proto_block_sum(nrm, s_red);
+    const double tot = block_tree_sum<PROTO_THREADS>(nrm, s_red);
     if (tid == 0) norm_part[b] = tot;
 }
 
@@ -238,17 +225,11 @@ __device__ __forceinline__ float proto_row_sum(const float *__restrict__ part, i
     return t;
 }
 
-// one float64 per workgroup: a halving tree over 1024 slots (slot b = workgroup b, zeros beyond G); thread 0 has the sum
+// one float64 per workgroup: the tree of vp_reduce.h over 1024 slots (slot b = workgroup b, zeros beyond G)
 __device__ __forceinline__ double proto_part_sum(const double *__restrict__ part, int G, double *red)
 {
     const int tid = threadIdx.x;
-    red[tid] = tid < G ? part[tid] : 0.0;
-    __syncthreads();
-    for (int h = PROTO_COMBINE / 2; h >= 1; h /= 2) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
+    return block_tree_sum<PROTO_COMBINE>(tid < G ? part[tid] : 0.0, red);
 }
 static_assert(PROTO_GRID <= PROTO_COMBINE, "one slot per workgroup");
 
@@ -362,7 +343,7 @@ __global__ __launch_bounds__(PROTO_COMBINE) void k_proto_temps(int D, int G, int
         n_slot[slot] = nf;
         for (int c = 0; c < D; ++c) utab[slot * D + c] = u_id[tid * D + c] / phi;
     }
-    const double tot = proto_block_sum(active ? (double)nk : 0.0, s_red);  // integers below 2^53: exact
+    const double tot = block_tree_sum<PROTO_THREADS>(active ? (double)nk : 0.0, s_red);  // integers below 2^53: exact
     if (tid == 0) {
         hdr->K = K;
         stats[1] = (double)K;
@@ -454,7 +435,7 @@ __global__ __launch_bounds__(PROTO_THREADS) void k_proto_loss(const float *__res
     __syncthreads();
     const size_t b = blockIdx.x;
     for (int i = tid; i < K * D; i += PROTO_THREADS) t_part[b * PROTO_IDS * D + i] = proto_acc[i];
-    const double tot = proto_block_sum(lsum, s_red);
+    const double tot = block_tree_sum<PROTO_THREADS>(lsum, s_red);
     if (tid == 0) loss_part[b] = tot;
 }
 
@@ -531,10 +512,3 @@ __global__ __launch_bounds__(PROTO_THREADS) void k_proto_gradient(const float *_
         }
 }
 
-// the call with DP, the registers a pixel's row takes, as a compile-time constant
-template <typename F> inline void proto_with_dp(int D, F &&f)
-{
-    if (D <= 16) f(std::integral_constant<int, 16>{});
-    else if (D <= 32) f(std::integral_constant<int, 32>{});
-    else f(std::integral_constant<int, 64>{});
-}

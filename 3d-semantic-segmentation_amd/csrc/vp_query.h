@@ -73,7 +73,7 @@ __global__ __launch_bounds__(64) void k_query_text(const float *__restrict__ tex
     double ss = 0.0;
     if (p < P)
         for (int c = lane; c < C; c += 64) ss += (double)t[c] * (double)t[c];
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    ss = lanes_sum_down<64>(ss);
     const double inv = 1.0 / fmax(sqrt(ss), 1e-12);
     T *dst = out + (long long)p * Cpad;
     for (int c = lane; c < Cpad; c += 64) dst[c] = (T)((p < P && c < C) ? (float)((double)t[c] * inv) : 0.0f);

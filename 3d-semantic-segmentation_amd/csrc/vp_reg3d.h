@@ -14,14 +14,15 @@
 // kl_pick_lanes takes the smallest power of two G with 4 G >= P, and 8 where P is in 9..16; the variants it can pick are
 // (G, CPL) = (4,1) P <= 4, (4,2) P <= 8, (8,2) P <= 16, (8,4) P <= 32, (16,4) P <= 64, (32,4) P <= 128, (64,4) P <= 256 (CPL 4
 // also serves three channels per lane).  Sums over a row's channels: per lane in ascending channel order, then a butterfly
-// over the group (commutative steps: every lane ends with the same bits).
+// over the group, masks descending from G / 2 (lanes_sum_down, vp_reduce.h).
 //
 //   k_kl_lse       row_lse[i] = max + logf(sum expf(z - max)) for every row.
 //   k_kl_forward   a group per sample position: p_s = expf(z_s - lse_s) and logf(p_s + eps) stay in registers, the k - 1
 //                  neighbour rows are gathered one after the other; sample_loss[s] = sum_j sum_c p_sc (log(p_sc + eps) -
 //                  log(p_jc + eps)), unscaled.
-//   k_kl_sum1/2    the per-sample sums in float64: 256 workgroups over consecutive stretches (per thread strided, a halving
-//                  tree), then the 256 partial sums in ascending order.  No atomics: the same bits on every run.
+//   k_kl_sum1/2    the per-sample sums in float64: 256 workgroups over consecutive stretches of ceil(S / 256) samples (slot t:
+//                  the stretch's samples t, t + 256, .. added in ascending order; the tree of vp_reduce.h), then the 256
+//                  partial sums in ascending order.  No atomics: the same bits on every run.
 //   k_kl_gradient  a group per ROW: the row gathers what it receives as a sample (its own neighbours, through the sample list
 //                  of the row) and as a neighbour (through the reversed table, CSR over rows), in that fixed order, then
 //                  goes through the softmax: dz = p (g - <g, p>).  Every row of grad_logits is written, zeros included.
@@ -45,18 +46,6 @@ static inline int kl_pick_lanes(int P)
     return (P > 8 && G < 8) ? 8 : G;
 }
 
-__device__ __forceinline__ float kl_group_sum(float v, int G)
-{
-    for (int o = G >> 1; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ float kl_group_max(float v, int G)
-{
-    for (int o = G >> 1; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 template <int CPL>
 __global__ __launch_bounds__(KL_THREADS) void k_kl_lse(const float *__restrict__ z, long long stride, long long N, int P, int G,
                                                        float *__restrict__ row_lse)
@@ -71,12 +60,12 @@ __global__ __launch_bounds__(KL_THREADS) void k_kl_lse(const float *__restrict__
         v[u] = (active && c < P) ? z[row * stride + c] : -INFINITY;
         m = fmaxf(m, v[u]);
     }
-    m = kl_group_max(m, G);
+    m = lanes_max(m, G);
     float s = 0.0f;
 #pragma unroll
     for (int u = 0; u < CPL; ++u)
         if (active && l + u * G < P) s += expf(v[u] - m);
-    s = kl_group_sum(s, G);
+    s = lanes_sum_down(s, G);
     if (active && l == 0) row_lse[row] = m + logf(s);
 }
 
@@ -114,20 +103,8 @@ __global__ __launch_bounds__(KL_THREADS) void k_kl_forward(const float *__restri
             }
         }
     }
-    acc = kl_group_sum(acc, G);
+    acc = lanes_sum_down(acc, G);
     if (sp < S && l == 0) sl[sp] = acc;
-}
-
-// the workgroup's float64 sum by a fixed halving tree, in red[0]
-__device__ __forceinline__ void kl_block_sum(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int h = KL_THREADS / 2; h >= 1; h /= 2) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
 }
 
 __global__ __launch_bounds__(KL_THREADS) void k_kl_sum1(const float *__restrict__ sl, long long S, double *__restrict__ part)
@@ -136,8 +113,8 @@ __global__ __launch_bounds__(KL_THREADS) void k_kl_sum1(const float *__restrict_
     const long long per = (S + KL_PARTS - 1) / KL_PARTS, lo = min(S, blockIdx.x * per), hi = min(S, lo + per);
     double s = 0.0;
     for (long long i = lo + threadIdx.x; i < hi; i += KL_THREADS) s += (double)sl[i];
-    kl_block_sum(s, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+    s = block_tree_sum<KL_THREADS>(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __global__ void k_kl_sum2(const double *__restrict__ part, long long S, double *__restrict__ stats)
@@ -218,7 +195,7 @@ __global__ __launch_bounds__(KL_THREADS) void k_kl_gradient(const float *__restr
     float dot = 0.0f;
 #pragma unroll
     for (int u = 0; u < CPL; ++u) dot += g[u] * p[u];
-    dot = kl_group_sum(dot, G);
+    dot = lanes_sum_down(dot, G);
     if (!active) return;
     float coef = (float)coef64;
     if (grad_loss) coef *= grad_loss[0];
@@ -229,12 +206,7 @@ __global__ __launch_bounds__(KL_THREADS) void k_kl_gradient(const float *__restr
     }
 }
 
-template <typename F> inline void kl_with_cpl(int P, int G, F &&f)
-{
-    const int cpl = (P + G - 1) / G;
-    if (cpl <= 1) f(std::integral_constant<int, 1>{});
-    else if (cpl <= 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 4>{});
-}
+// channels per lane of a group of G lanes; the kernels are instantiated for 1, 2 and 4
+static inline int kl_cpl(int P, int G) { return (P + G - 1) / G; }
 
 }  // namespace

@@ -41,8 +41,9 @@ namespace {
 //   whose pointer is non-NULL are written.
 // k_splat_blend<DT, true> (vp_splat_rasterize_loss) is the same blend with a softmax cross-entropy epilogue: per pixel
 //   l = (m + logf(sum_c expf(C_c - m))) - C_t from its accumulators (m and the sum are the confidence's), weight w (0 when
-//   the target is outside [0, D)); pixel_loss = w l; the workgroup reduces {w l, w} in float64 through a fixed halving tree
-//   (in the feature rows' LDS) to one pair per tile.  k_splat_loss_sum (one workgroup) sums the pairs in ascending tile index.
+//   the target is outside [0, D)); pixel_loss = w l; {w l, w} go through the tree and the ordered sum of vp_reduce.h: slot
+//   16 ty + tx of a tile is its pixel (tx, ty), zeros outside the image; one pair per tile, tiles in row-major index.  The tree
+//   runs in the feature rows' LDS; the ordered sum is guarded by the device total like every kernel after the scan.
 // Every kernel after the scan reads the device total first: a total above the workspace's capacity writes nothing (the
 // emit kernel raises *status instead), so a too-small workspace never leaves a partial image.
 // ------------------------------------------------------------------------------------------------
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
     __shared__ float2 s_gb[NB];              // C, o
     __shared__ int s_id[NB];
     __shared__ __attribute__((aligned(16))) float s_f[NB * DT];   // feature rows, zero past D; the loss's tile sums at the end
-    static_assert(NB * DT * sizeof(float) >= SPLAT_THREADS * sizeof(double2), "the tile sums reuse the feature rows' LDS");
+    static_assert(NB * DT * sizeof(float) >= 2 * SPLAT_THREADS * sizeof(double), "the tile sums reuse the feature rows' LDS");
     if (*total_p > capacity) return;
     const int tid = threadIdx.x;
     const int px = blockIdx.x * SPLAT_TILE + (tid & (SPLAT_TILE - 1)), py = blockIdx.y * SPLAT_TILE + tid / SPLAT_TILE;
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
     }
     if (!LOSS && !inside) return;
     const long long pix = (long long)py * W + px, hw = (long long)H * W;
-    double2 sums = make_double2(0.0, 0.0);    // LOSS: this pixel's {w l, w}
+    double sums[2] = {0.0, 0.0};              // LOSS: this pixel's {w l, w}
     if (inside) {
         float m1 = acc[0];
         int lab = 0;
@@ -404,51 +405,13 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
                 if (c == t) ct = acc[c];
             const float wl = w != 0.0f ? w * ((m1 + logf(s)) - ct) : 0.0f;     // weight 0 contributes nothing, whatever l is
             if (ls.pixel_loss) ls.pixel_loss[pix] = wl;
-            sums = make_double2((double)wl, (double)w);
+            sums[0] = (double)wl;
+            sums[1] = (double)w;
         }
     }
     if constexpr (LOSS) {
-        // the tile's pair in float64: a fixed halving tree over the 256 pixels, in the feature rows' LDS
-        double2 *s_sum = (double2 *)s_f;
-        __syncthreads();
-        s_sum[tid] = sums;
-        __syncthreads();
-        for (int h = SPLAT_THREADS / 2; h >= 1; h /= 2) {
-            if (tid < h) {
-                const double2 a = s_sum[tid], b = s_sum[tid + h];
-                s_sum[tid] = make_double2(a.x + b.x, a.y + b.y);
-            }
-            __syncthreads();
-        }
-        if (tid == 0) ls.tile_sums[(long long)blockIdx.y * gridDim.x + blockIdx.x] = s_sum[0];
-    }
-}
-
-// loss_stats = the tile pairs summed in float64 in ascending tile index.  One workgroup: its threads stage 256 pairs at a
-// time in LDS, thread 0 adds them in order (float64 addition is not associative: the order is the contract).
-__global__ __launch_bounds__(SPLAT_THREADS) void k_splat_loss_sum(const double2 *__restrict__ tile_sums, long long n_tiles,
-                                                                   const long long *total_p, long long capacity,
-                                                                   double *__restrict__ loss_stats)
-{
-    __shared__ double2 s_sum[SPLAT_THREADS];
-    if (*total_p > capacity) return;
-    const int tid = threadIdx.x;
-    double2 a = make_double2(0.0, 0.0);
-    for (long long t0 = 0; t0 < n_tiles; t0 += SPLAT_THREADS) {
-        const int n = (int)(n_tiles - t0 < SPLAT_THREADS ? n_tiles - t0 : SPLAT_THREADS);
-        __syncthreads();
-        if (tid < n) s_sum[tid] = tile_sums[t0 + tid];
-        __syncthreads();
-        if (tid == 0)
-#pragma unroll 8
-            for (int k = 0; k < n; ++k) {      // unrolled: the LDS reads run ahead of the dependent additions
-                a.x += s_sum[k].x;
-                a.y += s_sum[k].y;
-            }
-    }
-    if (tid == 0) {
-        loss_stats[0] = a.x;
-        loss_stats[1] = a.y;
+        block_tree_sum<SPLAT_THREADS>(sums, (double *)s_f);          // the blend is over: the feature rows become the tree's
+        if (tid == 0) ls.tile_sums[(long long)blockIdx.y * gridDim.x + blockIdx.x] = make_double2(sums[0], sums[1]);
     }
 }
 
@@ -686,6 +649,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
                 s5[4] += v * (0.5f * dy * dy);
             }
         }
+        // six butterflies step by step, not lanes_sum_down one after the other: the steps of one value wait on each other
 #pragma unroll
         for (int m = QSEG / 2; m >= 1; m /= 2) {
             q += __shfl_xor(q, m);
@@ -709,30 +673,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend_backward(
 inline int splat_reduce_group(int D) { return D + 1 <= 16 ? 16 : D + 1 <= 32 ? 32 : 64; }
 
 // The kernels are instantiated for DT = 8, 16, 32, 64 accumulators (the smallest that holds D) and for reduce groups of
-// 16, 32, 64 lanes: f gets the choice as a std::integral_constant, and a run-time flag as std::true_type / false_type.
-template <class F>
-inline void splat_with_dt(int D, F &&f)
-{
-    if (D <= 8) f(std::integral_constant<int, 8>{});
-    else if (D <= 16) f(std::integral_constant<int, 16>{});
-    else if (D <= 32) f(std::integral_constant<int, 32>{});
-    else f(std::integral_constant<int, 64>{});
-}
-
-template <class F>
-inline void splat_with_group(int gs, F &&f)
-{
-    if (gs == 16) f(std::integral_constant<int, 16>{});
-    else if (gs == 32) f(std::integral_constant<int, 32>{});
-    else f(std::integral_constant<int, 64>{});
-}
-
-template <class F>
-inline void splat_with_flag(bool flag, F &&f)
-{
-    if (flag) f(std::true_type{});
-    else f(std::false_type{});
-}
+// 16, 32, 64 lanes (with_step, vp_common.h).
 
 // GS lanes per Gaussian, grid-stride over the Gaussians; each lane sums its channel over the Gaussian's count[g] contiguous
 // slots in ascending order, four loads in flight.  GEOM: rows of D + 1 + SPLAT_SCREEN floats, and the five screen sums of a

@@ -1026,8 +1026,8 @@ int vp_neighbor_kl_gradient(const float *logits, int64_t N, int P, int64_t row_s
  *     loss = (1 - lambda) stats[0] / n + lambda (1 - stats[2] / n),     PSNR = -10 log10(stats[1] / n).
  *   Order: no float atomics.  The image is cut into tiles of 32 x 32 pixels per channel, tile index (c, tile row, tile column)
  *   ascending; the fp32 terms of a tile are added in float64 by a halving tree over its 1024 pixels (pixel (tx, ty) of the
- *   tile in slot 32 ty + tx, a pixel outside the image adding 0), then the tiles in ascending index (k_feature_loss_sum's
- *   rule).  Bit-identical from run to run, with or without ssim_map and workspace.
+ *   tile in slot 32 ty + tx, a pixel outside the image adding 0), then the tiles in ascending index (k_ordered_sum,
+ *   csrc/vp_reduce.h).  Bit-identical from run to run, with or without ssim_map and workspace.
  *   workspace may be NULL: evaluation only.  The same stats bits, but the tiles are then walked by ONE workgroup, because there
  *   is nowhere to keep a sum per tile: slow on a large image, and nothing is left for a gradient call.  Otherwise the
  *   workspace holds vp_photo_loss_workspace_bytes and the forward leaves three f32 maps [3,C,H,W] at its start, followed
