@@ -38,6 +38,7 @@
 //   vp_aggregate.h  the aggregator's per-view fp16 accumulate over the hit rows (AGG:307-313)
 //   vp_render.h  the transpose: every pixel copies the row of its first-hit voxel (k_render_walk, k_render_small)
 //   vp_query.h   text query of a feature table: cosine logits, argmax label, softmax margin on the matrix cores (k_query)
+//   vp_tilebin.h binning primitives into 16 x 16 tiles: the workspace's shared sections, key emit, sort and tile runs (k_tile_emit, k_tile_ranges)
 //   vp_splat.h   tile-based Gaussian splatting of D-channel features with a fused label / confidence epilogue (stage 5.2)
 //   vp_lift.h    lifting a 2D feature map onto the Gaussians: the splatter's transpose on the matrix cores (k_splat_lift)
 //   vp_splat_render.h  rendering wide feature rows into a view: the splatter's forward on the matrix cores (k_splat_render)
@@ -87,6 +88,7 @@
 #include "vp_aggregate.h"
 #include "vp_render.h"
 #include "vp_query.h"
+#include "vp_tilebin.h"
 #include "vp_splat.h"
 #include "vp_lift.h"
 #include "vp_splat_render.h"
@@ -109,6 +111,57 @@ static int check_workspace(const void *workspace, size_t workspace_bytes, size_t
     if (!workspace || workspace_bytes < need)
         return fail(VP_EWORKSPACE, "workspace has %zu bytes, need %zu", workspace ? workspace_bytes : 0, need);
     if ((uintptr_t)workspace & 255) return fail(VP_EWORKSPACE, "workspace must be 256-byte aligned");
+    return VP_OK;
+}
+
+// The refusals of a caller-provided buffer by name ("workspace", "backward workspace", "loss workspace", "lift workspace"),
+// for the families that tell a NULL buffer from a small one.
+static int check_buffer(const void *buf, const char *name)
+{
+    if (!buf) return fail(VP_EWORKSPACE, "%s is NULL", name);
+    if ((uintptr_t)buf & 255) return fail(VP_EWORKSPACE, "%s must be 256-byte aligned", name);
+    return VP_OK;
+}
+
+static int check_size(size_t have, size_t need, const char *name)
+{
+    if (have < need) return fail(VP_EWORKSPACE, "%s has %zu bytes, need %zu", name, have, need);
+    return VP_OK;
+}
+
+// Opening a laid-out workspace: the buffer's refusals, then the layout (lay_out() fills l and is false when a rocprim
+// scratch size query fails; those need the device, so every host check of an entry point comes before), then the size.
+template <typename L, typename F>
+static int open_workspace(const void *buf, size_t have, const L &l, F &&lay_out)
+{
+    if (int rc = check_buffer(buf, "workspace")) return rc;
+    if (!lay_out()) return fail(VP_EHIP, "rocprim scratch size query failed");
+    return check_size(have, l.bytes, "workspace");
+}
+
+// The tile-binned workspaces: l gets the typed pointers of every section of buf.
+static int open_workspace(const void *buf, size_t have, int64_t n, int W, int H, int64_t capacity, SplatLayout &l)
+{
+    return open_workspace(buf, have, l, [&] { return splat_layout((char *)buf, n, W, H, capacity, l); });
+}
+
+static int open_workspace(const void *buf, size_t have, int64_t n, int W, int H, int64_t capacity, MeshLayout &l)
+{
+    return open_workspace(buf, have, l, [&] { return mesh_layout((char *)buf, n, W, H, capacity, l); });
+}
+
+static int check_count(const char *name, int64_t v)
+{
+    if (v < 0 || v > INT32_MAX) return fail(VP_EINVAL, "%s = %lld outside [0, 2^31 - 1]", name, (long long)v);
+    return VP_OK;
+}
+
+constexpr int VP_MAX_WH = 32768;                         // the largest image side, of every family that takes an image
+
+static int check_image(int W, int H)
+{
+    if (W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH)
+        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, VP_MAX_WH);
     return VP_OK;
 }
 
@@ -278,43 +331,14 @@ int vp_query_features(const void *rows, int rows_is_f16, int64_t n_rows, int C, 
 
 // ------------------------------------------------------------------------------------------------
 // Gaussian splatting.  The checks every entry point repeats, each VP_OK or the refusal; none of them needs a GPU, and every
-// entry point makes all of its own before splat_layout (rocprim's scratch sizes depend on the device).
+// entry point makes all of its own before open_workspace (rocprim's scratch sizes depend on the device).
 // ------------------------------------------------------------------------------------------------
-static int splat_check_count(int64_t n_gaussians)
-{
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX)
-        return fail(VP_EINVAL, "n_gaussians = %lld outside [0, 2^31 - 1]", (long long)n_gaussians);
-    return VP_OK;
-}
-
-static int splat_check_image(int W, int H)
-{
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, SPLAT_MAX_WH);
-    return VP_OK;
-}
-
 static int splat_check_rows(int D, int64_t row_stride, int W, int H, int64_t capacity)
 {
     if (D < 1 || D > SPLAT_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, SPLAT_MAX_D);
     if (row_stride < D) return fail(VP_EINVAL, "row_stride %lld < D = %d", (long long)row_stride, D);
-    if (int rc = splat_check_image(W, H)) return rc;
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    return VP_OK;
-}
-
-// name: "workspace", "backward workspace" or "loss workspace"
-static int splat_check_buffer(const void *buf, const char *name)
-{
-    if (!buf) return fail(VP_EWORKSPACE, "%s is NULL", name);
-    if ((uintptr_t)buf & 255) return fail(VP_EWORKSPACE, "%s must be 256-byte aligned", name);
-    return VP_OK;
-}
-
-static int splat_check_size(size_t have, size_t need, const char *name)
-{
-    if (have < need) return fail(VP_EWORKSPACE, "%s has %zu bytes, need %zu", name, have, need);
-    return VP_OK;
+    if (int rc = check_image(W, H)) return rc;
+    return check_count("capacity", capacity);
 }
 
 // the pose and the intrinsics into cam; the planes, eps2d and the image size are the caller's to check and fill
@@ -333,11 +357,11 @@ static int splat_check_camera(const float *viewmat, float fx, float fy, float cx
 
 size_t vp_splat_workspace_bytes(int64_t n_gaussians, int W, int H, int64_t capacity)
 {
-    if (n_gaussians < 0 || n_gaussians > INT32_MAX || W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH || capacity < 0 ||
+    if (n_gaussians < 0 || n_gaussians > INT32_MAX || W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH || capacity < 0 ||
         capacity > INT32_MAX)
         return 0;
     SplatLayout l;
-    return splat_layout(n_gaussians, W, H, capacity, l) ? l.bytes : 0;
+    return splat_layout(nullptr, n_gaussians, W, H, capacity, l) ? l.bytes : 0;
 }
 
 int vp_splat_project(const float *means, const float *quats, const float *scales, const float *opacities, int64_t n_gaussians,
@@ -345,67 +369,26 @@ int vp_splat_project(const float *means, const float *quats, const float *scales
                      float far_plane, float eps2d, int64_t *n_isect, int32_t *n_nonfinite, void *workspace,
                      size_t workspace_bytes, void *stream_)
 {
-    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (int rc = check_count("n_gaussians", n_gaussians)) return rc;
     if (n_gaussians > 0 && (!means || !quats || !scales || !opacities))
         return fail(VP_EINVAL, "null pointer argument (means, quats, scales or opacities)");
     SplatCam cam;
     if (int rc = splat_check_camera(viewmat, fx, fy, cx, cy, cam)) return rc;
-    if (int rc = splat_check_image(W, H)) return rc;
+    if (int rc = check_image(W, H)) return rc;
     if (!(near_plane > 0.0f) || !(far_plane > near_plane) || !(eps2d >= 0.0f) || !std::isfinite(eps2d))
         return fail(VP_EINVAL, "need 0 < near < far and a finite eps2d >= 0 (got %g %g %g)", (double)near_plane,
                     (double)far_plane, (double)eps2d);
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
     SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, 0, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, n_gaussians, W, H, 0, l)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
     cam.near_z = near_plane; cam.far_z = far_plane; cam.eps2d = eps2d;
     cam.W = W; cam.H = H; cam.tiles_x = l.tiles_x;
-    long long *total = (long long *)(ws + l.total), *offs = (long long *)(ws + l.offs);
     if (n_gaussians > 0) {
         hipLaunchKernelGGL(k_splat_project, dim3((unsigned)((n_gaussians + 255) / 256)), dim3(256), 0, stream, means, quats,
-                           scales, opacities, (long long)n_gaussians, cam, (SplatRec *)(ws + l.rec), (int4 *)(ws + l.box),
-                           (int *)(ws + l.count), (int *)n_nonfinite);
-        VP_HIP(hipGetLastError());
-        size_t tmp = l.scan_bytes;
-        VP_HIP(rocprim::inclusive_scan(ws + l.scan_tmp, tmp, (const int *)(ws + l.count), offs, (size_t)n_gaussians,
-                                       rocprim::plus<long long>(), stream));
-    }
-    hipLaunchKernelGGL(k_splat_total, dim3(1), dim3(1), 0, stream, (const long long *)offs, (long long)n_gaussians, total,
-                       (long long *)n_isect);
-    VP_HIP(hipGetLastError());
-    return VP_OK;
-}
-
-// emit the (tile, depth) keys of the projected Gaussians, sort them and find every tile's run: what the blend reads
-static int splat_sort_tiles(char *ws, const SplatLayout &l, int64_t n_gaussians, int64_t capacity, int32_t *status,
-                            hipStream_t stream)
-{
-    const long long n_tiles = (long long)l.tiles_x * l.tiles_y;
-    const long long *total = (const long long *)(ws + l.total);
-    unsigned long long *k0 = (unsigned long long *)(ws + l.keys0), *k1 = (unsigned long long *)(ws + l.keys1);
-    int *v0 = (int *)(ws + l.vals0), *v1 = (int *)(ws + l.vals1);
-    longlong2 *ranges = (longlong2 *)(ws + l.ranges);
-    // emit: one thread per Gaussian (at least one workgroup, which also pads [total, capacity) and raises the status)
-    const long long n_emit = std::max<long long>(n_gaussians, 1);
-    const unsigned g_emit = (unsigned)((n_emit + 255) / 256);
-    hipLaunchKernelGGL(k_splat_emit, dim3(g_emit), dim3(256), 0, stream, (const SplatRec *)(ws + l.rec),
-                       (const int4 *)(ws + l.box), (const long long *)(ws + l.offs), (long long)n_gaussians, l.tiles_x,
-                       n_tiles, total, (long long)capacity, k0, v0, (int *)status);
-    VP_HIP(hipGetLastError());
-    if (capacity > 0) {
-        size_t tmp = l.sort_bytes;
-        VP_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, tmp, k0, k1, v0, v1, (size_t)capacity, 0u, (unsigned)l.end_bit,
-                                         stream));
-    }
-    VP_HIP(hipMemsetAsync(ranges, 0, (size_t)n_tiles * sizeof(longlong2), stream));
-    if (capacity > 0) {
-        hipLaunchKernelGGL(k_splat_ranges, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, stream, k1, total,
-                           (long long)capacity, ranges);
+                           scales, opacities, (long long)n_gaussians, cam, l.rec, l.box, l.count, (int *)n_nonfinite);
         VP_HIP(hipGetLastError());
     }
-    return VP_OK;
+    return tile_scan(l, n_gaussians, (long long *)n_isect, stream);
 }
 
 // The forward after the caller's own checks: the shared checks, the tile sort and the blend.  ls: the loss variant's maps and
@@ -415,29 +398,24 @@ static int splat_forward_impl(const float *features, int D, int64_t row_stride, 
                               int32_t *status, void *workspace, size_t workspace_bytes, const SplatLoss *ls,
                               double *loss_stats, void *stream_)
 {
-    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (int rc = check_count("n_gaussians", n_gaussians)) return rc;
     if (int rc = splat_check_rows(D, row_stride, W, H, capacity)) return rc;
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
     SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, n_gaussians, W, H, capacity, l)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
-    const long long *total = (const long long *)(ws + l.total);
-    if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+    if (int rc = splat_sort(l, n_gaussians, capacity, status, stream)) return rc;
+    const dim3 grid = l.tile_grid(), block(SPLAT_THREADS);
     with_step<8, 16, 32, 64>(D, [&](auto dt) {
         with_flags([&](auto loss) {
-            hipLaunchKernelGGL((k_splat_blend<dt.value, loss.value>), grid, block, 0, stream,
-                               (const SplatRec *)(ws + l.rec), (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges),
-                               total, (long long)capacity, features, D, (long long)row_stride, W, H, (int *)labels, confidence,
+            hipLaunchKernelGGL((k_splat_blend<dt.value, loss.value>), grid, block, 0, stream, l.rec, l.vals1, l.ranges, l.total,
+                               (long long)capacity, features, D, (long long)row_stride, W, H, (int *)labels, confidence,
                                alpha, logits, ls ? *ls : SplatLoss{});
         }, ls != nullptr);
     });
     VP_HIP(hipGetLastError());
     if (ls) {
         hipLaunchKernelGGL((k_ordered_sum<2, SPLAT_THREADS>), dim3(1), block, 0, stream, (const double *)ls->tile_sums,
-                           (long long)l.tiles_x * l.tiles_y, total, (long long)capacity, loss_stats);
+                           l.n_tiles(), l.total, (long long)capacity, loss_stats);
         VP_HIP(hipGetLastError());
     }
     return VP_OK;
@@ -488,7 +466,7 @@ static int splat_backward_impl(const SplatBackward &a)
 {
     const int D = a.D;
     const int64_t n_gaussians = a.n_gaussians, capacity = a.capacity;
-    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (int rc = check_count("n_gaussians", n_gaussians)) return rc;
     if (n_gaussians > 0 && !a.features) return fail(VP_EINVAL, "null pointer argument (features)");
     if (a.chain && n_gaussians > 0 && (!a.means || !a.quats || !a.scales))
         return fail(VP_EINVAL, "null pointer argument (means, quats or scales, needed by grad_means / grad_quats / grad_scales)");
@@ -501,27 +479,24 @@ static int splat_backward_impl(const SplatBackward &a)
         cam.eps2d = a.eps2d;
         cam.W = a.W; cam.H = a.H;
     }
-    if (int rc = splat_check_buffer(a.workspace, "workspace")) return rc;
-    if (int rc = splat_check_buffer(a.bwd_workspace, "backward workspace")) return rc;
+    // the buffers' refusals come before either size's: the workspace, the backward workspace and its size, then the layout
+    if (int rc = check_buffer(a.workspace, "workspace")) return rc;
+    if (int rc = check_buffer(a.bwd_workspace, "backward workspace")) return rc;
     const size_t bwd_need = a.geom ? splat_geom_bytes(capacity, D) : splat_bwd_bytes(capacity, D);
-    if (int rc = splat_check_size(a.bwd_bytes, bwd_need, "backward workspace")) return rc;
+    if (int rc = check_size(a.bwd_bytes, bwd_need, "backward workspace")) return rc;
     SplatLayout l;
-    if (!splat_layout(n_gaussians, a.W, a.H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(a.workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(a.workspace, a.workspace_bytes, n_gaussians, a.W, a.H, capacity, l)) return rc;
     if (n_gaussians == 0) return VP_OK;                  // no rows to write; nothing can exceed a capacity of 0 either
     hipStream_t stream = (hipStream_t)a.stream;
-    char *ws = (char *)a.workspace;
-    const long long *total = (const long long *)(ws + l.total);
-    const int *count = (const int *)(ws + l.count);
-    const long long *offs = (const long long *)(ws + l.offs);
+    const long long *total = l.total, *offs = l.offs;
+    const int *count = l.count;
     float *part = (float *)a.bwd_workspace;
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+    const dim3 grid = l.tile_grid(), block(SPLAT_THREADS);
     with_step<8, 16, 32, 64>(D, [&](auto dt) {
         with_flags([&](auto geom, auto loss) {
-            hipLaunchKernelGGL((k_splat_blend_backward<dt.value, geom.value, loss.value>), grid, block, 0, stream,
-                               (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), count, offs,
-                               (const int *)(ws + l.vals1), (const longlong2 *)(ws + l.ranges), total, (long long)capacity,
-                               a.features, D, (long long)a.row_stride, a.W, a.H, a.logits, a.grad_alpha, part, a.ls);
+            hipLaunchKernelGGL((k_splat_blend_backward<dt.value, geom.value, loss.value>), grid, block, 0, stream, l.rec, l.box,
+                               count, offs, l.vals1, l.ranges, total, (long long)capacity, a.features, D,
+                               (long long)a.row_stride, a.W, a.H, a.logits, a.grad_alpha, part, a.ls);
         }, a.geom, a.loss);
     });
     VP_HIP(hipGetLastError());
@@ -579,7 +554,7 @@ int vp_splat_rasterize_backward_geometry(const float *means, const float *quats,
 
 size_t vp_splat_loss_workspace_bytes(int W, int H)
 {
-    if (W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH) return 0;
+    if (W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH) return 0;
     const size_t n_tiles = (size_t)((W + SPLAT_TILE - 1) / SPLAT_TILE) * (size_t)((H + SPLAT_TILE - 1) / SPLAT_TILE);
     return align256(n_tiles * sizeof(double2));
 }
@@ -592,9 +567,9 @@ int vp_splat_rasterize_loss(const float *features, int D, int64_t row_stride, in
 {
     if (n_gaussians > 0 && !features) return fail(VP_EINVAL, "null pointer argument (features)");
     if (!target || !loss_stats) return fail(VP_EINVAL, "null pointer argument (target or loss_stats)");
-    if (int rc = splat_check_image(W, H)) return rc;     // the loss workspace's size needs a valid image
-    if (int rc = splat_check_buffer(loss_workspace, "loss workspace")) return rc;
-    if (int rc = splat_check_size(loss_bytes, vp_splat_loss_workspace_bytes(W, H), "loss workspace")) return rc;
+    if (int rc = check_image(W, H)) return rc;           // the loss workspace's size needs a valid image
+    if (int rc = check_buffer(loss_workspace, "loss workspace")) return rc;
+    if (int rc = check_size(loss_bytes, vp_splat_loss_workspace_bytes(W, H), "loss workspace")) return rc;
     SplatLoss ls = {};
     ls.target = (const int *)target;
     ls.weight = pixel_weight;
@@ -639,32 +614,29 @@ int vp_splat_lift(const void *feats_f16, int C, int64_t pix_stride, const float 
                   int64_t capacity, int sorted, float *sum, int64_t sum_stride, float *wsum, int32_t *status, void *workspace,
                   size_t workspace_bytes, void *lift_workspace, size_t lift_bytes_, void *stream_)
 {
-    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (int rc = check_count("n_gaussians", n_gaussians)) return rc;
     if (!feats_f16 || !sum) return fail(VP_EINVAL, "null pointer argument (feats_f16 or sum)");
     if (C < 1 || C > LIFT_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, LIFT_MAX_C);
     if (pix_stride < C) return fail(VP_EINVAL, "pix_stride %lld < C = %d", (long long)pix_stride, C);
     if (sum_stride < C) return fail(VP_EINVAL, "sum_stride %lld < C = %d", (long long)sum_stride, C);
     if (sorted != 0 && sorted != 1) return fail(VP_EINVAL, "sorted = %d is neither 0 nor 1", sorted);
-    if (int rc = splat_check_image(W, H)) return rc;
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
-    if (int rc = splat_check_buffer(lift_workspace, "lift workspace")) return rc;
-    if (int rc = splat_check_size(lift_bytes_, lift_bytes(capacity, C), "lift workspace")) return rc;
+    if (int rc = check_image(W, H)) return rc;
+    if (int rc = check_count("capacity", capacity)) return rc;
+    if (int rc = check_buffer(workspace, "workspace")) return rc;
+    if (int rc = check_buffer(lift_workspace, "lift workspace")) return rc;
+    if (int rc = check_size(lift_bytes_, lift_bytes(capacity, C), "lift workspace")) return rc;
     SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, n_gaussians, W, H, capacity, l)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
     if (!sorted)
-        if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
+        if (int rc = splat_sort(l, n_gaussians, capacity, status, stream)) return rc;
     if (n_gaussians == 0) return VP_OK;                  // no rows to add to; nothing can exceed a capacity of 0 either
-    const long long *total = (const long long *)(ws + l.total);
-    const int *count = (const int *)(ws + l.count);
-    const long long *offs = (const long long *)(ws + l.offs);
+    const long long *total = l.total, *offs = l.offs;
+    const int *count = l.count;
     const _Float16 *feats = (const _Float16 *)feats_f16;
     float *part = (float *)lift_workspace, *wpart = (float *)((char *)lift_workspace + lift_part_bytes(capacity, C));
     const bool vec = C % 8 == 0 && pix_stride % 8 == 0 && ((uintptr_t)feats_f16 & 15) == 0;
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+    const dim3 grid = l.tile_grid(), block(SPLAT_THREADS);
     with_flags([&](auto wide, auto v) {
         constexpr int CC = wide.value ? 64 : 16;
         static_assert(lift_chunk(wide.value ? 17 : 16) == CC, "the pass width is lift_chunk's");
@@ -672,10 +644,8 @@ int vp_splat_lift(const void *feats_f16, int C, int64_t pix_stride, const float 
         const unsigned g_red = (unsigned)std::min<long long>((n_gaussians + 256 / CC - 1) / (256 / CC), 2048LL);
         for (int c0 = 0; c0 < C; c0 += CC) {
             float *wp = c0 == 0 && wsum ? wpart : nullptr;
-            hipLaunchKernelGGL((k_splat_lift<CC, v.value>), grid, block, 0, stream, (const SplatRec *)(ws + l.rec),
-                               (const int4 *)(ws + l.box), count, offs, (const int *)(ws + l.vals1),
-                               (const longlong2 *)(ws + l.ranges), total, (long long)capacity, feats, C, (long long)pix_stride, c0,
-                               pixel_weight, W, H, part, wp);
+            hipLaunchKernelGGL((k_splat_lift<CC, v.value>), grid, block, 0, stream, l.rec, l.box, count, offs, l.vals1, l.ranges,
+                               total, (long long)capacity, feats, C, (long long)pix_stride, c0, pixel_weight, W, H, part, wp);
             hipLaunchKernelGGL((k_splat_lift_reduce<CC>), dim3(g_red), dim3(256), 0, stream, count, offs,
                                (long long)n_gaussians, total, (long long)capacity, (const float *)part, (const float *)wp,
                                std::min(CC, C - c0), c0, sum, (long long)sum_stride, wsum, (int *)status);
@@ -689,7 +659,7 @@ int vp_splat_render(const void *rows, int rows_is_f16, int C, int64_t row_stride
                     int64_t capacity, int sorted, void *out, int out_is_f16, int64_t pix_stride, float *alpha, int32_t *status,
                     void *workspace, size_t workspace_bytes, void *stream_)
 {
-    if (int rc = splat_check_count(n_gaussians)) return rc;
+    if (int rc = check_count("n_gaussians", n_gaussians)) return rc;
     if (!rows || !out) return fail(VP_EINVAL, "null pointer argument (rows or out)");
     if (C < 1 || C > RENDER_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, RENDER_MAX_C);
     if (row_stride < C) return fail(VP_EINVAL, "row_stride %lld < C = %d", (long long)row_stride, C);
@@ -697,31 +667,26 @@ int vp_splat_render(const void *rows, int rows_is_f16, int C, int64_t row_stride
     if (sorted != 0 && sorted != 1) return fail(VP_EINVAL, "sorted = %d is neither 0 nor 1", sorted);
     if (rows_is_f16 != 0 && rows_is_f16 != 1) return fail(VP_EINVAL, "rows_is_f16 = %d is neither 0 nor 1", rows_is_f16);
     if (out_is_f16 != 0 && out_is_f16 != 1) return fail(VP_EINVAL, "out_is_f16 = %d is neither 0 nor 1", out_is_f16);
-    if (int rc = splat_check_image(W, H)) return rc;
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
+    if (int rc = check_image(W, H)) return rc;
+    if (int rc = check_count("capacity", capacity)) return rc;
     SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, n_gaussians, W, H, capacity, l)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
     if (!sorted)
-        if (int rc = splat_sort_tiles(ws, l, n_gaussians, capacity, status, stream)) return rc;
+        if (int rc = splat_sort(l, n_gaussians, capacity, status, stream)) return rc;
     // n_gaussians == 0 still launches: every tile's run is empty, and every pixel gets its zeros
     const int epl = rows_is_f16 ? 8 : 4;                 // elements of one 16-byte load
     const bool vec = C % epl == 0 && row_stride % epl == 0 && ((uintptr_t)rows & 15) == 0;
     const int CC = render_chunk(C);
-    const dim3 grid((unsigned)l.tiles_x, (unsigned)l.tiles_y), block(SPLAT_THREADS);
+    const dim3 grid = l.tile_grid(), block(SPLAT_THREADS);
     // 16-channel tiles of a pass: 1 or 4
     with_step<1, 4>(CC / 16, [&](auto nt) {
         with_flags([&](auto f32, auto v, auto o16) {
             for (int c0 = 0; c0 < C; c0 += CC)
-                hipLaunchKernelGGL((k_splat_render<nt.value, f32.value, v.value, o16.value>), grid, block, 0, stream,
-                                   (const SplatRec *)(ws + l.rec), (const int4 *)(ws + l.box), (const int *)(ws + l.count),
-                                   (const long long *)(ws + l.offs), (const int *)(ws + l.vals1),
-                                   (const longlong2 *)(ws + l.ranges), (const long long *)(ws + l.total), (long long)capacity,
-                                   rows, C, (long long)row_stride, c0, W, H, out, (long long)pix_stride,
-                                   c0 == 0 ? alpha : nullptr, (int *)status);
+                hipLaunchKernelGGL((k_splat_render<nt.value, f32.value, v.value, o16.value>), grid, block, 0, stream, l.rec,
+                                   l.box, l.count, l.offs, l.vals1, l.ranges, l.total, (long long)capacity, rows, C,
+                                   (long long)row_stride, c0, W, H, out, (long long)pix_stride, c0 == 0 ? alpha : nullptr,
+                                   (int *)status);
         }, !rows_is_f16, vec, out_is_f16 != 0);
     });
     VP_HIP(hipGetLastError());
@@ -1028,23 +993,16 @@ int vp_aggregate_view_f16(float *view_sum, int32_t *view_count, void *run16, int
 // ------------------------------------------------------------------------------------------------
 size_t vp_label_scores_workspace_bytes(int W, int H)
 {
-    if (W < 1 || W > EVAL_MAX_WH || H < 1 || H > EVAL_MAX_WH) return 0;
+    if (W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH) return 0;
     // the prediction's band | the target's band | the row pass's ok map, one byte per pixel each
     return 3 * align256((size_t)W * H);
-}
-
-static int eval_check_image(int W, int H)
-{
-    if (W < 1 || W > EVAL_MAX_WH || H < 1 || H > EVAL_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, EVAL_MAX_WH);
-    return VP_OK;
 }
 
 int vp_label_boundary(const int32_t *labels, int W, int H, int radius, uint8_t *band, void *workspace, size_t workspace_bytes,
                       void *stream_)
 {
     if (!labels || !band) return fail(VP_EINVAL, "null pointer argument (labels or band)");
-    if (int rc = eval_check_image(W, H)) return rc;
+    if (int rc = check_image(W, H)) return rc;
     if (radius < 1 || radius > EVAL_MAX_RADIUS) return fail(VP_EINVAL, "radius = %d outside [1, %d]", radius, EVAL_MAX_RADIUS);
     if (int rc = check_workspace(workspace, workspace_bytes, vp_label_scores_workspace_bytes(W, H))) return rc;
     unsigned char *ok = (unsigned char *)workspace + 2 * align256((size_t)W * H);
@@ -1058,7 +1016,7 @@ int vp_label_scores(const int32_t *pred, const int32_t *target, int W, int H, in
                     void *stream_)
 {
     if (!pred || !target || !confusion || !skipped) return fail(VP_EINVAL, "null pointer argument (pred, target, confusion or skipped)");
-    if (int rc = eval_check_image(W, H)) return rc;
+    if (int rc = check_image(W, H)) return rc;
     if (P < 1 || P > EVAL_MAX_P) return fail(VP_EINVAL, "P = %d outside [1, %d]", P, EVAL_MAX_P);
     if (radius < 0 || radius > EVAL_MAX_RADIUS) return fail(VP_EINVAL, "radius = %d outside [0, %d]", radius, EVAL_MAX_RADIUS);
     if (radius > 0 && (!bnd_inter || !bnd_union)) return fail(VP_EINVAL, "radius > 0 needs bnd_inter and bnd_union");
@@ -1091,7 +1049,7 @@ int vp_label_scores(const int32_t *pred, const int32_t *target, int W, int H, in
 // ------------------------------------------------------------------------------------------------
 size_t vp_feature_loss_workspace_bytes(int W, int H)
 {
-    if (W < 1 || W > FLOSS_MAX_WH || H < 1 || H > FLOSS_MAX_WH) return 0;
+    if (W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH) return 0;
     return floss_bytes((long long)W * H);
 }
 
@@ -1101,8 +1059,7 @@ static int floss_check_maps(const void *image, int image_is_f16, int64_t pix_str
     if (!image || !target_f16) return fail(VP_EINVAL, "null pointer argument (image or target_f16)");
     if (image_is_f16 != 0 && image_is_f16 != 1) return fail(VP_EINVAL, "image_is_f16 = %d is neither 0 nor 1", image_is_f16);
     if (C < 1 || C > FLOSS_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, FLOSS_MAX_C);
-    if (W < 1 || W > FLOSS_MAX_WH || H < 1 || H > FLOSS_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, FLOSS_MAX_WH);
+    if (int rc = check_image(W, H)) return rc;
     if (pix_stride < C) return fail(VP_EINVAL, "pix_stride %lld < C = %d", (long long)pix_stride, C);
     if (tgt_stride < C) return fail(VP_EINVAL, "tgt_stride %lld < C = %d", (long long)tgt_stride, C);
     return check_workspace(workspace, workspace_bytes, floss_bytes((long long)W * H));
@@ -1180,7 +1137,7 @@ int vp_feature_loss_gradient(const void *image, int image_is_f16, int64_t pix_st
 // ------------------------------------------------------------------------------------------------
 size_t vp_proto_contrast_workspace_bytes(int D, int W, int H)
 {
-    if (D < 1 || D > PROTO_MAX_D || W < 1 || W > PROTO_MAX_WH || H < 1 || H > PROTO_MAX_WH) return 0;
+    if (D < 1 || D > PROTO_MAX_D || W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH) return 0;
     return proto_carve(nullptr, D, (long long)W * H).bytes;
 }
 
@@ -1188,8 +1145,7 @@ static int proto_check(const float *image, int D, int W, int H, const int32_t *i
 {
     if (!image || !ids) return fail(VP_EINVAL, "null pointer argument (image or ids)");
     if (D < 1 || D > PROTO_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, PROTO_MAX_D);
-    if (W < 1 || W > PROTO_MAX_WH || H < 1 || H > PROTO_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, PROTO_MAX_WH);
+    if (int rc = check_image(W, H)) return rc;
     return check_workspace(workspace, workspace_bytes, vp_proto_contrast_workspace_bytes(D, W, H));
 }
 
@@ -1271,7 +1227,7 @@ int vp_proto_contrast_gradient(const float *image, int D, int W, int H, const in
 // ------------------------------------------------------------------------------------------------
 size_t vp_photo_loss_workspace_bytes(int C, int W, int H)
 {
-    if (C < 1 || C > PHOTO_MAX_C || W < 1 || W > PHOTO_MAX_WH || H < 1 || H > PHOTO_MAX_WH) return 0;
+    if (C < 1 || C > PHOTO_MAX_C || W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH) return 0;
     return photo_bytes(C, W, H);
 }
 
@@ -1280,8 +1236,7 @@ static int photo_check(const float *image, const float *target, int C, int W, in
 {
     if (!image || !target) return fail(VP_EINVAL, "null pointer argument (image or target)");
     if (C < 1 || C > PHOTO_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, PHOTO_MAX_C);
-    if (W < 1 || W > PHOTO_MAX_WH || H < 1 || H > PHOTO_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, PHOTO_MAX_WH);
+    if (int rc = check_image(W, H)) return rc;
     if (!workspace && !need_workspace) return VP_OK;
     return check_workspace(workspace, workspace_bytes, photo_bytes(C, W, H));
 }
@@ -1331,8 +1286,8 @@ int vp_densify_accumulate(const float *grad_screen, int64_t n_gaussians, int W, 
                           float eps2d, float *grad_accum, int32_t *denom, float *max_radius, const void *workspace,
                           size_t workspace_bytes, void *stream_)
 {
-    if (int rc = splat_check_count(n_gaussians)) return rc;
-    if (int rc = splat_check_image(W, H)) return rc;
+    if (int rc = check_count("n_gaussians", n_gaussians)) return rc;
+    if (int rc = check_image(W, H)) return rc;
     if (n_gaussians > 0 && (!grad_screen || !grad_accum || !denom))
         return fail(VP_EINVAL, "null pointer argument (grad_screen, grad_accum or denom)");
     if (!std::isfinite(scale)) return fail(VP_EINVAL, "scale = %g is not finite", (double)scale);
@@ -1345,16 +1300,13 @@ int vp_densify_accumulate(const float *grad_screen, int64_t n_gaussians, int W, 
         cam.eps2d = eps2d;
         cam.W = W; cam.H = H;
     }
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
     SplatLayout l;
-    if (!splat_layout(n_gaussians, W, H, 0, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, n_gaussians, W, H, 0, l)) return rc;
     if (n_gaussians == 0) return VP_OK;
     const double hw = 0.5 * (double)W, hh = 0.5 * (double)H;
     hipLaunchKernelGGL(k_densify_accumulate, dim3((unsigned)((n_gaussians + DENSIFY_THREADS - 1) / DENSIFY_THREADS)),
                        dim3(DENSIFY_THREADS), 0, (hipStream_t)stream_, grad_screen, (long long)n_gaussians, hw * hw, hh * hh,
-                       (double)scale, means, quats, scales, cam, (const int *)((const char *)workspace + l.count), grad_accum,
-                       (int *)denom, max_radius);
+                       (double)scale, means, quats, scales, cam, l.count, grad_accum, (int *)denom, max_radius);
     VP_HIP(hipGetLastError());
     return VP_OK;
 }
@@ -1379,10 +1331,8 @@ int vp_densify_plan(const float *grad_accum, const int32_t *denom, const float *
     if (!(grad_threshold > 0.0f)) return fail(VP_EINVAL, "grad_threshold must be > 0 (got %g)", (double)grad_threshold);
     if (std::isnan(size_threshold) || std::isnan(min_opacity) || std::isnan(max_screen_size) || std::isnan(max_world_size))
         return fail(VP_EINVAL, "size_threshold, min_opacity, max_screen_size and max_world_size must not be NaN");
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
     DensifyLayout l;
-    if (!densify_layout(n_gaussians, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, l, [&] { return densify_layout(n_gaussians, l); })) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     char *ws = (char *)workspace;
     unsigned char *flags = (unsigned char *)(ws + l.flags);
@@ -1550,23 +1500,22 @@ int vp_sh_colors_backward(const float *f_dc, const float *f_rest, const float *m
 
 // ------------------------------------------------------------------------------------------------
 // Triangle-mesh rasterizer (vp_mesh.h, declared in voxproj_mesh.h).  Every check is host arithmetic and comes before
-// mesh_layout (rocprim's scratch sizes depend on the device) and before any launch.
+// open_workspace (rocprim's scratch sizes depend on the device) and before any launch.
 // ------------------------------------------------------------------------------------------------
 static int mesh_check_shape(int64_t n_faces, int W, int H, int64_t capacity)
 {
-    if (n_faces < 0 || n_faces > INT32_MAX) return fail(VP_EINVAL, "n_faces = %lld outside [0, 2^31 - 1]", (long long)n_faces);
-    if (int rc = splat_check_image(W, H)) return rc;
-    if (capacity < 0 || capacity > INT32_MAX) return fail(VP_EINVAL, "capacity = %lld outside [0, 2^31 - 1]", (long long)capacity);
-    return VP_OK;
+    if (int rc = check_count("n_faces", n_faces)) return rc;
+    if (int rc = check_image(W, H)) return rc;
+    return check_count("capacity", capacity);
 }
 
 size_t vp_mesh_workspace_bytes(int64_t n_faces, int W, int H, int64_t capacity)
 {
-    if (n_faces < 0 || n_faces > INT32_MAX || W < 1 || W > SPLAT_MAX_WH || H < 1 || H > SPLAT_MAX_WH || capacity < 0 ||
+    if (n_faces < 0 || n_faces > INT32_MAX || W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH || capacity < 0 ||
         capacity > INT32_MAX)
         return 0;
     MeshLayout l;
-    return mesh_layout(n_faces, W, H, capacity, l) ? l.bytes : 0;
+    return mesh_layout(nullptr, n_faces, W, H, capacity, l) ? l.bytes : 0;
 }
 
 int vp_mesh_project(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const float *viewmat,
@@ -1574,41 +1523,27 @@ int vp_mesh_project(const float *verts, int64_t n_verts, const int32_t *faces, i
                     int64_t *n_isect, int32_t *counters, void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (int rc = mesh_check_shape(n_faces, W, H, 0)) return rc;
-    if (n_verts < 0 || n_verts > INT32_MAX) return fail(VP_EINVAL, "n_verts = %lld outside [0, 2^31 - 1]", (long long)n_verts);
+    if (int rc = check_count("n_verts", n_verts)) return rc;
     if (n_faces > 0 && (!faces || (n_verts > 0 && !verts))) return fail(VP_EINVAL, "null pointer argument (verts or faces)");
     SplatCam sc;
     if (int rc = splat_check_camera(viewmat, fx, fy, cx, cy, sc)) return rc;
     if (!(near_plane > 0.0f) || !(far_plane > near_plane) || !std::isfinite(far_plane))
         return fail(VP_EINVAL, "need 0 < near < far, both finite (got %g %g)", (double)near_plane, (double)far_plane);
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
     MeshLayout l;
-    if (!mesh_layout(n_faces, W, H, 0, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, n_faces, W, H, 0, l)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
     MeshCam cam;
     for (int k = 0; k < 12; ++k) cam.r[k] = sc.r[k];
     cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy; cam.near_z = near_plane; cam.far_z = far_plane;
     cam.W = W; cam.H = H;
-    long long *total = (long long *)(ws + l.total), *offs = (long long *)(ws + l.offs);
     hipLaunchKernelGGL(k_mesh_project, dim3((unsigned)l.n_blocks), dim3(256), 0, stream, verts, (long long)n_verts,
-                       (const int *)faces, (long long)n_faces, cam, (MeshCam *)(ws + l.cam), (MeshRec *)(ws + l.rec),
-                       (int4 *)(ws + l.box), (int *)(ws + l.count), (int *)(ws + l.part));
+                       (const int *)faces, (long long)n_faces, cam, l.cam, l.rec, l.box, l.count, l.part);
     VP_HIP(hipGetLastError());
     if (counters) {
-        hipLaunchKernelGGL(k_mesh_counters, dim3(1), dim3(256), 0, stream, (const int *)(ws + l.part), l.n_blocks,
-                           (int *)counters);
+        hipLaunchKernelGGL(k_mesh_counters, dim3(1), dim3(256), 0, stream, l.part, l.n_blocks, (int *)counters);
         VP_HIP(hipGetLastError());
     }
-    if (n_faces > 0) {
-        size_t tmp = l.scan_bytes;
-        VP_HIP(rocprim::inclusive_scan(ws + l.scan_tmp, tmp, (const int *)(ws + l.count), offs, (size_t)n_faces,
-                                       rocprim::plus<long long>(), stream));
-    }
-    hipLaunchKernelGGL(k_splat_total, dim3(1), dim3(1), 0, stream, (const long long *)offs, (long long)n_faces, total,
-                       (long long *)n_isect);
-    VP_HIP(hipGetLastError());
-    return VP_OK;
+    return tile_scan(l, n_faces, (long long *)n_isect, stream);
 }
 
 int vp_mesh_rasterize(const uint8_t *vertex_labels, const int32_t *faces, int64_t n_faces, int W, int H, int64_t capacity,
@@ -1618,37 +1553,13 @@ int vp_mesh_rasterize(const uint8_t *vertex_labels, const int32_t *faces, int64_
     if (int rc = mesh_check_shape(n_faces, W, H, capacity)) return rc;
     if (labels && n_faces > 0 && (!vertex_labels || !faces))
         return fail(VP_EINVAL, "null pointer argument (labels needs vertex_labels and faces)");
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
     MeshLayout l;
-    if (!mesh_layout(n_faces, W, H, capacity, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, n_faces, W, H, capacity, l)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    char *ws = (char *)workspace;
-    const long long n_tiles = (long long)l.tiles_x * l.tiles_y;
-    const long long *total = (const long long *)(ws + l.total);
-    unsigned *k0 = (unsigned *)(ws + l.keys0), *k1 = (unsigned *)(ws + l.keys1);
-    int *v0 = (int *)(ws + l.vals0), *v1 = (int *)(ws + l.vals1);
-    longlong2 *ranges = (longlong2 *)(ws + l.ranges);
-    // emit: one thread per face (at least one workgroup, which also pads [total, capacity) and raises the status)
-    hipLaunchKernelGGL(k_mesh_emit, dim3((unsigned)l.n_blocks), dim3(256), 0, stream, (const int4 *)(ws + l.box),
-                       (const long long *)(ws + l.offs), (long long)n_faces, l.tiles_x, (unsigned)n_tiles, total,
-                       (long long)capacity, k0, v0, (int *)status);
-    VP_HIP(hipGetLastError());
-    if (capacity > 0) {
-        size_t tmp = l.sort_bytes;
-        VP_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, tmp, k0, k1, v0, v1, (size_t)capacity, 0u, (unsigned)l.end_bit,
-                                         stream));
-    }
-    VP_HIP(hipMemsetAsync(ranges, 0, (size_t)n_tiles * sizeof(longlong2), stream));
-    if (capacity > 0) {
-        hipLaunchKernelGGL(k_mesh_ranges, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, stream, k1, total,
-                           (long long)capacity, ranges);
-        VP_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_mesh_tiles, dim3((unsigned)l.tiles_x, (unsigned)l.tiles_y), dim3(SPLAT_THREADS), 0, stream,
-                       (const MeshRec *)(ws + l.rec), (const int *)v1, (const longlong2 *)ranges, total, (long long)capacity,
-                       (const MeshCam *)(ws + l.cam), (const int *)faces, (const unsigned char *)vertex_labels,
-                       (int *)face_ids, depth, (unsigned char *)labels);
+    if (int rc = tile_sort(l, nullptr, 0, n_faces, capacity, status, stream)) return rc;
+    hipLaunchKernelGGL(k_mesh_tiles, l.tile_grid(), dim3(SPLAT_THREADS), 0, stream, l.rec, l.vals1, l.ranges, l.total,
+                       (long long)capacity, l.cam, (const int *)faces, (const unsigned char *)vertex_labels, (int *)face_ids,
+                       depth, (unsigned char *)labels);
     VP_HIP(hipGetLastError());
     return VP_OK;
 }
@@ -1664,7 +1575,7 @@ int vp_ball_count(const float *pts_sorted, const int32_t *perm, const int32_t *c
 {
     if (!pts_sorted || !perm || !cell_start || !grid_origin3 || !queries || !count)
         return fail(VP_EINVAL, "null pointer argument (pts_sorted, perm, cell_start, grid_origin3, queries or count)");
-    if (M < 0 || M > INT32_MAX) return fail(VP_EINVAL, "M = %lld outside [0, 2^31 - 1]", (long long)M);
+    if (int rc = check_count("M", M)) return rc;
     if (!(cell_size > 0.0) || !std::isfinite(cell_size) || nx <= 0 || ny <= 0 || nz <= 0)
         return fail(VP_EINVAL, "bad grid (cell size %g, dims %d %d %d)", cell_size, nx, ny, nz);
     if ((long long)nx * ny * nz >= (1ll << 31)) return fail(VP_EINVAL, "the grid has >= 2^31 cells");
@@ -1703,16 +1614,14 @@ int vp_voxel_grid(const float *points, const uint8_t *colors, const uint8_t *kee
                   int32_t *n_voxels, float *min_corner, int32_t *status, void *workspace, size_t workspace_bytes,
                   void *stream_)
 {
-    if (N < 0 || N > INT32_MAX) return fail(VP_EINVAL, "N = %lld outside [0, 2^31 - 1]", (long long)N);
+    if (int rc = check_count("N", N)) return rc;
     if (!(voxel_size > 0.0) || !std::isfinite(voxel_size) || !((float)voxel_size > 0.0f) || !std::isfinite((float)voxel_size))
         return fail(VP_EINVAL, "voxel_size = %g must be finite and > 0 (in float32 too)", voxel_size);
     if (!n_voxels || !min_corner) return fail(VP_EINVAL, "null pointer argument (n_voxels or min_corner)");
     if (N > 0 && (!points || !colors || !centers || !voxel_colors || !counts || !voxel_index || !point_voxel))
         return fail(VP_EINVAL, "null pointer argument (points, colors, centers, voxel_colors, counts, voxel_index or point_voxel)");
-    if (int rc = splat_check_buffer(workspace, "workspace")) return rc;
     GridLayout l;
-    if (!grid_layout(N, l)) return fail(VP_EHIP, "rocprim scratch size query failed");
-    if (int rc = splat_check_size(workspace_bytes, l.bytes, "workspace")) return rc;
+    if (int rc = open_workspace(workspace, workspace_bytes, l, [&] { return grid_layout(N, l); })) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     char *ws = (char *)workspace;
     GridMeta *meta = (GridMeta *)(ws + l.meta);
@@ -1759,7 +1668,7 @@ int vp_voxel_grid(const float *points, const uint8_t *colors, const uint8_t *kee
 // ------------------------------------------------------------------------------------------------
 size_t vp_codebook_workspace_bytes(int D, int K, int W, int H)
 {
-    if (D < 1 || D > CB_MAX_D || K < 1 || K > CB_MAX_K || W < 1 || W > CB_MAX_WH || H < 1 || H > CB_MAX_WH) return 0;
+    if (D < 1 || D > CB_MAX_D || K < 1 || K > CB_MAX_K || W < 1 || W > VP_MAX_WH || H < 1 || H > VP_MAX_WH) return 0;
     // sized for min(tiles, 256) workgroups, which the plan never exceeds: the size does not shrink when the image grows
     return cb_carve(nullptr, D, K, (int)std::min<long long>(cb_plan(W, H).tiles, CB_GRID)).bytes;
 }
@@ -1770,8 +1679,7 @@ static int cb_check(const float *image, int D, int W, int H, const int32_t *ids,
     if (!image || !ids || !codebook) return fail(VP_EINVAL, "null pointer argument (image, ids or codebook)");
     if (D < 1 || D > CB_MAX_D) return fail(VP_EINVAL, "D = %d outside [1, %d]", D, CB_MAX_D);
     if (K < 1 || K > CB_MAX_K) return fail(VP_EINVAL, "K = %d outside [1, %d]", K, CB_MAX_K);
-    if (W < 1 || W > CB_MAX_WH || H < 1 || H > CB_MAX_WH)
-        return fail(VP_EINVAL, "image %d x %d outside [1, %d]^2", W, H, CB_MAX_WH);
+    if (int rc = check_image(W, H)) return rc;
     return check_workspace(workspace, workspace_bytes, vp_codebook_workspace_bytes(D, K, W, H));
 }
 

@@ -27,7 +27,6 @@
 #pragma once
 
 constexpr int CB_MAX_D = 64;
-constexpr int CB_MAX_WH = 32768;
 constexpr int CB_IDS = VP_PROTO_MAX_IDS;
 constexpr int CB_MAX_K = VP_CODEBOOK_MAX_CODES;
 constexpr int CB_THREADS = 256;

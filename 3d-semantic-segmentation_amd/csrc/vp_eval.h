@@ -18,7 +18,6 @@
 // Both count the skipped pixels and, when the two bands are given, the boundary intersections and unions per class (LDS).
 #pragma once
 
-constexpr int EVAL_MAX_WH = 32768;
 constexpr int EVAL_MAX_P = 256;
 constexpr int EVAL_MAX_RADIUS = 4096;
 constexpr int EVAL_LDS_P = 64;            // P*P u32 = 16 KiB of LDS at most

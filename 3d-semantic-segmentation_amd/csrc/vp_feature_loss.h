@@ -19,7 +19,6 @@
 #pragma once
 
 constexpr int FLOSS_MAX_C = 4096;
-constexpr int FLOSS_MAX_WH = 32768;
 constexpr int FLOSS_THREADS = 256;        // = pixels per workgroup
 constexpr int FLOSS_HEADER = 256;         // bytes: word 0 = the bit pattern of the map's maximum
 

@@ -1,6 +1,6 @@
 // vp_mesh.h -- triangle-mesh rasterizer: per pixel the nearest face of an annotated mesh, its depth and its label (the
-// ground-truth maps evaluate_label_maps.py scores against).  Included by voxproj.hip only, after vp_splat.h (it reuses
-// SPLAT_TILE, SPLAT_THREADS, SPLAT_MAX_WH, splat_bits and k_splat_total).
+// ground-truth maps evaluate_label_maps.py scores against).  Included by voxproj.hip only, after vp_tilebin.h (the tile
+// binning) and vp_splat.h (SPLAT_TILE, SPLAT_THREADS).
 #pragma once
 
 namespace {
@@ -20,9 +20,8 @@ namespace {
 //   boxes.  A face with a vertex index outside [0, n_verts), a non-finite vertex or a snapped coordinate that is non-finite
 //   or beyond +-2^29 has no tiles; its kind is counted per workgroup by ballot (no atomics) and k_mesh_counters adds the
 //   workgroups' counts to counters[3].
-// k_mesh_emit     after an inclusive scan of the tile counts (rocprim, int64): key = tile, value = face, in face order; the
-//   slots [total, capacity) get the key n_tiles.  rocprim::radix_sort_pairs is stable: each tile's run is in ascending face
-//   index.  k_mesh_ranges: [start, end) of every tile's run.
+// tile_sort       the tile binning of vp_tilebin.h with 32-bit keys, the tile alone: each tile's run is in ascending face
+//   index.
 // k_mesh_tiles    one 256-thread workgroup per 16x16 tile, one pixel per thread, the pixel's depth and face in registers; the
 //   tile's run is staged through LDS in batches of MESH_BATCH records (104 bytes each; every thread reads the same record:
 //   broadcasts).  Per (pixel, sub-triangle): three edge values E = dx (P.y - a.y) - dy (P.x - a.x) with P = (256 j + 128,
@@ -30,8 +29,7 @@ namespace {
 //   E == 0 on an edge with dy < 0 or dy == 0 and dx > 0.  A covered sample divides once: z = d / ((n.x rx + n.y ry) + n.z),
 //   NaN dropped, clamped to the face's range, kept inside [near, far], rounded to fp32; the strict < keeps the lowest face
 //   index on equal depths.  Epilogue: face id (-1), depth (0), majority label of the face's three vertex labels (255).
-// Every kernel after the scan reads the device total first: a total above the capacity writes nothing (the emit kernel
-// raises *status).
+// Every kernel after the scan reads the device total first, as vp_tilebin.h states it.
 // ------------------------------------------------------------------------------------------------
 constexpr int MESH_BATCH = 256;                  // records per LDS staging: 26 KiB
 constexpr double MESH_GUARD = 536870912.0;       // 2^29 sub-pixel units
@@ -183,48 +181,6 @@ __global__ __launch_bounds__(256) void k_mesh_counters(const int *__restrict__ p
     if (tid < 3) counters[tid] += s_sum[0][tid];
 }
 
-__global__ __launch_bounds__(256) void k_mesh_emit(const int4 *__restrict__ box, const long long *__restrict__ offs, long long n,
-                                                   int tiles_x, unsigned n_tiles, const long long *total_p, long long capacity,
-                                                   unsigned *__restrict__ keys, int *__restrict__ vals, int *status)
-{
-    const long long total = *total_p;
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (total > capacity) {
-        if (gid == 0 && status) *status = 1;
-        return;
-    }
-    if (gid < n) {
-        const int4 b = box[gid];
-        long long k = offs[gid] - (long long)(b.z - b.x + 1) * (b.w - b.y + 1);
-        for (int ty = b.y; ty <= b.w; ++ty)
-            for (int tx = b.x; tx <= b.z; ++tx, ++k) {
-                keys[k] = (unsigned)(ty * tiles_x + tx);
-                vals[k] = (int)gid;
-            }
-    }
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long k = total + gid; k < capacity; k += stride) {
-        keys[k] = n_tiles;
-        vals[k] = 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_mesh_ranges(const unsigned *__restrict__ keys, const long long *total_p,
-                                                     long long capacity, longlong2 *__restrict__ ranges)
-{
-    const long long total = *total_p;
-    if (total > capacity) return;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const long long tile = keys[i];
-    const long long prev = i > 0 ? (long long)keys[i - 1] : -1;
-    if (tile != prev) {
-        ranges[tile].x = i;
-        if (prev >= 0) ranges[prev].y = i;
-    }
-    if (i == total - 1) ranges[tile].y = total;
-}
-
 // Is the sample (PX, PY) covered by the positively oriented sub-triangle p = x0 y0 x1 y1 x2 y2?  Every difference is below
 // 2^31 (coordinates within +-2^29, samples within [0, 2^23]), every product below 2^61.
 __device__ inline bool mesh_covers(const int *p, int PX, int PY)
@@ -307,48 +263,26 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_mesh_tiles(
     }
 }
 
-// workspace layout of one (n_faces, W, H, capacity); the part before `keys0` does not depend on the capacity
-struct MeshLayout {
-    size_t total, cam, rec, box, count, offs, part, scan_tmp, keys0, keys1, vals0, vals1, sort_tmp, ranges, bytes;
-    size_t scan_bytes, sort_bytes;
+// workspace of one (n_faces, W, H, capacity): the tile bins with the camera and the records after `total`, and the
+// workgroups' drop counts (n_blocks of them, k_mesh_project's grid) after `offs`
+struct MeshLayout : TileBins<unsigned> {
+    MeshCam *cam;
+    MeshRec *rec;
+    int *part;
     long long n_blocks;
-    int tiles_x, tiles_y, end_bit;
 };
 
-// host only: the rocprim calls with a NULL scratch pointer only report their scratch sizes
-inline bool mesh_layout(long long n, int W, int H, long long capacity, MeshLayout &l)
+inline bool mesh_layout(char *base, long long n, int W, int H, long long capacity, MeshLayout &l)
 {
-    l.tiles_x = (W + SPLAT_TILE - 1) / SPLAT_TILE;
-    l.tiles_y = (H + SPLAT_TILE - 1) / SPLAT_TILE;
-    const long long n_tiles = (long long)l.tiles_x * l.tiles_y;
-    l.end_bit = splat_bits(n_tiles);                      // the padding key n_tiles needs the bit of n_tiles too
     l.n_blocks = (std::max<long long>(n, 1) + 255) / 256;
-    l.scan_bytes = 0;
-    l.sort_bytes = 0;
-    if (n > 0 && rocprim::inclusive_scan(nullptr, l.scan_bytes, (const int *)nullptr, (long long *)nullptr, (size_t)n,
-                                         rocprim::plus<long long>()) != hipSuccess)
-        return false;
-    if (capacity > 0 && rocprim::radix_sort_pairs(nullptr, l.sort_bytes, (const unsigned *)nullptr, (unsigned *)nullptr,
-                                                  (const int *)nullptr, (int *)nullptr, (size_t)capacity, 0u,
-                                                  (unsigned)l.end_bit) != hipSuccess)
-        return false;
-    size_t off = 0;
-    l.total = off;    off += align256(sizeof(long long));
-    l.cam = off;      off += align256(sizeof(MeshCam));
-    l.rec = off;      off += align256((size_t)n * sizeof(MeshRec));
-    l.box = off;      off += align256((size_t)n * sizeof(int4));
-    l.count = off;    off += align256((size_t)n * sizeof(int));
-    l.offs = off;     off += align256((size_t)n * sizeof(long long));
-    l.part = off;     off += align256((size_t)l.n_blocks * 3 * sizeof(int));
-    l.scan_tmp = off; off += align256(l.scan_bytes);
-    l.keys0 = off;    off += align256((size_t)capacity * sizeof(unsigned));
-    l.keys1 = off;    off += align256((size_t)capacity * sizeof(unsigned));
-    l.vals0 = off;    off += align256((size_t)capacity * sizeof(int));
-    l.vals1 = off;    off += align256((size_t)capacity * sizeof(int));
-    l.sort_tmp = off; off += align256(l.sort_bytes);
-    l.ranges = off;   off += align256((size_t)n_tiles * sizeof(longlong2));
-    l.bytes = off;
-    return true;
+    return tile_layout(base, n, W, H, capacity, l, [&](Sections &s, int at) {
+        if (at == 0) {
+            s.place(l.cam, sizeof(MeshCam));
+            s.place(l.rec, (size_t)n * sizeof(MeshRec));
+        } else {
+            s.place(l.part, (size_t)l.n_blocks * 3 * sizeof(int));
+        }
+    });
 }
 
 }  // namespace

@@ -26,7 +26,6 @@
 #pragma once
 
 constexpr int PHOTO_MAX_C = 64;
-constexpr int PHOTO_MAX_WH = 32768;
 constexpr int PHOTO_T = 32;                               // the tile
 constexpr int PHOTO_R = 5;                                // the window's radius
 constexpr int PHOTO_TAPS = 2 * PHOTO_R + 1;

@@ -21,7 +21,6 @@
 #pragma once
 
 constexpr int PROTO_MAX_D = 64;
-constexpr int PROTO_MAX_WH = 32768;
 constexpr int PROTO_IDS = VP_PROTO_MAX_IDS;
 constexpr int PROTO_THREADS = 256;        // = pixels per tile = ids
 constexpr int PROTO_GRID = 768;           // workgroups of the three reads, at most (a constant: the order of a sum is fixed)

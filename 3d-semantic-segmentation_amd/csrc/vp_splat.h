@@ -2,11 +2,6 @@
 // with a fused argmax label / softmax-confidence epilogue.  Included by voxproj.hip only.
 #pragma once
 
-#if !__has_include(<rocprim/device/device_radix_sort.hpp>)
-#error "vp_splat.h needs rocPRIM's headers (ROCm's include/rocprim): the Gaussian splatting sort is rocprim::radix_sort_pairs"
-#endif
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <type_traits>
 
 namespace {
@@ -24,11 +19,8 @@ namespace {
 //   quaternion / scale / opacity culls the Gaussian and adds 1 to *n_nonfinite.
 //   Support box: sigma <= ln(255 o) holds inside |dx| <= sqrt(2 ln(255 o) Sigma2_00) (likewise y); the pixel range adds one
 //   pixel on each side, clipped to the image, and its 16x16 tiles are the Gaussian's tiles.
-// k_splat_emit      one thread per Gaussian, after an inclusive scan of the tile counts (rocprim, int64): key
-//   tile << 32 | bits(z) (z > 0, so the bits order like the floats) and value = Gaussian index, in index order; slots
-//   [total, capacity) get the key n_tiles << 32 (after every real tile).  rocprim::radix_sort_pairs is stable and sorts bits
-//   [0, 32 + bits(n_tiles)): each tile's run is in (z, index) order.
-// k_splat_ranges    one thread per sorted key: [start, end) of every tile's run.
+// splat_sort        the tile binning of vp_tilebin.h with 64-bit keys tile << 32 | bits(z) (z > 0, so the bits order like the
+//   floats): each tile's run is in (z, index) order.  A Gaussian without tiles has no key, and its record is not read.
 // k_splat_blend<DT> one 256-thread workgroup per 16x16 tile, one pixel per thread, DT >= D accumulators in registers.  The
 //   tile's run is staged through LDS in batches of SPLAT_BATCH(DT) Gaussians (records, then the feature rows zero-padded to
 //   DT).  Per visited pair: sigma, one exp, the 1/255 and 1e-4 tests (splat_pair, the one statement of them) and DT FMAs
@@ -44,13 +36,11 @@ namespace {
 //   the target is outside [0, D)); pixel_loss = w l; {w l, w} go through the tree and the ordered sum of vp_reduce.h: slot
 //   16 ty + tx of a tile is its pixel (tx, ty), zeros outside the image; one pair per tile, tiles in row-major index.  The tree
 //   runs in the feature rows' LDS; the ordered sum is guarded by the device total like every kernel after the scan.
-// Every kernel after the scan reads the device total first: a total above the workspace's capacity writes nothing (the
-// emit kernel raises *status instead), so a too-small workspace never leaves a partial image.
+// Every kernel after the scan reads the device total first, as vp_tilebin.h states it.
 // ------------------------------------------------------------------------------------------------
-constexpr int SPLAT_TILE = 16;
+constexpr int SPLAT_TILE = TILE_PX;
 constexpr int SPLAT_THREADS = SPLAT_TILE * SPLAT_TILE;
 constexpr int SPLAT_MAX_D = 64;
-constexpr int SPLAT_MAX_WH = 32768;
 
 __host__ __device__ constexpr int splat_batch(int DT) { return DT <= 32 ? 256 : 128; }   // LDS: 41 KiB at DT 32, 37 KiB at 64
 
@@ -178,60 +168,6 @@ __global__ __launch_bounds__(256) void k_splat_project(const float *__restrict__
     rec[i] = g;
     box[i] = b;
     count[i] = cnt;
-}
-
-// total = the scan's last element (0 without Gaussians), into the workspace and, when given, the caller's int64
-__global__ void k_splat_total(const long long *__restrict__ offs, long long n, long long *total, long long *n_isect)
-{
-    const long long t = n > 0 ? offs[n - 1] : 0;
-    *total = t;
-    if (n_isect) *n_isect = t;
-}
-
-__global__ __launch_bounds__(256) void k_splat_emit(const SplatRec *__restrict__ rec, const int4 *__restrict__ box,
-                                                    const long long *__restrict__ offs, long long n, int tiles_x,
-                                                    long long n_tiles, const long long *total_p, long long capacity,
-                                                    unsigned long long *__restrict__ keys, int *__restrict__ vals, int *status)
-{
-    const long long total = *total_p;
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (total > capacity) {
-        if (gid == 0 && status) *status = 1;
-        return;
-    }
-    if (gid < n) {
-        const int4 b = box[gid];
-        long long k = offs[gid] - (long long)(b.z - b.x + 1) * (b.w - b.y + 1);
-        if (b.z >= b.x) {
-            const unsigned long long zb = __float_as_uint(rec[gid].z);
-            for (int ty = b.y; ty <= b.w; ++ty)
-                for (int tx = b.x; tx <= b.z; ++tx, ++k) {
-                    keys[k] = ((unsigned long long)(ty * tiles_x + tx) << 32) | zb;
-                    vals[k] = (int)gid;
-                }
-        }
-    }
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long k = total + gid; k < capacity; k += stride) {
-        keys[k] = (unsigned long long)n_tiles << 32;
-        vals[k] = 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_splat_ranges(const unsigned long long *__restrict__ keys, const long long *total_p,
-                                                      long long capacity, longlong2 *__restrict__ ranges)
-{
-    const long long total = *total_p;
-    if (total > capacity) return;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const long long tile = (long long)(keys[i] >> 32);
-    const long long prev = i > 0 ? (long long)(keys[i - 1] >> 32) : -1;
-    if (tile != prev) {
-        ranges[tile].x = i;
-        if (prev >= 0) ranges[prev].y = i;
-    }
-    if (i == total - 1) ranges[tile].y = total;
 }
 
 // What the loss variants of the blend kernels read and write besides the images (vp_splat_rasterize_loss,
@@ -420,7 +356,7 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat_blend(
 // activated opacities o, through the branch the forward took.  It reads what vp_splat_rasterize left in the workspace (rec,
 // box, count, offs, the sorted values, the tile ranges, the device total) and writes per-(tile, Gaussian) partials of D + 1
 // floats into its own scratch, at the Gaussian's emission slot for the tile:  slot = offs[g] - count[g] +
-// (ty - b.y)(b.z - b.x + 1) + (tx - b.x), the position k_splat_emit gave the pair.  Every slot of [0, total) is written
+// (ty - b.y)(b.z - b.x + 1) + (tx - b.x), the position k_tile_emit gave the pair.  Every slot of [0, total) is written
 // exactly once (a tile's run holds each of its pairs once): no zero fill, no second sort, no atomics.
 //
 // k_splat_blend_backward<DT>  one 256-thread workgroup per 16x16 tile, pixel per thread; the tile's upstream gradient G
@@ -813,51 +749,22 @@ inline size_t splat_bwd_bytes(long long capacity, int D)
     return align256((size_t)(capacity > 0 ? capacity : 1) * (size_t)(D + 1) * sizeof(float));
 }
 
-// workspace layout of one (N, W, H, capacity); the part before `keys0` does not depend on the capacity
-struct SplatLayout {
-    size_t total, rec, box, count, offs, scan_tmp, keys0, keys1, vals0, vals1, sort_tmp, ranges, bytes;
-    size_t scan_bytes, sort_bytes;
-    int tiles_x, tiles_y, end_bit;
+// workspace of one (N, W, H, capacity): the tile bins with the records after `total`
+struct SplatLayout : TileBins<unsigned long long> {
+    SplatRec *rec;
 };
 
-inline int splat_bits(long long v)
+inline bool splat_layout(char *base, long long n, int W, int H, long long capacity, SplatLayout &l)
 {
-    int b = 0;
-    while (b < 63 && (1LL << b) <= v) ++b;
-    return b;
+    return tile_layout(base, n, W, H, capacity, l, [&](Sections &s, int at) {
+        if (at == 0) s.place(l.rec, (size_t)n * sizeof(SplatRec));
+    });
 }
 
-// host only: the rocprim calls with a NULL scratch pointer only report their scratch sizes
-inline bool splat_layout(long long n, int W, int H, long long capacity, SplatLayout &l)
+// the tile sort of the projected Gaussians: the key's low word is the record's depth
+inline int splat_sort(const SplatLayout &l, long long n, long long capacity, int *status, hipStream_t stream)
 {
-    l.tiles_x = (W + SPLAT_TILE - 1) / SPLAT_TILE;
-    l.tiles_y = (H + SPLAT_TILE - 1) / SPLAT_TILE;
-    const long long n_tiles = (long long)l.tiles_x * l.tiles_y;
-    l.end_bit = 32 + splat_bits(n_tiles);                 // the padding key n_tiles << 32 needs the bit of n_tiles too
-    l.scan_bytes = 0;
-    l.sort_bytes = 0;
-    if (n > 0 && rocprim::inclusive_scan(nullptr, l.scan_bytes, (const int *)nullptr, (long long *)nullptr, (size_t)n,
-                                         rocprim::plus<long long>()) != hipSuccess)
-        return false;
-    if (capacity > 0 &&
-        rocprim::radix_sort_pairs(nullptr, l.sort_bytes, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                  (const int *)nullptr, (int *)nullptr, (size_t)capacity, 0u, (unsigned)l.end_bit) != hipSuccess)
-        return false;
-    size_t off = 0;
-    l.total = off;    off += align256(sizeof(long long));
-    l.rec = off;      off += align256((size_t)n * sizeof(SplatRec));
-    l.box = off;      off += align256((size_t)n * sizeof(int4));
-    l.count = off;    off += align256((size_t)n * sizeof(int));
-    l.offs = off;     off += align256((size_t)n * sizeof(long long));
-    l.scan_tmp = off; off += align256(l.scan_bytes);
-    l.keys0 = off;    off += align256((size_t)capacity * sizeof(unsigned long long));
-    l.keys1 = off;    off += align256((size_t)capacity * sizeof(unsigned long long));
-    l.vals0 = off;    off += align256((size_t)capacity * sizeof(int));
-    l.vals1 = off;    off += align256((size_t)capacity * sizeof(int));
-    l.sort_tmp = off; off += align256(l.sort_bytes);
-    l.ranges = off;   off += align256((size_t)n_tiles * sizeof(longlong2));
-    l.bytes = off;
-    return true;
+    return tile_sort(l, &l.rec->z, (int)(sizeof(SplatRec) / sizeof(float)), n, capacity, status, stream);
 }
 
 }  // namespace

@@ -671,10 +671,11 @@ def _splat_workspace_bytes(n_gaussians, W, H, capacity):
     return nbytes
 
 
-def _splat_forward_workspace(workspace, n_gaussians, W, H, capacity, dev):
-    """Grow the projection's workspace to ``capacity`` intersections (the projection's bytes kept): its pointer."""
-    keep = int(lib().vp_splat_workspace_bytes(int(n_gaussians), int(W), int(H), 0))
-    return workspace.ensure(_splat_workspace_bytes(n_gaussians, W, H, capacity), dev, keep=keep)
+def _splat_forward_workspace(workspace, n_gaussians, W, H, capacity, dev, size=_splat_workspace_bytes):
+    """Grow the projection's workspace to ``capacity`` intersections (the projection's bytes kept): its pointer.  ``size``:
+    the family's size function (the mesh rasterizer passes its own)."""
+    need = size(n_gaussians, W, H, capacity)
+    return workspace.ensure(need, dev, keep=size(n_gaussians, W, H, 0))
 
 
 def _filled_workspace(caller, forward, workspace, need, dev):
@@ -1599,10 +1600,8 @@ def mesh_rasterize(faces, vertex_labels, W, H, capacity, workspace, *, want_dept
         _require_tensors((vertex_labels, "vertex_labels", (torch.uint8,)))
         _require(vertex_labels.dim() == 1 and vertex_labels.device == dev, "vertex_labels must be uint8 [V] on the faces' device")
         vertex_labels = vertex_labels.contiguous()
-    keep = _mesh_workspace_bytes(F, W, H, 0)
-    _require(workspace is not None and workspace.buf is not None and workspace.buf.device == dev and workspace.capacity() >= keep,
-             "mesh_rasterize needs the workspace of a mesh_project call")
-    ptr = workspace.ensure(_mesh_workspace_bytes(F, W, H, capacity), dev, keep=keep)
+    _filled_workspace("mesh_rasterize", "mesh_project", workspace, _mesh_workspace_bytes(F, W, H, 0), dev)
+    ptr = _splat_forward_workspace(workspace, F, W, H, capacity, dev, _mesh_workspace_bytes)
     if out is None:
         out = (torch.empty((H, W), dtype=torch.int32, device=dev),
                torch.empty((H, W), dtype=torch.float32, device=dev) if want_depth else None,

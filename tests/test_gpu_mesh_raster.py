@@ -167,7 +167,7 @@ def test_more_than_65536_faces_and_counters_from_the_second_lap():
 
 
 def test_padding_beyond_two_strides_of_the_emit_kernel():
-    """k_mesh_emit pads the slots [total, capacity) with a stride of gridDim * 256 = 256 * ceil(n_faces / 256) slots: 2048 for
+    """k_tile_emit pads the slots [total, capacity) with a stride of gridDim * 256 = 256 * ceil(n_faces / 256) slots: 2048 for
     the 2028 faces of a room.  A spare capacity of 2 * 2048 + 500 gives some threads a third lap, on a workspace whose every
     byte is 0xA5: a slot left unpadded holds the key 0xA5A5A5A5, whose low bits sort it among the real ones."""
     import voxproj_host as vh
@@ -237,6 +237,32 @@ def test_spare_capacity_recycled_workspace_and_second_run_give_the_same_bits():
                          counters=want["counters"]))
     for r in runs:
         _same(r, want)
+
+
+@pytest.mark.parametrize("size,n_tiles", [((1, 1), 1), ((16, 16), 1), ((17, 16), 2), ((64, 64), 16), ((128, 32), 16),
+                                          ((61, 47), 12), ((256, 256), 256)])
+def test_tile_counts_around_the_extra_key_bit(size, n_tiles):
+    """The padding key of the sort is n_tiles, which needs a bit that n_tiles - 1 does not need exactly when n_tiles is a
+    power of two: an end bit one short would sort the padding of a spare capacity among the keys of tile 0.  Exact capacity,
+    then 300 spare slots on a workspace whose every byte is 0xA5; both equal the twin bit for bit."""
+    import voxproj_host as vh
+    W, H = size
+    tx, ty = (W + 15) // 16, (H + 15) // 16
+    assert tx * ty == n_tiles
+    s, want = _twin(f"room:1,{W},{H}")
+    last = want["face_ids"][16 * (ty - 1):, 16 * (tx - 1):]
+    assert last.size > 0 and (last >= 0).all(), "the last tile should hold drawn faces"
+    dirty = vh.SplatWorkspace()
+    dirty.ensure(8 << 20, DEV)
+    dirty.buf.fill_(0xA5)
+    total = None
+    for ws, spare in ((vh.SplatWorkspace(), 0), (dirty, 300)):
+        (tv, tf, tl), n = _project(s, ws)
+        assert n >= n_tiles and total in (None, n)
+        total = n
+        ids, depth, labels = vh.mesh_rasterize(tf, tl, W, H, n + spare, ws)
+        _same(dict(face_ids=ids.cpu().numpy(), depth=depth.cpu().numpy(), labels=labels.cpu().numpy(),
+                   counters=want["counters"]), want)
 
 
 def test_depth_and_ids_without_labels():
