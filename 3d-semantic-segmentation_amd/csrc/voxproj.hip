@@ -53,6 +53,7 @@
 //   vp_sh.h            view-dependent colour: spherical harmonics of degree 0 .. 3 into colour rows, and the adjoint (voxproj_ext.h)
 //   vp_mesh.h          triangle-mesh rasterizer: nearest face, depth and label per pixel, integer-decided (voxproj_mesh.h)
 //   vp_grid.h          stage 2, the voxel grid of a Gaussian cloud: ball statistics on the bucketed grid, voxelisation (voxproj_grid.h)
+//   vp_cluster.h       label sums over a feature table (sort by label, one wavefront per part, ordered combine), inverse row norms (voxproj_cluster.h)
 //   vp_project.h the projector's host side: the per-call context and its stages (check, pick set, tables, plan, march, gather, commit)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
@@ -76,6 +77,7 @@
 #include "voxproj_ext.h"
 #include "voxproj_mesh.h"
 #include "voxproj_grid.h"
+#include "voxproj_cluster.h"
 
 #include "vp_plan.h"
 #include "vp_common.h"
@@ -103,6 +105,7 @@
 #include "vp_sh.h"
 #include "vp_mesh.h"
 #include "vp_grid.h"
+#include "vp_cluster.h"
 #include "vp_project.h"
 
 // The refusal of a caller-provided workspace that is missing, smaller than ``need`` or not 256-byte aligned.
@@ -1660,6 +1663,100 @@ int vp_voxel_grid(const float *points, const uint8_t *colors, const uint8_t *kee
                            voxel_size, centers, (unsigned char *)voxel_colors, (int *)counts, (int *)voxel_index);
         VP_HIP(hipGetLastError());
     }
+    return VP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Label sums over a feature table (vp_cluster.h, declared in voxproj_cluster.h).  Every check is host arithmetic and comes
+// before cluster_layout (rocprim's scratch sizes depend on the device) and before any launch.
+// ------------------------------------------------------------------------------------------------
+static int cluster_check_rows(const void *rows, int rows_f16, int64_t n_rows, int C, int64_t stride)
+{
+    if (int rc = check_count("n_rows", n_rows)) return rc;
+    if (n_rows > 0 && !rows) return fail(VP_EINVAL, "null pointer argument (rows)");
+    if (rows_f16 != 0 && rows_f16 != 1) return fail(VP_EINVAL, "rows_f16 = %d is neither 0 nor 1", rows_f16);
+    if (C < 1 || C > CL_MAX_C) return fail(VP_EINVAL, "C = %d outside [1, %d]", C, CL_MAX_C);
+    if (stride < C) return fail(VP_EINVAL, "stride %lld < C = %d", (long long)stride, C);
+    return VP_OK;
+}
+
+int vp_row_inv_norms(const void *rows, int rows_f16, int64_t n_rows, int C, int64_t stride, float *inv, int32_t *status,
+                     void *stream_)
+{
+    if (int rc = cluster_check_rows(rows, rows_f16, n_rows, C, stride)) return rc;
+    if (!status || (n_rows > 0 && !inv)) return fail(VP_EINVAL, "null pointer argument (inv or status)");
+    hipStream_t stream = (hipStream_t)stream_;
+    VP_HIP(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), stream));
+    if (n_rows == 0) return VP_OK;
+    const bool vec16 = cluster_vec(rows, rows_f16, C, stride);
+    with_flags([&](auto f16, auto vec, auto quarter) {
+        constexpr int LPR = decltype(quarter)::value ? 16 : 64;
+        const long long per_block = 4 * (64 / LPR);
+        hipLaunchKernelGGL((k_row_inv_norms<decltype(f16)::value, decltype(vec)::value, LPR>),
+                           dim3((unsigned)((n_rows + per_block - 1) / per_block)), dim3(256), 0, stream, rows, (long long)n_rows, C,
+                           (long long)stride, inv, (int *)status);
+    }, rows_f16 == 1, vec16, C <= 16 * (vec16 ? (rows_f16 ? 8 : 4) : 1));      // a quarter of a wavefront covers the row
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+size_t vp_label_sums_workspace_bytes(int64_t n_rows, int K, int C)
+{
+    if (n_rows < 0 || n_rows > INT32_MAX || K < 1 || K > CL_MAX_K || C < 1 || C > CL_MAX_C) return 0;
+    ClusterLayout l;
+    return cluster_layout(n_rows, K, C, 0, l) ? l.bytes : 0;
+}
+
+int vp_label_sums(const void *rows, int rows_f16, int64_t n_rows, int C, int64_t stride, const int32_t *labels,
+                  const float *row_scale, int K, int64_t part_rows, float *sums, int32_t *counts, int32_t *status,
+                  void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = cluster_check_rows(rows, rows_f16, n_rows, C, stride)) return rc;
+    if (K < 1 || K > CL_MAX_K) return fail(VP_EINVAL, "K = %d outside [1, %d]", K, CL_MAX_K);
+    if (part_rows < 0) return fail(VP_EINVAL, "part_rows = %lld is negative (0 = the default)", (long long)part_rows);
+    if (!sums || !counts || !status || (n_rows > 0 && !labels))
+        return fail(VP_EINVAL, "null pointer argument (labels, sums, counts or status)");
+    ClusterLayout l;
+    cluster_layout_own(n_rows, K, C, part_rows, l);
+    if (int rc = check_buffer(workspace, "workspace")) return rc;
+    if (int rc = check_size(workspace_bytes, l.own_bytes, "workspace")) return rc;      // before the device is asked anything
+    if (int rc = open_workspace(workspace, workspace_bytes, l, [&] { return cluster_layout(n_rows, K, C, part_rows, l); })) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *ws = (char *)workspace;
+    unsigned *k0 = (unsigned *)(ws + l.keys0), *k1 = (unsigned *)(ws + l.keys1);
+    int *v0 = (int *)(ws + l.vals0), *v1 = (int *)(ws + l.vals1);
+    int *run_start = (int *)(ws + l.run_start), *n_parts = (int *)(ws + l.n_parts), *part_off = (int *)(ws + l.part_off);
+    float *partials = (float *)(ws + l.partials);
+    VP_HIP(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), stream));
+    if (n_rows > 0) {
+        hipLaunchKernelGGL(k_label_keys, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, stream, (const int *)labels,
+                           (long long)n_rows, K, k0, v0, (int *)status);
+        VP_HIP(hipGetLastError());
+        size_t tmp = l.sort_bytes;
+        VP_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, tmp, k0, k1, v0, v1, (size_t)n_rows, 0u, (unsigned)l.bits, stream));
+    }
+    hipLaunchKernelGGL(k_label_runs, dim3((unsigned)(K / 256 + 1)), dim3(256), 0, stream, (const unsigned *)k1, (int)n_rows, K,
+                       l.R, run_start, n_parts);
+    VP_HIP(hipGetLastError());
+    size_t tmp = l.scan_bytes;
+    VP_HIP(rocprim::exclusive_scan(ws + l.scan_tmp, tmp, (const int *)n_parts, part_off, 0, (size_t)(K + 1), rocprim::plus<int>(),
+                                   stream));
+    if (l.max_parts > 0) {
+        const bool vec = cluster_vec(rows, rows_f16, C, stride);
+        const int per_slot = 64 * (vec ? (rows_f16 ? 8 : 4) : 1), slots = (C + per_slot - 1) / per_slot;
+        const dim3 grid((unsigned)((l.max_parts + CL_WAVES - 1) / CL_WAVES)), block(64 * CL_WAVES);
+        with_flags([&](auto f16, auto v) {
+            with_step<1, 2, 4>(slots, [&](auto ns) {
+                hipLaunchKernelGGL((k_label_part_sums<decltype(f16)::value, decltype(v)::value, decltype(ns)::value>), grid, block, 0,
+                                   stream, rows, (long long)stride, C, (const int *)v1, row_scale, (const int *)run_start,
+                                   (const int *)part_off, K, l.R, l.max_parts, partials);
+            });
+        }, rows_f16 == 1, vec);
+        VP_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_label_combine, dim3((unsigned)K, (unsigned)((C + 63) / 64)), dim3(64), 0, stream, (const float *)partials,
+                       (const int *)run_start, (const int *)part_off, C, sums, (int *)counts);
+    VP_HIP(hipGetLastError());
     return VP_OK;
 }
 

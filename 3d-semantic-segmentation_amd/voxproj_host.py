@@ -145,6 +145,14 @@ _SIGNATURES_GRID = {
     "vp_voxel_grid": "i: ppp l d ppppp ppp p z p",
 }
 EXPORTS_GRID = list(_SIGNATURES_GRID)
+# The entry points of include/voxproj_cluster.h (label sums over a feature table, the rows' inverse norms): the fifth table, same
+# notation, same tolerant binding.  tests/test_label_sums_cpu.py compares every entry with that header's prototype.
+_SIGNATURES_CLUSTER = {
+    "vp_row_inv_norms": "i: p i l i l pp p",
+    "vp_label_sums_workspace_bytes": "z: l ii",
+    "vp_label_sums": "i: p i l i l pp i l ppp p z p",
+}
+EXPORTS_CLUSTER = list(_SIGNATURES_CLUSTER)
 VP_SH_MAX_DEGREE = 3
 VP_OPT_HEAVY_THRESHOLD = 1
 VP_OPT_MARCH_LDS_KB = 2
@@ -171,7 +179,8 @@ def build(force=False):
     """Compile libvoxproj.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f == "voxproj.hip" or (f.startswith("vp_") and f.endswith(".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("voxproj.h", "voxproj_ext.h", "voxproj_mesh.h", "voxproj_grid.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("voxproj.h", "voxproj_ext.h", "voxproj_mesh.h", "voxproj_grid.h",
+                                                                                   "voxproj_cluster.h")]
     newest = max(os.path.getmtime(f) for f in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
         subprocess.check_call(["make", "-C", os.path.join(_HERE, "csrc"), "-s"] + (["-B"] if force else []))
@@ -212,7 +221,7 @@ def lib():
                     "(there is no CPU fallback)")
             L = ctypes.CDLL(LIB_PATH)
             for name, signature in list(_SIGNATURES.items()) + list(_SIGNATURES_EXT.items()) + list(_SIGNATURES_MESH.items()) + \
-                    list(_SIGNATURES_GRID.items()):
+                    list(_SIGNATURES_GRID.items()) + list(_SIGNATURES_CLUSTER.items()):
                 fn = getattr(L, name, None)
                 if fn is not None:               # a symbol the library lacks is skipped here; _entry raises when it is called
                     restype, argtypes = signature.split(":")
@@ -1945,6 +1954,86 @@ def voxel_grid(points, colors, voxel_size, keep=None, workspace=None):
     V = int(n_voxels.item())
     return dict(centers=centers[:V], colors=vcolors[:V], counts=counts[:V], voxel_index=vindex[:V], point_voxel=point_voxel,
                 n_voxels=n_voxels, min_corner=min_corner, status=status)
+
+
+def _feature_rows(rows, caller):
+    """The [N, C] table of the label-sum calls: float16 or float32 on a GPU, unit channel stride, row stride >= C."""
+    import torch
+    _require_tensors((rows, "rows", (torch.float16, torch.float32)))
+    _require(rows.dim() == 2 and rows.shape[1] > 0, f"{caller}: rows must be [N, C] with C >= 1")
+    _require(int(rows.shape[1]) <= 4096, f"{caller}: C = {int(rows.shape[1])} must be in [1, 4096]")
+    if rows.shape[0] > 1 and (rows.stride(1) != 1 or rows.stride(0) < rows.shape[1]):
+        rows = rows.contiguous()
+    stride = int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+    return rows, int(rows.shape[0]), int(rows.shape[1]), stride
+
+
+def row_inv_norms(rows, check=False):
+    """vp_row_inv_norms (the contract is in include/voxproj_cluster.h): (inv float32 [N], status int32 [2]) on the rows' device,
+    inv[r] = 1 / max(|rows[r]|, 1e-12) with the norm in float64; an all-zero row gets 0 and is counted in status[0], a row with a
+    non-finite element gets 0 and is counted in status[1].  Asynchronous on the current stream, except with ``check``: then the
+    call synchronises and raises VoxprojError if any row was zero or non-finite."""
+    import torch
+    rows, N, C, stride = _feature_rows(rows, "row_inv_norms")
+    dev = rows.device
+    inv = torch.empty(N, dtype=torch.float32, device=dev)
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    _call(dev, "vp_row_inv_norms", _ptr(rows) if N else None, int(rows.dtype == torch.float16), N, C, stride, _ptr(inv) if N else None,
+          status.data_ptr())
+    if check:
+        zero, bad = (int(v) for v in status.tolist())
+        if zero or bad:
+            raise VoxprojError(f"row_inv_norms: {zero} all-zero row(s) and {bad} row(s) with a non-finite element (inverse norm 0)")
+    return inv, status
+
+
+def _label_sums_part_rows(n_rows, part_rows):
+    return int(part_rows) if part_rows else max(256, -(-int(n_rows) // 32768))
+
+
+def label_sums_workspace_bytes(n_rows, K, C, part_rows=0):
+    """vp_label_sums_workspace_bytes, plus the room the partial rows of a ``part_rows`` below the default take (the rule is in
+    include/voxproj_cluster.h)."""
+    n_rows, K, C = int(n_rows), int(K), int(C)
+    nbytes = int(_entry("vp_label_sums_workspace_bytes")(n_rows, K, C))
+    _require(nbytes > 0, f"no workspace size for n_rows = {n_rows}, K = {K}, C = {C}")
+    parts = [min(n_rows, n_rows // max(min(R, max(n_rows, 1)), 1) + min(K, n_rows))
+             for R in (_label_sums_part_rows(n_rows, part_rows), _label_sums_part_rows(n_rows, 0))]
+    return nbytes + (-(-max(parts[0] - parts[1], 0) * C * 4 // 256)) * 256
+
+
+def label_sums(rows, labels, K, row_scale=None, part_rows=0, check=True, workspace=None):
+    """vp_label_sums (the contract is in include/voxproj_cluster.h): sums[k] = the sum of row_scale[r] * rows[r] over the rows
+    with labels[r] == k, in a fixed order, without float atomics.  rows float16 or float32 [N, C] on a GPU (any row stride),
+    labels int32 [N], row_scale float32 [N] or None (1), 1 <= K <= 65536.  Returns (sums float32 [K, C], counts int32 [K],
+    status int32 [2]: rows with label < 0 (ignored), rows with label >= K (left out as well)) on the device.  Asynchronous on
+    the current stream, except with ``check``: then the call synchronises and raises VoxprojError if a label was >= K.
+    ``workspace``: a SplatWorkspace, kept across calls."""
+    import torch
+    rows, N, C, stride = _feature_rows(rows, "label_sums")
+    dev = rows.device
+    K, part_rows = int(K), int(part_rows)
+    _require(1 <= K <= 65536, f"K = {K} must be in [1, 65536]")
+    _require(part_rows >= 0, f"part_rows = {part_rows} must be >= 0 (0 = the default)")
+    _require_tensors((labels, "labels", (torch.int32,)))
+    _require(tuple(labels.shape) == (N,) and labels.device == dev, f"labels must be int32 [{N}] on the rows' device")
+    labels = labels.contiguous()
+    if row_scale is not None:
+        _require_tensors((row_scale, "row_scale", (torch.float32,)))
+        _require(tuple(row_scale.shape) == (N,) and row_scale.device == dev, f"row_scale must be float32 [{N}] on the rows' device")
+        row_scale = row_scale.contiguous()
+    ws = workspace if workspace is not None else SplatWorkspace()
+    ptr = ws.ensure(label_sums_workspace_bytes(N, K, C, part_rows), dev)
+    sums = torch.empty((K, C), dtype=torch.float32, device=dev)
+    counts = torch.empty(K, dtype=torch.int32, device=dev)
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    _call(dev, "vp_label_sums", _ptr(rows) if N else None, int(rows.dtype == torch.float16), N, C, stride, _ptr(labels) if N else None,
+          _ptr(row_scale), K, part_rows, sums.data_ptr(), counts.data_ptr(), status.data_ptr(), ptr, ws.capacity())
+    if check:
+        over = int(status[1].item())
+        if over:
+            raise VoxprojError(f"label_sums: {over} row(s) carry a label >= K = {K} (left out of every sum)")
+    return sums, counts, status
 
 
 def reverse_table(nbr, n_rows):
