@@ -1988,7 +1988,8 @@ def row_inv_norms(rows, check=False):
 
 
 def _label_sums_part_rows(n_rows, part_rows):
-    return int(part_rows) if part_rows else max(256, -(-int(n_rows) // 32768))
+    """cl_part_rows (csrc/vp_cluster.h): a given R is capped by the table's length, the default R is not."""
+    return min(int(part_rows), max(int(n_rows), 1)) if part_rows else max(256, -(-int(n_rows) // 32768))
 
 
 def label_sums_workspace_bytes(n_rows, K, C, part_rows=0):
@@ -1997,7 +1998,9 @@ def label_sums_workspace_bytes(n_rows, K, C, part_rows=0):
     n_rows, K, C = int(n_rows), int(K), int(C)
     nbytes = int(_entry("vp_label_sums_workspace_bytes")(n_rows, K, C))
     _require(nbytes > 0, f"no workspace size for n_rows = {n_rows}, K = {K}, C = {C}")
-    parts = [min(n_rows, n_rows // max(min(R, max(n_rows, 1)), 1) + min(K, n_rows))
+    # (the default R of a table of fewer than 256 rows is longer than the table: capping it too counted one default part too
+    # many, and a call with part_rows on such a table was refused wherever C * 4 bytes exceed the slack of the other sections)
+    parts = [min(n_rows, n_rows // R + min(K, n_rows))
              for R in (_label_sums_part_rows(n_rows, part_rows), _label_sums_part_rows(n_rows, 0))]
     return nbytes + (-(-max(parts[0] - parts[1], 0) * C * 4 // 256)) * 256
 

@@ -17,7 +17,10 @@ maps the bytes are also those of the same role's run on the widened fp32 maps.
   d  three one-view calls into one ``out``: serial, fixed parts, the workgroup arm
   e  one-view calls with device-sized parts (no option set), with and without the 256-pixel floor
   f  the part-slot bound raising the part size (rows of 32 KiB)
-  g  one fixed call sequence on one workspace: ranged pipelined pair, whole pipelined call, one-view call, smaller call"""
+  g  one fixed call sequence on one workspace: ranged pipelined pair, whole pipelined call, one-view call, smaller call
+  h  more than 512 split voxels in one call: k_combine_parts' workgroups take a second lap (tests/README_laps.md), adding parts
+     and redoing voxels over whole images there; k_worklist hands out split entries from two workgroups; job mode
+  i  two one-view calls on one workspace whose hit counters k_zero_call clears in two laps"""
 import numpy as np
 import pytest
 import torch
@@ -409,3 +412,194 @@ def test_a_call_sequence_on_one_workspace_adds_up_exactly(oracle_mod):
     print(f"g: {int(split.sum())} rows split by some call, largest row {int(count.max())} pixels over the sequence, counters {ctrs}")
     assert_headroom(count, maps)
     assert_exact(got_o, ref, count, "g call sequence f32 C=12", split=split)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# h. More split voxels in one call than k_combine_parts has workgroups
+# ------------------------------------------------------------------------------------------------------------------------------
+# k_combine_parts runs on min(512, slot_cap / 2) workgroups that take the call's split voxels j, j + 512, ...: voxels 512 and
+# later are some workgroup's SECOND lap.  A close-up frame has hundreds of split voxels; the scenes above have a few dozen.  Here
+# 8000 voxels are seen at 160 x 120 and cut above 12 pixels into parts of 5: every call below that claims it has more than 512
+# split voxels, the 8001 (1501) rows are binned by two (one) workgroups of k_worklist, and the split list is in the order the
+# atomics handed its entries out -- which voxels land beyond entry 512 differs from run to run, that some do does not.
+LAP = 512                         # COMBINE_BLOCKS (csrc/vp_gather.h); slot_cap / 2 is 4096 or more in every call here
+LAP_ROWS = [("f32", 12), ("f32", 259), ("f16", 520)]        # <1,4,4>; scalar, two channel passes; fp16, two channel passes
+
+
+def _close_up(oracle_mod):
+    """8000 voxels with IDs of their own (8001 rows), three views of 160 x 120: 671 / 535 / 318 voxels above 12 pixels in views
+    0 / 1 / 2 (3542 / 2795 / 3102 parts of 5), 1524 over the three views together (9439 parts, the largest row 479 pixels)."""
+    if "close_up" not in _scenes:
+        s = make_scene(8000, 3, 160, 120, seed=71, room=ROOM)
+        _scenes["close_up"] = _Scene(oracle_mod, "close_up", s, s.occ[None].astype(np.int64), s.c2w, s.intr[None], 1, s.n_vox + 1)
+    return _scenes["close_up"]
+
+
+def _close_up_redo(oracle_mod):
+    """The same cells under 1500 IDs (occ % 1500 + 1, 1501 rows, about five cells per ID as in _redo_scene): the box around one
+    cell of an ID misses the others' pixels.  1134 rows above 12 pixels over the three views, 556 / 556 / 340 per view."""
+    if "close_up_redo" not in _scenes:
+        s = _close_up(oracle_mod).s
+        occ = np.where(s.occ > 0, (s.occ % 1500) + 1, 0).astype(np.int64)[None]
+        _scenes["close_up_redo"] = _Scene(oracle_mod, "close_up_redo", s, occ, s.c2w, s.intr[None], 1, 1501)
+    return _scenes["close_up_redo"]
+
+
+def _multi_view_parts_of_5(vh):
+    return {vh.VP_OPT_HEAVY_THRESHOLD: 12, vh.VP_OPT_PART_PIXELS: 5}, lambda ctr, c: _ran_parts(ctr, c, 12, 5)
+
+
+def _say(label, ctrs):
+    print(f"{label}: " + "; ".join(f"n_split {c['n_split']}, n_parts {c['n_parts']}, box_miss {c['box_miss']}" for c in ctrs))
+
+
+@pytest.mark.parametrize("kind,C", LAP_ROWS)
+def test_one_view_calls_with_more_split_voxels_than_combine_workgroups(oracle_mod, kind, C):
+    """The adding arm, one view per call: part_px = 5 survives the slot bound (ceil(2 * 19200 / 8192) = 5), no box misses a
+    pixel, and views 0 and 1 each leave more than 512 voxels to add (the oracle counts 671 and 535; _ran_parts holds the
+    counters to the oracle's numbers)."""
+    sc = _close_up(oracle_mod)
+    assert sc.n_rows == 8001 and [int((sc.counts([v]) > 12).sum()) for v in range(3)] == [671, 535, 318]
+    split, ctrs = _check_role(f"h {kind} C={C} one view, parts of 5 above 12", sc, C, kind, "one_parts")
+    _say(f"h {kind} C={C} one view", ctrs)
+    assert ctrs[0]["n_split"] > LAP and ctrs[1]["n_split"] > LAP and all(ctr["box_miss"] == 0 for ctr in ctrs), ctrs
+    assert [ctr["n_parts"] for ctr in ctrs] == [3542, 2795, 3102]
+
+
+@pytest.mark.parametrize("kind,C", LAP_ROWS)
+def test_multi_view_call_with_more_split_voxels_than_combine_workgroups(oracle_mod, kind, C):
+    """The adding arm, the three views in one call (k_gather's parts): 1524 split voxels, three laps of k_combine_parts."""
+    import voxproj_host as vh
+    sc = _close_up(oracle_mod)
+    options, ran = _multi_view_parts_of_5(vh)
+    split, ctrs = _check_role(f"h {kind} C={C} three views, parts of 5 above 12", sc, C, kind, "parts", options=options, ran=ran)
+    _say(f"h {kind} C={C} three views", ctrs)
+    assert ctrs[0]["n_split"] == 1524 > 2 * LAP and ctrs[0]["n_parts"] == 9439 and ctrs[0]["box_miss"] == 0, ctrs
+    assert int(sc.counts().max()) == 479
+
+
+def test_whole_image_redos_beyond_the_first_lap_of_the_combine(oracle_mod):
+    """The redo arm, fp32 C = 12.  Three views in one call: more than 512 of the 1134 split rows have parts that found fewer
+    pixels than the march counted, so by pigeonhole a workgroup of k_combine_parts redoes at least one of them over whole
+    images in its second or third lap, whatever order the split list came out in.  One view per call: more than 512 split rows
+    in views 0 and 1, redone and added rows side by side."""
+    import voxproj_host as vh
+    sc = _close_up_redo(oracle_mod)
+    assert sc.n_rows == 1501 and int((sc.counts() > 12).sum()) == 1134
+    assert [int((sc.counts([v]) > 12).sum()) for v in range(3)] == [556, 556, 340]
+    options, ran = _multi_view_parts_of_5(vh)
+    _, ctrs = _check_role("h redo f32 C=12 three views", sc, 12, "f32", "parts", box_miss=True, options=options, ran=ran)
+    _say("h redo f32 C=12 three views", ctrs)
+    assert ctrs[0]["n_split"] == 1134 and ctrs[0]["n_parts"] == 11515 and ctrs[0]["box_miss"] > LAP, ctrs
+    # box_miss also counts the rows of up to 12 pixels that their one wavefront redoes (k_gather): at most all of them
+    light = int(((sc.counts() > 0) & (sc.counts() <= 12)).sum())
+    print(f"h redo three views: {light} rows of 1 .. 12 pixels, so at least {ctrs[0]['box_miss'] - light} split rows were redone")
+    assert ctrs[0]["box_miss"] - light > LAP, (ctrs, light)
+    _, ctrs = _check_role("h redo f32 C=12 one view", sc, 12, "f32", "one_parts", box_miss=True)
+    _say("h redo f32 C=12 one view", ctrs)
+    assert ctrs[0]["n_split"] > LAP and ctrs[1]["n_split"] > LAP and all(ctr["box_miss"] > 0 for ctr in ctrs), ctrs
+
+
+def test_job_mode_leaves_the_blocking_calls_bytes_beyond_the_first_lap(oracle_mod):
+    """A blocking one-view call launches k_combine_parts only when the gather's first wavefront notes split voxels to the host
+    (project_gather_one, csrc/vp_project.h); job mode always launches it.  Both must leave the same bytes: each view of the
+    close-up as a job on a workspace of its own, all adding into one out, against the three blocking calls."""
+    import voxproj_host as vh
+    dev = torch.device(DEV)
+    sc = _close_up(oracle_mod)
+    options = _role(vh, "one_parts")[0]
+    maps, ref, count = _maps(sc, 12, "f32")
+    want_c, want_o, want_v, want_ctrs = _blocking_calls(sc, maps, options, [[v] for v in range(sc.V)])
+    assert_exact(want_o, ref, count, "h blocking f32 C=12 one view", split=count > 12)
+    count_t = torch.zeros(sc.n_rows, dtype=torch.int32, device=dev)
+    out_t = torch.zeros(sc.n_rows, 12, device=dev)
+    views_t = torch.zeros(sc.n_rows, dtype=torch.int32, device=dev)
+    occ_t, intr_t = torch.from_numpy(sc.occ).to(dev), torch.from_numpy(sc.intr).to(dev)
+    ctrs = []
+    for v in range(sc.V):
+        ws = vh.Workspace()
+        for opt, val in options.items():
+            ws.set_option(opt, val)
+        feats, c2w = torch.from_numpy(np.ascontiguousarray(maps[:, [v]])).to(dev), torch.from_numpy(sc.c2w[[v]]).reshape(-1).to(dev)
+        vh.project_features_raw(feats, occ_t, c2w, intr_t, [float(x) for x in sc.s.opts()], count_t, out_t,
+                                [float(x) for x in sc.s.grid_origin], sc.s.voxel_size, workspace=ws, sync=False, pipeline=True,
+                                views_hit=views_t)
+        vh.workspace_status(ws, dev)
+        assert np.array_equal(vh.hit_image(ws, dev).cpu().numpy(), sc.hits[:, [v]])
+        ctrs.append(vh.counters(ws, dev))
+        ws.release()
+    _say("h job mode f32 C=12 one view", ctrs)
+    assert [(c["n_split"], c["n_parts"], c["box_miss"]) for c in ctrs] == [(c["n_split"], c["n_parts"], c["box_miss"]) for c in want_ctrs]
+    assert ctrs[0]["n_split"] > LAP and ctrs[1]["n_split"] > LAP
+    assert np.array_equal(count_t.cpu().numpy(), want_c) and np.array_equal(views_t.cpu().numpy(), want_v)
+    assert out_t.cpu().numpy().tobytes() == want_o.tobytes()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# i. The march's hit counters, cleared beyond the first lap of k_zero_call
+# ------------------------------------------------------------------------------------------------------------------------------
+def _pulled_back(oracle_mod):
+    """The close-up's cells under 1000 IDs (1001 rows: ONE workgroup of k_zero_call, 256 threads) and two views of 160 x 120
+    (80 tiles of 16 x 16, 320 hit counters): view 0 of the close-up, inside the room, and a camera 5.5 m in front of the room's
+    -x wall, to which the room is some forty pixels in the image centre."""
+    if "pulled_back" not in _scenes:
+        s = _close_up(oracle_mod).s
+        occ = np.where(s.occ > 0, (s.occ % 1000) + 1, 0).astype(np.int64)[None]
+        back = np.zeros((4, 4), np.float32)         # looks along +x: x right = -y of the world, y down = -z
+        back[:3, 0], back[:3, 1], back[:3, 2], back[:3, 3], back[3, 3] = (0, -1, 0), (0, 0, -1), (1, 0, 0), (-8.0, 0.0, 1.2), 1.0
+        _scenes["pulled_back"] = _Scene(oracle_mod, "pulled_back", s, occ, np.stack([s.c2w[0], back]), s.intr[None], 1, 1001)
+    return _scenes["pulled_back"]
+
+
+def test_hit_counters_of_the_previous_call_are_cleared_beyond_the_first_lap(oracle_mod):
+    """A one-view call with no part option sizes its parts from the view's hit total, which k_worklist adds up from one counter
+    per wavefront of the march (4 per 16 x 16 tile).  A wavefront without a hit never writes its counter, so k_zero_call clears
+    them all -- on a grid sized by n_rows: here 256 threads for 320 counters, a second lap for the counters of tiles 64 .. 79.
+    View 0 hits in those tiles; the second call, on the SAME workspace, has hits but none in some of them: a counter left from
+    the first call would inflate its n_hit.  Both calls: the oracle's hit image and hit total, the device's part size, exact
+    rows; the second call equal to itself on a fresh workspace.  (part_t: twice the part size, but not below 256 pixels on a view
+    of at most 262144 pixels -- csrc/vp_plan.h, as in section e.)"""
+    import voxproj_host as vh
+    dev = torch.device(DEV)
+    sc = _pulled_back(oracle_mod)
+    C, W, H = 12, sc.W, sc.H
+    tx, ty = -(-W // 16), -(-H // 16)
+    assert sc.n_rows <= 1024 and 4 * tx * ty == 320 > 256 * -(-sc.n_rows // 1024)           # the clearing loop laps
+    per_tile = []
+    for v in range(2):
+        pad = np.zeros((ty * 16, tx * 16), bool)
+        pad[:H, :W] = sc.hits[0, v] > 0
+        per_tile.append(pad.reshape(ty, 16, tx, 16).sum(axis=(1, 3)).reshape(-1))          # tile index = ty * tiles per line + tx
+    stale = np.nonzero((per_tile[0] > 0) & (per_tile[1] == 0))[0]
+    n_hits = [int(t.sum()) for t in per_tile]
+    print(f"i: hits {n_hits} of {W * H} pixels; tiles the first view hits and the second does not: {stale.tolist()}")
+    assert n_hits[0] > 0.95 * W * H and n_hits[1] > 0 and (stale >= 64).any()
+    maps, _, _ = _maps(sc, C, "f32")
+    occ_t, intr_t = torch.from_numpy(sc.occ).to(dev), torch.from_numpy(sc.intr).to(dev)
+
+    def call(ws, v):
+        count_t = torch.zeros(sc.n_rows, dtype=torch.int32, device=dev)
+        out_t = torch.zeros(sc.n_rows, C, device=dev)
+        views_t = torch.zeros(sc.n_rows, dtype=torch.int32, device=dev)
+        vh.project_features_raw(torch.from_numpy(np.ascontiguousarray(maps[:, [v]])).to(dev), occ_t,
+                                torch.from_numpy(sc.c2w[[v]]).reshape(-1).to(dev), intr_t, [float(x) for x in sc.s.opts()], count_t, out_t,
+                                [float(x) for x in sc.s.grid_origin], sc.s.voxel_size, workspace=ws, sync=True, views_hit=views_t)
+        assert np.array_equal(vh.hit_image(ws, dev).cpu().numpy(), sc.hits[:, [v]]), f"hit image of view {v}"
+        return count_t.cpu().numpy(), out_t.cpu().numpy(), views_t.cpu().numpy(), vh.counters(ws, dev)
+
+    ws, fresh = vh.Workspace(), vh.Workspace()
+    first, second, alone = call(ws, 0), call(ws, 1), call(fresh, 1)
+    ws.release()
+    fresh.release()
+    for v, (got_c, got_o, got_v, ctr) in ((0, first), (1, second), (1, alone)):
+        ref, count = int_reference(sc.hits[:, [v]], maps[:, [v]], sc.n_rows)
+        print(f"i: view {v}: counters {ctr}")
+        assert ctr["n_hit"] == n_hits[v] == int(count.sum()), (ctr, n_hits[v])
+        px = max(32, -(-2 * n_hits[v] // 8192))
+        split = _ran_parts(ctr, count, max(2 * px, 256), px)
+        assert ctr["bad_id"] == 0, ctr
+        assert np.array_equal(got_c, count) and np.array_equal(got_v, sc.views_hit([v]))
+        assert_headroom(count, maps)
+        assert_exact(got_o, ref, count, f"i view {v}", split=split)
+    assert second[3] == alone[3], (second[3], alone[3])
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(second[:3], alone[:3]))

@@ -1,7 +1,7 @@
 """vp_label_sums and vp_row_inv_norms on the GPU against tests/label_sums_reference.py: sums and counts equal the twin byte
 for byte, and every element independently meets clause (F) of tests/sum_criteria.py against float64 sums that share nothing
 with the twin's code path.  The shapes are the ones at which the kernels can go wrong, not the workload's: one row, one
-wavefront of rows and one more, element-wise and 16-byte rows, one and several slots per lane, a ragged tail, the ninth key
+wavefront of rows and one more, element-wise and 16-byte rows, one and several slots per lane, rows wider than one channel pass of every row variant, a ragged tail, the ninth key
 bit, the largest K, every row its own part, ragged last parts, one part, the default."""
 import os
 import sys
@@ -113,6 +113,15 @@ CASES = [
     (6000, 512, 300, 0, np.float32, "wide", "reversed", False),
     (1000, 8, 10, 0, np.float16, "plain", "all_ignored", False),
     (64, 520, 1, 0, np.float16, "odd", "one_label", True),
+    # Rows wider than one channel pass of k_label_part_sums (64 * W * NS channels, NS = 4 above with_step's ladder: 1024 for
+    # 16-byte fp32 rows, 2048 for 16-byte fp16 rows, 256 element-wise; tests/README_laps.md): the cases above take a second
+    # pass in the element-wise variants only.
+    (65, 1028, 4, 3, np.float32, "plain", "with_ignored", True),      # 1024 + 4: one active lane in the second pass
+    (65, 2052, 3, 3, np.float32, "wide", "random", False),            # three passes, the third of one lane
+    (65, 4096, 2, 3, np.float32, "plain", "random", True),            # CL_MAX_C: four full passes
+    (1000, 2056, 10, 0, np.float16, "plain", "with_ignored", True),   # 2048 + 8, the default R
+    (65, 4096, 4, 3, np.float16, "wide", "reversed", False),          # two full passes
+    (65, 1025, 5, 3, np.float32, "shifted", "random", True),          # element-wise, five passes, the last of one lane
 ]
 
 

@@ -650,21 +650,13 @@ def test_feature_feeder_closes_its_files_on_errors_and_early_exits(tmp_path):
     assert {f for f in open_fds() if str(tmp_path) in f} == before
 
 
-@pytest.mark.parametrize("dims,n_vox", [((1, 1, 1), 1), ((1, 1, 300), 40), ((3, 1, 2), 6), ((2, 130, 5), 300), ((70, 9, 33), 2500),
-                                         ((150, 170, 190), 3000), ((64, 64, 64), 64 ** 3), ((5, 4, 1030), 900)])
-def test_rgb_voxel_list_along_the_curve_on_awkward_grids(oracle_mod, dims, n_vox):
-    """k_color_cells walks the grid's 4x4x4 blocks along a Morton curve and k_project_colors sums the voxels in that order:
-    grids of one cell, of one row, with axes that are no multiple of four or run out of bits early, a full grid (every block
-    of the curve occupied), more curve positions than walking wavefronts.  Five views in two calls, with and without the
-    sampled pixels: sums (view order), hit counts, first views and pixels equal the oracle's bit for bit; IDs that label no
-    cell stay untouched."""
+def _rgb_curve_case(oracle_mod, occ, n_rows, rng):
+    """Five views in two calls, with and without the sampled pixels: sums (view order), hit counts, first views and pixels
+    equal the oracle's bit for bit; IDs that label no cell stay untouched.  Returns the reference's hit counts."""
     import voxproj_host
     dev = torch.device(DEV)
-    rng = np.random.default_rng(sum(dims) + n_vox)
+    dims = occ.shape
     Z, Y, X = dims
-    occ = np.zeros(dims, np.int32)
-    n_rows = n_vox + 4                                             # three IDs beyond the labelled ones: rows without a cell
-    occ.reshape(-1)[rng.choice(occ.size, n_vox, replace=False)] = rng.permutation(n_vox) + 1
     vs = 0.05
     origin = np.array([-0.5 * X * vs, -0.5 * Y * vs, -0.5 * Z * vs], np.float32)
     V, iw, ih = 5, 96, 64
@@ -705,3 +697,90 @@ def test_rgb_voxel_list_along_the_curve_on_awkward_grids(oracle_mod, dims, n_vox
         assert np.array_equal(hits.cpu().numpy(), ref_hits) and np.array_equal(first.cpu().numpy(), ref_first)
         if want_uv:
             assert np.array_equal(uv_t.cpu().numpy(), ref_uv)
+    return ref_hits
+
+
+@pytest.mark.parametrize("dims,n_vox", [((1, 1, 1), 1), ((1, 1, 300), 40), ((3, 1, 2), 6), ((2, 130, 5), 300), ((70, 9, 33), 2500),
+                                         ((150, 170, 190), 3000), ((64, 64, 64), 64 ** 3), ((5, 4, 1030), 900)])
+def test_rgb_voxel_list_along_the_curve_on_awkward_grids(oracle_mod, dims, n_vox):
+    """k_color_cells walks the grid's 4x4x4 blocks along a Morton curve and k_project_colors sums the voxels in that order:
+    grids of one cell, of one row, with axes that are no multiple of four or run out of bits early, a full grid (every block
+    of the curve occupied), walking wavefronts of a single workgroup up to 4096 of them.  No grid here has more than 2^18
+    curve positions, so every walking wavefront takes at most 64 of them, ONE lap of its loop: the grids whose walkers lap
+    are in test_rgb_voxel_list_when_the_walking_wavefronts_lap."""
+    rng = np.random.default_rng(sum(dims) + n_vox)
+    occ = np.zeros(dims, np.int32)
+    n_rows = n_vox + 4                                             # three IDs beyond the labelled ones: rows without a cell
+    occ.reshape(-1)[rng.choice(occ.size, n_vox, replace=False)] = rng.permutation(n_vox) + 1
+    assert _curve_laps(dims, np.stack(np.nonzero(occ), 1))[1].max() == 0
+    _rgb_curve_case(oracle_mod, occ, n_rows, rng)
+
+
+def _curve_laps(dims, zyx):
+    """The walk of k_color_cells (csrc/vp_aux.h: curve_block, and the walkers of vp_project_colors in voxproj.hip) in Python:
+    (walkers, lap [n], walker [n]) for the cells ``zyx`` [n, 3] of a grid of ``dims`` = (Z, Y, X) -- which walking wavefront
+    meets the cell's 4x4x4 block, and in which lap of its loop of 64 curve positions (0 = the first)."""
+    nb = [(d + 3) // 4 for d in dims]
+    bz, by, bx = [(n - 1).bit_length() for n in nb]
+    slots = 1 << (bx + by + bz)
+    blk = np.asarray(zyx, np.int64) // 4
+    s = np.zeros(len(blk), np.int64)
+    pos = 0
+    for l in range(max(bx, by, bz)):                               # the inverse of curve_block: x, y, z bits interleaved from bit 0 up
+        for axis, bits in ((2, bx), (1, by), (0, bz)):
+            if l < bits:
+                s |= ((blk[:, axis] >> l) & 1) << pos
+                pos += 1
+    assert pos == bx + by + bz
+    want = (slots + 63) // 64
+    walkers = 8192 if want > 8192 else (want + 3) // 4 * 4         # COLOR_WALKERS
+    start = slots * np.arange(walkers + 1, dtype=np.int64) // walkers
+    w = np.searchsorted(start, s, "right") - 1
+    assert (start[w] <= s).all() and (s < start[w + 1]).all()
+    return walkers, (s - start[w]) // 64, w
+
+
+def _second_lap_flat_grid():
+    """(1, 2052, 2052): 513 x 513 x 1 blocks, 10 + 10 + 0 bits, 2^20 curve positions for 8192 walking wavefronts: stretches of
+    exactly 128 positions.  EVERY occupied cell lies in a block of a second lap (curve position s with s % 128 >= 64; bit 6 of
+    s is bit 3 of the block's x index here): a walk that ends after its first lap finds no voxel at all."""
+    dims, n_vox = (1, 2052, 2052), 3000
+    rng = np.random.default_rng(2052)
+    bx_ok = np.array([b for b in range(513) if b & 8])
+    y = rng.integers(0, 513, 2 * n_vox) * 4 + rng.integers(0, 4, 2 * n_vox)
+    x = rng.choice(bx_ok, 2 * n_vox) * 4 + rng.integers(0, 4, 2 * n_vox)
+    cells = rng.permutation(np.unique(y * 2052 + x))[:n_vox]
+    assert len(cells) == n_vox
+    occ = np.zeros(dims, np.int32)
+    occ.reshape(-1)[cells] = rng.permutation(n_vox) + 1
+    walkers, lap, w = _curve_laps(dims, np.stack(np.nonzero(occ), 1))
+    assert (lap == 1).all() and len(np.unique(w)) > 1000
+    return occ, n_vox, rng, walkers, lap, w
+
+
+def _second_lap_deep_grid():
+    """(36, 516, 516): 129 x 129 x 9 blocks, 8 + 8 + 4 bits (z runs out of bits early), 2^20 curve positions again; random
+    occupancy, of which the curve puts at least a third into second laps."""
+    dims, n_vox = (36, 516, 516), 3000
+    rng = np.random.default_rng(516)
+    occ = np.zeros(dims, np.int32)
+    occ.reshape(-1)[rng.choice(occ.size, n_vox, replace=False)] = rng.permutation(n_vox) + 1
+    walkers, lap, w = _curve_laps(dims, np.stack(np.nonzero(occ), 1))
+    assert lap.max() == 1 and 3 * int((lap == 1).sum()) >= n_vox
+    return occ, n_vox, rng, walkers, lap, w
+
+
+@pytest.mark.parametrize("scene", [_second_lap_flat_grid, _second_lap_deep_grid])
+def test_rgb_voxel_list_when_the_walking_wavefronts_lap(oracle_mod, scene):
+    """More than 64 * COLOR_WALKERS = 2^19 curve positions: the walkers are capped at 8192, each takes 128 positions, and its
+    loop of 64 positions at a time runs twice -- in k_color_cells<1> (cells of the IDs, counts), in k_color_cells<2> (the list
+    positions base + n carried across the laps) and with eight counts per thread in k_color_scan.  The comparison is
+    _rgb_curve_case's: a voxel the walk loses keeps a zero sum, a zero hit count and pixels of -1."""
+    occ, n_vox, rng, walkers, lap, w = scene()
+    zyx = np.stack(np.nonzero(occ), 1)
+    ref_hits = _rgb_curve_case(oracle_mod, occ, n_vox + 4, rng)
+    seen = ref_hits[occ[zyx[:, 0], zyx[:, 1], zyx[:, 2]]] > 0
+    print(f"{occ.shape}: {walkers} walkers, {int((lap == 1).sum())} of {n_vox} voxels ({(lap == 1).mean():.1%}) in second laps on "
+          f"{len(np.unique(w[lap == 1]))} walkers; some view sees {int(seen.sum())} voxels, {int((seen & (lap == 1)).sum())} of them in second laps")
+    assert walkers == 8192
+    assert (seen & (lap == 1)).sum() >= 100                    # the views' sums depend on the second laps
