@@ -1851,8 +1851,10 @@ def ball_count(points, radius_or_radii, queries=None, normals=None, query_normal
     them.  ``radius_or_radii``: a Python float, or a float32 [M] tensor with one radius per query.  ``queries`` None: the
     points themselves.  With ``normals`` (unit, f32 [N,3]; ``query_normals`` f32 [M,3] for queries that are not the points)
     and ``min_dot`` also the number of points within the ball whose normal has a float64 dot product > min_dot with the
-    query's.  Returns (count int32 [M], consistent int32 [M] or None) on the device, in the caller's row order; nothing is
-    read back here.  The queries are launched in the grid's cell order, so that a wavefront's lanes walk the same cells."""
+    query's.  Returns (count int32 [M], consistent int32 [M] or None) on the device, in the caller's row order.  The points'
+    bounds (and the largest radius of a radii tensor) are read back to lay out the grid before the kernel is launched, as
+    knn_points does: the call synchronises the current stream once; the counts themselves are not read back.  The queries
+    are launched in the grid's cell order, so that a wavefront's lanes walk the same cells."""
     import torch
     import voxel_to_gaussian_map
     points = _rows3(points, "points")

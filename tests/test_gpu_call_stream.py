@@ -1,48 +1,123 @@
-"""The wrappers of voxproj_host launch on the caller's current stream and device: the same call on the default stream and
-inside ``torch.cuda.stream(side)``, read after ``side.synchronize()`` alone, gives the same bits.  The kernels used here have
-no atomics and sum in a fixed order, so equality is exact.
+"""Every call of voxproj_host runs on the caller's current stream, in order, behind work that is still pending there.
 
-Shapes: the photometric loss on [3, 17, 33] (one tile row, two tile columns, a ragged edge on both axes); the k nearest
-neighbours of 257 points (two workgroups, the second ragged) with k = 4."""
+The protocol is tests/stream_order.py's: the inputs of a call are produced ON the side stream behind a delay (until then the
+buffers hold a decoy), caller-provided workspaces and accumulators are dirtied in-stream, the call is made while the stream
+is still busy, its results are cloned in-stream, and the clones must be the bits the same call gives on the idle default
+stream.  A launch, fill, copy or rocPRIM call that went to the null stream would run at once: it would read the decoy, or be
+overwritten by the caller's fill.  The decoy's own result must fail the comparison, so no case is vacuous.  Every kernel
+reached here sums in a fixed order (no float atomics anywhere in csrc/), so equality is exact.
+
+Index-valued inputs (ids, labels, faces, targets, neighbour tables, plans) are valid in the real and in the decoy state, so
+the wrong outcome of a misplaced launch is a wrong number, never an access out of range.  tests/README_streams.md lists the
+wrappers, their cases and what was shown able to fail.
+
+Shapes of the two cases this module had before: the photometric loss on [3, 17, 33] (one tile row, two tile columns, a ragged
+edge on both axes); the k nearest neighbours of 257 points (two workgroups, the second ragged) with k = 4."""
+import functools
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(os.path.dirname(HERE), "3d-semantic-segmentation_amd")
-if PKG not in sys.path:
-    sys.path.insert(0, PKG)
+ROOT = os.path.dirname(HERE)
+PKG = os.path.join(ROOT, "3d-semantic-segmentation_amd")
+for p in (HERE, ROOT, PKG):
+    if p not in sys.path:
+        sys.path.insert(0, p)
 
+import mesh_scenes  # noqa: E402
+import splat_scenes  # noqa: E402
+import stream_order  # noqa: E402
+from stream_order import PerWrapper  # noqa: E402
+import test_gpu_label_sums as label_cases  # noqa: E402  (make_rows / make_labels)
 import voxproj_host  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
-def _on_both_streams(fn):
-    """fn() on the default stream, then on a side stream that is synchronised before the results are read."""
-    first = fn()
-    torch.cuda.synchronize(DEV)
-    side = torch.cuda.Stream(DEV)
-    side.wait_stream(torch.cuda.current_stream(DEV))
-    with torch.cuda.stream(side):
-        second = fn()
-    side.synchronize()
-    return first, second
+class Case:
+    """What run_behind_pending_work takes.  ``real`` / ``decoy``: {name: device tensor}; the buffers are made here."""
+
+    def __init__(self, real, decoy, blocking=False):
+        self.real = {k: v.to(DEV).contiguous() for k, v in real.items()}
+        self.decoy = {k: v.to(DEV).contiguous() for k, v in decoy.items()}
+        self.buf = {k: v.clone() for k, v in self.decoy.items()}
+        self.blocking = blocking
+        self.workspaces = []          # SplatWorkspace objects dirtied in-stream (their buffers exist after the first run)
+        self.dirty = []               # tensors dirtied in-stream
+        self.between = None
+        self.call = None
+        self.release = []             # projector Workspaces (announced to the library): released after the run
+
+    def workspace(self):
+        ws = voxproj_host.SplatWorkspace()
+        self.workspaces.append(ws)
+        return ws
+
+    def projector_workspace(self):
+        ws = voxproj_host.Workspace()
+        self.release.append(ws)
+        return ws
+
+    def scratch(self):
+        """What the side stream dirties, asked for when it gets there: the workspaces are sized by the first run."""
+        return [ws.buf for ws in self.workspaces if ws.buf is not None] + list(self.dirty)
+
+    def run(self):
+        return stream_order.run_behind_pending_work(self.call, self.real, self.decoy, self.buf, scratch=self.scratch,
+                                                    blocking=self.blocking, between=self.between)
+
+    def close(self):
+        torch.cuda.synchronize()
+        for ws in self.release:
+            ws.release()
+        self.release = []
+
+
+def t(x, dtype=None):
+    x = torch.from_numpy(np.ascontiguousarray(x))
+    return x if dtype is None else x.to(dtype)
+
+
+def two(make, seeds=(1, 2)):
+    """make(rng) -> {name: array or tensor} for the real and for the decoy input, from two seeds."""
+    out = []
+    for seed in seeds:
+        made = make(np.random.default_rng(seed))
+        out.append({k: (v if isinstance(v, torch.Tensor) else t(v)) for k, v in made.items()})
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the two tests this module had: the same equalities, now behind pending work
+
+def _on_both_streams(fn, real, decoy, blocking=False):
+    """fn(buffers) on the idle default stream with ``real`` resident, then on a side stream behind the producer of ``real``:
+    (the default stream's tensors, the side stream's in-stream clones)."""
+    case = Case(real, decoy, blocking=blocking)
+    case.call = lambda: fn(case)
+    got, expected = case.run()
+    return expected, got
 
 
 def test_photo_loss_and_its_gradient_follow_the_current_stream():
-    gen = torch.Generator().manual_seed(17)
-    image = torch.rand((3, 17, 33), generator=gen, dtype=torch.float32).to(DEV)
-    target = torch.rand((3, 17, 33), generator=gen, dtype=torch.float32).to(DEV)
+    def images(seed):
+        gen = torch.Generator().manual_seed(seed)
+        return dict(image=torch.rand((3, 17, 33), generator=gen, dtype=torch.float32),
+                    target=torch.rand((3, 17, 33), generator=gen, dtype=torch.float32))
 
-    def both_calls():
-        stats, _, ws = voxproj_host.photo_loss(image, target)
-        return stats, voxproj_host.photo_loss_gradient(image, target, ws, lambda_dssim=0.2)
+    def both_calls(case):
+        if not case.workspaces:
+            case.workspace()
+        stats, _, ws = voxproj_host.photo_loss(case.buf["image"], case.buf["target"], workspace=case.workspaces[0])
+        grad = voxproj_host.photo_loss_gradient(case.buf["image"], case.buf["target"], ws, lambda_dssim=0.2)
+        return PerWrapper(photo_loss=stats, photo_loss_gradient=grad)
 
-    (stats0, grad0), (stats1, grad1) = _on_both_streams(both_calls)
+    (stats0, grad0), (stats1, grad1) = _on_both_streams(both_calls, images(17), images(18))
     assert stats0.data_ptr() != stats1.data_ptr() and grad0.data_ptr() != grad1.data_ptr()
     assert bool(torch.isfinite(stats0).all()) and float(stats0[0]) > 0.0 and bool((grad0 != 0).any())
     assert torch.equal(stats0.view(torch.int64), stats1.view(torch.int64))
@@ -50,9 +125,727 @@ def test_photo_loss_and_its_gradient_follow_the_current_stream():
 
 
 def test_knn_points_follows_the_current_stream():
-    gen = torch.Generator().manual_seed(257)
-    points = torch.rand((257, 3), generator=gen, dtype=torch.float32).to(DEV)
-    (idx0, d0), (idx1, d1) = _on_both_streams(lambda: voxproj_host.knn_points(points, 4))
+    def points(seed):
+        gen = torch.Generator().manual_seed(seed)
+        return dict(points=torch.rand((257, 3), generator=gen, dtype=torch.float32))
+
+    # knn_points reads the points' bounds back to lay out its grid: blocking by contract
+    (idx0, d0), (idx1, d1) = _on_both_streams(lambda case: voxproj_host.knn_points(case.buf["points"], 4), points(257), points(258),
+                                              blocking=True)
     assert tuple(idx0.shape) == (257, 4) and bool((idx0 >= 0).all()) and bool((d0 > 0).all())
     assert torch.equal(idx0, idx1)
     assert torch.equal(d0.view(torch.int64), d1.view(torch.int64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# one case per wrapper (or chain of wrappers, as the training tools issue them with no synchronisation in between)
+
+CASES = {}
+
+
+def case(name):
+    def register(builder):
+        CASES[name] = builder
+        return builder
+    return register
+
+
+@case("sh_colors_and_backward")
+def _sh():
+    # 1000 Gaussians: four workgroups of 256 lanes, the last ragged; degree 3 of 3
+    def make(rng):
+        n = 1000
+        return dict(f_dc=rng.normal(0, 0.5, (n, 3)).astype(np.float32), f_rest=rng.normal(0, 0.3, (n, 15, 3)).astype(np.float32),
+                    means=(rng.uniform(-1, 1, (n, 3)) + [0, 0, 3]).astype(np.float32),
+                    grad_colors=rng.normal(size=(n, 3)).astype(np.float32))
+    c = Case(*two(make))
+    vm = torch.eye(4)
+    vm[:3, 3] = torch.tensor([0.1, -0.2, 0.3])
+    c.out_rest = torch.empty((1000, 15, 3), dtype=torch.float32, device=DEV)
+    c.dirty.append(c.out_rest)
+
+    def call():
+        b = c.buf
+        colors, clamped = voxproj_host.sh_colors(b["f_dc"], b["f_rest"], b["means"], vm, 3)
+        grads = voxproj_host.sh_colors_backward(b["f_dc"], b["f_rest"], b["means"], vm, 3, b["grad_colors"], clamped, out_rest=c.out_rest)
+        return PerWrapper(sh_colors=(colors, clamped), sh_colors_backward=grads)
+    c.call = call
+    return c
+
+
+def _upsample(dtype, C, h, w, H, W, keep):
+    def make(rng):
+        return dict(src=t(rng.normal(size=(C, h, w)).astype(np.float32), dtype))
+    c = Case(*two(make))
+    c.out = torch.empty((H, W, C), dtype=torch.float16 if keep else torch.float32, device=DEV)
+    c.dirty.append(c.out)
+    c.call = lambda: voxproj_host.upsample_features(c.buf["src"], H, W, keep_dtype=keep, out=c.out)
+    return c
+
+
+@case("upsample_features_f32_vec")
+def _ups32():
+    # C = 8, 12 x 20 source pixels: the 16-byte transpose on four workgroups, then the upsample to 48 x 80
+    return _upsample(torch.float32, 8, 12, 20, 48, 80, False)
+
+
+@case("upsample_features_f16_kept")
+def _ups16():
+    # C = 12, 11 x 13: the element-wise transpose (three workgroups, ragged), the element-wise upsample to 45 x 70
+    return _upsample(torch.float16, 12, 11, 13, 45, 70, True)
+
+
+@case("photo_loss_evaluate_only")
+def _photo_eval():
+    def make(rng):
+        return dict(image=rng.random((3, 17, 33), np.float32), target=rng.random((3, 17, 33), np.float32))
+    c = Case(*two(make))
+    c.call = lambda: voxproj_host.photo_loss(c.buf["image"], c.buf["target"], evaluate_only=True, want_ssim_map=True)[:2]
+    return c
+
+
+@case("feature_loss_and_gradient")
+def _feature_loss():
+    # 40 x 50 pixels of 24 channels: several workgroups, the last ragged; weights and alpha cut pixels out
+    H, W, C = 40, 50, 24
+
+    def make(rng):
+        return dict(image=t(rng.normal(size=(H, W, C)).astype(np.float32)), target=t(rng.normal(size=(H, W, C)).astype(np.float16)),
+                    weight=(rng.random((H, W)) * (rng.random((H, W)) > 0.1)).astype(np.float32),
+                    alpha=rng.random((H, W)).astype(np.float32), grad_loss=rng.uniform(0.5, 2.0, 1).astype(np.float32))
+    c = Case(*two(make))
+    ws = c.workspace()
+    c.out = torch.empty((H, W, C), dtype=torch.float16, device=DEV)
+    c.dirty.append(c.out)
+
+    def call():
+        b = c.buf
+        stats, pl, _ = voxproj_host.feature_loss(b["image"], b["target"], b["weight"], b["alpha"], kind="cosine", min_alpha=0.2,
+                                                 want_pixel_loss=True, workspace=ws)
+        Gq, k = voxproj_host.feature_loss_gradient(b["image"], b["target"], stats, ws, reduction="mean", grad_loss=b["grad_loss"],
+                                                   out=c.out)
+        return PerWrapper(feature_loss=(stats, pl), feature_loss_gradient=(Gq, k))
+    c.call = call
+    return c
+
+
+def _mask_image(rng, D, H, W, n_ids):
+    ids = rng.integers(0, n_ids, (H // 8 + 1, W // 8 + 1)).repeat(8, 0).repeat(8, 1)[:H, :W]
+    ids = np.where(rng.random((H, W)) < 0.1, -1, ids).astype(np.int32)
+    return rng.normal(size=(D, H, W)).astype(np.float32), ids
+
+
+@case("proto_contrast_and_gradient")
+def _proto():
+    D, H, W = 8, 40, 50                       # 2000 pixels: eight tiles of 256
+
+    def make(rng):
+        image, ids = _mask_image(rng, D, H, W, 6)            # ids in [-1, 6): valid in both states
+        return dict(image=image, ids=ids, count=rng.integers(1, 3, (H, W)).astype(np.int32),
+                    grad_loss=rng.uniform(0.5, 2.0, 1).astype(np.float32))
+    c = Case(*two(make))
+    ws = c.workspace()
+
+    def call():
+        b = c.buf
+        stats, pl, own, _ = voxproj_host.proto_contrast(b["image"], b["ids"], b["count"], min_count=5, want_pixel_loss=True,
+                                                        want_own_prob=True, workspace=ws)
+        G = voxproj_host.proto_contrast_gradient(b["image"], b["ids"], b["count"], ws, weight_contrast=1.0, weight_norm=0.5,
+                                                 grad_loss=b["grad_loss"])
+        return PerWrapper(proto_contrast=(stats, pl, own), proto_contrast_gradient=G)
+    c.call = call
+    return c
+
+
+@case("codebook_assoc_and_loss")
+def _codebook():
+    D, H, W, K = 8, 40, 50, 8
+
+    def make(rng):
+        image, ids = _mask_image(rng, D, H, W, 6)
+        return dict(image=image, ids=ids, conf=rng.random((H, W)).astype(np.float32), codebook=rng.normal(size=(K, D)).astype(np.float32))
+    c = Case(*two(make))
+    ws = c.workspace()
+    assign = torch.full((256,), -1, dtype=torch.int32)
+    assign[:6] = torch.tensor([3, 0, 7, 1, 5, 2], dtype=torch.int32)          # id -> code, fixed and resident: an index input
+    assign = assign.to(DEV)
+
+    def call():
+        b = c.buf
+        score, id_pixels, pred, _ = voxproj_host.codebook_assoc(b["image"], b["ids"], b["codebook"], want_pred=True, workspace=ws)
+        loss = voxproj_host.codebook_loss(b["image"], b["ids"], b["conf"], b["codebook"], assign, want_pixel_loss=True, workspace=ws)
+        return PerWrapper(codebook_assoc=(score, id_pixels, pred), codebook_loss=loss[:4])
+    c.call = call
+    return c
+
+
+@case("neighbor_kl_and_gradient")
+def _neighbor_kl():
+    # the neighbour table is an index input: built once from fixed points and resident; the logits arrive in-stream
+    N, P, k = 600, 16, 4
+    points = t(np.random.default_rng(5).random((N, 3)).astype(np.float32)).to(DEV)
+    table = voxproj_host.NeighborTable(points, k)
+    sample = table.select(t(np.random.default_rng(6).integers(0, N, 300)))
+    torch.cuda.synchronize()
+    c = Case(*two(lambda rng: dict(logits=rng.normal(size=(N, P)).astype(np.float32),
+                                   grad_loss=rng.uniform(0.5, 2.0, 1).astype(np.float32))))
+    ws = c.workspace()
+
+    def call():
+        b = c.buf
+        stats, lse, sl, _ = voxproj_host.neighbor_kl(b["logits"], sample, want_sample_loss=True, workspace=ws)
+        grad = voxproj_host.neighbor_kl_gradient(b["logits"], sample, lse, grad_loss=b["grad_loss"])
+        return PerWrapper(neighbor_kl=(stats, lse, sl), neighbor_kl_gradient=grad)
+    c.call = call
+    return c
+
+
+def _label_sums(check):
+    # 1000 rows of 40 channels, 10 labels, parts of 64 rows: the key sort, the run scan, 16 parts per label and the combine
+    N, C, K = 1000, 40, 10
+
+    def make(seed):
+        return dict(rows=label_cases.make_rows(N, C, np.float16, "plain", seed)[0], labels=t(label_cases.make_labels(N, K, "with_ignored", seed)),
+                    scale=t(np.random.default_rng(seed).uniform(0.5, 2.0, N).astype(np.float32)))
+    c = Case(make(31), make(32), blocking=check)
+    ws = c.workspace()
+    c.call = lambda: voxproj_host.label_sums(c.buf["rows"], c.buf["labels"], K, row_scale=c.buf["scale"], part_rows=64, check=check,
+                                            workspace=ws)
+    return c
+
+
+@case("label_sums_async")
+def _label_sums_async():
+    return _label_sums(False)
+
+
+@case("label_sums_checked")
+def _label_sums_blocking():
+    return _label_sums(True)
+
+
+@case("row_inv_norms")
+def _row_inv_norms():
+    c = Case(*two(lambda rng: dict(rows=rng.normal(size=(1000, 40)).astype(np.float16))))
+    c.call = lambda: voxproj_host.row_inv_norms(c.buf["rows"], check=False)
+    return c
+
+
+@case("query_features")
+def _query():
+    # 700 rows (three workgroups, ragged) of 40 channels against 5 prompts: the text kernel, then the row kernel
+    c = Case(*two(lambda rng: dict(rows=rng.normal(size=(700, 40)).astype(np.float16), text=rng.normal(size=(5, 40)).astype(np.float32))))
+    c.call = lambda: voxproj_host.query_features(c.buf["rows"], c.buf["text"], scale=3.0, check=False)
+    return c
+
+
+@case("render_features")
+def _render():
+    # ids in [0, n_rows) in both states
+    n_rows, C = 300, 8
+    c = Case(*two(lambda rng: dict(ids=rng.integers(0, n_rows, (1, 2, 24, 40)).astype(np.int32),
+                                   rows=rng.normal(size=(n_rows, C)).astype(np.float32))))
+    c.out = torch.empty((1, 2, 24, 40, C), dtype=torch.float16, device=DEV)
+    c.dirty.append(c.out)
+    c.call = lambda: voxproj_host.render_features(c.buf["ids"], c.buf["rows"], dtype=torch.float16, out=c.out, check=False)
+    return c
+
+
+@case("ball_count")
+def _ball_count():
+    def make(rng):
+        n = rng.normal(size=(500, 3))
+        return dict(points=rng.random((500, 3)).astype(np.float32), normals=(n / np.linalg.norm(n, axis=1, keepdims=True)).astype(np.float32))
+    c = Case(*two(make), blocking=True)       # reads the points' bounds back to lay out its grid
+    c.call = lambda: voxproj_host.ball_count(c.buf["points"], 0.15, normals=c.buf["normals"], min_dot=0.3)
+    return c
+
+
+@case("voxel_grid")
+def _voxel_grid():
+    def make(rng):
+        return dict(points=rng.random((1500, 3)).astype(np.float32), colors=rng.integers(0, 256, (1500, 3)).astype(np.uint8),
+                    keep=(rng.random(1500) < 0.8).astype(np.uint8))
+    c = Case(*two(make), blocking=True)       # reads the voxel count back to trim its rows
+    ws = c.workspace()
+    c.call = lambda: voxproj_host.voxel_grid(c.buf["points"], c.buf["colors"], 0.1, keep=c.buf["keep"], workspace=ws)
+    return c
+
+
+@case("label_boundary_and_scores")
+def _label_scores():
+    H, W, P = 45, 70, 7
+
+    def make(rng):
+        def label_map():
+            m = rng.integers(-1, P + 1, (H // 6 + 1, W // 6 + 1)).repeat(6, 0).repeat(6, 1)[:H, :W]
+            return np.where(rng.random((H, W)) < 0.05, rng.integers(-1, P + 1, (H, W)), m).astype(np.int32)
+        return dict(pred=label_map(), target=label_map())
+    c = Case(*two(make))
+    ws = c.workspace()
+    out = voxproj_host.LabelScores(P, DEV)
+    c.dirty += [out.confusion, out.skipped, out.bnd_inter, out.bnd_union]
+    c.between = out.zero_                     # the accumulators are the caller's: dirtied, then zeroed, in-stream
+
+    def call():
+        band = voxproj_host.label_boundary(c.buf["pred"], 2, workspace=ws)
+        voxproj_host.label_scores(c.buf["pred"], c.buf["target"], P, radius=2, out=out, workspace=ws)
+        return PerWrapper(label_boundary=band, label_scores=(out.confusion, out.skipped, out.bnd_inter, out.bnd_union))
+    c.call = call
+    return c
+
+
+@case("mesh_project_and_rasterize")
+def _mesh():
+    # the closed room of the mesh tests (2028 faces, eight workgroups) at 64 x 48 (12 tiles).  The faces are an index
+    # input: fixed and resident; vertices and labels arrive in-stream
+    W, H = 64, 48
+    verts0, faces, labels0 = mesh_scenes.room(0)
+    verts1, _, labels1 = mesh_scenes.room(1)
+    assert verts0.shape == verts1.shape
+    faces = t(faces).to(DEV)
+    vm, K = mesh_scenes.room_camera(2), mesh_scenes.intrinsics(W, H)
+    c = Case(dict(verts=t(verts0), labels=t(labels0)), dict(verts=t(verts1), labels=t(labels1)))
+    ws = c.workspace()
+    counters = torch.zeros(3, dtype=torch.int32, device=DEV)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    c.dirty += [counters, status]
+    c.between = lambda: (counters.zero_(), status.zero_())
+    cap = 0
+    for verts in (c.real["verts"], c.decoy["verts"]):         # the capacity holds either state: nothing reads back in the call
+        cap = max(cap, int(voxproj_host.mesh_project(verts, faces, vm, K, W, H, workspace=ws).item()))
+    assert cap > 0
+
+    def call():
+        n_isect = voxproj_host.mesh_project(c.buf["verts"], faces, vm, K, W, H, workspace=ws, counters=counters)
+        images = voxproj_host.mesh_rasterize(faces, c.buf["labels"], W, H, cap, ws, status=status)
+        return PerWrapper(mesh_project=(n_isect, counters), mesh_rasterize=(images, status))
+    c.call = call
+    return c
+
+
+def _splat_case(extra):
+    """The 500 Gaussians of the camera tests' "anisotropic" scene at 77 x 53 (5 x 4 tiles, two workgroups of Gaussians); the
+    decoy is another draw for the same camera.  ``extra(rng, N, D, W, H)``: the further in-stream inputs."""
+    sc = splat_scenes.camera_scene("anisotropic", D=8)
+    W, H, vm, K = sc["W"], sc["H"], sc["vm"], sc["K"]
+    other = splat_scenes.scene_for_camera(500, 8, 77, vm, K, W, H)
+    real, decoy = ({k: t(s[k]) for k in ("means", "quats", "scales", "opacities", "features")} for s in (sc["s"], other))
+    for seed, d in ((3, real), (4, decoy)):
+        d.update({k: (v if isinstance(v, torch.Tensor) else t(v)) for k, v in extra(np.random.default_rng(seed), 500, 8, W, H).items()})
+    c = Case(real, decoy)
+    c.N, c.D, c.W, c.H, c.vm, c.K = 500, 8, W, H, vm, K
+    c.ws = c.workspace()
+    c.status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    c.dirty.append(c.status)
+    c.cap = 0
+    for d in (c.real, c.decoy):                               # the capacity holds either state: nothing reads back in the call
+        n = voxproj_host.splat_project(d["means"], d["quats"], d["scales"], d["opacities"], vm, K, W, H, workspace=c.ws)
+        c.cap = max(c.cap, int(n.item()))
+    assert c.cap > 0
+    return c
+
+
+@case("splat_backward_chain")
+def _splat_backward():
+    c = _splat_case(lambda rng, N, D, W, H: dict(grad_logits=rng.normal(size=(D, H, W)).astype(np.float32),
+                                                 grad_alpha=rng.normal(size=(H, W)).astype(np.float32)))
+    N, W, H, vm, K, ws, cap = c.N, c.W, c.H, c.vm, c.K, c.ws, c.cap
+    bws, gws = c.workspace(), c.workspace()
+    stats = voxproj_host.DensifyStats(N, DEV, want_radius=True)
+    accum = [stats.grad_accum, stats.denom, stats.max_radius]
+    c.dirty += accum
+    c.between = lambda: [x.zero_() for x in accum + [c.status]]
+
+    def call():
+        b = c.buf
+        n_isect = voxproj_host.splat_project(b["means"], b["quats"], b["scales"], b["opacities"], vm, K, W, H, workspace=ws)
+        images = voxproj_host.splat_rasterize(b["features"], N, W, H, cap, ws, want_logits=True, want_alpha=True, status=c.status)
+        plain = voxproj_host.splat_rasterize_backward(b["features"], N, W, H, cap, ws, b["grad_logits"], b["grad_alpha"], bwd_workspace=bws)
+        geom = voxproj_host.splat_rasterize_backward_geometry(b["means"], b["quats"], b["scales"], b["features"], vm, K, W, H, cap, ws,
+                                                              b["grad_logits"], b["grad_alpha"], bwd_workspace=gws, want_screen=True)
+        voxproj_host.densify_accumulate(stats, geom["screen"], ws, W, H, scale=2.0, geometry=(b["means"], b["quats"], b["scales"], vm, K))
+        return PerWrapper(splat_project=n_isect, splat_rasterize=(images, c.status), splat_rasterize_backward=plain,
+                          splat_rasterize_backward_geometry=geom, densify_accumulate=accum)
+    c.call = call
+    return c
+
+
+@case("splat_loss_chain")
+def _splat_loss():
+    C = 32
+    c = _splat_case(lambda rng, N, D, W, H: dict(target=rng.integers(-1, D, (H, W)).astype(np.int32),          # valid or ignored in both
+                                                 weight=rng.random((H, W)).astype(np.float32),
+                                                 grad_loss=rng.uniform(0.5, 2.0, 1).astype(np.float32),
+                                                 feats=rng.normal(size=(H, W, C)).astype(np.float16),
+                                                 rows=rng.normal(size=(N, C)).astype(np.float16)))
+    N, W, H, vm, K, ws, cap = c.N, c.W, c.H, c.vm, c.K, c.ws, c.cap
+    lws, bws, fws = c.workspace(), c.workspace(), c.workspace()
+    total = torch.zeros((N, C), dtype=torch.float32, device=DEV)
+    wsum = torch.zeros(N, dtype=torch.float32, device=DEV)
+    image = torch.empty((H, W, C), dtype=torch.float16, device=DEV)
+    c.dirty += [total, wsum, image]
+    c.between = lambda: [x.zero_() for x in (total, wsum, c.status)]
+
+    def call():
+        b = c.buf
+        n_isect = voxproj_host.splat_project(b["means"], b["quats"], b["scales"], b["opacities"], vm, K, W, H, workspace=ws)
+        fwd = voxproj_host.splat_rasterize_loss(b["features"], N, W, H, cap, ws, b["target"], b["weight"], want_pixel_loss=True,
+                                                want_logits=True, loss_workspace=lws, status=c.status)
+        grads = voxproj_host.splat_loss_backward(b["means"], b["quats"], b["scales"], b["features"], vm, K, W, H, cap, ws, b["target"],
+                                                 b["weight"], fwd[0], logits=fwd[5], grad_loss=b["grad_loss"], bwd_workspace=bws,
+                                                 want_means=True, want_quats=True, want_scales=True)
+        voxproj_host.splat_lift(b["feats"], N, W, H, cap, ws, total, wsum, b["weight"], sorted=True, status=c.status, lift_workspace=fws)
+        out, alpha = voxproj_host.splat_render(b["rows"], N, W, H, cap, ws, out=image, want_alpha=True, sorted=True, status=c.status,
+                                               check=False)
+        return PerWrapper(splat_project=n_isect, splat_rasterize_loss=fwd, splat_loss_backward=grads, splat_lift=(total, wsum),
+                          splat_render=(out, alpha, c.status))
+    c.call = call
+    return c
+
+
+@case("densify_plan")
+def _densify_plan():
+    N = 1000
+
+    def make(rng):
+        return dict(grad_accum=rng.random(N).astype(np.float32), denom=rng.integers(0, 4, N).astype(np.int32),
+                    max_radius=(rng.random(N) * 30).astype(np.float32), scales=(rng.random((N, 3)) * 0.2).astype(np.float32),
+                    opacities=rng.random(N).astype(np.float32))
+    c = Case(*two(make), blocking=True)       # reads the four counters back: the one synchronisation of a densification
+    ws = c.workspace()
+    stats = voxproj_host.DensifyStats(N, DEV, want_radius=True)
+    stats.grad_accum, stats.denom, stats.max_radius = c.buf["grad_accum"], c.buf["denom"], c.buf["max_radius"]
+
+    def call():
+        plan = voxproj_host.densify_plan(stats, c.buf["scales"], c.buf["opacities"], grad_threshold=0.3, size_threshold=0.1,
+                                         min_opacity=0.05, max_screen_size=20.0, max_world_size=0.19, workspace=ws)
+        return plan.src[:plan.n_out], plan.kind[:plan.n_out], plan.counts
+    c.call = call
+    return c
+
+
+@case("densify_resample_and_split")
+def _densify_rows():
+    # the plan is an index input: made once from fixed statistics and resident; the arrays it moves arrive in-stream
+    N = 1000
+    rng = np.random.default_rng(9)
+    stats = voxproj_host.DensifyStats(N, DEV)
+    stats.grad_accum, stats.denom = t(rng.random(N).astype(np.float32)).to(DEV), t(rng.integers(0, 4, N).astype(np.int32)).to(DEV)
+    plan = voxproj_host.densify_plan(stats, t((rng.random((N, 3)) * 0.2).astype(np.float32)).to(DEV), t(rng.random(N).astype(np.float32)).to(DEV),
+                                     grad_threshold=0.3, size_threshold=0.1, min_opacity=0.05, max_world_size=0.19)
+    assert plan.clones > 0 and plan.split > 0 and plan.kept < N and plan.n_out > 256
+
+    def make(rng):
+        return dict(means=rng.normal(size=(N, 3)).astype(np.float32), quats=rng.normal(size=(N, 4)).astype(np.float32),
+                    log_scales=rng.normal(-2, 0.5, (N, 3)).astype(np.float32), rows=rng.normal(size=(N, 5)).astype(np.float32),
+                    moments=rng.normal(size=(N, 3, 2)).astype(np.float32), steps=rng.integers(0, 100, N).astype(np.int32))
+    c = Case(*two(make))
+
+    def call():
+        b = c.buf
+        moved = plan.resample({"rows": (b["rows"], "copy"), "moments": (b["moments"], "zero"), "steps": (b["steps"], "copy")})
+        split = plan.split_geometry(b["means"], b["quats"], b["log_scales"], seed=12345)
+        return PerWrapper(resample=moved, split_geometry=(split, plan.status))
+    c.call = call
+    return c
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the projector.  Its Workspace is announced to the library and keeps state (tables, header, sticky words) by contract, so it
+# is not dirtied; the accumulators count / out / views_hit are the caller's and are.
+
+@functools.lru_cache(maxsize=None)
+def _projector_scene(seed):
+    """The scene of smoke(): 2000 voxels, four 48 x 32 views (six march workgroups per view, 500 rows per gather wavefront
+    quartet).  Both seeds give the same grid shape and the IDs 1 .. 2000, so either occupancy is valid for n_rows = 2001."""
+    from synthetic_scene import make_scene
+    return make_scene(2000, 4, 48, 32, seed=seed, room=(5.0, 4.0, 2.4))
+
+
+def _projector_inputs(seed, C, dtype, scene_seed=None):
+    from synthetic_scene import make_features_np
+    s = _projector_scene(seed if scene_seed is None else scene_seed)
+    return dict(feats=t(make_features_np(4, 32, 48, C, seed=seed)[None], dtype), occ=t(s.occ[None].astype(np.int64)),
+                vmi=t(s.c2w).reshape(-1), intr=t(s.intr[None] * np.float32(1.0 if seed == 1 else 0.9)))
+
+
+def _projector_inputs_case(dtype, C=8, blocking=False, keys=("feats", "occ", "vmi", "intr")):
+    """The in-stream inputs ``keys`` of a projector call on the two scenes, and the scene's host-side arguments."""
+    s = _projector_scene(1)
+    assert _projector_scene(2).occ.shape == s.occ.shape and _projector_scene(2).n_vox == s.n_vox
+    real, decoy = ({k: v for k, v in _projector_inputs(seed, C, dtype).items() if k in keys} for seed in (1, 2))
+    c = Case(real, decoy, blocking=blocking)
+    c.scene, c.n_rows = s, s.n_vox + 1
+    c.opts, c.origin = [float(v) for v in s.opts()], [float(v) for v in s.grid_origin]
+    return c
+
+
+def _projector_case(dtype, C=8, blocking=False):
+    """_projector_inputs_case with a workspace and the caller's accumulators count / out / views_hit."""
+    c = _projector_inputs_case(dtype, C, blocking)
+    c.ws = c.projector_workspace()
+    c.ws.set_option(voxproj_host.VP_OPT_HEAVY_THRESHOLD, 6)       # many voxels above it: the part rows and their combine launch too
+    c.count = torch.zeros(c.n_rows, dtype=torch.int32, device=DEV)
+    c.out = torch.zeros((c.n_rows, C), dtype=torch.float32, device=DEV)
+    c.views = torch.zeros(c.n_rows, dtype=torch.int32, device=DEV)
+    c.dirty += [c.count, c.out, c.views]
+    c.between = lambda: [x.zero_() for x in (c.count, c.out, c.views)]
+    return c
+
+
+def _project_async(dtype):
+    c = _projector_case(dtype)
+
+    def call():
+        b = c.buf
+        voxproj_host.project_features_raw(b["feats"], b["occ"], b["vmi"], b["intr"], c.opts, c.count, c.out, c.origin, c.scene.voxel_size,
+                                          workspace=c.ws, sync=False, views_hit=c.views)
+        return c.count, c.out, c.views
+    c.call = call
+    return c
+
+
+@case("project_features_raw_f32")
+def _project_f32():
+    return _project_async(torch.float32)              # C = 8: 32-byte rows
+
+
+@case("project_features_raw_f16")
+def _project_f16():
+    return _project_async(torch.float16)              # C = 8: 16-byte rows
+
+
+@case("project_features_raw_sync")
+def _project_blocking():
+    c = _projector_case(torch.float32, blocking=True)             # VP_FLAG_SYNC: the call synchronises at its end, behind all it queued
+
+    def call():
+        b = c.buf
+        voxproj_host.project_features_raw(b["feats"], b["occ"], b["vmi"], b["intr"], c.opts, c.count, c.out, c.origin, c.scene.voxel_size,
+                                          workspace=c.ws, sync=True, views_hit=c.views)
+        return c.count, c.out, c.views
+    c.call = call
+    return c
+
+
+@case("hit_image")
+def _hit_image():
+    # behind an asynchronous projection on the same stream: the copy out of the workspace is queued while the march that writes
+    # the image has not run (the workspace still holds the image of the run before).  hit_image synchronises at its end.
+    c = _projector_case(torch.float32, blocking=True)
+
+    def call():
+        b = c.buf
+        voxproj_host.project_features_raw(b["feats"], b["occ"], b["vmi"], b["intr"], c.opts, c.count, c.out, c.origin, c.scene.voxel_size,
+                                          workspace=c.ws, sync=False, views_hit=c.views)
+        return PerWrapper(project_features_raw=(c.count, c.out, c.views), hit_image=voxproj_host.hit_image(c.ws, DEV))
+    c.call = call
+    return c
+
+
+@case("first_hit_ids")
+def _first_hit_ids():
+    # alone: occ, vmi and intr arrive in-stream, the tables and the march are queued behind them, the call synchronises at its end
+    c = _projector_inputs_case(torch.float32, blocking=True, keys=("occ", "vmi", "intr"))
+    ws = c.projector_workspace()
+    c.call = lambda: voxproj_host.first_hit_ids(c.buf["occ"], c.buf["vmi"], c.buf["intr"], c.opts, c.origin, c.scene.voxel_size, 32, 48,
+                                                c.n_rows, workspace=ws)
+    return c
+
+
+@case("project_features_gather_only_row_range")
+def _project_ranges():
+    # a pipelined call on the rows below 900, then VP_FLAG_GATHER_ONLY for the rest behind it.  occ, vmi and intr are ready
+    # beforehand (the library's own stream reads them and does not wait for the caller's); the tables are built here, so the
+    # calls under test reuse them and nothing synchronises
+    c = _projector_case(torch.float32)
+    fixed = {k: c.real[k] for k in ("occ", "vmi", "intr")}
+    for d in (c.real, c.decoy, c.buf):
+        for k in fixed:
+            del d[k]
+
+    def project(**kw):
+        voxproj_host.project_features_raw(c.buf["feats"], fixed["occ"], fixed["vmi"], fixed["intr"], c.opts, c.count, c.out, c.origin,
+                                          c.scene.voxel_size, workspace=c.ws, views_hit=c.views, **kw)
+    project(sync=True)
+    torch.cuda.synchronize()
+
+    def call():
+        c.ws.set_row_range(0, 900)
+        project(sync=False, pipeline=True)
+        c.ws.set_row_range(900, c.n_rows)
+        project(sync=False, pipeline=True, gather_only=True)
+        c.ws.set_row_range()
+        return c.count, c.out, c.views
+    c.call = call
+    return c
+
+
+def test_pipelined_calls_stay_in_order_behind_pending_feature_maps(oracle_mod):
+    """include/voxproj.h on VP_FLAG_PIPELINE: "the gather and every write to count/out/views_hit stay on `stream`, in order".
+    Three consecutive pipelined calls on one workspace; only the feature maps arrive in-stream (the march runs ahead on the
+    library's stream and reads occ / vmi / intr, which the header wants ready beforehand).  count and out are cloned in-stream
+    after every call: the clones are the bits of the same three calls on the idle default stream, and the oracle's running
+    totals after one, two and three calls (counts exact, sums to 1e-4 of the row's magnitude, as smoke() asks)."""
+    from synthetic_scene import make_features_np
+    C = 8
+    c = _projector_case(torch.float32, C)
+    s = c.scene
+    fixed = {k: c.real[k] for k in ("occ", "vmi", "intr")}
+    maps = [[make_features_np(4, 32, 48, C, seed=10 * which + k)[None] for k in range(3)] for which in (1, 2)]
+    for d, which in ((c.real, 0), (c.decoy, 1), (c.buf, 1)):
+        d.clear()
+        d.update({f"feats{k}": t(maps[which][k]).to(DEV) for k in range(3)})
+
+    def project(feats, **kw):
+        voxproj_host.project_features_raw(feats, fixed["occ"], fixed["vmi"], fixed["intr"], c.opts, c.count, c.out, c.origin, s.voxel_size,
+                                          workspace=c.ws, views_hit=c.views, **kw)
+    project(c.buf["feats0"], sync=True)                # builds the tables: the pipelined calls reuse them and never synchronise
+    torch.cuda.synchronize()
+
+    def call():
+        after = []
+        for k in range(3):
+            project(c.buf[f"feats{k}"], sync=False, pipeline=True)
+            after += [c.count.clone(), c.out.clone()]
+        return after, c.views
+    c.call = call
+    try:
+        got, _ = c.run()
+        voxproj_host.workspace_status(c.ws, DEV)
+    finally:
+        c.close()
+    count = np.zeros(c.n_rows, np.int64)
+    total = np.zeros((c.n_rows, C), np.float64)
+    for k in range(3):
+        one, rows = np.zeros(c.n_rows, np.int32), np.zeros((c.n_rows, C), np.float32)
+        r = oracle_mod.project_features(maps[0][k], s.occ[None].astype(np.int64), s.c2w.reshape(-1), s.intr[None], s.opts(), s.grid_origin,
+                                        s.voxel_size, one, rows, want_f64=True)
+        count, total = count + one, total + r["out64"]
+        assert np.array_equal(got[2 * k].cpu().numpy(), count), f"hit counts after call {k + 1} are not the oracle's running total"
+        err = (np.abs(got[2 * k + 1].cpu().numpy() - total) / (np.abs(total).max(axis=1, keepdims=True) + 1e-30)).max()
+        print(f"after call {k + 1}: {int(count.sum())} hit pixels, sums off by {err:.2e} of their row's magnitude")
+        assert err <= 1e-4
+        assert int((one > 6).sum()) > 50               # voxels above the heavy threshold: the part rows were in play
+
+
+@case("project_colors_raw")
+def _project_colors():
+    # 600 voxels in a 12 x 20 x 24 grid (three workgroups of rows), three 48 x 32 views; the ids 1 .. 600 label a cell in both states
+    dims, n_vox, V, iw, ih = (12, 20, 24), 600, 3, 48, 32
+    n_rows, vs = n_vox + 4, 0.05
+    origin = [-0.5 * dims[2] * vs, -0.5 * dims[1] * vs, -0.5 * dims[0] * vs]
+
+    def make(rng):
+        occ = np.zeros(dims, np.int32)
+        occ.reshape(-1)[rng.choice(occ.size, n_vox, replace=False)] = rng.permutation(n_vox) + 1
+        c2w = np.zeros((V, 4, 4), np.float32)
+        for v in range(V):
+            a = 2.0 * np.pi * v / V + rng.uniform(0, 1)
+            pos = 1.2 * np.array([np.cos(a), np.sin(a), 0.3 * np.sin(2 * a)])
+            f = -pos / np.linalg.norm(pos)
+            right = np.cross(f, [0.0, 0.0, 1.0])
+            right /= np.linalg.norm(right)
+            c2w[v, :3, 0], c2w[v, :3, 1], c2w[v, :3, 2], c2w[v, :3, 3], c2w[v, 3, 3] = right, np.cross(f, right), f, pos, 1.0
+        return dict(occ=occ, c2w=c2w, intr=np.tile(np.array([35.0, 36.0, iw / 2 + 0.5, ih / 2], np.float32), (V, 1)),
+                    images=rng.integers(0, 256, (V, ih, iw, 3), dtype=np.uint8))
+    c = Case(*two(make), blocking=True)                            # vp_project_colors synchronises by contract
+    csum = torch.zeros(n_rows, 3, device=DEV)
+    hits = torch.zeros(n_rows, dtype=torch.int32, device=DEV)
+    first = torch.zeros(n_rows, dtype=torch.int32, device=DEV)
+    uv = torch.zeros((V, n_rows, 2), dtype=torch.int32, device=DEV)
+    c.dirty += [csum, hits, first, uv]
+    c.between = lambda: (csum.zero_(), hits.zero_(), first.fill_(2 ** 30), uv.fill_(77))
+
+    def call():
+        b = c.buf
+        voxproj_host.project_colors_raw(b["occ"], b["c2w"], b["intr"], origin, vs, b["images"], csum, hits, first_view=first, view_base=7,
+                                        pixel_uv=uv)
+        return csum, hits, first, uv
+    c.call = call
+    return c
+
+
+@case("build_occupancy_device")
+def _build_occupancy():
+    c = Case(*two(lambda rng: dict(points=(rng.random((1500, 3)) * [2.0, 1.5, 1.0] - [1.0, 0.5, 0.0]).astype(np.float32))), blocking=True)
+    c.call = lambda: voxproj_host.build_occupancy_device(c.buf["points"], [-0.03, -0.01, -0.02], 0.08)[0]      # reads the bounds back
+    return c
+
+
+@case("aggregate_view_f16")
+def _aggregate_view():
+    # 300 rows of 40 channels: 75 workgroups.  The call consumes view_sum / view_count (and leaves them zeroed)
+    n_rows, C = 300, 40
+
+    def make(rng):
+        cnt = (rng.random(n_rows) < 0.4).astype(np.int32) * rng.integers(1, 50, n_rows).astype(np.int32)
+        cnt[0] = 0
+        return dict(view_sum=(rng.standard_normal((n_rows, C)) * 30).astype(np.float32) * (cnt > 0)[:, None], view_count=cnt)
+    c = Case(*two(make))
+    run16 = torch.zeros(n_rows, C, dtype=torch.float16, device=DEV)
+    views = torch.zeros(n_rows, dtype=torch.int32, device=DEV)
+    first = torch.zeros(n_rows, dtype=torch.int32, device=DEV)
+    flags = torch.zeros(4, dtype=torch.int32, device=DEV)
+    c.dirty += [run16, views, first, flags]
+    c.between = lambda: (run16.zero_(), views.zero_(), first.fill_(2 ** 30), flags.zero_())
+
+    def call():
+        voxproj_host.aggregate_view_f16(c.buf["view_sum"], c.buf["view_count"], run16, views, first, 2, flags, 2)      # default stream argument
+        return run16, views, first, flags, c.buf["view_sum"], c.buf["view_count"]
+    c.call = call
+    return c
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the autograd layers: one forward and backward step, parameters in-stream, gradients cloned in-stream.  Both forwards read
+# back by contract (the intersection count that sizes the sort; the blocking projector call), so the cases are blocking.
+
+@case("splat_autograd_splat_gaussians_step")
+def _splat_autograd():
+    import splat_autograd
+    c = _splat_case(lambda rng, N, D, W, H: dict(grad_logits=rng.normal(size=(D, H, W)).astype(np.float32),
+                                                 grad_alpha=rng.normal(size=(H, W)).astype(np.float32)))
+    c.blocking = True
+    c.workspaces.clear()                               # the layer makes its own workspace per step
+
+    def call():
+        b = c.buf
+        params = [b[k].detach().requires_grad_() for k in ("means", "quats", "scales", "opacities", "features")]
+        logits, alpha, labels, conf = splat_autograd.splat_gaussians(*params, c.vm, c.K, c.W, c.H)
+        torch.autograd.backward([logits, alpha], [b["grad_logits"], b["grad_alpha"]])
+        return PerWrapper(forward=(logits.detach(), alpha.detach(), labels, conf), backward=[p.grad for p in params])
+    c.call = call
+    return c
+
+
+@case("project_features_autograd_step")
+def _project_autograd():
+    import project_features_autograd
+    c = _projector_inputs_case(torch.float32, blocking=True)      # the layer has its own workspace and makes its outputs
+    grads = two(lambda rng: dict(grad_out=rng.normal(size=(c.n_rows, 8)).astype(np.float32)))
+    for d, g in ((c.real, grads[0]), (c.decoy, grads[1]), (c.buf, grads[1])):
+        d["grad_out"] = g["grad_out"].to(DEV).clone()
+
+    def call():
+        b = c.buf
+        feats = b["feats"].detach().requires_grad_()
+        out, count = project_features_autograd.project_features(feats, b["occ"], b["vmi"], b["intr"], c.opts, c.origin, c.scene.voxel_size,
+                                                                c.n_rows, reduce="mean")
+        out.backward(b["grad_out"])
+        return PerWrapper(forward=(out.detach(), count), backward=feats.grad)
+    c.call = call
+    return c
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_the_call_runs_on_the_callers_stream_behind_pending_work(name):
+    c = CASES[name]()
+    try:
+        got, expected = c.run()
+    finally:
+        c.close()
+    assert len(got) == len(expected) and any(g.numel() > 0 for g in got)
+    print(f"{name}: {len(got)} tensors, {sum(g.numel() * g.element_size() for g in got)} bytes compared; delay "
+          f"{stream_order.calibration(DEV)}")
